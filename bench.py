@@ -3,11 +3,19 @@
 1333x800, at 1/2/4/8 MI355X).
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+  python bench.py ... --full                             (also the instrumented passes and the extra measurements)
+  python bench.py ... --dump-outputs DIR                 (the last timed step's outputs as DIR/<name>.npy)
 
 A "step" = one full pass of the hot path over one synthetic batch: image pack -> ResNet-50 -> FPN ->
 FCOS head -> target assignment -> focal/GIoU/centerness loss -> hand-written backward -> (N>1: RCCL
 gradient all-reduce overlapped with backward) -> fused SGD step + bf16 re-pack.  Inputs are resident
 in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the line.  Everything else it can
+measure - the kernel-class roofline (two instrumented passes), the stream-layout check, the extra
+timings (semi-supervised iteration, fp8 towers, data path, train_detector, comm proxy), the CPU
+baseline and, with N > 1, the communication trace - runs only with --full (--no-prof / --no-dsl /
+--no-cpu-baseline leave parts of it out there).
 """
 import argparse
 import ctypes as C
@@ -423,6 +431,25 @@ def dsl_iteration_timing(steps=12, warm=6, variants=None, extra_hook=None, raw=F
     return out
 
 
+DUMP_SAMPLE = 1 << 22      # elements of the gradient / parameter sample (16 MB each in fp32)
+
+
+def dump_outputs(out_dir, out, det):
+    """What a caller of the timed step receives from its last step: the losses (log vars), the gradients of the trainable parameters
+    and the parameters after the SGD update - of the flat fp32 buffers (~32 M values each) the same fixed, seeded sample of
+    DUMP_SAMPLE positions in every run."""
+    st = det.store
+    st.wait_pending()
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out['log_vars'].items():
+        np.save(os.path.join(out_dir, f'{k}.npy'), np.asarray(float(v), dtype=np.float64).reshape(1))
+    n = st.grad.numel()
+    idx = torch.from_numpy(np.unique(np.random.RandomState(0).randint(0, n, min(n, DUMP_SAMPLE)))).to(st.grad.device)
+    np.save(os.path.join(out_dir, 'grad_sample.npy'), st.grad[idx].float().cpu().numpy())
+    np.save(os.path.join(out_dir, 'param_sample.npy'), st.train[idx].float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -435,6 +462,10 @@ def main():
     ap.add_argument('--prof-light', action='store_true', help='bracket only the dominant kernel class in the instrumented pass')
     ap.add_argument('--foreign-streams', default='', help="'before' / 'after' / 'before,after': the process creates and uses streams of its own "
                     "(as a DataLoader's copy stream or an evaluation hook would) before / after the model is built - the stream-layout robustness probe")
+    ap.add_argument('--full', action='store_true', help='after the timed region also run the instrumented passes (roofline), the '
+                    'stream-layout check, the extra timings, the CPU baseline and (N > 1) the communication trace')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="write what the last timed step computed (losses, a fixed sample "
+                    "of the gradients and of the updated parameters) as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get('RANK', 0))
@@ -526,11 +557,14 @@ def main():
 
     # (1) the timed region: EXACTLY --steps steps, no instrumentation
     dt, out = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, det)
+    prof = args.full and not args.no_prof
     # (2) the same steps again with a HIP event pair around every launch of the dominant kernel (on its launch
     # stream).  Kept out of region (1) because the event records serialise the concurrently running streams
     # (measured: -6 % throughput with one class, -12 % with every conv / wgrad launch bracketed).
     dt_prof = None
-    if not args.no_prof:
+    if prof:
         if world > 1:
             dist.barrier()
         # (2a) phases only: two event pairs per step around the head's forward / backward data path (both towers on two streams);
@@ -559,7 +593,7 @@ def main():
     # committed result of the separate rocprofv3 --pmc passes of this same command (tools/pmc_traffic.py)
     traffic = traffic_src = step_traffic = None
     tf = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'traffic.json')
-    if os.path.exists(tf):
+    if prof and os.path.exists(tf):
         tj = json.load(open(tf))
         step_traffic = tj.get('step')          # whole-step HBM bytes (sum over every kernel of the PMC passes) and the floor they imply
         hit = [k for k in tj.get('kernels', {}) if k.startswith(DOMINANT[:-1])]     # the symbol carries further template args
@@ -569,14 +603,14 @@ def main():
     # MFMA-pipe busy fraction of the kernel classes from the SQ counters of the same separate --pmc pass (profiles/pmc_sq.json)
     mfma_busy = None
     sf = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'pmc_sq.json')
-    if os.path.exists(sf):
+    if prof and os.path.exists(sf):
         sj = json.load(open(sf)).get('kernels', {})
         pick = lambda pre: next((v for k, v in sj.items() if k.startswith(pre)), None)
         mfma_busy = {name: (dict(mfma_busy_frac=v['mfma_busy_frac'], wait_any_frac=v['wait_any_frac'], avg_us=v['avg_us']) if v else None)
                      for name, v in (('conv_128x128', pick(DOMINANT[:-1])), ('head_tile_256x192', pick('conv_pipe_kernel<256, 192')),
                                      ('wgrad_256x256', pick('wgrad_pipe_kernel<256, 256')))}
         mfma_busy['source'] = 'profiles/pmc_sq.json (separate rocprofv3 --pmc pass of this command; SQ_VALU_MFMA_BUSY_CYCLES / (SQ_BUSY_CYCLES x 32))'
-    if not args.no_prof:
+    if prof:
         launches = (C.c_int64 * NC)()
         ms = (C.c_double * NC)()
         fl = (C.c_double * NC)()
@@ -629,7 +663,7 @@ def main():
                         mfma_busy_frac=mfma_busy,
                         whole_step_frac=round(value / world * GFLOP_PER_IMAGE_STEP / 1e3 / PEAK_BF16_TFLOPS, 4))
     cpu = extra = None
-    if world > 1:
+    if world > 1 and args.full:
         # communication trace (outside the timed region): per gradient bucket, when its all-reduce was issued behind the bucket's
         # named event and when it was complete, in ms from the start of the step - what the scaling efficiency hinges on
         det.comm_trace = []
@@ -678,7 +712,7 @@ def main():
                                     'same loop with every collective skipped (max over ranks): the difference to ms_per_step is what '
                                     'communication costs, the difference to the 1-GPU figure is what running beside other ranks costs'))
     layout = None
-    if rank == 0 and world == 1 and not args.no_dsl and not foreign:
+    if rank == 0 and world == 1 and args.full and not args.no_dsl and not foreign:
         # stream-layout robustness (which streams share a hardware queue is a 20 % variable): the same loop again with
         # three foreign streams of torch's pool created now and used in every step, as a loader's copy stream would be
         dt_a, _ = timed(args.steps)
@@ -693,7 +727,7 @@ def main():
                            'the before / after variants in fresh processes')
         foreign.clear()
     gc.unfreeze()        # (the extras below build and drop models of their own; their runs freeze and unfreeze by themselves)
-    if rank == 0 and world == 1 and not args.no_dsl:
+    if rank == 0 and world == 1 and args.full and not args.no_dsl:
         del opt
         # (train_detector last: every model instance creates streams, and stream creation order decides which streams share one of
         # the four hardware queues - DESIGN 3.2i; the semi-supervised variants keep the order their round-3 numbers were taken in)
@@ -703,7 +737,7 @@ def main():
         extra['stream_layout_check'] = layout
         if roof is not None:        # BASELINE.json configs[2] beside the headline, also where a record that keeps `roofline` keeps it
             roof['configs2_dsl_iteration_ms'] = {k: v for k, v in extra['dsl_iteration'].items() if k.startswith('ms_per_iter')}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, _ = cpu_baseline(batch)
     if rank == 0:
         print(json.dumps({

@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import fcos_model_cfg, rel_l2
+from util import fcos_model_cfg, oracle_threads, rel_l2
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -136,8 +136,9 @@ def test_rla_train_step_vs_oracle(monkeypatch, side):
     torch.cuda.synchronize()
     got = {k: float(v.detach()) for k, v in losses.items()}
     sd = RO.synth_state_dict(0)
-    l32, g32, aux = RO.train_step(sd, img, gtb, gtl, None, emulate_bf16=False)
-    lem, gem, _ = RO.train_step(sd, img, gtb, gtl, None, emulate_bf16=True)
+    with oracle_threads():
+        l32, g32, aux = RO.train_step(sd, img, gtb, gtl, None, emulate_bf16=False)
+        lem, gem, _ = RO.train_step(sd, img, gtb, gtl, None, emulate_bf16=True)
     print('losses hip', got, 'oracle-bf16', lem, 'fp32', l32)
     for k in got:
         assert got[k] == pytest.approx(lem[k], rel=3e-3), (k, got[k], lem[k])

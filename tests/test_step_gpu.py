@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import fcos_model_cfg, levels_to_flat, rel_l2
+from util import fcos_model_cfg, levels_to_flat, oracle_threads, rel_l2
 
 pytestmark = pytest.mark.gpu
 T = torch.from_numpy
@@ -58,7 +58,8 @@ def test_train_step_vs_reference_and_oracle(golden, monkeypatch, name, knobs):
     # (b) oracle with bf16 storage emulation at the same points: the 1e-3 bar of north_star
     sd = O.synth_state_dict(0)
     kw = dict(loss_weight=3.0, soft_weight=1.0, soft_scale=1.0) if dsl else {}
-    ol, og, aux = O.train_step(sd, img, gtb, gtl, ig, emulate_bf16=True, **kw)
+    with oracle_threads():
+        ol, og, aux = O.train_step(sd, img, gtb, gtl, ig, emulate_bf16=True, **kw)
     print(name, 'losses hip', got, 'oracle-bf16', ol, 'ref-fp32', {k: float(d[k]) for k in got})
     for k in got:
         assert got[k] == pytest.approx(ol[k], rel=3e-3), (k, got[k], ol[k])
@@ -75,7 +76,8 @@ def test_train_step_vs_reference_and_oracle(golden, monkeypatch, name, knobs):
     # gradients.  Two bf16-storage computations of the same network decorrelate to the bf16 noise floor
     # (a rounding flips whenever fp32 summation order differs), so the HIP gradients are judged against
     # the fp32 oracle RELATIVE to the error the bf16-emulating oracle itself makes against fp32.
-    _, g32, _ = O.train_step(sd, img, gtb, gtl, ig, emulate_bf16=False, **kw)
+    with oracle_threads():
+        _, g32, _ = O.train_step(sd, img, gtb, gtl, ig, emulate_bf16=False, **kw)
     named = dict(model.named_parameters())
     keys = [str(k) for k in d['grad_keys']]
     bad = []
