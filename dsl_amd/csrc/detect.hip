@@ -29,7 +29,8 @@ struct DetK {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-// key[m] = max_c sigmoid(cls) * sigmoid(ctr)     (fcos_head.py:472-473)
+// key[m] = max_c sigmoid(cls) * sigmoid(ctr)     (fcos_head.py:472-473).  Full groups of 4 classes, then the partial
+// last group (C % 4 != 0) with its lanes c >= C left out: the row's padding columns hold whatever the buffer held.
 __global__ void det_key_kernel(const DetK p) {
   const int M = p.mstart[p.nlvl];
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
@@ -37,10 +38,17 @@ __global__ void det_key_kernel(const DetK p) {
   const float* c = p.cls + (long long)m * p.ld_cls;
   const float ctr = sigmoidf_(p.rc[(long long)m * p.ld_rc + 4]);
   float best = -1.f;
-  for (int k = 0; k < p.num_classes; k += 4) {
+  const int full = p.num_classes & ~3;
+  for (int k = 0; k < full; k += 4) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(c + k);
 #pragma unroll
     for (int e = 0; e < 4; ++e) best = fmaxf(best, sigmoidf_(v[e]) * ctr);
+  }
+  if (full < p.num_classes) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(c + full);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (full + e < p.num_classes) best = fmaxf(best, sigmoidf_(v[e]) * ctr);
   }
   p.keys[m] = best;
 }
@@ -514,7 +522,8 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   DSL_CHECK(d->cls_logits && d->regctr && d->scales && d->img_shapes && d->dets && d->det_labels && d->det_count &&
                 d->workspace,
             "dsl_fcos_detect: null pointer");
-  DSL_CHECK(d->num_classes % 4 == 0 && d->ld_cls % 4 == 0 && d->ld_rc >= 5, "dsl_fcos_detect: unsupported layout");
+  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= 5,
+            "dsl_fcos_detect: unsupported layout");
   DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS && d->nms_pre > 0, "dsl_fcos_detect: max_per_img must be in 1..%d", NMS_THREADS);
   size_t off[8];
   const size_t need = ws_layout(d, off);

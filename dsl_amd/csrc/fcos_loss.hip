@@ -221,11 +221,14 @@ __device__ __forceinline__ void focal_fb(float x, bool t, float& loss, float& gr
 __device__ __forceinline__ float dmax_a(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
 __device__ __forceinline__ float dmin_a(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
 
+// kTail: C % 4 != 0, the last group of 4 classes of a location is partial.  Its lanes c + e >= C add no loss and no
+// sisoft term and write 0 into g_cls; for C % 4 == 0 the kTail = false instantiation is the only one launched.
+template <bool kTail>
 __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
   __shared__ float sh[16];
   const int M = p.mstart[p.nlvl];
   const int C = p.num_classes;
-  const int c4 = C / 4;
+  const int c4 = kTail ? (C + 3) / 4 : C / 4;
   const float num_pos = fmaxf(p.norm[0] * p.inv_world, 1.0f);
   const float denorm = fmaxf(p.norm[1] * p.inv_world, 1e-6f);
   const bool sisoft = (p.soft_weight != 0.f) && (p.n % 2 != 0) && p.n >= 3;
@@ -242,10 +245,14 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
     const float wgt = p.cls_weight[m];
     const float gs = wgt / num_pos * p.grad_scale;
     float g[4];
+    bool live[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) live[e] = !kTail || c + e < C;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float l, d;
       focal_fb(xv[e], label == c + e, l, d);
+      if (kTail && !live[e]) l = d = 0.f;
       lsum += l * wgt;
       g[e] = d * gs;
     }
@@ -260,7 +267,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
         const float inv_cnt = 1.f / ((float)C * (float)p.h[lvl] * (float)p.w[lvl]);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float d = xv[e] - bv[e];
+          const float d = (kTail && !live[e]) ? 0.f : xv[e] - bv[e];
           ssum += d * d * inv_cnt;
           g[e] += 2.f * d * inv_cnt * p.soft_weight * p.grad_scale;
         }
@@ -271,7 +278,8 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
         const f32x4 av = *reinterpret_cast<const f32x4*>(p.cls_logits + (long long)m2 * p.ld_cls + c);
         const float inv_cnt = 1.f / ((float)C * (float)p.h[nl] * (float)p.w[nl]);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) g[e] -= 2.f * (av[e] - xv[e]) * inv_cnt * p.soft_weight * p.grad_scale;
+        for (int e = 0; e < 4; ++e)
+          if (!kTail || live[e]) g[e] -= 2.f * (av[e] - xv[e]) * inv_cnt * p.soft_weight * p.grad_scale;
       }
     }
     u32x2 o = {pack2bf(g[0], g[1]), pack2bf(g[2], g[3])};
@@ -451,14 +459,19 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(d->labels && d->bbox_targets && d->cls_weight && d->pos_weight && d->cls_logits && d->regctr &&
                 d->scales && d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses,
             "dsl_fcos_loss: null pointer");
-  DSL_CHECK(d->num_classes % 4 == 0 && d->ld_cls % 4 == 0 && d->ld_gcls % 4 == 0 && d->ld_grc % 8 == 0 && d->ld_rc >= 5,
+  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_gcls % 4 == 0 &&
+                d->ld_gcls >= d->ld_cls && d->ld_grc % 8 == 0 && d->ld_rc >= 5,
             "dsl_fcos_loss: unsupported strides / class count");
   hipStream_t st = (hipStream_t)stream;
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d), "dsl_fcos_loss: workspace too small");
   const int M = k.mstart[k.nlvl];
-  int blocks = (int)(((long long)M * (d->num_classes / 4) + 255) / 256);
+  const bool tail = d->num_classes % 4 != 0;
+  int blocks = (int)(((long long)M * ((d->num_classes + 3) / 4) + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(loss_kernel, dim3(blocks), dim3(256), 0, st, k);
+  if (tail)
+    hipLaunchKernelGGL(loss_kernel<true>, dim3(blocks), dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL(loss_kernel<false>, dim3(blocks), dim3(256), 0, st, k);
   hipLaunchKernelGGL(fcos_finalize_kernel, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
                      DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec);
   DSL_LAUNCH_CHECK("loss_kernel");

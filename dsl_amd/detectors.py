@@ -23,7 +23,7 @@ import torch.nn as nn
 
 C_void = ctypes.c_void_p
 
-from .params import ParamStore
+from .params import ParamStore, class_layout
 from .registry import BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, build_backbone, build_head, build_loss, build_neck
 
 
@@ -180,7 +180,8 @@ class FCOSHead(nn.Module):
                  norm_cfg=dict(type='GN', num_groups=32, requires_grad=True), train_cfg=None, test_cfg=None,
                  init_cfg=None, **kw):
         super().__init__()
-        _expect(num_classes == 80 and in_channels == 256 and feat_channels == 256 and stacked_convs == 4, '80 classes, 256ch, 4 convs')
+        class_layout(num_classes)            # 1..MAX_CLASSES, else NotImplementedError naming the range
+        _expect(in_channels == 256 and feat_channels == 256 and stacked_convs == 4, '256ch, 4 convs')
         _expect(list(strides) == [8, 16, 32, 64, 128], 'strides 8..128')
         _expect(center_sampling and norm_on_bbox and centerness_on_reg and not dcn_on_last_conv and conv_bias is True,
                 'the fcos_semi "tricks" head: center_sampling, norm_on_bbox, centerness_on_reg, conv_bias=True')

@@ -214,7 +214,7 @@ class Plan:
         if training and store.backbone != 'rla' and tune('pipe_prefix') != '0' and tune('side') != '0':
             self._split_prefix()
         if training:
-            self.lossplan = FcosLossPlan(N, self.level_sizes, dev, max_gt=max_gt)
+            self.lossplan = FcosLossPlan(N, self.level_sizes, dev, num_classes=store.num_classes, max_gt=max_gt)
             self.lossplan.bind_outputs(self.bufs['cls_logits'], self.bufs['regctr'], store.t32_ptr('head.scales'))
             # scale gradients go straight into the flat gradient buffer
             self.lossplan.desc.g_scales = store.t32_ptr('head.scales', store.grad)
@@ -332,8 +332,9 @@ class Plan:
         self.conv_ws_side = torch.empty(32 << 20, dtype=torch.uint8, device=self.dev)
         FSIDE = 2 if (tune('side') != '0' and not self.single_stream) else 0      # side stream 1 carries the weight gradients (and may be CU-masked)
         # phase marks for bench.py: 8 tower convs + 2 predictors over all M locations, 8 GroupNorm+ReLU passes
-        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (80 + 5) * 2304)
-        self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (80 + 8) * 4.0
+        ncls, cls_pad, cls_ld = st.num_classes, st.cls_pad, st.cls_ld
+        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + 5) * 2304)
+        self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + 8) * 4.0
         f.prof(4, 0, self._head_flops, self._head_bytes)
         # fp8 forward of the tower convolutions (FCOS(fp8=dict(...)), BASELINE.json configs[4], off by default), DELAYED scaling
         # (round 6): every fp8 tensor is written by its producer's own pass - GroupNorm's apply pass writes the e4m3 copy of its output
@@ -406,10 +407,10 @@ class Plan:
                 lays.append(dict(spec=spec, xin=xin, pre=pre, act=act, stats=stats, gn=base))
                 xin, xin8 = act, act8
             self.tower[tower] = lays
-        cls_logits = self.buf('cls_logits', self.M, 80, dtype=torch.float32)
+        cls_logits = self.buf('cls_logits', self.M, cls_ld, dtype=torch.float32)
         regctr = self.buf('regctr', self.M, 8, dtype=torch.float32, zero=True)
         f.conv(ops.conv_desc(self.tower['cls_convs'][3]['act'], st.t16_ptr('head.cls_w'), cls_logits, n=N, grid=ls,
-                             src_hw=ls, dst_hw=ls, cs=256, cd=80, cd_pad=128, ldd=80, kh=3, kw=3, stride=1, pad=1,
+                             src_hw=ls, dst_hw=ls, cs=256, cd=ncls, cd_pad=cls_pad, ldd=cls_ld, kh=3, kw=3, stride=1, pad=1,
                              flags=L.CONV_OUT_F32, bias=st.t32_ptr('head.cls_b'), workspace=self.conv_ws))
         f.conv(ops.conv_desc(self.tower['reg_convs'][3]['act'], st.t16_ptr('head.regctr_w'), regctr, n=N, grid=ls,
                              src_hw=ls, dst_hw=ls, cs=256, cd=5, cd_pad=64, ldd=8, kh=3, kw=3, stride=1, pad=1,
@@ -690,7 +691,7 @@ class Plan:
             return cd_
         towers = (('reg_convs', BT), ('cls_convs', 0)) if BT else (('cls_convs', 0), ('reg_convs', 0))
         # the predictors' weight gradients need nothing from this pass but the loss gradients: first thing on the side stream
-        self._wgrad(ol, None, lp.g_cls, self.tower['cls_convs'][3]['act'], N, ls, ls, cy=128, cd=80, wregion='head.cls_w',
+        self._wgrad(ol, None, lp.g_cls, self.tower['cls_convs'][3]['act'], N, ls, ls, cy=st.cls_pad, cd=st.num_classes, wregion='head.cls_w',
                     bregion='head.cls_b', side=SIDE)
         self._wgrad(ol, None, lp.g_rc, self.tower['reg_convs'][3]['act'], N, ls, ls, cy=64, cd=5, wregion='head.regctr_w',
                     bregion='head.regctr_b', side=SIDE)
@@ -718,7 +719,8 @@ class Plan:
             wsf = side_ws if sd else (lambda c: c)
             g_act[tower] = self.buf(f'g_{tower}_act3', M, 256)
             if tower == 'cls_convs':
-                ol.conv(gn_records(wsf(self._dgrad('head.cls', lp.g_cls, g_act[tower], N, ls, ls, cs=128, cd=256, k=3, stride=1, pad=1, cs_real=80)),
+                ol.conv(gn_records(wsf(self._dgrad('head.cls', lp.g_cls, g_act[tower], N, ls, ls, cs=st.cls_pad, cd=256, k=3, stride=1, pad=1,
+                                                         cs_real=st.num_classes)),
                                    tower, 3, sd), side=sd)
             else:
                 ol.conv(gn_records(wsf(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=64, cd=256, k=3, stride=1, pad=1, cs_real=5)),

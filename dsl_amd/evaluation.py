@@ -9,8 +9,14 @@
                                    image, so this evaluator is checked on constructed cases only: PARITY UNPINNED against
                                    pycocotools; the json files are the interop path to the real tool.
 
+  eval_map / VOCEvalDataset       mmdet/core/evaluation/mean_ap.py (average_precision, tpfp_default, get_cls_results, eval_map)
+                                   and VOCDataset.evaluate(metric='mAP') (mmdet/datasets/voc.py:27-90), in-process numpy;
+                                   pinned to the reference by tests/golden/voc_map.npz.
+
 The dataset side is a plain object (or dict) with `img_ids`, `cat_ids` and, for the built-in evaluator, `annotations`:
-one list per image of dict(bbox=[x, y, w, h], category_id, iscrowd=0, area=optional).
+one list per image of dict(bbox=[x, y, w, h], category_id, iscrowd=0, area=optional).  With `metric='mAP'` (the VOC configs'
+`evaluation = dict(metric='mAP')`) the annotations are instead one dict per image of `bboxes` [n, 4] xyxy, `labels` [n] (0-based),
+`bboxes_ignore` [k, 4], `labels_ignore` [k], and an optional `year` (2007 selects VOC07's 11-point AP).
 """
 import json
 import os
@@ -148,6 +154,203 @@ def coco_bbox_eval(dets, img_ids, cat_ids, annotations, iou_thrs=None, max_dets=
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# PASCAL VOC mAP (mean_ap.py): per class, detections of all images sorted by score, greedy matching per image at one IoU
+def average_precision(recalls, precisions, mode='area'):
+    """AP of one or several (num_scales rows) precision / recall curves: 'area' = area under the precision envelope,
+    '11points' = mean of the best precision at recall >= 0, 0.1, ..., 1 (VOC07)."""
+    rec, prec = np.asarray(recalls), np.asarray(precisions)
+    single = rec.ndim == 1
+    rec, prec = np.atleast_2d(rec), np.atleast_2d(prec)
+    assert rec.shape == prec.shape
+    ap = np.zeros(rec.shape[0], dtype=np.float32)
+    if mode == 'area':
+        for i in range(rec.shape[0]):
+            r = np.concatenate(([0.], rec[i], [1.])).astype(rec.dtype)
+            p = np.concatenate(([0.], prec[i], [0.])).astype(prec.dtype)
+            p = np.maximum.accumulate(p[::-1])[::-1]                  # precision envelope
+            step = np.nonzero(r[1:] != r[:-1])[0]
+            ap[i] = np.sum((r[step + 1] - r[step]) * p[step + 1])
+    elif mode == '11points':
+        for i in range(rec.shape[0]):
+            for t in np.arange(0, 1 + 1e-3, 0.1):
+                sel = prec[i, rec[i] >= t]
+                ap[i] += sel.max() if sel.size else 0
+        ap /= 11
+    else:
+        raise ValueError('Unrecognized mode, only "area" and "11points" are supported')
+    return ap[0] if single else ap
+
+
+def _overlaps(a, b):
+    """[n, k] IoU of xyxy boxes in float32 (evaluation/bbox_overlaps.py: no +1, union clamped at 1e-6)."""
+    a, b = np.asarray(a, np.float32).reshape(-1, 4), np.asarray(b, np.float32).reshape(-1, 4)
+    if not len(a) or not len(b):
+        return np.zeros((len(a), len(b)), np.float32)
+    area_a = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    iw = np.maximum(np.minimum(a[:, None, 2], b[None, :, 2]) - np.maximum(a[:, None, 0], b[None, :, 0]), 0)
+    ih = np.maximum(np.minimum(a[:, None, 3], b[None, :, 3]) - np.maximum(a[:, None, 1], b[None, :, 1]), 0)
+    inter = iw * ih
+    return inter / np.maximum(area_a[:, None] + area_b[None] - inter, np.float32(1e-6))
+
+
+def tpfp_default(det_bboxes, gt_bboxes, gt_bboxes_ignore=None, iou_thr=0.5, area_ranges=None):
+    """(tp, fp), each [num_scales, num_dets] float32, for one image and class.  A detection whose best-IoU ground truth
+    (>= iou_thr) is an ignore box or out of the area range counts as neither; a second detection of a covered box is a false
+    positive; an unmatched detection is a false positive when its own area is inside the range."""
+    det = np.asarray(det_bboxes, np.float32).reshape(-1, 5)
+    gt = np.asarray(gt_bboxes, np.float32).reshape(-1, 4)
+    ig = np.zeros((0, 4), np.float32) if gt_bboxes_ignore is None else np.asarray(gt_bboxes_ignore, np.float32).reshape(-1, 4)
+    is_ig = np.concatenate((np.zeros(len(gt), bool), np.ones(len(ig), bool)))
+    allgt = np.vstack((gt, ig))
+    ranges = [(None, None)] if area_ranges is None else list(area_ranges)
+    tp = np.zeros((len(ranges), len(det)), np.float32)
+    fp = np.zeros((len(ranges), len(det)), np.float32)
+    det_area = (det[:, 2] - det[:, 0]) * (det[:, 3] - det[:, 1])
+    if len(allgt) == 0:
+        for k, (lo, hi) in enumerate(ranges):
+            fp[k] = 1 if lo is None else ((det_area >= lo) & (det_area < hi))
+        return tp, fp
+    ious = _overlaps(det[:, :4], allgt)
+    best, arg = ious.max(axis=1), ious.argmax(axis=1)
+    order = np.argsort(-det[:, -1])
+    gt_area = (allgt[:, 2] - allgt[:, 0]) * (allgt[:, 3] - allgt[:, 1])
+    for k, (lo, hi) in enumerate(ranges):
+        covered = np.zeros(len(allgt), bool)
+        out_of_range = np.zeros(len(allgt), bool) if lo is None else (gt_area < lo) | (gt_area >= hi)
+        for i in order:
+            if best[i] >= iou_thr:
+                j = arg[i]
+                if is_ig[j] or out_of_range[j]:
+                    continue
+                if covered[j]:
+                    fp[k, i] = 1
+                else:
+                    covered[j], tp[k, i] = True, 1
+            elif lo is None or lo <= det_area[i] < hi:
+                fp[k, i] = 1
+    return tp, fp
+
+
+def get_cls_results(det_results, annotations, class_id):
+    """Per image: the class's detections, ground truth and ignore boxes."""
+    dets = [r[class_id] for r in det_results]
+    gts, igs = [], []
+    for a in annotations:
+        gts.append(np.asarray(a['bboxes'])[np.asarray(a['labels']) == class_id, :])
+        if a.get('labels_ignore', None) is not None:
+            igs.append(np.asarray(a['bboxes_ignore'])[np.asarray(a['labels_ignore']) == class_id, :])
+        else:
+            igs.append(np.empty((0, 4), dtype=np.float32))
+    return dets, gts, igs
+
+
+def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=None, logger=None):
+    """det_results[img][cls] = (k, 5) xyxy + score; annotations[img] = dict(bboxes, labels[, bboxes_ignore, labels_ignore]).
+    scale_ranges: [(lo, hi), ...] in sqrt(area).  dataset='voc07' selects 11-point AP.  Returns (mean_ap, per-class dicts of
+    num_gts, num_dets, recall, precision, ap); mean_ap averages the classes with ground truth (per scale: a list)."""
+    assert len(det_results) == len(annotations)
+    num_classes = len(det_results[0])
+    nscale = len(scale_ranges) if scale_ranges is not None else 1
+    area_ranges = [(lo ** 2, hi ** 2) for lo, hi in scale_ranges] if scale_ranges is not None else None
+    mode = '11points' if dataset == 'voc07' else 'area'
+    eps = np.finfo(np.float32).eps
+    results = []
+    for c in range(num_classes):
+        dets, gts, igs = get_cls_results(det_results, annotations, c)
+        tpfp = [tpfp_default(d, g, i, iou_thr, area_ranges) for d, g, i in zip(dets, gts, igs)]
+        num_gts = np.zeros(nscale, dtype=int)
+        for g in gts:
+            g = np.asarray(g).reshape(-1, 4)
+            if area_ranges is None:
+                num_gts[0] += g.shape[0]
+            else:
+                a = (g[:, 2] - g[:, 0]) * (g[:, 3] - g[:, 1])
+                for k, (lo, hi) in enumerate(area_ranges):
+                    num_gts[k] += np.sum((a >= lo) & (a < hi))
+        dets = np.vstack([np.asarray(d).reshape(-1, 5) for d in dets])
+        order = np.argsort(-dets[:, -1])
+        tp = np.cumsum(np.hstack([t for t, _ in tpfp])[:, order], axis=1)
+        fp = np.cumsum(np.hstack([f for _, f in tpfp])[:, order], axis=1)
+        rec = tp / np.maximum(num_gts[:, None], eps)
+        prec = tp / np.maximum(tp + fp, eps)
+        if scale_ranges is None:
+            rec, prec, num_gts = rec[0], prec[0], num_gts.item()
+        results.append(dict(num_gts=num_gts, num_dets=dets.shape[0], recall=rec, precision=prec,
+                            ap=average_precision(rec, prec, mode)))
+    if scale_ranges is not None:
+        aps = np.vstack([r['ap'] for r in results])
+        ngt = np.vstack([r['num_gts'] for r in results])
+        mean_ap = [aps[ngt[:, k] > 0, k].mean() if np.any(ngt[:, k] > 0) else 0.0 for k in range(nscale)]
+    else:
+        aps = [r['ap'] for r in results if r['num_gts'] > 0]
+        mean_ap = np.array(aps).mean().item() if aps else 0.0
+    if logger is not None and logger != 'silent':
+        for c, r in enumerate(results):
+            logger.info('class %d: gts %s dets %d ap %s', c, r['num_gts'], r['num_dets'], np.round(r['ap'], 3))
+        logger.info('mAP %s', mean_ap)
+    return mean_ap, results
+
+
+def voc_evaluate(results, annotations, metric='mAP', iou_thr=0.5, year=2007, logger=None):
+    """VOCDataset.evaluate(metric='mAP') (voc.py:27-90): AP<iou*100> per IoU threshold (rounded to 3 places) and their mean as
+    'mAP'; VOC 2007 uses the 11-point AP, other years the area."""
+    if not isinstance(metric, str):
+        assert len(metric) == 1
+        metric = metric[0]
+    if metric != 'mAP':
+        raise KeyError(f'metric {metric} is not supported')
+    thrs = [iou_thr] if isinstance(iou_thr, float) else list(iou_thr)
+    out, means = OrderedDict(), []
+    for t in thrs:
+        m, _ = eval_map(results, annotations, scale_ranges=None, iou_thr=t, dataset='voc07' if year == 2007 else None,
+                        logger=logger)
+        means.append(m)
+        out[f'AP{int(t * 100):02d}'] = round(m, 3)
+    out['mAP'] = sum(means) / len(means)
+    return out
+
+
+def voc_annotations(ds):
+    """The per-image VOC annotation dicts of a dataset object: its own (`get_ann_info` / `annotations` in VOC form), or its
+    COCO-form `annotations` converted (xywh -> xyxy, category_id -> index in `cat_ids`, iscrowd -> ignore box)."""
+    if hasattr(ds, 'get_ann_info'):
+        return [ds.get_ann_info(i) for i in range(len(ds))]
+    out = []
+    for anns in ds.annotations:
+        if isinstance(anns, dict):
+            out.append(anns)
+            continue
+        box = {0: [], 1: []}
+        lab = {0: [], 1: []}
+        for a in anns:
+            x, y, w, h = a['bbox']
+            crowd = int(bool(a.get('iscrowd', 0)))
+            box[crowd].append([x, y, x + w, y + h])
+            lab[crowd].append(ds.cat_ids.index(a['category_id']))
+        out.append(dict(bboxes=np.array(box[0], np.float32).reshape(-1, 4), labels=np.array(lab[0], np.int64),
+                        bboxes_ignore=np.array(box[1], np.float32).reshape(-1, 4), labels_ignore=np.array(lab[1], np.int64)))
+    return out
+
+
+class VOCEvalDataset:
+    """The evaluation side of VOCDataset as a plain object: `annotations` one dict per image (bboxes, labels, bboxes_ignore,
+    labels_ignore), `year` 2007 (11-point AP) or 2012 (area); `evaluate` is voc.py's."""
+
+    def __init__(self, annotations, year=2007, CLASSES=None):
+        self.annotations, self.year, self.CLASSES = list(annotations), year, CLASSES
+
+    def __len__(self):
+        return len(self.annotations)
+
+    def get_ann_info(self, idx):
+        return self.annotations[idx]
+
+    def evaluate(self, results, metric='mAP', logger=None, iou_thr=0.5, scale_ranges=None, **kw):
+        return voc_evaluate(results, self.annotations, metric=metric, iou_thr=iou_thr, year=self.year, logger=logger)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 def _unwrap(x):
     return x[0] if isinstance(x, (list, tuple)) and len(x) == 1 and isinstance(x[0], (list, tuple, torch.Tensor)) else x
 
@@ -226,6 +429,8 @@ class EvalHook:
             ds = getattr(self.dataloader, 'dataset', self.dataloader)
             if hasattr(ds, 'evaluate'):
                 metrics = ds.evaluate(results, metric=self.metric, **self.eval_kwargs)
+            elif self.metric in ('mAP', ['mAP']):
+                metrics = voc_evaluate(results, voc_annotations(ds), year=getattr(ds, 'year', 2007), **self.eval_kwargs)
             else:
                 prefix = self.jsonfile_prefix or (os.path.join(runner.work_dir, f'eval_epoch_{runner.epoch + 1}') if runner.work_dir else None)
                 files, tmp = format_results(results, ds.img_ids, ds.cat_ids, prefix)

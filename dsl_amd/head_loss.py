@@ -10,17 +10,21 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .params import class_layout
 
 STRIDES = (8, 16, 32, 64, 128)
 REGRESS_RANGES = ((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8))   # fcos_head.py:61-62
 
 
 class FcosLossPlan:
-    LD_CLS, LD_RC, LD_GCLS, LD_GRC = 80, 8, 128, 64
+    """Row strides: the logits are read LD_CLS = round_up(C, 4) wide, the class gradients written LD_GCLS = round_up(C, 64)
+    wide (the predictor's data / weight gradient read them as that many channels: the columns from C on stay zero)."""
+    LD_RC, LD_GRC = 8, 64
 
     def __init__(self, n, sizes, device, strides=STRIDES, ranges=REGRESS_RANGES, num_classes=80,
                  radius=1.5, max_gt=1024):
-        assert num_classes == 80, 'kernel strides are laid out for 80 classes'
+        self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
+        self.num_classes = num_classes
         self.n, self.sizes, self.strides, self.device = n, [tuple(s) for s in sizes], strides, device
         self.M = n * sum(h * w for h, w in self.sizes)
         M, dev = self.M, device

@@ -106,6 +106,17 @@ def neck_specs():
     return specs
 
 
+MAX_CLASSES = 128    # the classification predictor is stored round_up(C, 64) rows wide: one or two 64-row weight tiles
+
+
+def class_layout(num_classes):
+    """(cp, c4) of a C-class head: the classification predictor's stored rows / gradient columns (round_up(C, 64)) and the
+    row stride of its fp32 logits (round_up(C, 4), the loss / detection kernels' 4-class groups).  80 classes: (128, 80)."""
+    if not (isinstance(num_classes, int) and 1 <= num_classes <= MAX_CLASSES):
+        raise NotImplementedError(f'dsl_amd hot path: num_classes must be in 1..{MAX_CLASSES}, got {num_classes!r}')
+    return _round_up(num_classes, 64), _round_up(num_classes, 4)
+
+
 def head_specs():
     specs = []
     for tower in ('cls_convs', 'reg_convs'):
@@ -117,7 +128,8 @@ class ParamStore:
     """Flat buffers + named views.  One instance for the student, one for the EMA teacher."""
 
     def __init__(self, num_classes=80, device='cpu', backbone='resnet'):
-        assert num_classes == 80 and backbone in ('resnet', 'rla')
+        assert backbone in ('resnet', 'rla')
+        self.cls_pad, self.cls_ld = class_layout(num_classes)
         self.num_classes, self.backbone = num_classes, backbone
         self.defer_head = False       # deferred head update (FlatSGD._sync_defer decides; engine.Plan.defer reads it)
         self._pending_ev = None
@@ -174,9 +186,10 @@ class ParamStore:
             for i in range(4):
                 toff = add(self.train_regions, toff, f'bbox_head.{tower}.{i}.gn.weight', (256,))
                 toff = add(self.train_regions, toff, f'bbox_head.{tower}.{i}.gn.bias', (256,))
-        # predictors: rows padded to the kernel tile; conv_reg (4) + conv_centerness (1) share one region
-        toff = add(self.train_regions, toff, 'head.cls_w', (128, 3, 3, 256))
-        toff = add(self.train_regions, toff, 'head.cls_b', (128,))
+        # predictors: rows padded to the kernel tile; conv_reg (4) + conv_centerness (1) share one region.  The padding rows
+        # of conv_cls stay zero: their output columns' gradients are zero, so SGD / weight decay / EMA keep them at 0
+        toff = add(self.train_regions, toff, 'head.cls_w', (self.cls_pad, 3, 3, 256))
+        toff = add(self.train_regions, toff, 'head.cls_b', (self.cls_pad,))
         toff = add(self.train_regions, toff, 'head.regctr_w', (64, 3, 3, 256))
         toff = add(self.train_regions, toff, 'head.regctr_b', (64,))
         toff = add(self.train_regions, toff, 'head.scales', (8,))
@@ -263,8 +276,8 @@ class ParamStore:
             bn(n)
         cw, cb = self.tview('head.cls_w', tb), self.tview('head.cls_b', tb)
         rw, rb = self.tview('head.regctr_w', tb), self.tview('head.regctr_b', tb)
-        out['bbox_head.conv_cls.weight'] = cw[:80].permute(0, 3, 1, 2)
-        out['bbox_head.conv_cls.bias'] = cb[:80]
+        out['bbox_head.conv_cls.weight'] = cw[:self.num_classes].permute(0, 3, 1, 2)
+        out['bbox_head.conv_cls.bias'] = cb[:self.num_classes]
         out['bbox_head.conv_reg.weight'] = rw[:4].permute(0, 3, 1, 2)
         out['bbox_head.conv_reg.bias'] = rb[:4]
         out['bbox_head.conv_centerness.weight'] = rw[4:5].permute(0, 3, 1, 2)
@@ -284,15 +297,25 @@ class ParamStore:
             self._pending_ev = None
 
     def load_named(self, sd, strict=True):
+        """Copy a reference-layout state dict into the store.  Keys whose shape differs (a checkpoint of another class count:
+        conv_cls) follow mmcv's load_state_dict: strict=True raises, strict=False skips them with a warning."""
         self.wait_pending()
         views = self.named_views()
         missing = [k for k in views if k not in sd]
         unexpected = [k for k in sd if k not in views]
         if strict and (missing or unexpected):
             raise KeyError(f'state_dict mismatch: missing {missing[:5]}, unexpected {unexpected[:5]}')
+        mismatch = [f'{k}: checkpoint {tuple(sd[k].shape)}, model {tuple(v.shape)}' for k, v in views.items()
+                    if k in sd and sd[k].numel() != v.numel()]
+        if mismatch:
+            msg = 'size mismatch in state_dict: ' + '; '.join(mismatch)
+            if strict:
+                raise RuntimeError(msg)
+            import warnings
+            warnings.warn(msg + ' (skipped)', RuntimeWarning, stacklevel=3)
         with torch.no_grad():
             for k, v in views.items():
-                if k in sd:
+                if k in sd and sd[k].numel() == v.numel():
                     v.copy_(sd[k].to(v.device))
         self.dirty = True
         return missing, unexpected
@@ -329,8 +352,8 @@ class ParamStore:
                             k_c = s2_class(py, px)[0]
                             lay[f'{s.name}#s2{py}{px}'] = (off, s.cin_store * k_c * k_c * s.cout_pad)
                             off += _round_up(lay[f'{s.name}#s2{py}{px}'][1], 8)
-            lay['head.cls'] = (off, 256 * 9 * 128)
-            off += 256 * 9 * 128
+            lay['head.cls'] = (off, 256 * 9 * self.cls_pad)
+            off += 256 * 9 * self.cls_pad
             lay['head.regctr'] = (off, 256 * 9 * 64)
             off += 256 * 9 * 64
             self._wT, self._wT_total = lay, off
@@ -417,7 +440,7 @@ class ParamStore:
             items, start = [], 0
             for name, (off, n) in lay.items():
                 if name == 'head.cls':
-                    w, co, cop, taps, cin, sc = self.tview('head.cls_w'), 80, 128, 9, 256, None
+                    w, co, cop, taps, cin, sc = self.tview('head.cls_w'), self.num_classes, self.cls_pad, 9, 256, None
                 elif name == 'head.regctr':
                     w, co, cop, taps, cin, sc = self.tview('head.regctr_w'), 5, 64, 9, 256, None
                 else:

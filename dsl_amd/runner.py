@@ -510,7 +510,14 @@ class UnlabelPredHook(Hook):
         self.id2cat = dict(cat['id2cat']) if cat else None
         # save_results2file loops `for i in range(0, len(id2cat) - 1)` (:152): every class id but the last entry of the
         # category file (COCO files list the 80 classes + background)
-        self.num_classes = (len(self.id2cat) - 1) if self.id2cat else int(k.get('num_classes', 80))
+        # without one: the bank's, the key's, or the model config's class count
+        if self.id2cat:
+            self.num_classes = len(self.id2cat) - 1
+        elif bank is not None:
+            self.num_classes = bank.num_classes
+        else:
+            head = ((config.get('model') or {}).get('bbox_head') or {}) if hasattr(config, 'get') else {}
+            self.num_classes = int(k.get('num_classes', head.get('num_classes', 80)))
         names = [self.id2cat[str(i)] for i in range(self.num_classes)] if self.id2cat else k.get('class_names')
         ada = None
         if config is not None:

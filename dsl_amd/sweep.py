@@ -68,7 +68,8 @@ def detect_device(det, img, img_metas, rescale=False, store=None, single_stream=
     if dp is None:
         cfg = det.test_cfg or {}
         nms = cfg.get('nms', {})
-        dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, nms_pre=cfg.get('nms_pre', 1000),
+        dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
+                        ld_cls=store.cls_ld, nms_pre=cfg.get('nms_pre', 1000),
                         max_per_img=cfg.get('max_per_img', 100), score_thr=cfg.get('score_thr', 0.05),
                         iou_thr=nms.get('iou_threshold', nms.get('iou_thr', 0.5)))
         dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))

@@ -87,7 +87,8 @@ typedef struct dsl_conv_desc {
   void* workspace;                                   /* optional fp32 scratch for split-K (small-M, large-K convs) */
   size_t workspace_bytes;                            /* NULL/0: never split */
   int32_t cs_real;                                   /* 0 = cs; else the source's real channel count when cs is padded (the
-                                                      * 80- / 5-channel predictor gradients stored 128 / 64 wide): only the
+                                                      * C- / 5-channel predictor gradients stored round_up(C, 64) / 64 wide,
+                                                      * 1 <= C <= 128): only the
                                                       * algorithmic FLOP / byte counts of dsl_prof_* use it */
   int32_t lds;                                       /* 0 = cs; else the source's pixel stride in elements (>= cs, multiple of
                                                       * 8): the source is a channel slice [0, cs) of wider rows */
@@ -446,7 +447,7 @@ typedef struct dsl_fcos_desc {
   int32_t h[DSL_MAX_SEG], w[DSL_MAX_SEG], stride[DSL_MAX_SEG];
   float range_lo[DSL_MAX_SEG], range_hi[DSL_MAX_SEG];
   float radius;                        /* center_sample_radius (1.5) */
-  int32_t num_classes;                 /* 80 */
+  int32_t num_classes;                 /* C >= 1 (the host uses 1..128); ld_cls % 4 == 0, ld_cls >= C, ld_gcls >= ld_cls */
   /* ground truth, concatenated over images; gt_off[n+1] prefix offsets (device int32) */
   const float* gt_boxes;               /* [G][4] xyxy */
   const int64_t* gt_labels;            /* [G] */
