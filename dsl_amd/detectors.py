@@ -320,7 +320,9 @@ class _TrainStepFn(torch.autograd.Function):
 
 @DETECTORS.register_module()
 class FCOS(nn.Module):
-    """SingleStageDetector (detectors/single_stage.py:10-165) specialised by detectors/fcos.py:5-18."""
+    """SingleStageDetector (detectors/single_stage.py:10-165) specialised by detectors/fcos.py:5-18.
+    Data parallel with late exchange (FlatSGD(late_exchange=True), the default without clipping): after backward() `p.grad` holds
+    this rank's local gradient until wait_grads() or the optimizer's step() has run the exchanges."""
 
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None,
                  init_cfg=None, fp8=None):
@@ -459,6 +461,12 @@ class FCOS(nn.Module):
         img[-1] (semi_epoch_based_runner.py:186-204), whose metas / boxes are the lists' last entries; the stem kernel samples it
         from img[-1] (dsl_stem_pool_half), it is never written to memory."""
         eng = self._get_engine()
+        if self._pending or getattr(self, '_late_todo', None):
+            # a second training pass before step() (gradient accumulation, an aborted step): the previous backward pass's collectives
+            # are queued now (late exchange) and waited for - none is dropped (the ranks would disagree on the collective sequence)
+            # and none still writes store.grad under this pass.  Here and not in _run_backward: this pass's loss kernel already
+            # writes the scale gradients into store.grad, and every later writer (the weight gradients) runs behind the caller's stream
+            self.wait_grads()
         N, _, H, W = img.shape
         N += 1 if half_scale_copy else 0
         assert len(img_metas) == N == len(gt_bboxes) == len(gt_labels)

@@ -223,13 +223,16 @@ class FlatSGD:
         self.steps += 1
 
     def state_dict(self):
-        # regions: where every named parameter lives in the flat momentum buffer - what load_state_dict / step remap by
+        # regions: where every named parameter lives in the flat momentum buffer - what load_state_dict / step remap by.
+        # (late exchange / deferred head update: the last step's updates may still be writing the momentum on another stream)
+        self.store.wait_pending()
         return dict(momentum=self.momentum_buf, steps=self.steps, param_groups=self.param_groups,
                     regions={k: (int(v[0]), int(v[1])) for k, v in self.store.train_regions.items()})
 
     def load_state_dict(self, sd):
         """Restores momentum, the step count (first-step rule of torch.optim.SGD: buf = grad) and the groups' learning
         rates.  The momentum tensor may live on the CPU (runner.resume loads with map_location='cpu'); step() moves it."""
+        self.store.wait_pending()          # (the buffer replaced here may still be written by the last step's updates)
         m = sd['momentum']
         self.momentum_buf = m.detach().clone() if isinstance(m, torch.Tensor) else None
         self.steps = int(sd['steps']) if self.momentum_buf is not None else 0

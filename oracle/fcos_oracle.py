@@ -549,7 +549,8 @@ def train_step(sd, img, gt_bboxes, gt_labels, gt_bboxes_ignore=None, emulate_bf1
 # ----------------------------------------------------------------------------------------------
 def param_group_rule(key, base_lr, base_wd, bias_lr_mult=2.0, bias_decay_mult=0.0):
     leaf = key.rsplit('.', 1)[-1]
-    is_norm = ('.gn.' in key) or ('.bn' in key) or ('downsample.1' in key)
+    # (mmcv decides by module type: BatchNorm / GroupNorm layers, RLA_ResNet's per-block stage_bns BatchNorms included)
+    is_norm = ('.gn.' in key) or ('.bn' in key) or ('downsample.1' in key) or ('.stage_bns.' in key)
     lr, wd = base_lr, base_wd
     if leaf == 'bias' and not is_norm:
         lr, wd = base_lr * bias_lr_mult, base_wd * bias_decay_mult

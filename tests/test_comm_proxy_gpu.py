@@ -36,10 +36,12 @@ def test_comm_stream_is_placed_on_the_weight_gradient_queue():
 
 @pytest.mark.parametrize('carrier,late', [('lib', True), ('torch', True), ('lib', False)])
 def test_proxy_schedule_trains_to_the_same_bits(carrier, late):
-    """The proxy's passes preserve the values, so three steps in the data-parallel schedule (either carrier) end with bit-identical
-    weights to three plain steps: the events order every bucket's exchange behind its weight gradients and every update behind its
-    exchange - a missing edge shows up as a different weight.  late: the default schedule (collectives queued behind the backward pass,
-    the next forward pass waits per stage for SLOT_UPD + bucket) or the round-5 one (joined at the end of the step)."""
+    """The proxy's passes preserve the values, so five steps in the data-parallel schedule (either carrier) end with bit-identical
+    weights to five plain steps.  What this can show is the update -> next forward edge: a forward pass that read a bucket before its
+    update had landed gives a different weight.  It cannot show an update that runs before or during its bucket's exchange - the
+    exchange changes no value - nor a wrong update that both runs share (test_bucket_update_gpu checks the update against host math
+    and the late exchange with real collectives).  late: the default schedule (collectives queued behind the backward pass, the next
+    forward pass waits per stage for SLOT_UPD + bucket) or the round-5 one (joined at the end of the step)."""
     import bench
     b = bench.synth_batch(0, 2)
     finals = []
