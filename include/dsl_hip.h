@@ -78,11 +78,13 @@ typedef struct dsl_conv_desc {
   int32_t ldd, lda, ldm;                             /* row strides (elements) of dst/addend/mask */
   int32_t kh, kw, stride, pad, mode, os, flags;
   const void* src;                                   /* bf16 */
-  const void* wgt;                                   /* bf16 [cd_pad][kh*kw*cs] */
+  const void* wgt;                                   /* bf16 [cd_pad][kh*kw*cs] (SMALL_C: rows of round_up(kh*kw*8, 64); FP8: e4m3).
+                                                      * Mode 1 reads the dgrad pack with the same tap order: no flip */
   void* dst;                                         /* bf16 or fp32 */
   const float* scale;                                /* [cd] or NULL (=1) */
   const float* bias;                                 /* [cd] or NULL (=0) */
-  const void* addend;                                /* bf16 or NULL */
+  const void* addend;                                /* bf16 or NULL; may equal dst (in-place accumulation: each element is read
+                                                      * before it is written) */
   const void* mask;                                  /* bf16 or NULL */
   void* workspace;                                   /* optional fp32 scratch for split-K (small-M, large-K convs) */
   size_t workspace_bytes;                            /* NULL/0: never split */
