@@ -32,8 +32,11 @@ BETA_MAX = 2.0 ** -13
 # wgrad: 2^-14.  A weight-gradient accumulator sums a whole split's pixels (thousands of products) in one fp32 chain, so its error
 # grows with the partial sum, not with sqrt(n): the N = 3 towers' group measured 2^-15.7 S where dW ~ S (coherent terms), 1.4x a
 # 2^-16 bar.  2^-14 still flags one 32-pixel K stage of the 3 x 44 800-pixel towers' gradient (test_step_replay_gpu.py controls).
-BETA = dict(conv=2.0 ** -16, wgrad=2.0 ** -14, gn=2.0 ** -16, pool=2.0 ** -16)
+# loss: the FCOS loss kernel's bf16 gradients; loss_sum: its fp32 sums (losses, g_scales, the assignment's centerness sum), added
+# in block records of 256: measured at most 0.009 of a 2^-16 bar over the seven replay legs, hence 2^-20.
+BETA = dict(conv=2.0 ** -16, wgrad=2.0 ** -14, gn=2.0 ** -16, pool=2.0 ** -16, loss=2.0 ** -16, loss_sum=2.0 ** -20)
 F64 = torch.float64
+DSL_MAX_SEG = 5
 
 # op kinds (mirror include/dsl_hip.h; kept here so that the CPU tests need no library)
 OP_CONV, OP_WGRAD, OP_GN_FWD, OP_GN_BWD, OP_MAXPOOL, OP_SUM2X2, OP_COLSUM, OP_MEMSET, OP_PACK_IMAGE = range(1, 10)
@@ -47,7 +50,8 @@ KIND_NAMES = {OP_CONV: 'CONV', OP_WGRAD: 'WGRAD', OP_GN_FWD: 'GN_FWD', OP_GN_BWD
               OP_QUANT_FP8_W: 'QUANT_FP8_W', OP_FP8_COMB: 'FP8_COMB', OP_STEM_POOL: 'STEM_POOL', OP_BNECK: 'BNECK',
               OP_FP8_PREP: 'FP8_PREP', OP_QUANT_FP8_DELAYED: 'QUANT_FP8_DELAYED'}
 CHECKED = {OP_CONV, OP_WGRAD, OP_WGRAD_GROUP, OP_WGRAD_MULTI, OP_BNECK, OP_GN_FWD, OP_GN_BWD, OP_STEM_POOL, OP_MAXPOOL, OP_SUM2X2,
-           OP_COLSUM, OP_MEMSET, OP_PACK_IMAGE}
+           OP_COLSUM, OP_MEMSET, OP_PACK_IMAGE, OP_ASSIGN, OP_LOSS, OP_QUANT_FP8, OP_QUANT_FP8_W, OP_FP8_COMB, OP_FP8_PREP,
+           OP_QUANT_FP8_DELAYED}
 CONV_RELU_OUT, CONV_RELU_IN, CONV_OUT_F32, CONV_MASK_FIRST, CONV_MASK_LAST, CONV_ADD_UPSAMPLE, CONV_SMALL_C, CONV_FP8 = \
     1, 2, 4, 8, 16, 32, 64, 128
 
@@ -648,6 +652,429 @@ def stem_pool_ref(mem, img_ptr, wg_ptr, scale_ptr, bias_ptr, out_ptr, ld_out, n,
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
+# FCOS target assignment (csrc/fcos_loss.hip assign_kernel): bit-exact fp32 restatement, kernel operation order
+FCOS_INF = 1e8
+
+
+def _fcos_locations(d):
+    """Level-major [lvl][img][y][x] locations of a dsl_fcos_desc: (lvl, img, y, x) long tensors (CPU) and mstart[nlvl + 1]."""
+    lv, im, ys, xs, ms = [], [], [], [], [0]
+    for l in range(d.nlvl):
+        img, y, x = _grid(d.n, d.h[l], d.w[l], 'cpu')
+        lv.append(torch.full_like(img, l))
+        im.append(img)
+        ys.append(y)
+        xs.append(x)
+        ms.append(ms[-1] + img.numel())
+    return torch.cat(lv), torch.cat(im), torch.cat(ys), torch.cat(xs), ms
+
+
+def _assign_boxes(px, py, rs, lo, hi, boxes):
+    """assign_one over rows of locations against boxes [G][4] (fp32, CPU): (best area, first argmin, ltrb of that box)."""
+    x, y = px.view(-1, 1), py.view(-1, 1)
+    x1, y1, x2, y2 = (boxes[:, i].view(1, -1) for i in range(4))
+    area = (x2 - x1) * (y2 - y1)
+    l, tp, r, b = x - x1, y - y1, x2 - x, y2 - y
+    cx, cy = (x1 + x2) / 2, (y1 + y2) / 2
+    rr = rs.view(-1, 1)
+    xmin, ymin, xmax, ymax = cx - rr, cy - rr, cx + rr, cy + rr
+    c0 = torch.where(xmin > x1, xmin, x1)
+    c1 = torch.where(ymin > y1, ymin, y1)
+    c2 = torch.where(xmax > x2, x2, xmax)
+    c3 = torch.where(ymax > y2, y2, ymax)
+    cmin = torch.minimum(torch.minimum(x - c0, y - c1), torch.minimum(c2 - x, c3 - y))
+    mx = torch.maximum(torch.maximum(l, tp), torch.maximum(r, b))
+    ok = (cmin > 0) & (mx >= lo.view(-1, 1)) & (mx <= hi.view(-1, 1))
+    area = torch.where(ok, area.expand_as(ok), torch.full_like(mx, FCOS_INF))
+    best, idx = area.min(1)               # first index of the minimum (the kernel's `g == g0 || area < best`)
+    ar = torch.arange(px.numel())
+    t = torch.stack([v.expand_as(mx)[ar, idx] for v in (l, tp, r, b)], 1)
+    return best, idx, t
+
+
+def assign_ref(mem, d, name='assign', radius=None):
+    """dsl_fcos_assign: labels, assign_idx, bbox_targets (/ stride; background rows: gt 0's ltrb, zeros for an image without gt),
+    cls_weight (0 for background locations that an ignore box claims by the same rule, x loss_weight for images >= n / 2),
+    pos_weight, stats[0] (exact count), stats[1] (sum of centerness targets, beta S), stats[2..7] = 0.  radius: negative-control
+    hook (the centre-sampling radius in place of the descriptor's)."""
+    d = d if isinstance(d, types.SimpleNamespace) else _ns(d)
+    dev = mem.device_of(d.labels, f'{name}.labels')
+    f32 = torch.float32
+    lvl, img, y, x, ms = _fcos_locations(d)
+    M, C = ms[-1], d.num_classes
+    s = torch.tensor([d.stride[l] for l in range(d.nlvl)])[lvl]
+    px = x.to(f32) * s.to(f32) + (s // 2).to(f32)
+    py = y.to(f32) * s.to(f32) + (s // 2).to(f32)
+    rad = torch.tensor(d.radius if radius is None else radius, dtype=f32)
+    rs = s.to(f32) * rad
+    lo = torch.tensor([d.range_lo[l] for l in range(d.nlvl)], dtype=f32)[lvl]
+    hi = torch.tensor([d.range_hi[l] for l in range(d.nlvl)], dtype=f32)[lvl]
+    gt_off = mem.typed(d.gt_off, torch.int32, d.n + 1, f'{name}.gt_off').cpu().long()
+    G = int(gt_off[-1])
+    boxes = mem.typed(d.gt_boxes, f32, 4 * G, f'{name}.gt_boxes').cpu().view(G, 4)
+    glab = mem.typed(d.gt_labels, torch.int64, G, f'{name}.gt_labels').cpu()
+    ig = None
+    if d.ig_boxes and d.ig_off:
+        ig_off = mem.typed(d.ig_off, torch.int32, d.n + 1, f'{name}.ig_off').cpu().long()
+        ig = (ig_off, mem.typed(d.ig_boxes, f32, 4 * int(ig_off[-1]), f'{name}.ig_boxes').cpu().view(-1, 4))
+    labels = torch.full((M,), C, dtype=torch.int64)
+    aidx = torch.full((M,), -1, dtype=torch.int64)
+    tgt = torch.zeros(M, 4, dtype=f32)
+    wgt = torch.ones(M, dtype=f32)
+    for i in range(d.n):
+        sel = (img == i).nonzero().view(-1)
+        g0, g1 = int(gt_off[i]), int(gt_off[i + 1])
+        if g1 > g0:
+            best, idx, t = _assign_boxes(px[sel], py[sel], rs[sel], lo[sel], hi[sel], boxes[g0:g1])
+            pos = best != FCOS_INF
+            labels[sel[pos]] = glab[g0 + idx[pos]]
+            aidx[sel[pos]] = idx[pos]
+            tgt[sel] = t
+        if ig is not None and int(ig[0][i + 1]) > int(ig[0][i]):
+            bi, _, _ = _assign_boxes(px[sel], py[sel], rs[sel], lo[sel], hi[sel], ig[1][int(ig[0][i]):int(ig[0][i + 1])])
+            wgt[sel[(bi != FCOS_INF) & (labels[sel] == C)]] = 0.0
+    tgt = tgt / s.to(f32).view(-1, 1)
+    sw = torch.ones(M, dtype=f32)
+    if torch.tensor(d.loss_weight, dtype=f32) != 1.0:
+        sw[img >= d.n // 2] = torch.tensor(d.loss_weight, dtype=f32)
+    pos = labels < C
+    tp = tgt[pos]
+    ctr = torch.sqrt((torch.minimum(tp[:, 0], tp[:, 2]) / torch.maximum(tp[:, 0], tp[:, 2])) *
+                     (torch.minimum(tp[:, 1], tp[:, 3]) / torch.maximum(tp[:, 1], tp[:, 3]))).to(F64)
+    ar = lambda n: torch.arange(n, device=dev)
+    on = lambda t: t.to(dev).to(F64)
+    lr = LaunchRef('ASSIGN')
+    for nm, ptr, dt, idx, ref in (('labels', d.labels, torch.int64, ar(M), labels), ('assign_idx', d.assign_idx, torch.int32, ar(M), aidx),
+                                  ('bbox_targets', d.bbox_targets, f32, ar(4 * M).view(M, 4), tgt),
+                                  ('cls_weight', d.cls_weight, f32, ar(M), wgt * sw), ('pos_weight', d.pos_weight, f32, ar(M), sw)):
+        mem.find(ptr, idx.numel() * torch.empty(0, dtype=dt).element_size(), f'{name}.{nm}')
+        lr.outs.append(Out(f'{name}.{nm}', ptr, dt, idx, on(ref), on(ref).abs(), 0.0, exact=True))
+    mem.find(d.stats, 32, f'{name}.stats')
+    st = torch.zeros(8, dtype=F64)
+    st[0], st[1] = float(pos.sum()), float(ctr.sum())
+    Sst = torch.zeros(8, dtype=F64)
+    Sst[1] = float(ctr.abs().sum())
+    lr.outs.append(Out(f'{name}.stats', d.stats, f32, ar(8), on(st), on(Sst), BETA['loss_sum']))
+    _allow(mem, lr, d.workspace, d.workspace_bytes, f'{name}.workspace')
+    lr.extra.update(pos=int(pos.sum()), M=M)
+    return lr
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the fused FCOS loss (csrc/fcos_loss.hip loss_kernel + fcos_finalize_kernel), float64 from the launch's own inputs
+FOCAL_ALPHA = 0.25
+
+
+def loss_ref(mem, d, name='loss', beta=None, partner_level=-1, relu_mask=True):
+    """dsl_fcos_loss.  Focal (alpha 0.25, gamma 2) x cls_weight / num_pos; GIoU on distance2bbox(point, relu(raw x scale)) against
+    the targets, x centerness target x pos_weight / denorm, torch's 0.5 / 0.5 split of max / min gradients on ties and its eps
+    clamps; centerness BCE x pos_weight / num_pos; sisoft (soft_weight != 0, n odd >= 3): mean (x[lvl][n-2] - x[lvl-1][n-1][:h, :w])^2
+    over levels >= 1, gradients both ways; gradients x grad_scale; num_pos = max(norm[0] inv_world, 1), denorm = max(norm[1]
+    inv_world, 1e-6) from the norm[] in device memory.  The max / min decisions of the GIoU are taken on the fp32 box corners
+    (point -+ distance, rounded as the kernel forms them: they differ in the last bit of a 1000-pixel coordinate); everything else is
+    float64.  Outputs: g_cls (columns C .. ld_gcls zero), g_rc (columns 5 .. 7 zero), g_scales[5], losses[4], logvec (post: the fp32
+    recombination fcos_finalize_kernel documents, bit for bit, of the losses the launch wrote).
+    S: the sum of the absolute term contributions; a positive's focal term also carries 2^-8 |d term / d q| (q = 1 - p is formed in
+    fp32: an absolute error of 2^-24 = 2^-8 beta).  partner_level / relu_mask: negative-control hooks (sisoft partner level offset,
+    the ReLU mask of the box gradient)."""
+    d = d if isinstance(d, types.SimpleNamespace) else _ns(d)
+    beta = BETA['loss'] if beta is None else beta
+    bsum = BETA['loss_sum']
+    dev = mem.device_of(d.cls_logits, f'{name}.cls_logits')
+    f32 = torch.float32
+    lvl, img, y, x, ms = _fcos_locations(d)
+    lvl, img, y, x = (t.to(dev) for t in (lvl, img, y, x))
+    M, C, C4 = ms[-1], d.num_classes, (d.num_classes + 3) // 4 * 4
+    logits = _gather_rows(mem.typed(d.cls_logits, f32, (M - 1) * d.ld_cls + C4, f'{name}.cls_logits'), torch.arange(M, device=dev),
+                          d.ld_cls, C)
+    rc = _gather_rows(mem.typed(d.regctr, f32, (M - 1) * d.ld_rc + 5, f'{name}.regctr'), torch.arange(M, device=dev), d.ld_rc, 5)
+    labels = mem.typed(d.labels, torch.int64, M, f'{name}.labels')
+    tg = mem.typed(d.bbox_targets, f32, 4 * M, f'{name}.bbox_targets').view(M, 4)
+    cw = mem.typed(d.cls_weight, f32, M, f'{name}.cls_weight').to(F64)
+    pw = mem.typed(d.pos_weight, f32, M, f'{name}.pos_weight').to(F64)
+    scales = mem.typed(d.scales, f32, d.nlvl, f'{name}.scales')
+    norm = mem.typed(d.norm, f32, 2, f'{name}.norm').clone()
+    iw = torch.tensor(d.inv_world, dtype=f32, device=dev)
+    num_pos = float(torch.clamp_min(norm[0] * iw, 1.0))
+    denorm = float(torch.clamp_min(norm[1] * iw, 1e-6))
+    gs = float(torch.tensor(d.grad_scale, dtype=f32))
+    sw = float(torch.tensor(d.soft_weight, dtype=f32))
+    a = FOCAL_ALPHA
+    # -- focal
+    t = labels.view(-1, 1) == torch.arange(C, device=dev).view(1, -1)
+    p, q = torch.sigmoid(logits), torch.sigmoid(-logits)
+    sp_pos, sp_neg = torch.nn.functional.softplus(-logits), torch.nn.functional.softplus(logits)
+    l_el = torch.where(t, a * q * q * sp_pos, (1 - a) * p * p * sp_neg)
+    g_el = torch.where(t, -a * q * q * (2 * p * sp_pos + q), (1 - a) * p * p * (2 * q * sp_neg + p))
+    cond_g = torch.where(t, a * (2 * q * (2 * p * sp_pos + q) + q * q) * BF16_REL, torch.zeros_like(q))
+    cond_l = torch.where(t, a * 2 * q * sp_pos * BF16_REL, torch.zeros_like(q))
+    k = (cw / num_pos * gs).view(-1, 1)
+    g_cls = g_el * k
+    S_cls = (g_el.abs() + cond_g) * k.abs()
+    L_cls = (l_el * cw.view(-1, 1)).sum() / num_pos
+    S_Lcls = ((l_el.abs() + cond_l) * cw.abs().view(-1, 1)).sum() / num_pos
+    # -- sisoft
+    L_soft = S_soft = 0.0
+    if sw != 0.0 and d.n % 2 == 1 and d.n >= 3:
+        for l in range(1, d.nlvl):
+            pl = l + partner_level
+            h, w = d.h[l], d.w[l]
+            yy, xx = torch.meshgrid(torch.arange(h, device=dev), torch.arange(w, device=dev), indexing='ij')
+            ma = ms[l] + ((d.n - 2) * h + yy.reshape(-1)) * w + xx.reshape(-1)
+            mb = ms[pl] + ((d.n - 1) * d.h[pl] + yy.reshape(-1)) * d.w[pl] + xx.reshape(-1)
+            cnt = C * h * w
+            dd = logits[ma] - logits[mb]
+            L_soft += float((dd * dd).sum()) / cnt * sw
+            S_soft += float((dd * dd).sum()) / cnt * abs(sw)
+            gterm = 2 * dd / cnt * sw * gs
+            g_cls.index_add_(0, ma, gterm)
+            g_cls.index_add_(0, mb, -gterm)
+            S_cls.index_add_(0, ma, gterm.abs())
+            S_cls.index_add_(0, mb, gterm.abs())
+    # -- boxes and centerness at the positives
+    pos = (labels < C).nonzero().view(-1)
+    g_rc = torch.zeros(M, 8, dtype=F64, device=dev)
+    S_rc = torch.zeros_like(g_rc)
+    g_sc = torch.zeros(DSL_MAX_SEG, dtype=F64, device=dev)
+    S_sc = torch.zeros_like(g_sc)
+    L_box = S_box = L_ctr = S_ctr = 0.0
+    if pos.numel():
+        lv = lvl[pos]
+        s = torch.tensor([d.stride[l] for l in range(d.nlvl)], device=dev)[lv]
+        px = (x[pos].to(f32) * s.to(f32) + (s // 2).to(f32)).view(-1, 1)
+        py = (y[pos].to(f32) * s.to(f32) + (s // 2).to(f32)).view(-1, 1)
+        sc32 = scales[lv].view(-1, 1)
+        raw32 = mem.typed(d.regctr, f32, (M - 1) * d.ld_rc + 5, f'{name}.regctr').view(-1)[
+            pos.view(-1, 1) * d.ld_rc + torch.arange(4, device=dev).view(1, -1)]
+        d32 = torch.clamp_min(raw32 * sc32, 0.0)
+        t32 = tg[pos]
+        # fp32 corners (the kernel's), then float64
+        P1 = torch.cat([px - d32[:, :1], py - d32[:, 1:2], px + d32[:, 2:3], py + d32[:, 3:4]], 1).to(F64)
+        T1 = torch.cat([px - t32[:, :1], py - t32[:, 1:2], px + t32[:, 2:3], py + t32[:, 3:4]], 1).to(F64)
+        raw, sc, t64 = raw32.to(F64), sc32.to(F64), t32.to(F64)
+        # the centerness target in fp32, as the kernel and the reference (fcos_head.py:707-726 on fp32 targets) form it
+        ct32 = torch.sqrt((torch.minimum(t32[:, 0], t32[:, 2]) / torch.maximum(t32[:, 0], t32[:, 2])) *
+                          (torch.minimum(t32[:, 1], t32[:, 3]) / torch.maximum(t32[:, 1], t32[:, 3])))
+        ct = ct32.to(F64)
+        x1, y1, x2, y2 = P1.unbind(1)
+        X1, Y1, X2, Y2 = T1.unbind(1)
+        eps = float(torch.tensor(1e-6, dtype=f32))
+        dmax = lambda u, v: torch.where(u > v, 1.0, torch.where(u == v, 0.5, 0.0)).to(F64)
+        dmin = lambda u, v: torch.where(u < v, 1.0, torch.where(u == v, 0.5, 0.0)).to(F64)
+        a1, a2 = (x2 - x1) * (y2 - y1), (X2 - X1) * (Y2 - Y1)
+        w0, h0 = torch.minimum(x2, X2) - torch.maximum(x1, X1), torch.minimum(y2, Y2) - torch.maximum(y1, Y1)
+        iw_, ih = w0.clamp_min(0), h0.clamp_min(0)
+        ov = iw_ * ih
+        u0 = a1 + a2 - ov
+        U = u0.clamp_min(eps)
+        ew0, eh0 = torch.maximum(x2, X2) - torch.minimum(x1, X1), torch.maximum(y2, Y2) - torch.minimum(y1, Y1)
+        ew, eh = ew0.clamp_min(0), eh0.clamp_min(0)
+        e0 = ew * eh
+        E = e0.clamp_min(eps)
+        giou = ov / U - (E - U) / E
+        wb = (ct32 * pw[pos].float()).to(F64)           # (an fp32 product in the kernel and the reference alike)
+        L_box = float((wb * (1 - giou)).sum()) / denorm
+        S_box = float((wb.abs() * (1 + ov / U + (E - U).abs() / E)).sum()) / denorm
+        cw_, ch_ = (w0 >= 0).to(F64), (h0 >= 0).to(F64)
+        dov = torch.stack([ih * -dmax(x1, X1) * cw_, iw_ * -dmax(y1, Y1) * ch_, ih * dmin(x2, X2) * cw_, iw_ * dmin(y2, Y2) * ch_], 1)
+        da1 = torch.stack([-(y2 - y1), -(x2 - x1), y2 - y1, x2 - x1], 1)
+        ug = torch.where(u0 > eps, 1.0, torch.where(u0 == eps, 0.5, 0.0)).to(F64).view(-1, 1)
+        eg = torch.where(e0 > eps, 1.0, torch.where(e0 == eps, 0.5, 0.0)).to(F64).view(-1, 1)
+        cew, ceh = (ew0 >= 0).to(F64), (eh0 >= 0).to(F64)
+        de = torch.stack([eh * -dmin(x1, X1) * cew, ew * -dmin(y1, Y1) * ceh, eh * dmax(x2, X2) * cew, ew * dmax(y2, Y2) * ceh], 1) * eg
+        dU = (da1 - dov) * ug
+        U_, E_, ov_ = U.view(-1, 1), E.view(-1, 1), ov.view(-1, 1)
+        dg = dov / U_ - ov_ * dU / (U_ * U_) + dU / E_ - U_ * de / (E_ * E_)
+        Sdg = dov.abs() / U_ + ov_ * (da1.abs() + dov.abs()) * ug / (U_ * U_) + (da1.abs() + dov.abs()) * ug / E_ + U_ * de.abs() / (E_ * E_)
+        coef = (-wb / denorm * gs).view(-1, 1)
+        sign = torch.tensor([-1.0, -1.0, 1.0, 1.0], dtype=F64, device=dev)
+        dd = coef * dg * sign
+        Sdd = coef.abs() * Sdg
+        on = (raw * sc > 0).to(F64) if relu_mask else torch.ones_like(raw)
+        g_rc[pos, :4] = dd * on * sc
+        S_rc[pos, :4] = Sdd * on * sc.abs()
+        g_sc.index_add_(0, lv, (dd * on * raw).sum(1))
+        S_sc.index_add_(0, lv, (Sdd * on * raw.abs()).sum(1))
+        cl = rc[pos, 4]
+        ppw = pw[pos]
+        ce = torch.clamp_min(cl, 0) - cl * ct + torch.log1p(torch.exp(-cl.abs()))
+        L_ctr = float((ce * ppw).sum()) / num_pos
+        S_ctr = float(((torch.clamp_min(cl, 0) + (cl * ct).abs() + torch.log1p(torch.exp(-cl.abs()))) * ppw.abs()).sum()) / num_pos
+        sig = torch.sigmoid(cl)
+        g_rc[pos, 4] = (sig - ct) * ppw / num_pos * gs
+        S_rc[pos, 4] = (sig + ct) * (ppw / num_pos * gs).abs()
+    # -- outputs
+    ar = lambda n: torch.arange(n, device=dev)
+    lr = LaunchRef('LOSS')
+    G = torch.zeros(M, d.ld_gcls, dtype=F64, device=dev)
+    SG = torch.zeros_like(G)
+    G[:, :C], SG[:, :C] = g_cls, S_cls
+    mem.find(d.g_cls, M * d.ld_gcls * 2, f'{name}.g_cls')
+    lr.outs.append(Out(f'{name}.g_cls', d.g_cls, torch.bfloat16, ar(M * d.ld_gcls).view(M, d.ld_gcls), G, SG, beta))
+    mem.find(d.g_rc, ((M - 1) * d.ld_grc + 8) * 2, f'{name}.g_rc')
+    lr.outs.append(Out(f'{name}.g_rc', d.g_rc, torch.bfloat16, ar(M).view(-1, 1) * d.ld_grc + ar(8).view(1, -1), g_rc, S_rc, beta))
+    lr.outs.append(Out(f'{name}.g_scales', d.g_scales, f32, ar(DSL_MAX_SEG), g_sc, S_sc, bsum))
+    losses = torch.tensor([L_cls, L_box, L_ctr, L_soft], dtype=F64, device=dev)
+    S_l = torch.tensor([float(S_Lcls), S_box, S_ctr, S_soft], dtype=F64, device=dev)
+    lr.outs.append(Out(f'{name}.losses', d.losses, f32, ar(4), losses, S_l, bsum))
+    if d.logvec:
+        def post(mem=mem, d=d):
+            lo = mem.typed(d.losses, f32, 4, f'{name}.losses').clone()
+            terms = [lo[0], lo[1], lo[2]] + ([lo[3]] if sw != 0.0 else [])
+            tot = (lo[0] + lo[1]) + lo[2]
+            if sw != 0.0:
+                tot = tot + lo[3]
+            ref = torch.stack(terms + [tot]).to(F64)
+            return [Out(f'{name}.logvec', d.logvec, f32, ar(ref.numel()), ref, ref.abs(), 0.0, exact=True)]
+        mem.find(d.logvec, 20, f'{name}.logvec')
+        lr.post.append(post)
+    _allow(mem, lr, d.workspace, d.workspace_bytes, f'{name}.workspace')
+    lr.extra.update(pos=int(pos.numel()), num_pos=num_pos, denorm=denorm)
+    return lr
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# fp8 quantisers (csrc/optim.hip): bytes bit-exact against torch's e4m3 cast, scales and maxima in fp32
+E4M3_MAX = 448.0
+
+
+def e4m3_bytes(v32, scale32):
+    """clamp(v x scale, +-448) cast by torch.float8_e4m3fn (RNE), as bytes -> float64 (v, scale fp32: one fp32 product)."""
+    return (v32 * scale32).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn).view(torch.uint8).to(F64)
+
+
+def e4m3_scale(m):
+    """448 / m as the kernels form it: one correctly rounded fp32 division (IEEE divide; torch's `448.0 / tensor` is a reciprocal
+    and a product, two roundings), 1 where m == 0."""
+    return torch.where(m > 0, torch.full_like(m, E4M3_MAX) / m, torch.ones_like(m))
+
+
+def e4m3_inv(a):
+    """a / 448, correctly rounded (a tensor divisor: on the GPU torch divides by a scalar as a product with its reciprocal), 1 where
+    a == 0."""
+    return torch.where(a > 0, a / torch.full_like(a, E4M3_MAX), torch.ones_like(a))
+
+
+def _bf16_rows(mem, ptr, rows, c, ld, what):
+    return _gather_rows(mem.typed(ptr, torch.bfloat16, (rows - 1) * ld + c, what), torch.arange(rows, device=mem.device_of(ptr, what)),
+                        ld, c).float()
+
+
+def _block_max(xa, rows, c, per, grid):
+    """max over the per-element chunks that each of `grid` grid-stride workgroups of 256 threads visits (chunk j -> block
+    (j // 256) % grid) of |x| [rows][c] (fp32)."""
+    ch = xa.reshape(rows * (c // per), per).amax(1)
+    blk = (torch.arange(ch.numel(), device=xa.device) // 256) % grid
+    out = torch.zeros(grid, dtype=xa.dtype, device=xa.device)
+    return out.scatter_reduce(0, blk, ch, 'amax', include_self=True)
+
+
+def _fbits(bits):
+    return float(torch.tensor([bits & 0xffffffff], dtype=torch.int64).to(torch.int32).view(torch.float32)[0])
+
+
+def quant_fp8_ref(mem, x_ptr, y_ptr, rows, c, ld_x, scale_bits, partials=0, n_partials=0, name='quant_fp8', scale_mul=1.0):
+    """DSL_OP_QUANT_FP8: fixed scale (the float whose bits are l[1]), or absmax block maxima + scale = 448 / max.  scale_mul:
+    negative-control hook."""
+    x = _bf16_rows(mem, x_ptr, rows, c, ld_x, f'{name}.x')
+    dev = x.device
+    lr = LaunchRef('QUANT_FP8')
+    if partials:
+        pm = _block_max(x.abs(), rows, c, 8, n_partials)
+        amax = pm.max()
+        scale = e4m3_scale(amax)
+        lr.outs.append(Out(f'{name}.partials', partials, torch.float32, torch.arange(n_partials, device=dev), pm.to(F64), pm.to(F64), 0.0,
+                           exact=True))
+    else:
+        scale = torch.tensor(_fbits(scale_bits), dtype=torch.float32, device=dev)
+    q = e4m3_bytes(x, scale * scale_mul)
+    mem.find(y_ptr, rows * c, f'{name}.y')
+    lr.outs.insert(0, Out(f'{name}.y', y_ptr, torch.uint8, torch.arange(rows * c, device=dev).view(rows, c), q, q, 0.0, exact=True))
+    return lr
+
+
+def _w8_rows(w, cout, cout_pad, k, inv_act, bn=None):
+    """quantised weight rows [cout_pad][k] (bytes, float64) and comb [cout_pad] (fp32 arithmetic, the kernels' order) of fp32 w
+    [cout][k]; padding rows zero."""
+    s = e4m3_scale(w.abs().amax(1))
+    w8 = torch.zeros(cout_pad, k, dtype=F64, device=w.device)
+    w8[:cout] = e4m3_bytes(w, s.view(-1, 1))
+    comb = torch.zeros(cout_pad, dtype=torch.float32, device=w.device)
+    comb[:cout] = inv_act / s * (bn if bn is not None else 1.0)
+    return w8, comb.to(F64)
+
+
+def quant_fp8_w_ref(mem, w_ptr, w8_ptr, comb_ptr, bn_ptr, cout, cout_pad, k, inv_bits, name='quant_fp8_w'):
+    w = mem.typed(w_ptr, torch.float32, cout * k, f'{name}.w').view(cout, k)
+    bn = mem.typed(bn_ptr, torch.float32, cout, f'{name}.bn_scale') if bn_ptr else None
+    inv = torch.tensor(_fbits(inv_bits), dtype=torch.float32, device=w.device)
+    w8, comb = _w8_rows(w, cout, cout_pad, k, inv, bn)
+    mem.find(w8_ptr, cout_pad * k, f'{name}.w8')
+    lr = LaunchRef('QUANT_FP8_W')
+    ar = lambda n: torch.arange(n, device=w.device)
+    lr.outs.append(Out(f'{name}.w8', w8_ptr, torch.uint8, ar(cout_pad * k).view(cout_pad, k), w8, w8, 0.0, exact=True))
+    lr.outs.append(Out(f'{name}.comb', comb_ptr, torch.float32, ar(cout_pad), comb, comb, 0.0, exact=True))
+    return lr
+
+
+def fp8_comb_ref(mem, winv_ptr, comb_ptr, n, partials, n_partials, name='fp8_comb'):
+    winv = mem.typed(winv_ptr, torch.float32, n, f'{name}.winv')
+    amax = mem.typed(partials, torch.float32, n_partials, f'{name}.partials').max()
+    inv = e4m3_inv(amax)
+    ref = (winv * inv).to(F64)
+    lr = LaunchRef('FP8_COMB')
+    lr.outs.append(Out(f'{name}.comb', comb_ptr, torch.float32, torch.arange(n, device=winv.device), ref, ref, 0.0, exact=True))
+    return lr
+
+
+class Fp8PrepItem(C.Structure):
+    """dsl_fp8_prep_item (mirrors include/dsl_hip.h and dsl_amd/_lib.py; kept here so that the CPU tests need no library)"""
+    _fields_ = [('w', C.c_void_p), ('w8', C.c_void_p), ('comb', C.c_void_p), ('amax', C.c_void_p), ('scale', C.c_void_p),
+                ('n_amax', C.c_int32), ('cout', C.c_int32)]
+
+
+def fp8_prep_ref(mem, items_ptr, n_items, cout_pad, k, margin_bits, name='fp8_prep'):
+    """DSL_OP_FP8_PREP over the item table in device memory: per item a = margin x max(amax[0 .. n_amax)), scale[0] = 448 / a (1 when
+    a == 0: nothing recorded yet), w8 / comb = the weight rows quantised with comb[co] = (a / 448 or 1) / s_w[co]; rows >= cout zero."""
+    sz = C.sizeof(Fp8PrepItem)
+    raw = bytes(mem.typed(items_ptr, torch.uint8, n_items * sz, f'{name}.items').cpu().numpy().tobytes())
+    margin = torch.tensor(_fbits(margin_bits), dtype=torch.float32)
+    lr = LaunchRef('FP8_PREP')
+    lr.extra['cold'] = 0
+    for j in range(n_items):
+        it = Fp8PrepItem.from_buffer_copy(raw[j * sz:(j + 1) * sz])
+        w = mem.typed(it.w, torch.float32, it.cout * k, f'{name}[{j}].w').view(it.cout, k)
+        dev = w.device
+        a = mem.typed(it.amax, torch.float32, it.n_amax, f'{name}[{j}].amax').max() * margin.to(dev)
+        scale = e4m3_scale(a)
+        inv_act = e4m3_inv(a)
+        lr.extra['cold'] += int(not bool(a > 0))
+        w8, comb = _w8_rows(w, it.cout, cout_pad, k, inv_act)
+        ar = lambda n: torch.arange(n, device=dev)
+        mem.find(it.w8, cout_pad * k, f'{name}[{j}].w8')
+        lr.outs.append(Out(f'{name}[{j}].w8', it.w8, torch.uint8, ar(cout_pad * k).view(cout_pad, k), w8, w8, 0.0, exact=True))
+        lr.outs.append(Out(f'{name}[{j}].comb', it.comb, torch.float32, ar(cout_pad), comb, comb, 0.0, exact=True))
+        sc64 = scale.view(1).to(F64)
+        lr.outs.append(Out(f'{name}[{j}].scale', it.scale, torch.float32, ar(1), sc64, sc64, 0.0, exact=True))
+    return lr
+
+
+def quant_fp8_delayed_ref(mem, x_ptr, y_ptr, partials, scale_ptr, rows, c, ld_x, n_partials, name='quant_fp8_delayed', scale_mul=1.0):
+    """y = e4m3(clamp(x x scale[0], +-448)) with the scale in device memory; partials[b] = max |x| over the 16-element chunks
+    workgroup b visits (n_partials workgroups, grid-stride)."""
+    x = _bf16_rows(mem, x_ptr, rows, c, ld_x, f'{name}.x')
+    dev = x.device
+    scale = mem.typed(scale_ptr, torch.float32, 1, f'{name}.scale')[0].clone()
+    q = e4m3_bytes(x, scale * scale_mul)
+    pm = _block_max(x.abs(), rows, c, 16, n_partials).to(F64)
+    mem.find(y_ptr, rows * c, f'{name}.y')
+    lr = LaunchRef('QUANT_FP8_DELAYED')
+    lr.outs.append(Out(f'{name}.y', y_ptr, torch.uint8, torch.arange(rows * c, device=dev).view(rows, c), q, q, 0.0, exact=True))
+    lr.outs.append(Out(f'{name}.partials', partials, torch.float32, torch.arange(n_partials, device=dev), pm, pm, 0.0, exact=True))
+    return lr
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
 # dispatch over one dsl_op
 def op_ref(mem, op, multis=None, name=None):
     """LaunchRef of one dsl_op (ctypes), or None for kinds without a reference.  multis: {table_host pointer: ops.WgradMulti}."""
@@ -687,6 +1114,20 @@ def op_ref(mem, op, multis=None, name=None):
         return pack_image_ref(mem, op.p[0], op.p[1], *op.i[:3], name=nm)
     if k == OP_STEM_POOL:
         return stem_pool_ref(mem, op.p[0], op.p[1], op.l[0], op.l[1], op.p[2], op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], name=nm)
+    if k == OP_ASSIGN:
+        return assign_ref(mem, C.cast(op.desc, C.POINTER(L.FcosDesc)).contents, nm)
+    if k == OP_LOSS:
+        return loss_ref(mem, C.cast(op.desc, C.POINTER(L.FcosDesc)).contents, nm)
+    if k == OP_QUANT_FP8:
+        return quant_fp8_ref(mem, op.p[0], op.p[1], op.l[0], op.i[0], op.i[1], op.l[1], op.p[2] or 0, op.i[2], name=nm)
+    if k == OP_QUANT_FP8_W:
+        return quant_fp8_w_ref(mem, op.p[0], op.p[1], op.p[2], op.p[3] or 0, op.i[0], op.i[1], op.i[2], op.l[1], name=nm)
+    if k == OP_FP8_COMB:
+        return fp8_comb_ref(mem, op.p[0], op.p[1], op.i[0], op.p[2], op.i[2], name=nm)
+    if k == OP_FP8_PREP:
+        return fp8_prep_ref(mem, op.p[0], op.i[0], op.i[1], op.i[2], op.l[1], name=nm)
+    if k == OP_QUANT_FP8_DELAYED:
+        return quant_fp8_delayed_ref(mem, op.p[0], op.p[1], op.p[2], op.p[3], op.l[0], op.i[0], op.i[1], op.i[2], name=nm)
     return None
 
 

@@ -162,3 +162,84 @@ def test_points_and_deterministic_sums():
     for a, b in zip(*runs):
         assert torch.equal(a, b)
     assert float(runs[0][1][0]) > 0 and float(runs[0][1][2:].abs().sum()) == 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# edge cases against the float64 launch references of tests/op_ref.py (assignment bit-exact, loss within its bar)
+EDGE_SIZES = [(25, 42), (13, 21), (7, 11), (4, 6), (2, 3)]
+
+
+@pytest.mark.parametrize('case', ['ties_zero_relu', 'no_gt_out_of_range', 'ignore_over_positives', 'C1_nan_pad', 'C3_nan_pad_sisoft',
+                                  'grad_scale'])
+def test_loss_edges_vs_fp64_reference(case):
+    import op_ref as R
+    from dsl_amd.head_loss import FcosLossPlan
+    from oracle import fcos_oracle as O
+    C = {'C1_nan_pad': 1, 'C3_nan_pad_sisoft': 3}.get(case, 80)
+    B = 3 if case == 'C3_nan_pad_sisoft' else 4
+    rng = np.random.RandomState(11)
+    g = torch.Generator().manual_seed(11)
+    gtb, gtl = [], []
+    for i in range(B):
+        b = O.synth_boxes(rng, 6, H=200, W=336, lo=8, hi=150)
+        if case == 'no_gt_out_of_range' and i == 1:
+            b = b[:0]
+        if case == 'no_gt_out_of_range' and i == 2:
+            b = np.array([[100.0, 100.0, 100.5, 100.5]], 'float32')      # in no centre region, no range
+        gtb.append(T(b))
+        gtl.append(T(rng.randint(0, C, len(b)).astype('int64')))
+    # ignore boxes: every gt box again (over its positives, which keep weight 1) and two more (over background)
+    ig = [torch.cat([b, T(O.synth_boxes(rng, 2, H=200, W=336, lo=16, hi=100))]) for b in gtb] if case == 'ignore_over_positives' else None
+    plan = FcosLossPlan(B, EDGE_SIZES, 'cuda', num_classes=C)
+    plan.set_targets(gtb, gtl, ig)
+    plan.configure(loss_weight=3.0 if case != 'grad_scale' else 1.0, soft_weight=1.0 if case == 'C3_nan_pad_sisoft' else 0.0,
+                   grad_scale=0.375 if case == 'grad_scale' else 1.0)
+    M = plan.M
+    cls = torch.full((M, plan.LD_CLS), float('nan'))
+    cls[:, :C] = torch.randn(M, C, generator=g) * 2 - 2
+    rc = torch.zeros(M, 8)
+    rc[:, :4] = torch.randn(M, 4, generator=g) * 3 + 2
+    rc[:, 4] = torch.randn(M, generator=g)
+    cls_d, rc_d = cls.cuda(), rc.cuda()
+    sc = torch.tensor([1.0, 0.5, 2.0, 1.0, 0.25], device='cuda')
+    plan.bind_outputs(cls_d, rc_d, sc)
+    mem = R.Memory({'plan': plan, 'in': [cls_d, rc_d, sc]})
+
+    def run(fn):
+        def go():
+            fn()
+            torch.cuda.synchronize()
+        return go
+    torch.cuda.synchronize()
+    la = R.assign_ref(mem, plan.desc)
+    res = R.run_checked(mem, la, run(plan.assign))
+    labels = plan.labels.cpu()
+    pos = (labels < C).nonzero().view(-1)
+    assert pos.numel() > 8
+    lvl, img = R._fcos_locations(plan.desc)[:2]
+    if case == 'ties_zero_relu':
+        # the first positives regress exactly their targets (power-of-two scales: raw x scale == target in fp32); the next ones have
+        # raw == 0 in one coordinate (relu(0) passes no gradient)
+        tg = plan.bbox_targets.cpu()
+        rc_d[pos[:6].cuda(), :4] = (tg[pos[:6]] / sc.cpu()[lvl[pos[:6]]].view(-1, 1)).cuda()
+        rc_d[pos[6:10].cuda(), 2] = 0.0
+        assert torch.equal((rc_d[pos[:6].cuda(), :4] * sc[lvl[pos[:6]].cuda()].view(-1, 1)).cpu(), tg[pos[:6]])
+    if case == 'no_gt_out_of_range':
+        assert not bool((labels[(img == 1) | (img == 2)] < C).any())
+        assert not plan.bbox_targets.cpu()[img == 1].any()
+    if case == 'ignore_over_positives':
+        w = plan.cls_weight.cpu()
+        assert bool((w[pos] > 0).all()) and bool((w == 0).any())
+    torch.cuda.synchronize()
+    ll = R.loss_ref(mem, plan.desc)
+    res += R.run_checked(mem, ll, run(plan.loss))
+    bad = [r for r in res if r[2]]
+    assert not bad, (case, bad)
+    # negative controls (references of the same operands): flagged under the launch's own bar
+    flagged = lambda k, ref: R.compare(ll.outs[k].got(mem), ref.outs[k].ref, ll.outs[k].bound())[1] > 0
+    if case == 'ties_zero_relu':
+        assert flagged(1, R.loss_ref(mem, plan.desc, relu_mask=False))
+    if case == 'C3_nan_pad_sisoft':
+        assert flagged(0, R.loss_ref(mem, plan.desc, partner_level=0))
+    assert torch.isfinite(plan.losses).all() and torch.isfinite(plan.g_cls.float()).all()
+    print(case, ' '.join(f'{n.split(".")[-1]} {r:.3f}' for n, r, _, _ in res if not n.startswith('assign')))

@@ -462,3 +462,293 @@ def test_resolver_reports_stray_pointers_and_overruns():
     d.ldd, d.src = 64, d.src + (1 << 30)
     with pytest.raises(R.PointerError, match=r'conv\.src: pointer'):
         R.conv_ref(mem2, d)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# DSL_OP_ASSIGN / DSL_OP_LOSS against the oracle (fp32 assignment, fp64 autograd of oracle.fcos_loss)
+FCOS_SIZES = [(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)]
+FCOS_RANGES = ((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8))
+
+
+CTR_TOL = torch.tensor([1e-9] * 4 + [2.0 ** -20] + [1e-9] * 3, dtype=F64)
+
+
+def fcos_case(B=3, C=80, ig=True, loss_weight=3.0, soft_weight=1.0, grad_scale=0.5, world=8, seed=0, empty=(), out_of_range=()):
+    """A small FCOS batch whose box corners are exact in fp32 (quarter-pixel gt boxes, raw / 64 regressions, power-of-two scales):
+    the kernel's fp32 corners equal the oracle's float64 ones, so the references can be held to float64 agreement.
+    empty: images without gt; out_of_range: images whose only gt lies outside every regression range's reach."""
+    import numpy as np
+    from oracle import fcos_oracle as O
+    rng = np.random.RandomState(seed)
+    g = torch.Generator().manual_seed(seed)
+    H, W = 128, 192
+    gtb, gtl, igb = [], [], []
+    for i in range(B):
+        if i in empty:
+            b = np.zeros((0, 4), 'float32')
+        elif i in out_of_range:
+            b = np.array([[60.0, 60.0, 61.0, 61.0]], 'float32')          # 1 x 1: inside no centre region of any level's points
+        else:
+            b = np.round(O.synth_boxes(rng, 5, H=H, W=W, lo=8, hi=150) * 4) / 4
+        gtb.append(torch.from_numpy(b.astype('float32')))
+        gtl.append(torch.from_numpy(rng.randint(0, C, len(b)).astype('int64')))
+        igb.append(torch.from_numpy((np.round(O.synth_boxes(rng, 2, H=H, W=W, lo=16, hi=100) * 4) / 4).astype('float32')))
+    cls = [(torch.randn(B, C, h, w, generator=g, dtype=F64) - 2).float().double() for h, w in FCOS_SIZES]
+    raw = [(torch.randint(-128, 640, (B, 4, h, w), generator=g) / 64.0).double() for h, w in FCOS_SIZES]
+    ctr = [torch.randn(B, 1, h, w, generator=g, dtype=F64).float().double() for h, w in FCOS_SIZES]
+    scales = torch.tensor([1.0, 0.5, 2.0, 1.0, 0.25], dtype=F64)
+    return dict(B=B, C=C, gtb=gtb, gtl=gtl, igb=igb if ig else None, cls=cls, raw=raw, ctr=ctr, scales=scales, loss_weight=loss_weight,
+                soft_weight=soft_weight, grad_scale=grad_scale, world=world)
+
+
+def flat_lv(ts):
+    return torch.cat([t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]) for t in ts])
+
+
+def fcos_buffers(case, pad_nan=False):
+    """The launch's buffers (CPU) and a dsl_fcos_desc namespace over them, as FcosLossPlan lays them out."""
+    B, C = case['B'], case['C']
+    M = B * sum(h * w for h, w in FCOS_SIZES)
+    ld_cls, ld_gcls = (C + 3) // 4 * 4, (C + 63) // 64 * 64
+    logits = torch.zeros(M, ld_cls)
+    if pad_nan:
+        logits[:, C:] = float('nan')
+    logits[:, :C] = flat_lv(case['cls']).float()
+    rc = torch.zeros(M, 8)
+    rc[:, :4] = flat_lv(case['raw']).float()
+    rc[:, 4] = flat_lv(case['ctr'])[:, 0].float()
+    cat = lambda ts: torch.cat(ts) if ts else torch.zeros(0, 4)
+    off = lambda ts: torch.tensor([0] + [int(sum(t.shape[0] for t in ts[:i + 1])) for i in range(len(ts))], dtype=torch.int32)
+    b = dict(logits=logits, rc=rc, scales=case['scales'].float(), gt_boxes=cat(case['gtb']).reshape(-1, 4).contiguous() + 0,
+             gt_labels=torch.cat(case['gtl']), gt_off=off(case['gtb']),
+             labels=torch.full((M,), -7, dtype=torch.int64), bbox_targets=torch.full((M, 4), -7.0), assign_idx=torch.full((M,), -7, dtype=torch.int32),
+             cls_weight=torch.full((M,), -7.0), pos_weight=torch.full((M,), -7.0), stats=torch.full((8,), -7.0), norm=torch.zeros(2),
+             g_cls=torch.full((M, ld_gcls), 3.0, dtype=torch.bfloat16), g_rc=torch.full((M, 64), 3.0, dtype=torch.bfloat16),
+             g_scales=torch.full((8,), 3.0), losses=torch.full((4,), 3.0), logvec=torch.full((5,), 3.0), ws=torch.zeros(4096))
+    if case['igb'] is not None:
+        b['ig_boxes'], b['ig_off'] = cat(case['igb']).reshape(-1, 4).contiguous() + 0, off(case['igb'])
+    if b['gt_boxes'].numel() == 0:
+        b['gt_boxes'], b['gt_labels'] = torch.zeros(1, 4), torch.zeros(1, dtype=torch.int64)
+    p = lambda k: b[k].data_ptr() if k in b else 0
+    d = types.SimpleNamespace(nlvl=5, n=B, h=[h for h, _ in FCOS_SIZES], w=[w for _, w in FCOS_SIZES], stride=[8, 16, 32, 64, 128],
+                              range_lo=[r[0] for r in FCOS_RANGES], range_hi=[r[1] for r in FCOS_RANGES], radius=1.5, num_classes=C,
+                              gt_boxes=p('gt_boxes'), gt_labels=p('gt_labels'), gt_off=p('gt_off'), ig_boxes=p('ig_boxes'), ig_off=p('ig_off'),
+                              labels=p('labels'), bbox_targets=p('bbox_targets'), assign_idx=p('assign_idx'), cls_weight=p('cls_weight'),
+                              pos_weight=p('pos_weight'), stats=p('stats'), loss_weight=case['loss_weight'], cls_logits=p('logits'),
+                              regctr=p('rc'), ld_cls=ld_cls, ld_rc=8, scales=p('scales'), norm=p('norm'), g_cls=p('g_cls'), ld_gcls=ld_gcls,
+                              g_rc=p('g_rc'), ld_grc=64, g_scales=p('g_scales'), losses=p('losses'), soft_weight=case['soft_weight'],
+                              grad_scale=case['grad_scale'], inv_world=1.0 / case['world'], workspace=p('ws'), workspace_bytes=4 * 4096,
+                              logvec=p('logvec'))
+    return b, d, R.Memory({'b': b})
+
+
+def fill_outs(outs):
+    """Writes each Out's reference, rounded to its dtype, into its buffer (a correctly rounding launch)."""
+    def go(mem):
+        for o in outs:
+            n = int(o.idx.max()) + 1
+            v = o.ref.to(torch.float32).to(o.dtype) if o.dtype in (torch.bfloat16, torch.float32) else o.ref.to(o.dtype)
+            mem.typed(o.ptr, o.dtype, n, o.name).view(-1)[o.idx.reshape(-1)] = v.reshape(-1)
+    return go
+
+
+def oracle_loss(case):
+    """fp64 autograd of oracle.fcos_loss through Scale + ReLU; num_pos / denorm go through fp32 as the norm buffer holds them."""
+    from oracle import fcos_oracle as O
+    cls = [c.clone().requires_grad_() for c in case['cls']]
+    raw = [r.clone().requires_grad_() for r in case['raw']]
+    ctr = [c.clone().requires_grad_() for c in case['ctr']]
+    sc = case['scales'].clone().requires_grad_()
+    reg = [torch.relu(r * sc[i]) for i, r in enumerate(raw)]
+    out, aux = O.fcos_loss(cls, reg, ctr, case['gtb'], case['gtl'], case['igb'], loss_weight=case['loss_weight'],
+                           soft_weight=case['soft_weight'], num_classes=case['C'], world_mean=lambda t: t.float().double(), return_aux=True)
+    (sum(out.values()) * case['grad_scale']).backward()
+    return out, aux, cls, raw, ctr, sc
+
+
+def run_fcos_refs(case, norm=None, **kw):
+    """norm: the (num_pos, centerness sum) one rank contributes (default: the assignment's stats); norm[] holds `world` times it."""
+    b, d, mem = fcos_buffers(case, **kw)
+    la = R.assign_ref(mem, d)
+    res = R.run_checked(mem, la, lambda: fill_outs(la.outs)(mem))
+    b['norm'][:] = (b['stats'][:2] if norm is None else torch.tensor(norm, dtype=torch.float32)) * case['world']
+    ll = R.loss_ref(mem, d)
+
+    def launch():
+        fill_outs(ll.outs)(mem)
+        lo, n = b['losses'], 4 if case['soft_weight'] else 3
+        b['logvec'][:n] = lo[:n]
+        b['logvec'][n] = ((lo[0] + lo[1]) + lo[2]) + (lo[3] if n == 4 else 0.0)
+    res += R.run_checked(mem, ll, launch)
+    return b, d, mem, la, ll, res
+
+
+def _close(o, ref, tol=1e-9):
+    """o.ref == ref to float64 rounding (tol may be a tensor broadcast over o.ref: the oracle's centerness BCE takes the dtype of
+    its fp32 target and runs in fp32)."""
+    bound = tol * (o.S.abs() + o.ref.abs()) + 1e-300
+    ratio, nbad, worst = R.compare(o.ref, ref.to(F64).reshape(o.ref.shape), bound)
+    assert nbad == 0, (o.name, ratio, worst, float(o.ref.reshape(-1)[worst]), float(ref.reshape(-1)[worst]))
+
+
+@pytest.mark.parametrize('C,ig,lw,soft,gs,world', [(80, True, 3.0, 1.0, 0.5, 8), (3, False, 1.0, 1.0, 1.0, 1), (1, True, 2.0, 0.0, 2.0, 8)])
+def test_assign_and_loss_refs_match_oracle_autograd(C, ig, lw, soft, gs, world):
+    case = fcos_case(C=C, ig=ig, loss_weight=lw, soft_weight=soft, grad_scale=gs, world=world, empty=(1,) if C == 3 else ())
+    out, aux, cls, raw, ctr, sc = oracle_loss(case)
+    # (the oracle's centerness sum is an fp32 torch sum: the loss reads the norm[] it is given, whatever order made it)
+    b, d, mem, la, ll, res = run_fcos_refs(case, norm=[aux['num_pos'], aux['ctr_denorm']], pad_nan=C % 4 != 0)
+    assert all(r[2] == 0 for r in res), res
+    assert float(b['stats'][1]) == pytest.approx(float(aux['ctr_targets'].double().sum()), rel=2 ** -20)
+    o = {x.name.split('.')[-1]: x for x in la.outs + ll.outs}
+    # assignment: bit for bit at every location (background rows: gt 0's ltrb / stride, zeros for an image without gt)
+    assert torch.equal(b['labels'], aux['labels'])
+    assert torch.equal(b['assign_idx'].long(), aux['assign_idx'])
+    assert torch.equal(b['bbox_targets'], aux['bbox_targets'])
+    assert torch.equal(b['cls_weight'], aux['cls_weight'].float())
+    assert float(b['stats'][0]) == len(aux['pos_inds']) > 0 and not b['stats'][2:].any()
+    if ig:
+        assert bool((b['cls_weight'] == 0).any())
+    # the stream weight: loss_weight on images >= n / 2 (the unlabeled stream), 1 elsewhere
+    img = R._fcos_locations(d)[1]
+    want_pw = torch.where(img >= case['B'] // 2, torch.tensor(lw), torch.tensor(1.0))
+    assert torch.equal(b['pos_weight'], want_pw)
+    ig_zero = torch.zeros_like(b['cls_weight'], dtype=torch.bool) if aux['cls_weight'] is None else aux['cls_weight'] == 0
+    assert torch.equal(b['cls_weight'], torch.where(ig_zero, torch.tensor(0.0), want_pw))
+    # loss: float64 agreement with autograd
+    _close(o['g_cls'], torch.cat([flat_lv([c.grad for c in cls]), torch.zeros(b['g_cls'].shape[0], b['g_cls'].shape[1] - C, dtype=F64)], 1))
+    g_rc = torch.zeros(b['g_rc'].shape[0], 8, dtype=F64)
+    g_rc[:, :4], g_rc[:, 4] = flat_lv([r.grad for r in raw]), flat_lv([c.grad for c in ctr])[:, 0]
+    _close(o['g_rc'], g_rc, CTR_TOL)
+    _close(o['g_scales'], sc.grad)
+    want = [out['loss_cls'], out['loss_bbox'], out['loss_centerness'], out.get('loss_sisoft', torch.zeros((), dtype=F64))]
+    _close(o['losses'], torch.stack([w.detach().double().reshape(()) for w in want]), torch.tensor([1e-9, 1e-9, 2.0 ** -20, 1e-9]))
+    assert ('loss_sisoft' in out) == (soft != 0.0)
+    # logvec: the fp32 recombination of the written losses
+    lv = b['logvec']
+    n = 4 if soft else 3
+    assert torch.equal(lv[:n], b['losses'][:n]) and float(lv[n]) == float(((b['losses'][0] + b['losses'][1]) + b['losses'][2]) +
+                                                                        (b['losses'][3] if soft else 0.0))
+
+
+def test_loss_ref_edges_ties_zero_relu_no_gt():
+    """predicted box == target (GIoU max / min ties split 0.5 / 0.5, as torch), raw x scale == 0 exactly (ReLU passes nothing), an
+    image without gt and one whose gt is out of every range."""
+    case = fcos_case(B=4, C=3, soft_weight=0.0, empty=(2,), out_of_range=(3,))
+    b, d, mem = fcos_buffers(case)
+    la = R.assign_ref(mem, d)
+    fill_outs(la.outs)(mem)
+    pos = (b['labels'] < 3).nonzero().view(-1)
+    assert pos.numel() > 4 and not bool((b['labels'][pos] < 0).any())
+    lvl = R._fcos_locations(d)[0]
+    # ties: the first positives regress exactly their targets; the next ones have raw == 0 in one coordinate
+    sc = case['scales'][lvl[pos[:4]]].view(-1, 1)
+    exact = (b['bbox_targets'][pos[:4]].double() / sc)
+    for j, r_ in enumerate(exact):
+        m = int(pos[j])
+        b['rc'][m, :4] = r_.float()
+    b['rc'][pos[4:8], 1] = 0.0
+    # mirror into the case tensors for the oracle
+    M = b['rc'].shape[0]
+    o_ = 0
+    for l, (h, w) in enumerate(FCOS_SIZES):
+        n_ = case['B'] * h * w
+        case['raw'][l] = b['rc'][o_:o_ + n_, :4].double().view(case['B'], h, w, 4).permute(0, 3, 1, 2).contiguous()
+        o_ += n_
+    assert o_ == M
+    assert torch.equal((b['rc'][pos[:4], :4] * b['scales'][lvl[pos[:4]]].view(-1, 1)), b['bbox_targets'][pos[:4]])
+    out, aux, cls, raw, ctr, scg = oracle_loss(case)
+    b['norm'][:] = torch.tensor([aux['num_pos'], aux['ctr_denorm']], dtype=torch.float32) * case['world']
+    ll = R.loss_ref(mem, d)
+    g_rc = torch.zeros(M, 8, dtype=F64)
+    g_rc[:, :4], g_rc[:, 4] = flat_lv([r.grad for r in raw]), flat_lv([c.grad for c in ctr])[:, 0]
+    _close(ll.outs[1], g_rc, CTR_TOL)
+    _close(ll.outs[2], scg.grad)
+    assert not bool(ll.outs[1].ref[pos[4:8], 1].any())
+    # images 2 (no gt) and 3 (gt out of range): background everywhere, zero box gradient
+    assert not bool(((R._fcos_locations(d)[1] >= 2) & (b['labels'] < 3)).any())
+
+
+def test_negative_controls_assign_loss():
+    case = fcos_case(C=80)
+    b, d, mem, la, ll, res = run_fcos_refs(case)
+    got = lambda o: o.got(mem)
+    # ASSIGN with radius 1.0
+    bad = R.assign_ref(mem, d, radius=1.0)
+    assert R.compare(got(la.outs[0]), bad.outs[0].ref, la.outs[0].bound())[1] > 0
+    # LOSS: sisoft partner from level lvl instead of lvl - 1
+    bad = R.loss_ref(mem, d, partner_level=0)
+    assert R.compare(got(ll.outs[0]), bad.outs[0].ref, ll.outs[0].bound())[1] > 0
+    # LOSS: ReLU mask dropped from g_rc
+    bad = R.loss_ref(mem, d, relu_mask=False)
+    assert R.compare(got(ll.outs[1]), bad.outs[1].ref, ll.outs[1].bound())[1] > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# fp8 quantisers against torch's e4m3 cast
+def test_fp8_refs_match_torch_cast():
+    rows, c, ld = 300, 48, 64
+    x = (torch.randn(rows, ld) * 3).bfloat16()
+    x[5, 7] = 200.0                                       # saturates at scale 4
+    y = torch.zeros(rows * c, dtype=torch.uint8)
+    part = torch.full((7,), -1.0)
+    scale = torch.tensor([4.0])
+    mem = mem_of(x=x, y=y, part=part, scale=scale)
+    lr = R.quant_fp8_delayed_ref(mem, x.data_ptr(), y.data_ptr(), part.data_ptr(), scale.data_ptr(), rows, c, ld, 7)
+    want = (x[:, :c].float() * 4.0).clamp(-448, 448).to(torch.float8_e4m3fn)
+    assert torch.equal(lr.outs[0].ref.to(torch.uint8).view(rows, c), want.view(torch.uint8))
+    assert int(lr.outs[0].ref.view(rows, c)[5, 7]) == 0x7e                # +448
+    chunks = x[:, :c].float().abs().reshape(-1, 16).amax(1)
+    pm = torch.tensor([chunks[[j for j in range(chunks.numel()) if (j // 256) % 7 == b]].max() if b < (chunks.numel() + 255) // 256 else 0.0
+                       for b in range(7)])
+    assert torch.equal(lr.outs[1].ref.float(), pm) and float(pm.max()) == float(x[:, :c].float().abs().max())
+    # scale doubled: flagged
+    bad = R.quant_fp8_delayed_ref(mem, x.data_ptr(), y.data_ptr(), part.data_ptr(), scale.data_ptr(), rows, c, ld, 7, scale_mul=2.0)
+    R.run_checked(mem, lr, lambda: fill_outs(lr.outs)(mem))
+    assert R.compare(lr.outs[0].got(mem), bad.outs[0].ref, lr.outs[0].bound())[1] > 0
+    # fixed-scale and dynamic quantisers
+    s_bits = int(torch.tensor([0.75]).view(torch.int32)[0])
+    lr = R.quant_fp8_ref(mem, x.data_ptr(), y.data_ptr(), rows, c, ld, s_bits)
+    assert torch.equal(lr.outs[0].ref.to(torch.uint8).view(rows, c), (x[:, :c].float() * 0.75).to(torch.float8_e4m3fn).view(torch.uint8))
+    lr = R.quant_fp8_ref(mem, x.data_ptr(), y.data_ptr(), rows, c, ld, 0, part.data_ptr(), 7)
+    s = (448.0 / x[:, :c].double().abs().max()).float()             # correctly rounded quotient (the kernel's IEEE divide)
+    assert torch.equal(lr.outs[0].ref.to(torch.uint8).view(rows, c), (x[:, :c].float() * s).to(torch.float8_e4m3fn).view(torch.uint8))
+
+
+def test_fp8_weight_refs_prep_and_cold_scale():
+    cout, cout_pad, k = 5, 8, 36
+    w = torch.randn(cout, k)
+    w[3] = 0.0                                                  # a zero row: s = 1
+    w8 = torch.full((cout_pad * k,), 9, dtype=torch.uint8)
+    comb = torch.full((cout_pad,), 9.0)
+    bn = torch.rand(cout) + 0.5
+    amax_rec = torch.tensor([0.5, 3.0, 2.0])
+    amax_cold = torch.zeros(3)
+    scale = torch.full((2,), -1.0)
+    comb2, w82 = torch.full((cout_pad,), 9.0), torch.full((cout_pad * k,), 9, dtype=torch.uint8)
+    items = (R.Fp8PrepItem * 2)()
+    for j, (am, cb, q) in enumerate(((amax_rec, comb, w8), (amax_cold, comb2, w82))):
+        items[j].w, items[j].w8, items[j].comb, items[j].amax = w.data_ptr(), q.data_ptr(), cb.data_ptr(), am.data_ptr()
+        items[j].scale, items[j].n_amax, items[j].cout = scale.data_ptr() + 4 * j, 3, cout
+    table = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8)
+    mem = mem_of(w=w, w8=w8, comb=comb, bn=bn, a=amax_rec, z=amax_cold, scale=scale, c2=comb2, w82=w82, table=table)
+    mbits = int(torch.tensor([1.25]).view(torch.int32)[0])
+    lr = R.fp8_prep_ref(mem, table.data_ptr(), 2, cout_pad, k, mbits)
+    o = {x.name: x for x in lr.outs}
+    a = torch.tensor(3.0) * 1.25
+    sw = (448.0 / w.double().abs().amax(1)).float()                  # correctly rounded quotients (the kernel's IEEE divide)
+    sw[3] = 1.0
+    assert float(o['fp8_prep[0].scale'].ref[0]) == float((448.0 / a.double()).float())
+    assert float(o['fp8_prep[1].scale'].ref[0]) == 1.0 and lr.extra['cold'] == 1          # nothing recorded yet
+    assert torch.equal(o['fp8_prep[0].comb'].ref[:cout].float(), (a / 448.0) / sw) and not o['fp8_prep[0].comb'].ref[cout:].any()
+    assert torch.equal(o['fp8_prep[1].comb'].ref[:cout].float(), 1.0 / sw)
+    q = o['fp8_prep[0].w8'].ref.to(torch.uint8)
+    assert torch.equal(q[:cout], (w * sw.view(-1, 1)).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8))
+    assert not q[cout:].any() and not q[3].any()
+    lr = R.quant_fp8_w_ref(mem, w.data_ptr(), w8.data_ptr(), comb.data_ptr(), bn.data_ptr(), cout, cout_pad, k,
+                           int(torch.tensor([0.5]).view(torch.int32)[0]))
+    assert torch.equal(lr.outs[1].ref[:cout].float(), 0.5 / sw * bn)
+    assert lr.outs[0].exact and lr.outs[1].exact
+    lr = R.fp8_comb_ref(mem, bn.data_ptr(), comb.data_ptr(), cout, amax_rec.data_ptr(), 3)
+    assert torch.equal(lr.outs[0].ref.float(), bn * (torch.tensor(3.0) / 448.0))
+    lr = R.fp8_comb_ref(mem, bn.data_ptr(), comb.data_ptr(), cout, amax_cold.data_ptr(), 3)
+    assert torch.equal(lr.outs[0].ref.float(), bn)
