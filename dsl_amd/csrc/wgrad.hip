@@ -27,6 +27,28 @@ __device__ __forceinline__ void wait_vmcnt() {
 // ================================================================================================
 // weight gradient
 // ================================================================================================
+// THE tile table: one row per tile configuration (1 = 256x256, 2 = 256co x 128ci, 3 = 128co x 256ci, 4 = 128x128) and kernel
+// generation (the DMA-to-LDS kernel wgrad_glds serves 1-4, the pipelined kernel wgrad_pipe 1-3).  BCO x BCI outputs per workgroup
+// of WCO x WCI waves, an NST-deep LDS ring of KS-pixel stages.  Host geometry, LDS sizes, divisibility checks and the planner's
+// stage length read these rows; wgrad_dispatch instantiates the kernels from them.
+struct WgTile {
+  int bco, bci, wco, wci, ks, nst;
+  bool pipe;
+};
+constexpr WgTile kWgTiles[] = {
+    {256, 256, 2, 4, 64, 2, false}, {256, 128, 4, 2, 64, 3, false}, {128, 256, 2, 4, 64, 3, false}, {128, 128, 2, 2, 64, 2, false},
+    {256, 256, 2, 4, 32, 4, true},  {256, 128, 4, 2, 32, 5, true},  {128, 256, 2, 4, 32, 5, true},
+};
+constexpr int kWgDescRing = 16;      // pipelined kernel: depth (stages) of the LDS ring of pixel descriptors behind the stage ring
+constexpr bool wgrad_cfg_ok(int cfg, bool pipe) { return cfg >= 1 && cfg <= (pipe ? 3 : 4); }
+constexpr int wgrad_row(int cfg, bool pipe) { return (pipe ? 4 : 0) + cfg - 1; }
+constexpr const WgTile& wgrad_tile(int cfg, bool pipe) { return kWgTiles[wgrad_row(cfg, pipe)]; }
+// dynamic LDS of one workgroup: the stage ring (dY tile + X tile per stage, bf16) and, pipelined, the descriptor ring (8 bytes per pixel)
+constexpr size_t wgrad_lds_bytes(int bco, int bci, int ks, int nst, bool pipe) {
+  return (size_t)nst * ks * 2 * (bco + bci) + (pipe ? (size_t)kWgDescRing * ks * 8 : 0);
+}
+constexpr size_t wgrad_lds_bytes(const WgTile& t) { return wgrad_lds_bytes(t.bco, t.bci, t.ks, t.nst, t.pipe); }
+
 struct WgK {
   int nseg, n;
   int gh[DSL_MAX_SEG], gw[DSL_MAX_SEG], sh[DSL_MAX_SEG], sw[DSL_MAX_SEG];
@@ -63,170 +85,6 @@ struct WgK {
   unsigned pixtab_bytes;
   unsigned ybytes;          // extent of one member's dY in bytes (= totpx * cy * 2): rows past it read as zeros
 };
-
-template <int ROWBYTES>
-__device__ __forceinline__ int tr_swz(int row) {
-  return ROWBYTES == 256 ? (row & 3) : ((row >> 1) & 1);
-}
-
-// BCO couts x 128 cins per workgroup, 64 pixels per K stage; both operands are stored
-// [pixel][channel] in LDS and read with ds_read_b64_tr_b16 (hardware transpose) into MFMA fragments.
-template <int BCO>
-__global__ __launch_bounds__(256) void wgrad_kernel(const WgK p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int YB = BCO * 2;             // bytes per pixel row of the dY tile
-  constexpr int XB = 256;                 // 128 cin * 2
-  constexpr int TILE_Y = 64 * YB, TILE_X = 64 * XB, STAGE = TILE_Y + TILE_X;
-  constexpr int WM = BCO / 2, CT = WM / 32;
-  constexpr int YCPR = BCO / 8;           // 16-byte chunks per dY row
-  constexpr int YRPP = 256 / YCPR;        // rows per pass
-  constexpr int YPASS = 64 / YRPP;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wave_co = wave >> 1, wave_ci = wave & 1;
-  const int co0 = blockIdx.x * BCO;
-  const int colt = blockIdx.y;
-  const int tap = colt / p.ctiles_per_tap;
-  const int ci0 = (colt - tap * p.ctiles_per_tap) * 128;
-  const int tr = tap / p.kw, ts = tap - tr * p.kw;
-  const int sp = blockIdx.z;
-  const int kt0 = sp * p.tiles_per_split;
-  const int kt1 = min(kt0 + p.tiles_per_split, p.ktiles);
-  const int totpx = p.pxstart[p.nseg];
-
-  const int yrow = tid / YCPR, ychunk = tid % YCPR;
-  const int xrow = tid >> 4, xchunk = tid & 15;
-  u32x4 ry[YPASS], rx[4];
-
-  auto gload = [&](int kt) {
-#pragma unroll
-    for (int i = 0; i < YPASS; ++i) {
-      const int gp = kt * 64 + yrow + YRPP * i;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (gp < totpx) v = *reinterpret_cast<const u32x4*>(p.dy + (long long)gp * p.cy + co0 + ychunk * 8);
-      ry[i] = v;
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int gp = kt * 64 + xrow + 16 * i;
-      u32x4 v = {0u, 0u, 0u, 0u};
-      if (gp < totpx) {
-        int seg = 0;
-#pragma unroll
-        for (int s = 1; s < DSL_MAX_SEG; ++s)
-          if (s < p.nseg && gp >= p.pxstart[s]) seg = s;
-        const uint32_t q = gp - p.pxstart[seg];
-        const uint32_t img = fdiv(q, p.dhw[seg]);
-        const uint32_t rem = q - img * p.dhw[seg].d;
-        const uint32_t y = fdiv(rem, p.dwd[seg]);
-        const uint32_t x = rem - y * p.dwd[seg].d;
-        const int sy = (int)y * p.stride + tr - p.pad, sx = (int)x * p.stride + ts - p.pad;
-        if ((unsigned)sy < (unsigned)p.sh[seg] && (unsigned)sx < (unsigned)p.sw[seg]) {
-          const long long pix = p.xoff[seg] + ((long long)img * p.sh[seg] + sy) * p.sw[seg] + sx;
-          v = *reinterpret_cast<const u32x4*>(p.x + pix * p.ldx + ci0 + xchunk * 8);
-        }
-      }
-      rx[i] = v;
-    }
-  };
-  auto lds_store = [&](int buf) {
-    unsigned char* base = smem + buf * STAGE;
-#pragma unroll
-    for (int i = 0; i < YPASS; ++i) {
-      const int row = yrow + YRPP * i;
-      *reinterpret_cast<u32x4*>(base + row * YB + ((((ychunk >> 2) ^ tr_swz<YB>(row))) << 6) + ((ychunk & 3) << 4)) = ry[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = xrow + 16 * i;
-      *reinterpret_cast<u32x4*>(base + TILE_Y + row * XB + ((((xchunk >> 2) ^ tr_swz<XB>(row))) << 6) + ((xchunk & 3) << 4)) = rx[i];
-    }
-  };
-
-  f32x16 acc[CT][2];
-#pragma unroll
-  for (int a = 0; a < CT; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) acc[a][b][j] = 0.f;
-
-  // transpose-read geometry: 16-lane group g covers channel block (g&1)*16 and pixel block (g>>1)*8
-  const int g16 = lane >> 4, l16 = lane & 15;
-  const int iblk = (g16 & 1) * 16, kblk = (g16 >> 1) * 8;
-  const int krow_l = kblk + (l16 >> 2);           // + kk*16 + hh*4
-  const int ccol_l = iblk + 4 * (l16 & 3);        // channel (element) offset inside a 32-wide tile
-
-  auto tr_read = [&](const unsigned char* tile, int rowbytes_sel, int krow, int col) -> s16x4 {
-    int byte;
-    if (rowbytes_sel == 256)
-      byte = krow * 256 + ((((col * 2) >> 6) ^ tr_swz<256>(krow)) << 6) + ((col * 2) & 63);
-    else
-      byte = krow * 128 + ((((col * 2) >> 6) ^ tr_swz<128>(krow)) << 6) + ((col * 2) & 63);
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (__attribute__((address_space(3))) s16x4*)(tile + byte));
-  };
-
-  auto compute = [&](int buf) {
-    const unsigned char* base = smem + buf * STAGE;
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      bf16x8 a[CT], b[2];
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct) {
-        const int col = wave_co * WM + ct * 32 + ccol_l;
-        const s16x4 lo = tr_read(base, YB, kk * 16 + krow_l, col);
-        const s16x4 hi = tr_read(base, YB, kk * 16 + krow_l + 4, col);
-        union { struct { s16x4 l, h; } s; bf16x8 v; } u;
-        u.s.l = lo;
-        u.s.h = hi;
-        a[ct] = u.v;
-      }
-#pragma unroll
-      for (int pt = 0; pt < 2; ++pt) {
-        const int col = wave_ci * 64 + pt * 32 + ccol_l;
-        const s16x4 lo = tr_read(base + TILE_Y, XB, kk * 16 + krow_l, col);
-        const s16x4 hi = tr_read(base + TILE_Y, XB, kk * 16 + krow_l + 4, col);
-        union { struct { s16x4 l, h; } s; bf16x8 v; } u;
-        u.s.l = lo;
-        u.s.h = hi;
-        b[pt] = u.v;
-      }
-#pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int pt = 0; pt < 2; ++pt)
-          acc[ct][pt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ct], b[pt], acc[ct][pt], 0, 0, 0);
-    }
-  };
-
-  if (kt0 < kt1) {
-    gload(kt0);
-    lds_store(0);
-    __syncthreads();
-    for (int kt = kt0; kt < kt1; ++kt) {
-      const int cur = (kt - kt0) & 1;
-      if (kt + 1 < kt1) gload(kt + 1);
-      compute(cur);
-      if (kt + 1 < kt1) lds_store(cur ^ 1);
-      __syncthreads();
-    }
-  }
-
-  // partial tile -> workspace [split][cy][krow]
-  const int frow = lane & 31, fhalf = lane >> 5;
-#pragma unroll
-  for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-    for (int pt = 0; pt < 2; ++pt) {
-      const long long col = (long long)tap * p.cs + ci0 + wave_ci * 64 + pt * 32 + frow;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int co = co0 + wave_co * WM + ct * 32 + (j & 3) + 8 * (j >> 2) + 4 * fhalf;
-        p.ws[((long long)sp * p.cy + co) * p.krow + col] = acc[ct][pt][j];
-      }
-    }
-}
 
 // inline-asm helpers must be explicit __device__ functions: a lambda inside a kernel is implicitly
 // __host__ __device__, and its AMDGPU asm constraints break the (silently dropped) host instantiation
@@ -294,7 +152,6 @@ __device__ __forceinline__ void wait_frags(Frag (&fa)[CT], Frag (&fb)[IT]) {
 
 // v2 weight gradient: DMA-to-LDS operands, 256-wide tiles, 8 waves, NST-deep ring of KS-pixel stages with
 // counted vmcnt waits (the pixel streams come from HBM: one stage of lookahead does not cover the latency).
-// Same math/outputs as wgrad_kernel.
 struct SegSel {          // per-segment decode constants, selected with v_cndmask chains (no memory access:
   int px0;               // indexing kernel-argument arrays or LDS tables by a runtime segment id makes hipcc
   uint32_t m1lo, m1hi, d1, m2lo, m2hi, d2;   // drain the DMA queue with s_waitcnt vmcnt(0) inside the K loop)
@@ -335,6 +192,7 @@ __device__ __forceinline__ void wgrad_glds_body(const WgK& p, const int bid, uns
   static_assert(YB >= 256 && XB >= 256, "64-byte-chunk swizzle needs >= 4 chunks per row");
   static_assert(KK == 2 || KK == 4, "stage depth");
   static_assert((NST - 2) * LPT <= 63 && NST >= 2 && NST <= 4, "vmcnt range");
+  static_assert(wgrad_lds_bytes(BCO, BCI, KS, NST, false) == (size_t)NST * STAGE, "the host sizes the launch's LDS with wgrad_lds_bytes");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -669,7 +527,7 @@ __device__ __forceinline__ void wgrad_pipe_body(const WgK& p, const int bid, uns
   constexpr int P = NDSC + LY + LX;                              // DMA instructions per wave per stage
   constexpr int CT = BCO / WCO / 32, IT = BCI / WCI / 32, NM = CT * IT;
   constexpr int KK = KS / 16;
-  constexpr int DR = 16;                                         // descriptor ring depth (stages)
+  constexpr int DR = kWgDescRing;                                // descriptor ring depth (stages)
   constexpr int DESC_BASE = NST * STAGE;
   constexpr int DLEAD = 2 * NST - 2;                             // descriptors run this many stages ahead of the stage computed
   static_assert(NY % NW == 0 && NX % NW == 0 && LY >= 1 && LX >= 1, "tile / wave mismatch");
@@ -677,6 +535,7 @@ __device__ __forceinline__ void wgrad_pipe_body(const WgK& p, const int bid, uns
   static_assert(KK == 2 || KK == 4, "stage depth");
   static_assert(NST >= 3 && DLEAD < DR && NDSC >= 1, "ring depths");
   static_assert((NST - 1) * P + DLEAD * NDSC <= 63, "vmcnt range");
+  static_assert(wgrad_lds_bytes(BCO, BCI, KS, NST, true) == (size_t)DESC_BASE + DR * KS * 8, "the host sizes the launch's LDS with wgrad_lds_bytes");
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1039,53 +898,40 @@ struct WgMultiHdr {
   int nsub;
   int wg_end[kMaxMulti];
 };
+// THE sub-launch lookup: declares `sub`, the sub-launch that owns virtual block vb, and `start`, its first block.  A macro, not a
+// __forceinline__ function: every function form that was tried (header by reference, by value, by fields; results by reference or
+// as a struct) makes hipcc allocate the scalar registers of the pipelined multi kernels differently, K loop included; expanded in
+// place, their code is instruction for instruction what the hand-written copies of this chain gave.
+#define WG_MULTI_SUB(h, vb)                                    \
+  int sub = 0, start = 0;                                      \
+  _Pragma("unroll") for (int s = 1; s < kMaxMulti; ++s) {      \
+    const bool in = s < (h).nsub && (vb) >= (h).wg_end[s - 1]; \
+    sub = in ? s : sub;                                        \
+    start = in ? (h).wg_end[s - 1] : start;                    \
+  }
+
 template <int BCO, int BCI, int WCO, int WCI, int KS, int NST>
 __global__ __launch_bounds__(64 * WCO * WCI) void wgrad_glds_multi_kernel(const WgMultiHdr h, const WgK* __restrict__ tab) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int sub = 0, start = 0;
-#pragma unroll
-  for (int s = 1; s < kMaxMulti; ++s) {
-    const bool in = s < h.nsub && (int)blockIdx.x >= h.wg_end[s - 1];
-    sub = in ? s : sub;
-    start = in ? h.wg_end[s - 1] : start;
-  }
+  WG_MULTI_SUB(h, (int)blockIdx.x)
   const WgK p = tab[sub];
   wgrad_glds_body<BCO, BCI, WCO, WCI, KS, NST>(p, (int)blockIdx.x - start, smem);
 }
 
+// stride form of the pipelined multi launch: the grid's workgroups (a multiple of 8, at most the launch's workgroup budget) walk
+// the `total` blocks; with one workgroup per block it is the plain launch
 template <int BCO, int BCI, int WCO, int WCI, int KS, int NST>
-__global__ __launch_bounds__(64 * WCO * WCI) void wgrad_pipe_multi_kernel(const WgMultiHdr h, const WgK* __restrict__ tab) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  int sub = 0, start = 0;
-#pragma unroll
-  for (int s = 1; s < kMaxMulti; ++s) {
-    const bool in = s < h.nsub && (int)blockIdx.x >= h.wg_end[s - 1];
-    sub = in ? s : sub;
-    start = in ? h.wg_end[s - 1] : start;
-  }
-  const WgK p = tab[sub];
-  wgrad_pipe_body<BCO, BCI, WCO, WCI, KS, NST>(p, (int)blockIdx.x - start, smem);
-}
-
-// persistent form of the multi launch: `grid` (a multiple of 8) workgroups walk the block list
-template <int BCO, int BCI, int WCO, int WCI, int KS, int NST>
-__global__ __launch_bounds__(64 * WCO * WCI) void wgrad_pipe_multi_persist_kernel(const WgMultiHdr h, const WgK* __restrict__ tab, int total) {
+__global__ __launch_bounds__(64 * WCO * WCI) void wgrad_pipe_multi_kernel(const WgMultiHdr h, const WgK* __restrict__ tab, int total) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   for (int vb = (int)blockIdx.x; vb < total; vb += (int)gridDim.x) {
-    int sub = 0, start = 0;
-#pragma unroll
-    for (int s = 1; s < kMaxMulti; ++s) {
-      const bool in = s < h.nsub && vb >= h.wg_end[s - 1];
-      sub = in ? s : sub;
-      start = in ? h.wg_end[s - 1] : start;
-    }
+    WG_MULTI_SUB(h, vb)
     const WgK p = tab[sub];
     wgrad_pipe_body<BCO, BCI, WCO, WCI, KS, NST>(p, vb - start, smem);
     __syncthreads();
   }
 }
 
-// scheduled form (round 4, wgrad_plan_*): the host assigns every valid virtual block to a workgroup (longest-processing-time
+// scheduled form (wgrad_plan): the host assigns every valid virtual block to a workgroup (longest-processing-time
 // first inside the block's XCD class), sched[r * gridDim.x + b] = the r-th block of workgroup b or -1; what a workgroup computes
 // for a block, and hence every result, is the same as in the stride form
 template <int BCO, int BCI, int WCO, int WCI, int KS, int NST>
@@ -1095,18 +941,14 @@ __global__ __launch_bounds__(64 * WCO * WCI) void wgrad_pipe_multi_sched_kernel(
   for (int r = 0; r < rounds; ++r) {
     const int vb = __builtin_amdgcn_readfirstlane((int)sched[r * (int)gridDim.x + (int)blockIdx.x]);
     if (vb < 0) break;
-    int sub = 0, start = 0;
-#pragma unroll
-    for (int s = 1; s < kMaxMulti; ++s) {
-      const bool in = s < h.nsub && vb >= h.wg_end[s - 1];
-      sub = in ? s : sub;
-      start = in ? h.wg_end[s - 1] : start;
-    }
+    WG_MULTI_SUB(h, vb)
     const WgK p = tab[sub];
     wgrad_pipe_body<BCO, BCI, WCO, WCI, KS, NST>(p, vb - start, smem);
     __syncthreads();
   }
 }
+
+#undef WG_MULTI_SUB
 
 // the reduce passes of a multi launch: entry e (one member of one sub-launch with more than one split) owns the blocks
 // [blk_start, blk_start + nblk)
@@ -1154,8 +996,8 @@ __global__ void wgrad_reduce_multi_kernel(const RedEnt* __restrict__ tab, int n)
 struct RedK {
   float* dw[DSL_MAX_GROUP];
   const float* scale[DSL_MAX_GROUP];
-  float* db[DSL_MAX_GROUP];        // bias-gradient vectors: summed from dbws, or cleared for the column-sum kernel that follows (or NULL)
-  const float* dbws;               // [split][member][cy] column-sum partials of the DMA kernels (NULL: v1 kernel)
+  float* db[DSL_MAX_GROUP];        // bias-gradient vectors, summed from dbws (or NULL)
+  const float* dbws;               // [split][member][cy] column-sum partials of the weight-gradient kernels
 };
 
 // sums the split partials ws[split][member][cy][krow] of member blockIdx.y into its dW (x scale)
@@ -1176,7 +1018,7 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, const RedK r, 
     if (db)
       for (int c = threadIdx.x; c < cd; c += blockDim.x) {
         float sacc = 0.f;
-        if (r.dbws)                 // in-kernel column sums: fold the splits in order; else cleared for the column-sum pass
+        if (r.dbws)                 // in-kernel column sums: fold the splits in order
           for (int sp = 0; sp < splits; ++sp) sacc += r.dbws[((long long)sp * group + member) * cy + c];
         db[c] = sacc;
       }
@@ -1206,11 +1048,10 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ ws, const RedK r, 
 
 }  // namespace
 
-// ---- v3 weight gradient: per-geometry pixel descriptor tables (PixDesc).  The table lives in CALLER-OWNED device memory
+// ---- pipelined weight gradient: per-geometry pixel descriptor tables (PixDesc).  The table lives in CALLER-OWNED device memory
 // (dsl_wgrad_desc.pixtab, >= dsl_wgrad_pixtab_bytes): dsl_wgrad_pixtab_fill writes it with a kernel on the caller's stream, once per
-// geometry; the library allocates nothing and copies nothing (until round 6 it kept a process-lifetime hipMalloc'd cache here)
+// geometry; the library allocates nothing and copies nothing
 namespace {
-constexpr int kWgV3KS = 32, kWgV3DR = 16;
 struct PixGeo {
   int nseg, n, stride, pad, kh, kw;
   int gh[DSL_MAX_SEG], gw[DSL_MAX_SEG], sh[DSL_MAX_SEG], sw[DSL_MAX_SEG];
@@ -1239,25 +1080,24 @@ __global__ void pixtab_fill_kernel(PixDesc* __restrict__ out, PixGeo g) {
   out[i] = e;
 }
 
-int wgrad_slots();
-bool wgrad_persist() {
-  // measured (tools/exp_env.sh, bench.py N = 2): persistent grids of 128 workgroups +2.3 % (96 .. 160 within 0.3 %, 64: -1 %)
-  return true;
+int wgrad_slots() {
+  const int v = dsl_option("wgrad_slots");
+  return v > 0 ? v : 128;
 }
-bool wgrad_v3_enabled() {
-  return true;
+long long wgrad_px(const dsl_wgrad_desc* d) {      // dY pixels = the K extent of the weight gradient
+  long long px = 0;
+  for (int s = 0; s < d->nseg; ++s) px += (long long)d->n * d->gh[s] * d->gw[s];
+  return px;
 }
-// ring depth of the v3 kernel per tile configuration (1: 256x256 -> 4 x 32 KB; 2, 3: 24 KB stages)
-int wgrad_v3_nst(int cfg) { return cfg == 1 ? 4 : 5; }
+// whether the pipelined kernel serves this geometry in tile configuration cfg (else: the DMA-to-LDS kernel)
 bool wgrad_v3_ok(const dsl_wgrad_desc* d, int cfg) {
-  if (!wgrad_v3_enabled() || cfg < 1 || cfg > 3 || d->kh > 8 || d->kw > 8) return false;
-  long long px = 0, xo = 0;
+  if (!wgrad_cfg_ok(cfg, true) || d->kh > 8 || d->kw > 8) return false;
+  long long xo = 0;
   for (int s = 0; s < d->nseg; ++s) {
-    px += (long long)d->n * d->gh[s] * d->gw[s];
     xo += (long long)d->n * d->sh[s] * d->sw[s];
     if (d->sw[s] >= 65536) return false;
   }
-  const long long ldx = d->ldx > 0 ? d->ldx : d->cs;
+  const long long px = wgrad_px(d), ldx = d->ldx > 0 ? d->ldx : d->cs;
   return px * d->cy * 2 < 0x7fff0000LL && xo * ldx * 2 < 0x7fff0000LL && px < (1 << 20);
 }
 int wgrad_v3_fill(const dsl_wgrad_desc* d, WgK& k, long long px) {
@@ -1270,68 +1110,88 @@ int wgrad_v3_fill(const dsl_wgrad_desc* d, WgK& k, long long px) {
   k.ybytes = (unsigned)(px * d->cy * 2);
   return 0;
 }
-size_t wgrad_v3_lds(int cfg) {
-  const int bcos[5] = {0, 256, 256, 128, 128}, bcis[5] = {0, 256, 128, 256, 128};
-  return (size_t)wgrad_v3_nst(cfg) * kWgV3KS * 2 * (bcos[cfg] + bcis[cfg]) + (size_t)kWgV3DR * kWgV3KS * 8;
+
+// Calls f(std::integral_constant<int, row>) for the kWgTiles row of (cfg, pipelined): the caller instantiates its kernel from the
+// row that its LDS size and grid come from.  False: no such row.
+template <class F>
+bool wgrad_dispatch(int cfg, bool pipe, F&& f) {
+  if (!wgrad_cfg_ok(cfg, pipe)) return false;
+  switch (wgrad_row(cfg, pipe)) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    default: f(std::integral_constant<int, 6>{}); break;
+  }
+  return true;
+}
+static_assert(sizeof(kWgTiles) / sizeof(kWgTiles[0]) == 7, "wgrad_dispatch lists every row");
+#define WG_TILE_ARGS(T) T.bco, T.bci, T.wco, T.wci, T.ks, T.nst
+// launches a kernel of tile T; its first launch raises the kernel's dynamic-LDS limit to the tile's size
+template <auto KERNEL, class... Args>
+void wgrad_run(const WgTile& T, dim3 grid, hipStream_t st, const Args&... args) {
+  const size_t lds = wgrad_lds_bytes(T);
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(64 * T.wco * T.wci), lds, st, args...);
 }
 }  // namespace
 
-// wgrad tile configurations: 0 = v1 (BCO 128|64 x 128, register staged), 1 = 256x256, 2 = 256co x 128ci,
-// 3 = 128co x 256ci, 4 = 128x128 (v2)
+// tile configuration of a geometry: the largest tile (kWgTiles) that divides its channels; cy = 64 (mod 128) takes a 128-cout
+// tile whose upper half reads zeros
 static int wgrad_pick(const dsl_wgrad_desc* d) {
   const int force = d->splits < 0 ? -d->splits : 0;       // test hook: splits = -(cfg+1) forces a config
   if (force) return force - 1;
-  if (d->cy % 128) return d->cs % 256 == 0 ? 3 : 4;      // cy = 64 (mod 128): the 128-cout tiles, upper half reads zeros
+  if (d->cy % 128) return d->cs % 256 == 0 ? 3 : 4;
   if (d->cy % 256 == 0 && d->cs % 256 == 0) return 1;
   if (d->cy % 256 == 0) return 2;
   if (d->cs % 256 == 0) return 3;
   return 4;
 }
+// K tiles (in stages of the DMA-to-LDS kernel, the unit of the split rules), output tiles per member and cout tile of d's
+// configuration; all 0 for a forced configuration that does not exist (the launch refuses it)
 static int wgrad_geometry(const dsl_wgrad_desc* d, int* ktiles, int* tiles, int* bco) {
-  long long px = 0;
-  for (int s = 0; s < d->nseg; ++s) px += (long long)d->n * d->gh[s] * d->gw[s];
-  *ktiles = (int)((px + 63) / 64);
   const int cfg = wgrad_pick(d);
-  const int bcos[5] = {(d->cy % 128 == 0) ? 128 : 64, 256, 256, 128, 128};
-  const int bcis[5] = {128, 256, 128, 256, 128};
-  *bco = bcos[cfg];
-  *tiles = ((d->cy + *bco - 1) / *bco) * (d->kh * d->kw * d->cs / bcis[cfg]);
+  *ktiles = *tiles = *bco = 0;
+  if (!wgrad_cfg_ok(cfg, false)) return cfg;
+  const WgTile& t = wgrad_tile(cfg, false);       // (a configuration's tile is the same in both kernel generations)
+  *ktiles = (int)((wgrad_px(d) + t.ks - 1) / t.ks);
+  *bco = t.bco;
+  *tiles = ((d->cy + t.bco - 1) / t.bco) * (d->kh * d->kw * d->cs / t.bci);
   return cfg;
 }
 
 static int wgrad_splits_for(const dsl_wgrad_desc* d, int count) {
   int ktiles, tiles, bco;
   const int cfg = wgrad_geometry(d, &ktiles, &tiles, &bco);
+  if (tiles == 0) return 0;
   tiles *= count;
   const int max_by_k = ktiles / 4 > 0 ? ktiles / 4 : 1;    // at least 4 K stages per split
-  int splits;
-  if (cfg == 0) {
-    splits = (768 + tiles - 1) / tiles;                    // v1: 2-3 small workgroups per CU
-  } else {
-    const int per_cu = cfg == 4 ? 2 : 1;                   // 128x128 tiles: two workgroups per CU
-    // one full round, never a nearly-empty second one.  (Accumulating the split partials with XCD-local L2 float
-    // atomics instead of writing them out was measured: 117 vs 85 us on the head shape - L2 atomics retire about
-    // two lanes per clock per channel.)
-    // option wgrad_slots < 256 leaves CUs free: the weight gradients run on the side stream under the caller's chain of
-    // small convolutions, and a full round of 128 KB-LDS workgroups that live for 100-250 us would leave those
-    // kernels only the handful of CUs the round did not cover
-    // (measured, bench.py N = 2: 256 -> 305, 224 -> 306, 192 -> 309, 160 -> 313, 128 -> 310 img/s)
-    const int slots = d->slots > 0 ? d->slots : wgrad_slots();
-    splits = slots * per_cu / tiles;
-  }
+  const int per_cu = cfg == 4 ? 2 : 1;                     // 128x128 tiles: two workgroups per CU
+  // one full round, never a nearly-empty second one.  (Accumulating the split partials with XCD-local L2 float
+  // atomics instead of writing them out was measured: 117 vs 85 us on the head shape - L2 atomics retire about
+  // two lanes per clock per channel.)
+  // option wgrad_slots < 256 leaves CUs free: the weight gradients run on the side stream under the caller's chain of
+  // small convolutions, and a full round of 128 KB-LDS workgroups that live for 100-250 us would leave those
+  // kernels only the handful of CUs the round did not cover
+  // (measured, bench.py N = 2: 256 -> 305, 224 -> 306, 192 -> 309, 160 -> 313, 128 -> 310 img/s)
+  const int slots = d->slots > 0 ? d->slots : wgrad_slots();
+  int splits = slots * per_cu / tiles;
   if (splits > max_by_k) splits = max_by_k;
   if (splits < 1) splits = 1;
   if (splits > 256) splits = 256;
   {
-    // No EMPTY split (round 4): split i covers stages [i * tps, (i + 1) * tps), tps = ceil(stages / splits); with 9 or more splits
+    // No EMPTY split: split i covers stages [i * tps, (i + 1) * tps), tps = ceil(stages / splits); with 9 or more splits
     // and few stages the last ones start past the end - (splits - 1) * tps >= stages, e.g. 129 stages in 16 splits of 9 - their
-    // workgroups return without writing their partial tile and the reduce pass adds whatever the scratch buffer held.  The comment
-    // "cannot happen with the host's split factors" in the kernels was wrong for this corner; the planner of the multi launches
-    // normalises the same way (plan_norm_splits).
-    long long px = 0;
-    for (int s = 0; s < d->nseg; ++s) px += (long long)d->n * d->gh[s] * d->gw[s];
-    const int ks = wgrad_v3_ok(d, cfg) ? kWgV3KS : 64;
-    const int stages = (int)((px + ks - 1) / ks);
+    // workgroups return without writing their partial tile and the reduce pass adds whatever the scratch buffer held.  The
+    // planner of the multi launches normalises the same way (plan_norm_splits).
+    const int ks = wgrad_tile(cfg, wgrad_v3_ok(d, cfg)).ks;
+    const int stages = (int)((wgrad_px(d) + ks - 1) / ks);
     const int tps = (stages + splits - 1) / splits;
     splits = (stages + tps - 1) / tps;
   }
@@ -1345,9 +1205,7 @@ extern "C" int dsl_wgrad_splits(const dsl_wgrad_desc* d) { return wgrad_splits_f
 extern "C" size_t dsl_wgrad_pixtab_bytes(const dsl_wgrad_desc* d) {
   if (d == nullptr || d->nseg < 1 || d->nseg > DSL_MAX_SEG) return 0;
   if (!wgrad_v3_ok(d, wgrad_pick(d))) return 0;
-  long long px = 0;
-  for (int s = 0; s < d->nseg; ++s) px += (long long)d->n * d->gh[s] * d->gw[s];
-  return (size_t)px * sizeof(PixDesc);
+  return (size_t)wgrad_px(d) * sizeof(PixDesc);
 }
 extern "C" int dsl_wgrad_pixtab_fill(const dsl_wgrad_desc* d, void* table, size_t bytes, void* stream) {
   DSL_CHECK(d != nullptr && d->nseg >= 1 && d->nseg <= DSL_MAX_SEG, "dsl_wgrad_pixtab_fill: bad descriptor");
@@ -1375,7 +1233,7 @@ extern "C" int dsl_wgrad_pixtab_fill(const dsl_wgrad_desc* d, void* table, size_
 static size_t wgrad_cy_pad(const dsl_wgrad_desc* d) {       // rows of one partial tile set in the workspace
   int ktiles, tiles, bco;
   wgrad_geometry(d, &ktiles, &tiles, &bco);
-  return (size_t)(d->cy + bco - 1) / bco * bco;
+  return bco ? (size_t)(d->cy + bco - 1) / bco * bco : 0;
 }
 
 extern "C" size_t dsl_wgrad_workspace_bytes(const dsl_wgrad_desc* d) {
@@ -1389,9 +1247,6 @@ extern "C" size_t dsl_wgrad_group_workspace_bytes(const dsl_wgrad_desc* descs, i
   return (size_t)wgrad_splits_for(descs, count) * count * wgrad_cy_pad(descs) * ((size_t)descs->kh * descs->kw * descs->cs + 1) * sizeof(float);
 }
 
-extern "C" int dsl_colsum(const void* x, float* out, long rows, int c, int ld, void* stream);
-int dsl_colsum_acc(const void* x, float* out, long rows, int c, int ld, void* stream);   // no memset: out += column sums
-
 static bool wgrad_same_geometry(const dsl_wgrad_desc* a, const dsl_wgrad_desc* b) {
   if (a->ldx != b->ldx || a->shared != b->shared) return false;
   if (a->nseg != b->nseg || a->n != b->n || a->cs != b->cs || a->cy != b->cy || a->cd != b->cd || a->kh != b->kh ||
@@ -1402,196 +1257,9 @@ static bool wgrad_same_geometry(const dsl_wgrad_desc* a, const dsl_wgrad_desc* b
   return true;
 }
 
-// `count` convolutions of one geometry as one launch (count == 1: the plain weight gradient)
-static int wgrad_launch(const dsl_wgrad_desc* descs, int count, void* stream) {
-  const dsl_wgrad_desc* d = descs;
-  DSL_CHECK(d != nullptr && count >= 1 && count <= DSL_MAX_GROUP, "dsl_conv2d_wgrad: bad group (count=%d)", count);
-  DSL_CHECK(d->nseg >= 1 && d->nseg <= DSL_MAX_SEG, "dsl_conv2d_wgrad: nseg=%d", d->nseg);
-  DSL_CHECK(d->cs % 128 == 0, "dsl_conv2d_wgrad: Cin=%d must be a multiple of 128", d->cs);
-  DSL_CHECK(d->cy % 64 == 0 && d->cd <= d->cy, "dsl_conv2d_wgrad: bad cy=%d cd=%d", d->cy, d->cd);
-  for (int g = 0; g < count; ++g) {
-    DSL_CHECK(descs[g].dy && descs[g].x && descs[g].dw, "dsl_conv2d_wgrad: null pointer (member %d)", g);
-    DSL_CHECK(wgrad_same_geometry(d, &descs[g]), "dsl_conv2d_wgrad_group: member %d has a different geometry", g);
-  }
-  DSL_CHECK(d->workspace, "dsl_conv2d_wgrad: null workspace");
-  int ktiles, tiles, bco;
-  const int cfg = wgrad_geometry(d, &ktiles, &tiles, &bco);
-  if (cfg == 0 && count > 1) {          // the register-staged kernel has no group form: run the members one by one
-    for (int g = 0; g < count; ++g) {
-      dsl_wgrad_desc t = descs[g];
-      t.workspace = d->workspace;
-      t.workspace_bytes = d->workspace_bytes;
-      t.splits = 0;
-      const int rc = wgrad_launch(&t, 1, stream);
-      if (rc) return rc;
-    }
-    return 0;
-  }
-  const int splits = count == 1 ? (d->splits > 0 ? d->splits : dsl_wgrad_splits(d)) : wgrad_splits_for(d, count);
-  const int cyp = (int)wgrad_cy_pad(d);
-  const size_t need = (size_t)splits * count * cyp * ((size_t)d->kh * d->kw * d->cs + 1) * sizeof(float);
-  DSL_CHECK(d->workspace_bytes >= need, "dsl_conv2d_wgrad: workspace too small (%zu < %zu)", d->workspace_bytes, need);
-  WgK k;
-  memset(&k, 0, sizeof(k));
-  k.nseg = d->nseg; k.n = d->n;
-  int px = 0;
-  long long xo = 0;
-  for (int s = 0; s < d->nseg; ++s) {
-    k.gh[s] = d->gh[s]; k.gw[s] = d->gw[s]; k.sh[s] = d->sh[s]; k.sw[s] = d->sw[s];
-    k.pxstart[s] = px;
-    k.xoff[s] = xo;
-    k.dhw[s] = make_fastdiv((uint32_t)(d->gh[s] * d->gw[s]));
-    k.dwd[s] = make_fastdiv((uint32_t)d->gw[s]);
-    px += d->n * d->gh[s] * d->gw[s];
-    xo += (long long)d->n * d->sh[s] * d->sw[s];
-  }
-  DSL_CHECK(px < (1 << 20), "dsl_conv2d_wgrad: %d pixels exceed the 2^20 fast-division range", px);
-  const int ldx = d->ldx > 0 ? d->ldx : d->cs;
-  DSL_CHECK(ldx >= d->cs && ldx % 8 == 0, "dsl_conv2d_wgrad: ldx=%d must be >= cs=%d and a multiple of 8", ldx, d->cs);
-  DSL_CHECK(xo * ldx < (1LL << 31), "dsl_conv2d_wgrad: X has more than 2^31 elements");
-  k.pxstart[d->nseg] = px;
-  k.totpx = px;
-  k.cs = d->cs; k.cy = d->cy; k.kh = d->kh; k.kw = d->kw; k.stride = d->stride; k.pad = d->pad;
-  k.ktiles = ktiles;
-  k.tiles_per_split = (ktiles + splits - 1) / splits;
-  k.ctiles_per_tap = d->cs / 128;
-  k.krow = (long long)d->kh * d->kw * d->cs;
-  k.dy = (const uint16_t*)d->dy; k.x = (const uint16_t*)d->x; k.ws = (float*)d->workspace;
-  k.group = count;
-  k.ldx = ldx;
-  k.cyp = cyp;
-  for (int g = 0; g < DSL_MAX_GROUP; ++g) {
-    k.dyv[g] = (const uint16_t*)descs[g < count ? g : 0].dy;
-    k.xv[g] = (const uint16_t*)descs[g < count ? g : 0].x;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  // weight gradient: dY and X read once, dW written once (fp32)
-  const int prof = dsl_prof_active()
-                       ? dsl_prof_begin(3, 2.0 * count * px * (double)d->cd * d->kh * d->kw * d->cs, st,
-                                        count * ((double)px * d->cd * 2.0 + (double)xo * d->cs * 2.0 + (double)d->cd * d->kh * d->kw * d->cs * 4.0))
-                       : -1;
-  if (cfg >= 1) {
-    const int bcis[5] = {128, 256, 128, 256, 128};
-    const int bci = bcis[cfg];
-    DSL_CHECK(cyp % bco == 0 && d->cs % bci == 0, "dsl_conv2d_wgrad: tile config %d does not divide cy=%d / cs=%d", cfg, d->cy, d->cs);
-    k.gx = cyp / bco;
-    k.gy = d->kh * d->kw * d->cs / bci;
-    k.splits = splits;
-    k.dbws = (float*)d->workspace + (size_t)splits * count * cyp * k.krow;      // behind the dW partials
-    for (int g = 0; g < count; ++g)
-      if (descs[g].db) k.dbmask |= 1 << g;
-#ifdef DSL_ABLATE_BUILD
-    { const char* e = getenv("DSL_ABLATE"); k.dbg = e ? atoi(e) : 0; }
-#endif
-    k.chunk = (k.gx * k.gy * count * splits + 7) / 8;
-    dim3 grid2(k.chunk * 8);
-    const bool v3 = wgrad_v3_ok(d, cfg);
-    const int kss[5] = {64, 64, 64, 64, 64}, nsts[5] = {2, 2, 3, 3, 2};
-    const int ks = v3 ? kWgV3KS : kss[cfg];
-    // the stage length of this tile configuration defines the K-tile unit
-    k.ktiles = (px + ks - 1) / ks;
-    k.tiles_per_split = (k.ktiles + splits - 1) / splits;
-    if (v3)
-      if (int rc = wgrad_v3_fill(d, k, px)) return rc;
-    const size_t lds2 = v3 ? wgrad_v3_lds(cfg) : (size_t)nsts[cfg] * ks * 2 * (bco + bci);
-#define LAUNCHW(KERNEL, A, B, C_, D, KS_, S_)                                                                         \
-  do {                                                                                                               \
-    static bool a_ = false;                                                                                          \
-    if (!a_) {                                                                                                       \
-      hipFuncSetAttribute((const void*)KERNEL<A, B, C_, D, KS_, S_>,                                                 \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                    \
-      a_ = true;                                                                                                     \
-    }                                                                                                                \
-    hipLaunchKernelGGL((KERNEL<A, B, C_, D, KS_, S_>), grid2, dim3(64 * C_ * D), lds2, st, k);                        \
-  } while (0)
-    if (v3) {
-      if (wgrad_persist()) {
-        const int cap = ((d->slots > 0 ? d->slots : wgrad_slots()) + 7) / 8 * 8;
-        if ((int)grid2.x > cap) grid2.x = cap;
-      }
-      switch (cfg) {
-        case 1: LAUNCHW(wgrad_pipe_kernel, 256, 256, 2, 4, 32, 4); break;
-        case 2: LAUNCHW(wgrad_pipe_kernel, 256, 128, 4, 2, 32, 5); break;
-        default: LAUNCHW(wgrad_pipe_kernel, 128, 256, 2, 4, 32, 5); break;
-      }
-    } else {
-      switch (cfg) {
-        case 1: LAUNCHW(wgrad_glds_kernel, 256, 256, 2, 4, 64, 2); break;
-        case 2: LAUNCHW(wgrad_glds_kernel, 256, 128, 4, 2, 64, 3); break;
-        case 3: LAUNCHW(wgrad_glds_kernel, 128, 256, 2, 4, 64, 3); break;
-        default: LAUNCHW(wgrad_glds_kernel, 128, 128, 2, 2, 64, 2); break;
-      }
-    }
-#undef LAUNCHW
-  } else if (bco == 128) {
-    dim3 grid(d->cy / bco, d->kh * d->kw * d->cs / 128, splits);
-    const size_t lds = 2 * (size_t)(64 * bco * 2 + 64 * 256);
-    static bool a = false;
-    if (!a) { hipFuncSetAttribute((const void*)wgrad_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a = true; }
-    hipLaunchKernelGGL((wgrad_kernel<128>), grid, dim3(256), lds, st, k);
-  } else {
-    dim3 grid(d->cy / bco, d->kh * d->kw * d->cs / 128, splits);
-    const size_t lds = 2 * (size_t)(64 * bco * 2 + 64 * 256);
-    static bool a = false;
-    if (!a) { hipFuncSetAttribute((const void*)wgrad_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a = true; }
-    hipLaunchKernelGGL((wgrad_kernel<64>), grid, dim3(256), lds, st, k);
-  }
-  dsl_prof_end(prof, st);
-  DSL_LAUNCH_CHECK("wgrad_kernel");
-  const long long total4 = (long long)d->cd * k.krow / 4;
-  int rb = (int)((total4 + 255) / 256);
-  if (rb > 4096 / count) rb = 4096 / count;
-  RedK r;
-  for (int g = 0; g < DSL_MAX_GROUP; ++g) {
-    r.dw[g] = descs[g < count ? g : 0].dw;
-    r.scale[g] = descs[g < count ? g : 0].scale;
-    r.db[g] = g < count ? descs[g].db : nullptr;
-  }
-  r.dbws = cfg >= 1 ? k.dbws : nullptr;
-  if (d->shared && count > 1) {
-    // the members are applications of ONE convolution (weights shared along a recurrence): their partial tiles are just
-    // more splits of the same dW - [split][member] pairs are contiguous in the workspace
-    for (int g = 1; g < count; ++g)
-      DSL_CHECK(descs[g].dw == d->dw && descs[g].scale == d->scale && !descs[g].db, "dsl_conv2d_wgrad_group: shared members must share dw / scale and have no db");
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rb * count, 1), dim3(256), 0, st, (const float*)d->workspace, r, splits * count, 1,
-                       cyp, d->cd, k.krow);
-    DSL_LAUNCH_CHECK("wgrad_reduce_kernel");
-    return 0;
-  }
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rb, count), dim3(256), 0, st, (const float*)d->workspace, r, splits, count,
-                     cyp, d->cd, k.krow);
-  DSL_LAUNCH_CHECK("wgrad_reduce_kernel");
-  if (cfg == 0)              // register-staged kernel: separate column-sum pass (db was cleared by the reduce kernel above)
-    for (int g = 0; g < count; ++g)
-      if (descs[g].db) {
-        const int rc = dsl_colsum_acc(descs[g].dy, descs[g].db, (long)px, d->cd, d->cy, stream);
-        if (rc) return rc;
-      }
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// multi launch: the weight gradients of several geometries (one tile configuration) as ONE grid + ONE reduce grid
-// ------------------------------------------------------------------------------------------------
-namespace {
-constexpr int kMaxRed = 128, kMaxColsum = 64, kSchedMax = 8192;
-struct ColsumItem { const void* x; float* out; long long rows; int c, ld, clear; };
-struct WgMultiTable {
-  int magic, cfg, nsub, total_blocks;
-  WgMultiHdr hdr;
-  int n_red, red_blocks, n_colsum, v3;
-  double flops, bytes;
-  ColsumItem colsum[kMaxColsum];
-  WgK k[kMaxMulti];
-  RedEnt red[kMaxRed];
-  // scheduled persistent launch (wgrad_plan): sched_grid workgroups, sched_rounds blocks each at most; 0 rounds = stride form
-  int sched_grid, sched_rounds;
-  int plan_makespan, plan_items;      // (stages incl. the per-item overhead; valid blocks) - what dsl_wgrad_multi_info reports
-  short sched[kSchedMax];
-};
-constexpr int kMultiMagic = 0x574d5431;
-
-int wgrad_fill_k(const dsl_wgrad_desc* descs, int count, int splits, int cfg, bool v3, WgK& k, long long* px_out, long long* xo_out) {
+// THE kernel arguments of `count` same-geometry convolutions in tile configuration cfg (pipelined or not) with `splits` splits.
+// The caller adds what depends on its workspace layout: ws, dbws, direct.
+static int wgrad_fill_k(const dsl_wgrad_desc* descs, int count, int splits, int cfg, bool v3, WgK& k, long long* px_out, long long* xo_out) {
   const dsl_wgrad_desc* d = descs;
   memset(&k, 0, sizeof(k));
   k.nseg = d->nseg; k.n = d->n;
@@ -1629,14 +1297,13 @@ int wgrad_fill_k(const dsl_wgrad_desc* descs, int count, int splits, int cfg, bo
     if (g < count && m.db) k.dbmask |= 1 << g;
   }
   k.dy = k.dyv[0]; k.x = k.xv[0];
-  const int bcos[5] = {0, 256, 256, 128, 128}, bcis[5] = {0, 256, 128, 256, 128};
-  DSL_CHECK(k.cyp % bcos[cfg] == 0 && d->cs % bcis[cfg] == 0, "dsl_conv2d_wgrad: tile config %d does not divide cy=%d / cs=%d", cfg, d->cy, d->cs);
-  k.gx = k.cyp / bcos[cfg];
-  k.gy = d->kh * d->kw * d->cs / bcis[cfg];
+  const WgTile& t = wgrad_tile(cfg, v3);
+  DSL_CHECK(k.cyp % t.bco == 0 && d->cs % t.bci == 0, "dsl_conv2d_wgrad: tile config %d does not divide cy=%d / cs=%d", cfg, d->cy, d->cs);
+  k.gx = k.cyp / t.bco;
+  k.gy = d->kh * d->kw * d->cs / t.bci;
   k.splits = splits;
   k.chunk = (k.gx * k.gy * count * splits + 7) / 8;
-  const int ks = v3 ? kWgV3KS : 64;
-  k.ktiles = (px + ks - 1) / ks;
+  k.ktiles = (px + t.ks - 1) / t.ks;             // the stage length of the kernel defines the K-tile unit
   k.tiles_per_split = (k.ktiles + splits - 1) / splits;
   if (v3)
     if (int rc = wgrad_v3_fill(d, k, px)) return rc;
@@ -1645,10 +1312,97 @@ int wgrad_fill_k(const dsl_wgrad_desc* descs, int count, int splits, int cfg, bo
   return 0;
 }
 
-int wgrad_slots() {
-  const int v = dsl_option("wgrad_slots");
-  return v > 0 ? v : 128;
+// `count` convolutions of one geometry as one launch (count == 1: the plain weight gradient)
+static int wgrad_launch(const dsl_wgrad_desc* descs, int count, void* stream) {
+  const dsl_wgrad_desc* d = descs;
+  DSL_CHECK(d != nullptr && count >= 1 && count <= DSL_MAX_GROUP, "dsl_conv2d_wgrad: bad group (count=%d)", count);
+  DSL_CHECK(d->nseg >= 1 && d->nseg <= DSL_MAX_SEG, "dsl_conv2d_wgrad: nseg=%d", d->nseg);
+  DSL_CHECK(d->cs % 128 == 0, "dsl_conv2d_wgrad: Cin=%d must be a multiple of 128", d->cs);
+  DSL_CHECK(d->cy % 64 == 0 && d->cd <= d->cy, "dsl_conv2d_wgrad: bad cy=%d cd=%d", d->cy, d->cd);
+  for (int g = 0; g < count; ++g) {
+    DSL_CHECK(descs[g].dy && descs[g].x && descs[g].dw, "dsl_conv2d_wgrad: null pointer (member %d)", g);
+    DSL_CHECK(wgrad_same_geometry(d, &descs[g]), "dsl_conv2d_wgrad_group: member %d has a different geometry", g);
+  }
+  DSL_CHECK(d->workspace, "dsl_conv2d_wgrad: null workspace");
+  const int cfg = wgrad_pick(d);
+  DSL_CHECK(wgrad_cfg_ok(cfg, false), "dsl_conv2d_wgrad: there is no tile configuration %d (1 .. 4; the register-staged configuration 0 is gone)", cfg);
+  const int splits = count == 1 ? (d->splits > 0 ? d->splits : dsl_wgrad_splits(d)) : wgrad_splits_for(d, count);
+  const int cyp = (int)wgrad_cy_pad(d);
+  const size_t need = (size_t)splits * count * cyp * ((size_t)d->kh * d->kw * d->cs + 1) * sizeof(float);
+  DSL_CHECK(d->workspace_bytes >= need, "dsl_conv2d_wgrad: workspace too small (%zu < %zu)", d->workspace_bytes, need);
+  const bool v3 = wgrad_v3_ok(d, cfg);
+  WgK k;
+  long long px, xo;
+  if (int rc = wgrad_fill_k(descs, count, splits, cfg, v3, k, &px, &xo)) return rc;
+  k.ws = (float*)d->workspace;                   // [split][member][cyp][krow] partials: every launch of this path runs the reduce pass
+  k.dbws = k.ws + (size_t)splits * count * cyp * k.krow;      // behind the dW partials
+#ifdef DSL_ABLATE_BUILD
+  { const char* e = getenv("DSL_ABLATE"); k.dbg = e ? atoi(e) : 0; }
+#endif
+  hipStream_t st = (hipStream_t)stream;
+  // weight gradient: dY and X read once, dW written once (fp32)
+  const int prof = dsl_prof_active()
+                       ? dsl_prof_begin(3, 2.0 * count * px * (double)d->cd * d->kh * d->kw * d->cs, st,
+                                        count * ((double)px * d->cd * 2.0 + (double)xo * d->cs * 2.0 + (double)d->cd * d->kh * d->kw * d->cs * 4.0))
+                       : -1;
+  dim3 grid(k.chunk * 8);
+  if (v3) {
+    // persistent form: never more workgroups than the budget (measured, bench.py N = 2: grids of 128 workgroups +2.3 %; 96 .. 160
+    // within 0.3 %, 64: -1 %)
+    const int cap = ((d->slots > 0 ? d->slots : wgrad_slots()) + 7) / 8 * 8;
+    if ((int)grid.x > cap) grid.x = cap;
+  }
+  wgrad_dispatch(cfg, v3, [&](auto row) {
+    constexpr WgTile T = kWgTiles[decltype(row)::value];
+    if constexpr (T.pipe) wgrad_run<wgrad_pipe_kernel<WG_TILE_ARGS(T)>>(T, grid, st, k);
+    else wgrad_run<wgrad_glds_kernel<WG_TILE_ARGS(T)>>(T, grid, st, k);
+  });
+  dsl_prof_end(prof, st);
+  DSL_LAUNCH_CHECK(v3 ? "wgrad_pipe_kernel" : "wgrad_glds_kernel");
+  const long long total4 = (long long)d->cd * k.krow / 4;
+  int rb = (int)((total4 + 255) / 256);
+  if (rb > 4096 / count) rb = 4096 / count;
+  RedK r;
+  for (int g = 0; g < DSL_MAX_GROUP; ++g) {
+    r.dw[g] = descs[g < count ? g : 0].dw;
+    r.scale[g] = descs[g < count ? g : 0].scale;
+    r.db[g] = g < count ? descs[g].db : nullptr;
+  }
+  r.dbws = k.dbws;
+  if (d->shared && count > 1) {
+    // the members are applications of ONE convolution (weights shared along a recurrence): their partial tiles are just
+    // more splits of the same dW - [split][member] pairs are contiguous in the workspace
+    for (int g = 1; g < count; ++g)
+      DSL_CHECK(descs[g].dw == d->dw && descs[g].scale == d->scale && !descs[g].db, "dsl_conv2d_wgrad_group: shared members must share dw / scale and have no db");
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rb * count, 1), dim3(256), 0, st, (const float*)d->workspace, r, splits * count, 1,
+                       cyp, d->cd, k.krow);
+    DSL_LAUNCH_CHECK("wgrad_reduce_kernel");
+    return 0;
+  }
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rb, count), dim3(256), 0, st, (const float*)d->workspace, r, splits, count,
+                     cyp, d->cd, k.krow);
+  DSL_LAUNCH_CHECK("wgrad_reduce_kernel");
+  return 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// multi launch: the weight gradients of several geometries (one tile configuration) as ONE grid + ONE reduce grid
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kMaxRed = 128, kSchedMax = 8192;
+struct WgMultiTable {
+  int magic, cfg, nsub, total_blocks;
+  WgMultiHdr hdr;
+  int n_red, red_blocks, v3;
+  double flops, bytes;
+  WgK k[kMaxMulti];
+  RedEnt red[kMaxRed];
+  // scheduled persistent launch (wgrad_plan): sched_grid workgroups, sched_rounds blocks each at most; 0 rounds = stride form
+  int sched_grid, sched_rounds;
+  int plan_makespan, plan_items;      // (stages incl. the per-item overhead; valid blocks) - what dsl_wgrad_multi_info reports
+  short sched[kSchedMax];
+};
+constexpr int kMultiMagic = 0x574d5431;
 
 // ---- launch planner of the multi launches (round 4) ----------------------------------------------------------------------
 // A multi launch is a list of work items (one output tile x one K split) of very different lengths - the FPN's run from 3 to
@@ -1663,9 +1417,6 @@ int wgrad_slots() {
 // its assignment becomes the launch's schedule table.  Results do not depend on the schedule: an item computes the same tile
 // from the same stages whoever runs it, and the reduce pass folds the splits in split order.
 struct PlanSub { int stages, tiles, max_sp; long long tile_elems; };      // K stages of the kernel's unit, output tiles (all members), elements per tile set
-int wgrad_plan_mode() {
-  return 1;
-}
 inline int plan_norm_splits(int stages, int sp) {      // no empty split: sp -> ceil(stages / ceil(stages / sp))
   if (sp < 1) sp = 1;
   const int tps = (stages + sp - 1) / sp;
@@ -1727,10 +1478,9 @@ long long plan_simulate(const PlanSub* subs, const int* splits, int nsub, int G,
 // microseconds per stage / fixed stages per item of a tile configuration (fits of round 3's traces: the towers' direct tiles run
 // 1 400 32-pixel stages in 868 us alone; the predictors' 128 x 256 items 198 stages in ~85 us)
 inline double plan_stage_us(int cfg) { return cfg == 1 ? 0.62 : 0.43; }
-inline int plan_ovh(int cfg) { return cfg == 1 ? 8 : 8; }
+constexpr int kPlanOvh = 8;
 struct PlanOut { int splits[kMaxMulti]; int grid, makespan, items; double us; };
 void wgrad_plan(const PlanSub* subs, int nsub, int cfg, int cap, PlanOut* out) {
-  const int ovh = plan_ovh(cfg);
   long long total = 0;
   int smax = 1;
   for (int i = 0; i < nsub; ++i) { total += (long long)subs[i].stages * subs[i].tiles; smax = std::max(smax, subs[i].stages); }
@@ -1763,11 +1513,11 @@ void wgrad_plan(const PlanSub* subs, int nsub, int cfg, int cap, PlanOut* out) {
     int G = (int)std::min<long long>(cap, (items + 7) / 8 * 8);
     if (G < 8) G = 8;
     int n_items = 0;
-    long long ms = plan_simulate(subs, sp.data(), nsub, cap, ovh, nullptr, 0, nullptr, &n_items);
+    long long ms = plan_simulate(subs, sp.data(), nsub, cap, kPlanOvh, nullptr, 0, nullptr, &n_items);
     {
       int g = G;
       for (; g < cap; g += 8)
-        if (plan_simulate(subs, sp.data(), nsub, g, ovh, nullptr, 0, nullptr, nullptr) <= ms) break;
+        if (plan_simulate(subs, sp.data(), nsub, g, kPlanOvh, nullptr, 0, nullptr, nullptr) <= ms) break;
       G = g;
     }
     double red_bytes = 0;
@@ -1780,11 +1530,6 @@ void wgrad_plan(const PlanSub* subs, int nsub, int cfg, int cap, PlanOut* out) {
       out->grid = G; out->makespan = (int)ms; out->items = n_items; out->us = us;
     }
   }
-}
-long long wgrad_px(const dsl_wgrad_desc* d) {
-  long long px = 0;
-  for (int s = 0; s < d->nseg; ++s) px += (long long)d->n * d->gh[s] * d->gw[s];
-  return px;
 }
 bool wgrad_multi_v3(const dsl_wgrad_desc* descs, const int* counts, int nsub, int cfg) {
   bool v3 = true;
@@ -1817,18 +1562,17 @@ void wgrad_plan_subs(const dsl_wgrad_desc* descs, const int* counts, int nsub, i
   }
 }
 
-// split factors of a multi launch: every workgroup gets at most ~1/slots of the launch's K-tile iterations
+// split factors of a multi launch: the planner's for the pipelined kernel; else every workgroup gets at most ~1/slots of the
+// launch's K-tile iterations
 int wgrad_multi_splits(const dsl_wgrad_desc* descs, const int* counts, int nsub, int* splits) {
-  {
-    const int cfg0 = wgrad_pick(descs);
-    if (wgrad_plan_mode() && cfg0 >= 1 && cfg0 <= 3 && wgrad_persist() && wgrad_multi_v3(descs, counts, nsub, cfg0)) {
-      PlanSub subs[kMaxMulti];
-      wgrad_plan_subs(descs, counts, nsub, kWgV3KS, subs);
-      PlanOut po;
-      wgrad_plan(subs, nsub, cfg0, wgrad_multi_cap(descs, counts, nsub), &po);
-      for (int s = 0; s < nsub; ++s) splits[s] = po.splits[s];
-      return 0;
-    }
+  const int cfg = wgrad_pick(descs);
+  if (wgrad_multi_v3(descs, counts, nsub, cfg)) {
+    PlanSub subs[kMaxMulti];
+    wgrad_plan_subs(descs, counts, nsub, wgrad_tile(cfg, true).ks, subs);
+    PlanOut po;
+    wgrad_plan(subs, nsub, cfg, wgrad_multi_cap(descs, counts, nsub), &po);
+    for (int s = 0; s < nsub; ++s) splits[s] = po.splits[s];
+    return 0;
   }
   long long total = 0;
   int off = 0;
@@ -1838,7 +1582,6 @@ int wgrad_multi_splits(const dsl_wgrad_desc* descs, const int* counts, int nsub,
     total += (long long)ktiles * tiles * counts[s];
     off += counts[s];
   }
-  const int cfg = wgrad_pick(descs);
   const int slots = wgrad_multi_cap(descs, counts, nsub) * (cfg == 4 ? 2 : 1);
   long long lmax = (total + slots - 1) / slots;
   if (lmax < 4) lmax = 4;
@@ -1915,12 +1658,7 @@ extern "C" int dsl_wgrad_multi_build(const dsl_wgrad_desc* descs, const int* cou
   t->nsub = nsub;
   int splits[kMaxMulti], first[kMaxMulti], order[kMaxMulti];
   wgrad_multi_splits(descs, counts, nsub, splits);
-  {                                    // the pipelined kernel serves the launch only if it can serve every sub-launch
-    bool v3 = true;
-    int off = 0;
-    for (int s = 0; s < nsub; ++s) { v3 = v3 && wgrad_v3_ok(&descs[off], t->cfg); off += counts[s]; }
-    t->v3 = v3 ? 1 : 0;
-  }
+  t->v3 = wgrad_multi_v3(descs, counts, nsub, t->cfg) ? 1 : 0;      // the pipelined kernel serves the launch only if it can serve every sub-launch
   long long per_wg[kMaxMulti];
   {
     int off = 0;
@@ -1972,23 +1710,23 @@ extern "C" int dsl_wgrad_multi_build(const dsl_wgrad_desc* descs, const int* cou
   t->hdr.nsub = nsub;
   t->total_blocks = blocks;
   t->red_blocks = red_blocks;
-  if (wgrad_plan_mode() && t->v3 && t->cfg <= 3 && wgrad_persist()) {
+  if (t->v3) {
     // the schedule of the persistent grid, for the sub-launches in TABLE order (that is the block numbering the kernel sees)
     PlanSub subs[kMaxMulti], tsubs[kMaxMulti];
     int tsplits[kMaxMulti];
-    wgrad_plan_subs(descs, counts, nsub, kWgV3KS, subs);
+    wgrad_plan_subs(descs, counts, nsub, wgrad_tile(t->cfg, true).ks, subs);
     long long items = 0;
     for (int i = 0; i < nsub; ++i) { tsubs[i] = subs[order[i]]; tsplits[i] = splits[order[i]]; items += (long long)tsplits[i] * tsubs[i].tiles; }
     const int cap_ = wgrad_multi_cap(descs, counts, nsub);
     int G = (int)std::min<long long>(cap_, (items + 7) / 8 * 8);
     if (G < 8) G = 8;
     {
-      const long long ms_cap = plan_simulate(tsubs, tsplits, nsub, cap_, plan_ovh(t->cfg), nullptr, 0, nullptr, nullptr);
+      const long long ms_cap = plan_simulate(tsubs, tsplits, nsub, cap_, kPlanOvh, nullptr, 0, nullptr, nullptr);
       for (; G < cap_; G += 8)
-        if (plan_simulate(tsubs, tsplits, nsub, G, plan_ovh(t->cfg), nullptr, 0, nullptr, nullptr) <= ms_cap) break;
+        if (plan_simulate(tsubs, tsplits, nsub, G, kPlanOvh, nullptr, 0, nullptr, nullptr) <= ms_cap) break;
     }
     int rounds = 0, n_items = 0;
-    const long long ms = plan_simulate(tsubs, tsplits, nsub, G, plan_ovh(t->cfg), t->sched, kSchedMax, &rounds, &n_items);
+    const long long ms = plan_simulate(tsubs, tsplits, nsub, G, kPlanOvh, t->sched, kSchedMax, &rounds, &n_items);
     if (blocks < 32767 && rounds > 0) { t->sched_grid = G; t->sched_rounds = rounds; }
     t->plan_makespan = (int)ms; t->plan_items = n_items;
   }
@@ -2013,7 +1751,7 @@ extern "C" int dsl_wgrad_plan_probe(const int* stages, const int* tiles, const l
   {   // self-check of the schedule table the launch would use: every valid block exactly once, no holes in a workgroup's list
     std::vector<short> sched(kSchedMax);
     int rounds = 0, n_items = 0, total_blocks = 0;
-    plan_simulate(subs, po.splits, nsub, po.grid, plan_ovh(cfg), sched.data(), kSchedMax, &rounds, &n_items);
+    plan_simulate(subs, po.splits, nsub, po.grid, kPlanOvh, sched.data(), kSchedMax, &rounds, &n_items);
     for (int s = 0; s < nsub; ++s) total_blocks += (subs[s].tiles * po.splits[s] + 7) / 8 * 8;
     if (rounds > 0) {
       std::vector<int> hit(total_blocks, 0);
@@ -2051,7 +1789,7 @@ extern "C" int dsl_wgrad_plan_probe(const int* stages, const int* tiles, const l
       const int xcd = bid & 7, jj = bid >> 3, w = xcd * chunk + jj;
       if (jj >= chunk || w >= witems) continue;
       const int sp = w / tiles[s], k0 = sp * tps, k1 = std::min(k0 + tps, stages[s]);
-      if (k1 > k0) { load[(base + bid) % cap] += plan_ovh(cfg) + k1 - k0; ++oitems; }
+      if (k1 > k0) { load[(base + bid) % cap] += kPlanOvh + k1 - k0; ++oitems; }
     }
     base += chunk * 8;
   }
@@ -2075,91 +1813,36 @@ extern "C" int dsl_wgrad_multi_info(const void* table_host, double* flops, doubl
 extern "C" int dsl_conv2d_wgrad_multi(const void* table_host, const void* table_dev, void* stream) {
   const WgMultiTable* t = (const WgMultiTable*)table_host;
   DSL_CHECK(t && table_dev && t->magic == kMultiMagic, "dsl_conv2d_wgrad_multi: not a table of dsl_wgrad_multi_build");
-  const WgK* ktab = (const WgK*)((const unsigned char*)table_dev + offsetof(WgMultiTable, k));
-  const RedEnt* rtab = (const RedEnt*)((const unsigned char*)table_dev + offsetof(WgMultiTable, red));
+  const unsigned char* dev = (const unsigned char*)table_dev;
+  const WgK* ktab = (const WgK*)(dev + offsetof(WgMultiTable, k));
+  const RedEnt* rtab = (const RedEnt*)(dev + offsetof(WgMultiTable, red));
+  const short* sched = (const short*)(dev + offsetof(WgMultiTable, sched));
   hipStream_t st = (hipStream_t)stream;
   const int prof = dsl_prof_active() ? dsl_prof_begin(3, t->flops, st, t->bytes) : -1;
-  const int bcos[5] = {0, 256, 256, 128, 128}, bcis[5] = {0, 256, 128, 256, 128}, nsts[5] = {2, 2, 3, 3, 2};
-  const size_t lds2 = t->v3 ? wgrad_v3_lds(t->cfg) : (size_t)nsts[t->cfg] * 64 * 2 * (bcos[t->cfg] + bcis[t->cfg]);
-  const dim3 grid(t->total_blocks);
-#define LAUNCHM(KERNEL, A, B, C_, D, KS_, S_)                                                                        \
-  do {                                                                                                               \
-    static bool a_ = false;                                                                                          \
-    if (!a_) {                                                                                                       \
-      hipFuncSetAttribute((const void*)KERNEL<A, B, C_, D, KS_, S_>,                                                 \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                    \
-      a_ = true;                                                                                                     \
-    }                                                                                                                \
-    hipLaunchKernelGGL((KERNEL<A, B, C_, D, KS_, S_>), grid, dim3(64 * C_ * D), lds2, st, t->hdr, ktab);              \
-  } while (0)
-  const int cap = (wgrad_slots() + 7) / 8 * 8;
-  if (t->v3 && t->sched_rounds > 0) {
-    const short* sched = (const short*)((const unsigned char*)table_dev + offsetof(WgMultiTable, sched));
-    const dim3 sgrid(t->sched_grid);
-#define LAUNCHS(A, B, C_, D, KS_, S_)                                                                                \
-  do {                                                                                                               \
-    static bool a_ = false;                                                                                          \
-    if (!a_) {                                                                                                       \
-      hipFuncSetAttribute((const void*)wgrad_pipe_multi_sched_kernel<A, B, C_, D, KS_, S_>,                          \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                    \
-      a_ = true;                                                                                                     \
-    }                                                                                                                \
-    hipLaunchKernelGGL((wgrad_pipe_multi_sched_kernel<A, B, C_, D, KS_, S_>), sgrid, dim3(64 * C_ * D), lds2, st, t->hdr, ktab,   \
-                       sched, t->sched_rounds);                                                                      \
-  } while (0)
-    switch (t->cfg) {
-      case 1: LAUNCHS(256, 256, 2, 4, 32, 4); break;
-      case 2: LAUNCHS(256, 128, 4, 2, 32, 5); break;
-      default: LAUNCHS(128, 256, 2, 4, 32, 5); break;
+  const char* name = "wgrad_glds_multi_kernel";
+  const bool known = wgrad_dispatch(t->cfg, t->v3 != 0, [&](auto row) {
+    constexpr WgTile T = kWgTiles[decltype(row)::value];
+    if constexpr (!T.pipe) {
+      wgrad_run<wgrad_glds_multi_kernel<WG_TILE_ARGS(T)>>(T, dim3(t->total_blocks), st, t->hdr, ktab);
+    } else if (t->sched_rounds > 0) {
+      name = "wgrad_pipe_multi_sched_kernel";
+      wgrad_run<wgrad_pipe_multi_sched_kernel<WG_TILE_ARGS(T)>>(T, dim3(t->sched_grid), st, t->hdr, ktab, sched, t->sched_rounds);
+    } else {
+      name = "wgrad_pipe_multi_kernel";
+      const int cap = (wgrad_slots() + 7) / 8 * 8;
+      wgrad_run<wgrad_pipe_multi_kernel<WG_TILE_ARGS(T)>>(T, dim3(std::min(t->total_blocks, cap)), st, t->hdr, ktab, t->total_blocks);
     }
-#undef LAUNCHS
-  } else if (t->v3 && wgrad_persist() && t->total_blocks > cap) {
-    const dim3 pgrid(cap);
-#define LAUNCHP(A, B, C_, D, KS_, S_)                                                                                \
-  do {                                                                                                               \
-    static bool a_ = false;                                                                                          \
-    if (!a_) {                                                                                                       \
-      hipFuncSetAttribute((const void*)wgrad_pipe_multi_persist_kernel<A, B, C_, D, KS_, S_>,                        \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);                                    \
-      a_ = true;                                                                                                     \
-    }                                                                                                                \
-    hipLaunchKernelGGL((wgrad_pipe_multi_persist_kernel<A, B, C_, D, KS_, S_>), pgrid, dim3(64 * C_ * D), lds2, st, t->hdr, ktab, \
-                       t->total_blocks);                                                                             \
-  } while (0)
-    switch (t->cfg) {
-      case 1: LAUNCHP(256, 256, 2, 4, 32, 4); break;
-      case 2: LAUNCHP(256, 128, 4, 2, 32, 5); break;
-      default: LAUNCHP(128, 256, 2, 4, 32, 5); break;
-    }
-#undef LAUNCHP
-  } else if (t->v3) {
-    switch (t->cfg) {
-      case 1: LAUNCHM(wgrad_pipe_multi_kernel, 256, 256, 2, 4, 32, 4); break;
-      case 2: LAUNCHM(wgrad_pipe_multi_kernel, 256, 128, 4, 2, 32, 5); break;
-      default: LAUNCHM(wgrad_pipe_multi_kernel, 128, 256, 2, 4, 32, 5); break;
-    }
-  } else {
-    switch (t->cfg) {
-      case 1: LAUNCHM(wgrad_glds_multi_kernel, 256, 256, 2, 4, 64, 2); break;
-      case 2: LAUNCHM(wgrad_glds_multi_kernel, 256, 128, 4, 2, 64, 3); break;
-      case 3: LAUNCHM(wgrad_glds_multi_kernel, 128, 256, 2, 4, 64, 3); break;
-      default: LAUNCHM(wgrad_glds_multi_kernel, 128, 128, 2, 2, 64, 2); break;
-    }
-  }
-#undef LAUNCHM
+  });
   dsl_prof_end(prof, st);
-  DSL_LAUNCH_CHECK("wgrad_glds_multi_kernel");
+  DSL_CHECK(known, "dsl_conv2d_wgrad_multi: the table names tile configuration %d, which does not exist", t->cfg);
+  DSL_LAUNCH_CHECK(name);
   if (t->n_red > 0) {
     hipLaunchKernelGGL(wgrad_reduce_multi_kernel, dim3(t->red_blocks), dim3(256), 0, st, rtab, t->n_red);
     DSL_LAUNCH_CHECK("wgrad_reduce_multi_kernel");
   }
-  for (int i = 0; i < t->n_colsum; ++i) {
-    const ColsumItem& c = t->colsum[i];
-    const int rc = c.clear ? dsl_colsum(c.x, c.out, (long)c.rows, c.c, c.ld, stream) : dsl_colsum_acc(c.x, c.out, (long)c.rows, c.c, c.ld, stream);
-    if (rc) return rc;
-  }
   return 0;
 }
+#undef WG_TILE_ARGS
 
 extern "C" int dsl_conv2d_wgrad(const dsl_wgrad_desc* d, void* stream) {
   DSL_CHECK(d != nullptr, "dsl_conv2d_wgrad: null descriptor");

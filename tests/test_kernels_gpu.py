@@ -361,10 +361,10 @@ WG_CASES = [('3x3_s1', 2, 128, 128, 12, 17, 3, 1, 1), ('1x1_s2', 2, 256, 128, 14
             ('3x3_s2', 1, 128, 256, 13, 21, 3, 2, 1), ('1x1_s1_co64', 2, 128, 64, 9, 10, 1, 1, 0)]
 
 
-@pytest.mark.parametrize('cfg', [None, 0, 1, 2, 3, 4])
+@pytest.mark.parametrize('cfg', [None, 1, 2, 3, 4])
 @pytest.mark.parametrize('case', WG_CASES, ids=[c[0] for c in WG_CASES])
 def test_wgrad(K, case, cfg):
-    """cfg: None = library's choice, 0 = v1 kernel, 1..4 = v2 (DMA-to-LDS) tiles 256x256, 256x128, 128x256, 128x128."""
+    """cfg: None = library's choice, 1..4 = the tile configurations 256x256, 256x128, 128x256, 128x128 (couts x cins)."""
     L, ops = K
     _, N, Ci, Co, H, W, k, s, p = case
     need = {1: (256, 256), 2: (256, 128), 3: (128, 256), 4: (128, 128)}.get(cfg)

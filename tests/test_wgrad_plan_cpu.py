@@ -1,4 +1,4 @@
-"""The weight-gradient launch planner (csrc/conv.hip wgrad_plan, round 4) on the geometries of the benchmark step (N = 2, 800 x 1344):
+"""The weight-gradient launch planner (csrc/wgrad.hip wgrad_plan, round 4) on the geometries of the benchmark step (N = 2, 800 x 1344):
 pure host logic, callable without a device through dsl_wgrad_plan_probe.  What the launches compute does not depend on the plan
 (tests/test_kernels_gpu.py::test_wgrad_multi runs them on the GPU); here: the plan is never worse than round 3's rule, its schedule
 table holds every work item exactly once (the probe checks that itself and fails otherwise), and the three cases the planner was
@@ -50,6 +50,23 @@ def test_plan_not_worse_than_the_stride_walk(name):
         assert 1 <= s <= max(1, st // 8)
         tps = -(-st // s)
         assert (s - 1) * tps < st, 'an empty split would leave a partial tile unwritten'
+
+
+# split factors, grid and makespan of CASES as planned by the library before the tile table / single-dispatch refactor of
+# csrc/wgrad.hip: a change that moves a plan has to be meant
+PINNED = {
+    'fpn': ([1, 1, 1, 2, 7, 1, 2, 7], 128, 158),
+    'layer3': ([1, 1, 1, 1, 1], 120, 271),
+    'layer4': ([1, 1, 1, 1, 1], 128, 148),
+    'predictors': ([7, 7], 128, 208),
+}
+
+
+@pytest.mark.parametrize('name', sorted(CASES))
+def test_plan_is_pinned(name):
+    cfg, subs = CASES[name]
+    sp, info = probe(subs, cfg)
+    assert (sp, info['grid'], info['makespan']) == PINNED[name]
 
 
 def test_the_three_cases_the_planner_was_written_for():

@@ -60,10 +60,9 @@ def bench(name, ci, co, k, s, sizes_in):
         t_d = timeit(lambda: L.lib.dsl_conv2d(C.byref(ddg), L.stream_ptr()))
         res.append(f'dgrad {t_d*1e6:8.1f} us {flops/t_d/1e12:7.1f} TF')
     if ci % 128 == 0:
-        for cfg in (0, None):
-            dwg = ops.wgrad_desc(dy, x, dw, n=N, grid=sizes_out, src_hw=sizes_in, cs=ci, cy=co, cd=co, kh=k, kw=k, stride=s, pad=p, force_cfg=cfg)
-            t_w = timeit(lambda: L.lib.dsl_conv2d_wgrad(C.byref(dwg), L.stream_ptr()))
-            res.append(f'wgrad[{cfg}] {t_w*1e6:7.1f}us {flops/t_w/1e12:5.0f}TF')
+        dwg = ops.wgrad_desc(dy, x, dw, n=N, grid=sizes_out, src_hw=sizes_in, cs=ci, cy=co, cd=co, kh=k, kw=k, stride=s, pad=p)
+        t_w = timeit(lambda: L.lib.dsl_conv2d_wgrad(C.byref(dwg), L.stream_ptr()))
+        res.append(f'wgrad {t_w*1e6:7.1f}us {flops/t_w/1e12:5.0f}TF')
     print('  '.join(res), flush=True)
 
 
