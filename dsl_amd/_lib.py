@@ -100,7 +100,12 @@ class FcosDesc(C.Structure):
                 ('g_cls', C.c_void_p), ('ld_gcls', C.c_int32), ('g_rc', C.c_void_p), ('ld_grc', C.c_int32),
                 ('g_scales', C.c_void_p), ('losses', C.c_void_p),
                 ('soft_weight', C.c_float), ('grad_scale', C.c_float), ('inv_world', C.c_float),
-                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('logvec', C.c_void_p)]
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('logvec', C.c_void_p),
+                ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p), ('g_ctr', C.c_void_p), ('ld_gctr', C.c_int32)]
+
+
+# dsl_fcos_desc.head_flags / dsl_det_desc.head_flags (0 = the fcos_semi "tricks" head)
+HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
 
 
 class DetDesc(C.Structure):
@@ -112,7 +117,8 @@ class DetDesc(C.Structure):
                 ('regctr', C.c_void_p), ('ld_rc', C.c_int32),
                 ('scales', C.c_void_p), ('img_shapes', C.c_void_p), ('scale_factors', C.c_void_p),
                 ('dets', C.c_void_p), ('det_labels', C.c_void_p), ('det_count', C.c_void_p),
-                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t)]
+                ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
+                ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p)]
 
 
 class PackItem(C.Structure):

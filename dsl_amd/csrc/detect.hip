@@ -21,6 +21,8 @@ struct DetK {
   float score_thr, iou_thr;
   const float* cls; int ld_cls;
   const float* rc; int ld_rc;
+  const float* ctr; int ld_ctr;      // centerness logit of location m: ctr[m * ld_ctr] (column 4 of rc, or the classification predictor's)
+  int exp_decode;                    // norm_on_bbox=False: exp(scale x), no stride multiply (fcos_head.py:162-167)
   const float* scales; const float* img_shapes; const float* scale_factors;
   float* dets; long long* det_labels; int* det_count;
   // workspace
@@ -36,7 +38,7 @@ __global__ void det_key_kernel(const DetK p) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= M) return;
   const float* c = p.cls + (long long)m * p.ld_cls;
-  const float ctr = sigmoidf_(p.rc[(long long)m * p.ld_rc + 4]);
+  const float ctr = sigmoidf_(p.ctr[(long long)m * p.ld_ctr]);
   float best = -1.f;
   const int full = p.num_classes & ~3;
   for (int k = 0; k < full; k += 4) {
@@ -212,7 +214,7 @@ __global__ void det_pairscore_kernel(const DetK p) {
     const int loc = p.sel[((long long)img * p.nlvl + lvl) * p.nms_pre + slot];
     const int m = p.mstart[lvl] + img * P + loc;
     const float score = sigmoidf_(p.cls[(long long)m * p.ld_cls + c]);
-    if (score > p.score_thr) out = score * sigmoidf_(p.rc[(long long)m * p.ld_rc + 4]);
+    if (score > p.score_thr) out = score * sigmoidf_(p.ctr[(long long)m * p.ld_ctr]);
   }
   p.pairscore[((long long)img * p.nlvl + lvl) * p.nms_pre * p.num_classes + t] = out;
 }
@@ -234,7 +236,7 @@ __device__ __forceinline__ void det_emit(const DetK& p, int img, const float* ps
   const float sc = p.scales[lvl];
   float d[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) d[e] = fmaxf(rc[e] * sc, 0.f) * (float)s;      // fcos_head.py:159-165 (eval)
+  for (int e = 0; e < 4; ++e) d[e] = p.exp_decode ? expf(rc[e] * sc) : fmaxf(rc[e] * sc, 0.f) * (float)s;      // fcos_head.py:159-167 (eval)
   const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
   float b[4] = {px - d[0], py - d[1], px + d[2], py + d[3]};
   b[0] = fminf(fmaxf(b[0], 0.f), W);                    // distance2bbox clip (transforms.py:150-160)
@@ -522,7 +524,7 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   DSL_CHECK(d->cls_logits && d->regctr && d->scales && d->img_shapes && d->dets && d->det_labels && d->det_count &&
                 d->workspace,
             "dsl_fcos_detect: null pointer");
-  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= 5,
+  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr ? 4 : 5),
             "dsl_fcos_detect: unsupported layout");
   DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS && d->nms_pre > 0, "dsl_fcos_detect: max_per_img must be in 1..%d", NMS_THREADS);
   size_t off[8];
@@ -541,6 +543,8 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   k.mstart[d->nlvl] = m;
   k.score_thr = d->score_thr; k.iou_thr = d->iou_thr;
   k.cls = d->cls_logits; k.ld_cls = d->ld_cls; k.rc = d->regctr; k.ld_rc = d->ld_rc;
+  k.ctr = d->ctr ? d->ctr : d->regctr + 4; k.ld_ctr = d->ctr ? d->ld_ctr : d->ld_rc;
+  k.exp_decode = (d->head_flags & DSL_HEAD_EXP_DECODE) ? 1 : 0;
   k.scales = d->scales; k.img_shapes = d->img_shapes; k.scale_factors = d->scale_factors;
   k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;
   unsigned char* ws = (unsigned char*)d->workspace;

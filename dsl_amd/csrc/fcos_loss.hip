@@ -6,6 +6,11 @@
 // mmdet/models/losses/iou_loss.py:85-102,329-366 with core/bbox/iou_calculators/iou2d_calculator.py:212-260;
 // mmdet/models/losses/cross_entropy_loss.py:73-112 of the reference.
 //
+// Head options (dsl_fcos_desc.head_flags, uniform per launch; 0 = the fcos_semi "tricks" head): inside-box assignment
+// (center_sampling=False, fcos_head.py:676-678), unnormalised targets and exp decode (norm_on_bbox=False, :162-167, :618),
+// the IoU log loss (losses/iou_loss.py:14-36), and the centerness logit / gradient at a caller-given address
+// (centerness_on_reg=False, :155-158: it belongs to the classification tower's predictor then).
+//
 // The assignment must be BIT-identical to the reference's fp32 torch arithmetic, so this file is
 // compiled with floating-point contraction off and the comparisons are written exactly as there.
 #include "common.hpp"
@@ -29,6 +34,9 @@ struct FcK {
   const float* scales; const float* norm;
   uint16_t* g_cls; int ld_gcls; uint16_t* g_rc; int ld_grc;
   float* g_scales; float* losses;
+  int flags;              // DSL_HEAD_*
+  const float* ctr; int ld_ctr;      // centerness logit of location m: ctr[m * ld_ctr]
+  uint16_t* g_ctr; int ld_gctr;      // its gradient, when it does not live in column 4 of g_rc (else null)
   float* part;            // block records of the loss / assignment sums (fixed-order second pass, no float atomics)
 };
 
@@ -47,9 +55,10 @@ __device__ __forceinline__ void decode_loc(const FcK& p, int m, int& lvl, int& i
 
 // one image, one location against a list of boxes: area-argmin with centre sampling + range test
 // (fcos_head.py:632-700).  Returns min_area; idx = first argmin; ltrb of that box in t[4].
+// in_box: the location only has to lie inside the box itself (center_sampling=False, fcos_head.py:676-678)
 __device__ __forceinline__ float assign_one(float px, float py, float rs, float lo, float hi,
                                             const float* __restrict__ boxes, int g0, int g1, int& idx,
-                                            float t[4]) {
+                                            float t[4], bool in_box) {
   float best = kINF;
   idx = 0;
   t[0] = t[1] = t[2] = t[3] = 0.f;
@@ -63,7 +72,7 @@ __device__ __forceinline__ float assign_one(float px, float py, float rs, float 
     const float c1 = ymin > y1 ? ymin : y1;
     const float c2 = xmax > x2 ? x2 : xmax;
     const float c3 = ymax > y2 ? y2 : ymax;
-    const float cmin = fminf(fminf(px - c0, py - c1), fminf(c2 - px, c3 - py));
+    const float cmin = in_box ? fminf(fminf(l, tp), fminf(r, b)) : fminf(fminf(px - c0, py - c1), fminf(c2 - px, c3 - py));
     const bool inside = cmin > 0.f;
     const float mx = fmaxf(fmaxf(l, tp), fmaxf(r, b));
     const bool in_range = (mx >= lo) && (mx <= hi);
@@ -89,13 +98,14 @@ __global__ __launch_bounds__(256) void assign_kernel(const FcK p) {
     const float px = (float)x * (float)s + (float)(s / 2);
     const float py = (float)y * (float)s + (float)(s / 2);
     const float rs = (float)s * p.radius;
+    const bool in_box = (p.flags & DSL_HEAD_INSIDE_BOX) != 0;
     int idx;
     float t[4];
     const int g0 = p.gt_off[img], g1 = p.gt_off[img + 1];
     long long label = p.num_classes;
     int aidx = -1;
     if (g1 > g0) {
-      const float best = assign_one(px, py, rs, p.lo[lvl], p.hi[lvl], p.gt_boxes, g0, g1, idx, t);
+      const float best = assign_one(px, py, rs, p.lo[lvl], p.hi[lvl], p.gt_boxes, g0, g1, idx, t, in_box);
       if (best != kINF) {
         label = p.gt_labels[g0 + idx];
         aidx = idx;
@@ -103,7 +113,7 @@ __global__ __launch_bounds__(256) void assign_kernel(const FcK p) {
     } else {
       t[0] = t[1] = t[2] = t[3] = 0.f;
     }
-    const float fs = (float)s;
+    const float fs = (p.flags & DSL_HEAD_RAW_TARGETS) ? 1.f : (float)s;   // norm_on_bbox=False: targets stay in pixels (fcos_head.py:618)
     const float n0 = t[0] / fs, n1 = t[1] / fs, n2 = t[2] / fs, n3 = t[3] / fs;   // norm_on_bbox
     p.labels[m] = label;
     p.assign_idx[m] = aidx;
@@ -115,7 +125,7 @@ __global__ __launch_bounds__(256) void assign_kernel(const FcK p) {
       if (i1 > i0) {
         int ii;
         float tt[4];
-        const float bi = assign_one(px, py, rs, p.lo[lvl], p.hi[lvl], p.ig_boxes, i0, i1, ii, tt);
+        const float bi = assign_one(px, py, rs, p.lo[lvl], p.hi[lvl], p.ig_boxes, i0, i1, ii, tt, in_box);
         if (bi != kINF && label == p.num_classes) wgt = 0.f;
       }
     }
@@ -296,6 +306,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
   // ---------------- boxes + centerness: one thread per location ---------------------------------
   float bsum = 0.f, csum = 0.f;
   float gsc[DSL_MAX_SEG] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  const bool exp_dec = (p.flags & DSL_HEAD_EXP_DECODE) != 0, iou_loss = (p.flags & DSL_HEAD_IOU_LOSS) != 0;
   for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
     float gr[4] = {0.f, 0.f, 0.f, 0.f}, gc = 0.f;
     const int label = (int)p.labels[m];
@@ -310,7 +321,8 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         raw[k] = rc[k];
-        d[k] = fmaxf(raw[k] * sc, 0.f);
+        const float z = raw[k] * sc;
+        d[k] = exp_dec ? expf(z) : fmaxf(z, 0.f);      // fcos_head.py:162-167
       }
       const f32x4 t = *reinterpret_cast<const f32x4*>(p.bbox_targets + 4ll * m);
       const float pw = p.pos_weight[m];
@@ -331,9 +343,18 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
       const float ew = fmaxf(ew0, 0.f), eh = fmaxf(eh0, 0.f);
       const float e0 = ew * eh;
       const float E = fmaxf(e0, eps);
-      const float giou = ov / U - (E - U) / E;
       const float wb = ct * pw;
-      bsum += wb * (1.f - giou);
+      // IoULoss (iou_loss.py:14-36): -log(clamp(iou, eps)); clamp passes the gradient where iou >= eps
+      const float iou = ov / U;
+      float coef_iou = 0.f;                             // dL/diou of the log loss (set below, IoU mode only)
+      if (iou_loss) {
+        const float iouc = fmaxf(iou, eps);
+        bsum += wb * (-logf(iouc));
+        coef_iou = (-wb / denorm * p.grad_scale) / iouc;
+      } else {
+        const float giou = iou - (E - U) / E;
+        bsum += wb * (1.f - giou);
+      }
       // ---- backward of (1 - giou) w.r.t. (x1, y1, x2, y2) ----
       const float cw = w0 >= 0.f ? 1.f : 0.f, chh = h0 >= 0.f ? 1.f : 0.f;   // clamp(min=0) passes grad at 0
       const float dw_x1 = -dmax_a(x1, X1) * cw, dw_x2 = dmin_a(x2, X2) * cw;
@@ -351,25 +372,36 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float dU = (da1[k] - dov[k]) * ug;
-        const float dg = dov[k] / U - ov * dU / (U * U) + dU / E - U * de[k] / (E * E);
-        dbox[k] = coef * dg;
+        if (iou_loss) {
+          const float dg = dov[k] / U - ov * dU / (U * U);
+          dbox[k] = iou >= eps ? coef_iou * dg : 0.f;
+        } else {
+          const float dg = dov[k] / U - ov * dU / (U * U) + dU / E - U * de[k] / (E * E);
+          dbox[k] = coef * dg;
+        }
       }
       const float dd[4] = {-dbox[0], -dbox[1], dbox[2], dbox[3]};   // x1 = px - d0, ... x2 = px + d2
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float on = (raw[k] * sc > 0.f) ? 1.f : 0.f;
+        const float on = exp_dec ? d[k] : ((raw[k] * sc > 0.f) ? 1.f : 0.f);     // d exp(z) / dz = exp(z); relu's gate
         gr[k] = dd[k] * on * sc;
         gsc[lvl] += dd[k] * on * raw[k];
       }
       // centerness BCE-with-logits (cross_entropy_loss.py:73-112)
-      const float cl = rc[4];
+      const float cl = p.ctr[(long long)m * p.ld_ctr];
       const float e = __expf(-fabsf(cl));
       const float sig = cl >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
       csum += (fmaxf(cl, 0.f) - cl * ct + log1pf(e)) * pw;
       gc = (sig - ct) * pw / num_pos * p.grad_scale;
     }
-    u32x4 o = {pack2bf(gr[0], gr[1]), pack2bf(gr[2], gr[3]), pack2bf(gc, 0.f), 0u};
-    *reinterpret_cast<u32x4*>(p.g_rc + (long long)m * p.ld_grc) = o;
+    if (p.g_ctr) {      // the centerness gradient belongs to the classification predictor's columns
+      u32x4 o = {pack2bf(gr[0], gr[1]), pack2bf(gr[2], gr[3]), 0u, 0u};
+      *reinterpret_cast<u32x4*>(p.g_rc + (long long)m * p.ld_grc) = o;
+      p.g_ctr[(long long)m * p.ld_gctr] = f2bf(gc);
+    } else {
+      u32x4 o = {pack2bf(gr[0], gr[1]), pack2bf(gr[2], gr[3]), pack2bf(gc, 0.f), 0u};
+      *reinterpret_cast<u32x4*>(p.g_rc + (long long)m * p.ld_grc) = o;
+    }
   }
   bsum = block_sum(bsum, sh);
   csum = block_sum(csum, sh);
@@ -411,6 +443,11 @@ int fill(const dsl_fcos_desc* d, FcK& k) {
   k.scales = d->scales; k.norm = d->norm;
   k.g_cls = (uint16_t*)d->g_cls; k.ld_gcls = d->ld_gcls; k.g_rc = (uint16_t*)d->g_rc; k.ld_grc = d->ld_grc;
   k.g_scales = d->g_scales; k.losses = d->losses;
+  k.flags = d->head_flags;
+  // centerness_on_reg=False: the logit and its gradient live with the classification predictor (caller-given addresses)
+  k.ctr = d->ctr ? d->ctr : (d->regctr ? d->regctr + 4 : nullptr);
+  k.ld_ctr = d->ctr ? d->ld_ctr : d->ld_rc;
+  k.g_ctr = (uint16_t*)d->g_ctr; k.ld_gctr = d->ld_gctr;
   return 0;
 }
 
@@ -460,8 +497,9 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
                 d->scales && d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses,
             "dsl_fcos_loss: null pointer");
   DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_gcls % 4 == 0 &&
-                d->ld_gcls >= d->ld_cls && d->ld_grc % 8 == 0 && d->ld_rc >= 5,
+                d->ld_gcls >= d->ld_cls && d->ld_grc % 8 == 0 && d->ld_rc >= (d->ctr ? 4 : 5),
             "dsl_fcos_loss: unsupported strides / class count");
+  DSL_CHECK((d->ctr != nullptr) == (d->g_ctr != nullptr), "dsl_fcos_loss: ctr and g_ctr go together");
   hipStream_t st = (hipStream_t)stream;
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d), "dsl_fcos_loss: workspace too small");
   const int M = k.mstart[k.nlvl];

@@ -23,13 +23,14 @@ import torch.nn as nn
 
 C_void = ctypes.c_void_p
 
-from .params import ParamStore, class_layout
+from .params import HeadOptions, ParamStore, class_layout
 from .registry import BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, build_backbone, build_head, build_loss, build_neck
 
 
 # mmcv's model-zoo aliases used by configs/fcos_semi (mmcv/model_zoo/open_mmlab.json, mmcv 1.3.10): the file a
 # torch.hub download would leave in the checkpoint cache
-_ZOO_FILES = {'open-mmlab://detectron2/resnet50_caffe': 'resnet50_msra-5891d200.pth'}
+_ZOO_FILES = {'open-mmlab://detectron2/resnet50_caffe': 'resnet50_msra-5891d200.pth',
+              'open-mmlab://detectron/resnet50_caffe': 'resnet50_caffe-788b5fa3.pth'}      # (configs/fcos)
 
 
 def resolve_checkpoint(uri):
@@ -162,6 +163,21 @@ class GIoULoss(_LossCfg):
 
 
 @LOSSES.register_module()
+class IoULoss(nn.Module):
+    """mmdet/models/losses/iou_loss.py:223-290 with its defaults: -log(clamp(iou, 1e-6)), mean over avg_factor."""
+
+    def __init__(self, linear=False, eps=1e-6, reduction='mean', loss_weight=1.0, **kw):
+        super().__init__()
+        _expect(not linear, 'IoULoss linear=False (the log loss)')
+        _expect(eps == 1e-6, 'IoULoss eps=1e-6')
+        _expect(kw.get('mode', 'log') == 'log', "IoULoss mode='log'")
+        _expect(not (set(kw) - {'mode'}), f'IoULoss arguments linear, eps, reduction, loss_weight (got {sorted(kw)})')
+        _expect(reduction == 'mean', "IoULoss reduction='mean'")
+        _expect(loss_weight == 1.0, 'IoULoss loss_weight=1.0')
+        self.loss_weight = loss_weight
+
+
+@LOSSES.register_module()
 class CrossEntropyLoss(_LossCfg):
     def __init__(self, use_sigmoid=False, use_mask=False, class_weight=None, **kw):
         super().__init__(**kw)
@@ -181,11 +197,15 @@ class FCOSHead(nn.Module):
                  init_cfg=None, **kw):
         super().__init__()
         class_layout(num_classes)            # 1..MAX_CLASSES, else NotImplementedError naming the range
-        _expect(in_channels == 256 and feat_channels == 256 and stacked_convs == 4, '256ch, 4 convs')
+        _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
+        _expect(stacked_convs == 4, 'stacked_convs=4')
         _expect(list(strides) == [8, 16, 32, 64, 128], 'strides 8..128')
-        _expect(center_sampling and norm_on_bbox and centerness_on_reg and not dcn_on_last_conv and conv_bias is True,
-                'the fcos_semi "tricks" head: center_sampling, norm_on_bbox, centerness_on_reg, conv_bias=True')
-        _expect(norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers')
+        _expect(not dcn_on_last_conv, 'dcn_on_last_conv=False (no DCN)')
+        _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers')
+        # mmcv ConvModule: bias='auto' = no bias in front of a norm layer - with the GroupNorm towers, False
+        _expect(conv_bias is True or conv_bias is False or conv_bias == 'auto', "conv_bias True, False or 'auto'")
+        self.center_sampling, self.norm_on_bbox, self.centerness_on_reg = bool(center_sampling), bool(norm_on_bbox), bool(centerness_on_reg)
+        self.conv_bias = conv_bias is True
         self.num_classes, self.strides = num_classes, tuple(strides)
         self.regress_ranges = tuple(tuple(r) for r in regress_ranges)
         self.center_sample_radius = center_sample_radius
@@ -193,8 +213,11 @@ class FCOSHead(nn.Module):
         self.cur_iter = 0                               # fcos_head.py:103
         self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)
         self.loss_centerness = build_loss(loss_centerness)
-        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, GIoULoss)
-                and isinstance(self.loss_centerness, CrossEntropyLoss), 'FocalLoss + GIoULoss + CrossEntropyLoss')
+        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, (GIoULoss, IoULoss))
+                and isinstance(self.loss_centerness, CrossEntropyLoss), 'FocalLoss + GIoULoss or IoULoss + CrossEntropyLoss')
+        # what the kernels and the parameter layout are built for (fixed per model: ParamStore.head)
+        self.options = HeadOptions(self.center_sampling, self.norm_on_bbox, self.centerness_on_reg,
+                                   isinstance(self.loss_bbox, IoULoss), self.conv_bias)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
 
     def effective_soft_weight(self, batch_size):
@@ -337,10 +360,15 @@ class FCOS(nn.Module):
         bbox_head.update(train_cfg=train_cfg, test_cfg=test_cfg)
         self.bbox_head = build_head(bbox_head)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        self.store = ParamStore(self.bbox_head.num_classes, 'cpu', backbone=getattr(self.backbone, 'backbone_kind', 'resnet'))
+        self.store = ParamStore(self.bbox_head.num_classes, 'cpu', backbone=getattr(self.backbone, 'backbone_kind', 'resnet'),
+                                head=self.bbox_head.options)
         self.store.init_reference_style(0)
         if fp8:
             assert str(fp8.get('layers', 'towers')) == 'towers', "fp8: only layers='towers' is built"
+            # the fp8 tower convolutions fold the layer's bias into their epilogue and were validated on the default head only
+            _expect(self.bbox_head.options.is_default(),
+                    f'fp8 towers with the default head options only (center_sampling, norm_on_bbox, centerness_on_reg, GIoULoss, '
+                    f'conv_bias=True), got {self.bbox_head.options}')
             self.store.fp8 = dict(fp8)
         self._params = None
         self._engine = None

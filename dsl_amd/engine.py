@@ -214,7 +214,7 @@ class Plan:
         if training and store.backbone != 'rla' and tune('pipe_prefix') != '0' and tune('side') != '0':
             self._split_prefix()
         if training:
-            self.lossplan = FcosLossPlan(N, self.level_sizes, dev, num_classes=store.num_classes, max_gt=max_gt)
+            self.lossplan = FcosLossPlan(N, self.level_sizes, dev, num_classes=store.num_classes, max_gt=max_gt, head=store.head)
             self.lossplan.bind_outputs(self.bufs['cls_logits'], self.bufs['regctr'], store.t32_ptr('head.scales'))
             # scale gradients go straight into the flat gradient buffer
             self.lossplan.desc.g_scales = store.t32_ptr('head.scales', store.grad)
@@ -332,7 +332,10 @@ class Plan:
         self.conv_ws_side = torch.empty(32 << 20, dtype=torch.uint8, device=self.dev)
         FSIDE = 2 if (tune('side') != '0' and not self.single_stream) else 0      # side stream 1 carries the weight gradients (and may be CU-masked)
         # phase marks for bench.py: 8 tower convs + 2 predictors over all M locations, 8 GroupNorm+ReLU passes
-        ncls, cls_pad, cls_ld = st.num_classes, st.cls_pad, st.cls_ld
+        # (centerness_on_reg=False: the classification predictor has conv_centerness as one more computed row / output column and
+        # the regression predictor four, ParamStore.ctr_on_cls - the same two launches either way)
+        ncls, cls_pad, cls_ld = st.cls_rows, st.cls_pad, st.logit_ld
+        nreg = 4 if st.ctr_on_cls else 5
         self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + 5) * 2304)
         self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + 8) * 4.0
         f.prof(4, 0, self._head_flops, self._head_bytes)
@@ -344,6 +347,8 @@ class Plan:
         # (straight-through).  A plan's first forward pass runs twice more in front (Plan.fp8_warm): nothing is recorded yet.
         fp8 = getattr(st, 'fp8', None)
         f8 = bool(fp8) and 'towers' in str(fp8.get('layers', 'towers'))
+        if f8 and not st.head.is_default():
+            raise NotImplementedError(f'dsl_amd hot path: fp8 towers are built for the default head options only, got {st.head}')
         self.fp8_cold = f8
         feats8 = None
         if f8:
@@ -407,13 +412,13 @@ class Plan:
                 lays.append(dict(spec=spec, xin=xin, pre=pre, act=act, stats=stats, gn=base))
                 xin, xin8 = act, act8
             self.tower[tower] = lays
-        cls_logits = self.buf('cls_logits', self.M, cls_ld, dtype=torch.float32)
+        cls_logits = self.buf('cls_logits', self.M, cls_ld, dtype=torch.float32, zero=st.ctr_on_cls)      # (zero: the three floats behind the centerness column)
         regctr = self.buf('regctr', self.M, 8, dtype=torch.float32, zero=True)
         f.conv(ops.conv_desc(self.tower['cls_convs'][3]['act'], st.t16_ptr('head.cls_w'), cls_logits, n=N, grid=ls,
                              src_hw=ls, dst_hw=ls, cs=256, cd=ncls, cd_pad=cls_pad, ldd=cls_ld, kh=3, kw=3, stride=1, pad=1,
                              flags=L.CONV_OUT_F32, bias=st.t32_ptr('head.cls_b'), workspace=self.conv_ws))
         f.conv(ops.conv_desc(self.tower['reg_convs'][3]['act'], st.t16_ptr('head.regctr_w'), regctr, n=N, grid=ls,
-                             src_hw=ls, dst_hw=ls, cs=256, cd=5, cd_pad=64, ldd=8, kh=3, kw=3, stride=1, pad=1,
+                             src_hw=ls, dst_hw=ls, cs=256, cd=nreg, cd_pad=64, ldd=8, kh=3, kw=3, stride=1, pad=1,
                              flags=L.CONV_OUT_F32, bias=st.t32_ptr('head.regctr_b'), workspace=self.conv_ws_side),
                side=FSIDE)
         self._fside = FSIDE
@@ -691,9 +696,9 @@ class Plan:
             return cd_
         towers = (('reg_convs', BT), ('cls_convs', 0)) if BT else (('cls_convs', 0), ('reg_convs', 0))
         # the predictors' weight gradients need nothing from this pass but the loss gradients: first thing on the side stream
-        self._wgrad(ol, None, lp.g_cls, self.tower['cls_convs'][3]['act'], N, ls, ls, cy=st.cls_pad, cd=st.num_classes, wregion='head.cls_w',
+        self._wgrad(ol, None, lp.g_cls, self.tower['cls_convs'][3]['act'], N, ls, ls, cy=st.cls_pad, cd=st.cls_rows, wregion='head.cls_w',
                     bregion='head.cls_b', side=SIDE)
-        self._wgrad(ol, None, lp.g_rc, self.tower['reg_convs'][3]['act'], N, ls, ls, cy=64, cd=5, wregion='head.regctr_w',
+        self._wgrad(ol, None, lp.g_rc, self.tower['reg_convs'][3]['act'], N, ls, ls, cy=64, cd=4 if st.ctr_on_cls else 5, wregion='head.regctr_w',
                     bregion='head.regctr_b', side=SIDE)
         # (measured, tools/experiments_r2.txt (exp_r2t) / exp_r2u.sh: weight gradients that start while the head's large data-gradient launches
         # still run cost more than the idle side stream saves - predictors first: 5.97 vs 5.94 ms, tower halves: 6.10 vs 6.05)
@@ -720,10 +725,10 @@ class Plan:
             g_act[tower] = self.buf(f'g_{tower}_act3', M, 256)
             if tower == 'cls_convs':
                 ol.conv(gn_records(wsf(self._dgrad('head.cls', lp.g_cls, g_act[tower], N, ls, ls, cs=st.cls_pad, cd=256, k=3, stride=1, pad=1,
-                                                         cs_real=st.num_classes)),
+                                                         cs_real=st.cls_rows)),
                                    tower, 3, sd), side=sd)
             else:
-                ol.conv(gn_records(wsf(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=64, cd=256, k=3, stride=1, pad=1, cs_real=5)),
+                ol.conv(gn_records(wsf(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=64, cd=256, k=3, stride=1, pad=1, cs_real=4 if st.ctr_on_cls else 5)),
                                    tower, 3, sd), side=sd)
         # layer by layer, both towers: their weight gradients go out in two groups of four (layers 3, 2 and layers 1, 0 of
         # both towers) as soon as the GroupNorm backward passes that produce their dY are queued - the side stream works from
@@ -739,7 +744,7 @@ class Plan:
                 gd = ops.gn_desc(lay['pre'], lay['act'], st.t32_ptr(base + '.weight'), st.t32_ptr(base + '.bias'),
                                  lay['stats'], self._gn_workspace('bwd.' + tower), n=N, hw=ls, dy=g_act[tower], dx=g_pre[tower],
                                  dgamma=st.t32_ptr(base + '.weight', st.grad), dbeta=st.t32_ptr(base + '.bias', st.grad),
-                                 dbias=st.t32_ptr(lay['spec'].name + '.bias', st.grad))
+                                 dbias=st.t32_ptr(lay['spec'].name + '.bias', st.grad) if lay['spec'].bias else None)
                 gd.conv_stats = 1 if (tower, i) in gn_from_conv else 0
                 ol.gn_bwd(gd, side=sd)
                 tower_group.append(self._wgrad(ol, lay['spec'], g_pre[tower], lay['xin'], N, ls, ls, side=SIDE, emit=False, no_db=True,
@@ -1082,6 +1087,7 @@ class Engine:
     def plan(self, store, N, H, W, training=True, single_stream=False):
         if store.dirty:
             store.refresh()           # in place where the packs exist; a re-allocation bumps store.generation
+        # (the head options are fixed per store: id(store) stands for them)
         key = (id(store), getattr(store, 'generation', 0), bool(getattr(store, 'defer_head', False)), single_stream, N, H, W, training)
         p = self.plans.pop(key, None)
         if p is None:

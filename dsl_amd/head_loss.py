@@ -22,8 +22,15 @@ class FcosLossPlan:
     LD_RC, LD_GRC = 8, 64
 
     def __init__(self, n, sizes, device, strides=STRIDES, ranges=REGRESS_RANGES, num_classes=80,
-                 radius=1.5, max_gt=1024):
+                 radius=1.5, max_gt=1024, head=None):
+        """head: params.HeadOptions (None = the default head).  centerness_on_reg=False: the centerness logit is column
+        round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
+        self.head = head
+        self.ctr_col = None
+        if head is not None and not head.centerness_on_reg:
+            self.ctr_col = self.LD_CLS
+            self.LD_CLS, self.LD_GCLS = self.LD_CLS + 4, (self.LD_CLS + 1 + 63) // 64 * 64
         self.num_classes = num_classes
         self.n, self.sizes, self.strides, self.device = n, [tuple(s) for s in sizes], strides, device
         self.M = n * sum(h * w for h, w in self.sizes)
@@ -63,6 +70,10 @@ class FcosLossPlan:
                      losses=self.losses, logvec=self.logvec)
         self.desc.ld_cls, self.desc.ld_rc = self.LD_CLS, self.LD_RC
         self.desc.ld_gcls, self.desc.ld_grc = self.LD_GCLS, self.LD_GRC
+        if head is not None:
+            self.desc.head_flags = head.flags()
+        if self.ctr_col is not None:
+            self.desc.g_ctr, self.desc.ld_gctr = self.g_cls.data_ptr() + 2 * self.ctr_col, self.LD_GCLS
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         self.desc.workspace, self.desc.workspace_bytes = L.ptr(self.ws), need
@@ -121,6 +132,8 @@ class FcosLossPlan:
 
     def bind_outputs(self, cls_logits, regctr, scales):
         ops.set_ptrs(self.desc, cls_logits=cls_logits, regctr=regctr, scales=scales)
+        if self.ctr_col is not None:
+            self.desc.ctr, self.desc.ld_ctr = self.desc.cls_logits + 4 * self.ctr_col, self.LD_CLS
 
     def assign(self):
         L.check(L.lib.dsl_fcos_assign(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_assign')

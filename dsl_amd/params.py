@@ -117,24 +117,66 @@ def class_layout(num_classes):
     return _round_up(num_classes, 64), _round_up(num_classes, 4)
 
 
-def head_specs():
+class HeadOptions:
+    """The FCOSHead options that reach the kernels and the parameter layout, fixed per model (a ParamStore holds one; every plan
+    of that store is built for it).  The defaults are the fcos_semi "tricks" head; configs/fcos/fcos_r50_caffe_fpn_gn-head_*.py
+    turn all of them off:
+      center_sampling    False: a location is positive for a box it lies inside of (fcos_head.py:676-678)
+      norm_on_bbox       False: distances = exp(scale * x), targets in pixels (fcos_head.py:162-167, :618)
+      centerness_on_reg  False: conv_centerness reads the classification tower (fcos_head.py:155-158)
+      iou_loss           True: IoULoss, -log(clamp(iou, 1e-6)) (losses/iou_loss.py:14-36); False: GIoULoss
+      conv_bias          False: the eight tower convolutions have no bias ('auto' in front of GroupNorm, mmcv ConvModule)"""
+    FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
+
+    def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True):
+        self.center_sampling, self.norm_on_bbox, self.centerness_on_reg = bool(center_sampling), bool(norm_on_bbox), bool(centerness_on_reg)
+        self.iou_loss, self.conv_bias = bool(iou_loss), bool(conv_bias)
+
+    def key(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+    def is_default(self):
+        return self.key() == HeadOptions().key()
+
+    def flags(self):
+        """dsl_fcos_desc.head_flags / dsl_det_desc.head_flags."""
+        return ((0 if self.center_sampling else L.HEAD_INSIDE_BOX) | (0 if self.norm_on_bbox else L.HEAD_RAW_TARGETS | L.HEAD_EXP_DECODE)
+                | (L.HEAD_IOU_LOSS if self.iou_loss else 0))
+
+    def __repr__(self):
+        return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in self.FIELDS) + ')'
+
+
+def head_specs(conv_bias=True):
     specs = []
     for tower in ('cls_convs', 'reg_convs'):
-        specs += [ConvSpec(f'bbox_head.{tower}.{i}.conv', 256, 256, 3, 1, 1, bias=True) for i in range(4)]
+        specs += [ConvSpec(f'bbox_head.{tower}.{i}.conv', 256, 256, 3, 1, 1, bias=conv_bias) for i in range(4)]
     return specs
 
 
 class ParamStore:
     """Flat buffers + named views.  One instance for the student, one for the EMA teacher."""
 
-    def __init__(self, num_classes=80, device='cpu', backbone='resnet'):
+    def __init__(self, num_classes=80, device='cpu', backbone='resnet', head=None):
         assert backbone in ('resnet', 'rla')
+        self.head = head or HeadOptions()
         self.cls_pad, self.cls_ld = class_layout(num_classes)
         self.num_classes, self.backbone = num_classes, backbone
+        # centerness_on_reg=False: conv_centerness is one more row of the classification predictor, behind the classes' last group
+        # of four (row cls_ld; the rows between C and cls_ld are zero and stay zero, as the padding rows do), and its logit one more
+        # column of that predictor's fp32 output, whose rows are four floats longer (DESIGN 3.3)
+        self.ctr_on_cls = not self.head.centerness_on_reg
+        self.cls_rows = self.cls_ld + 1 if self.ctr_on_cls else num_classes     # stored rows that are computed and trained
+        self.logit_ld = self.cls_ld + 4 if self.ctr_on_cls else self.cls_ld      # row stride of the fp32 logits
+        if self.ctr_on_cls:
+            if self.cls_ld + 4 > MAX_CLASSES:
+                raise NotImplementedError(f'dsl_amd hot path: centerness_on_reg=False needs num_classes <= {MAX_CLASSES - 4} (its logit is a '
+                                          f'column of the classification predictor, at most {MAX_CLASSES} columns), got {num_classes}')
+            self.cls_pad = _round_up(self.cls_rows, 64)
         self.defer_head = False       # deferred head update (FlatSGD._sync_defer decides; engine.Plan.defer reads it)
         self._pending_ev = None
         bspecs = backbone_specs() if backbone == 'resnet' else rla_backbone_specs()
-        self.convs = {s.name: s for s in bspecs + neck_specs() + head_specs()}
+        self.convs = {s.name: s for s in bspecs + neck_specs() + head_specs(self.head.conv_bias)}
         self.extra_bns = rla_stage_bns() if backbone == 'rla' else []        # BatchNorms that follow no convolution
         self.train_regions = {}     # name -> (offset, numel, shape)   (shape = storage shape)
         self.frozen_regions = {}
@@ -280,8 +322,12 @@ class ParamStore:
         out['bbox_head.conv_cls.bias'] = cb[:self.num_classes]
         out['bbox_head.conv_reg.weight'] = rw[:4].permute(0, 3, 1, 2)
         out['bbox_head.conv_reg.bias'] = rb[:4]
-        out['bbox_head.conv_centerness.weight'] = rw[4:5].permute(0, 3, 1, 2)
-        out['bbox_head.conv_centerness.bias'] = rb[4:5]
+        if self.ctr_on_cls:       # (row 4 of the regression predictor is then zero and stays zero)
+            out['bbox_head.conv_centerness.weight'] = cw[self.cls_ld:self.cls_ld + 1].permute(0, 3, 1, 2)
+            out['bbox_head.conv_centerness.bias'] = cb[self.cls_ld:self.cls_ld + 1]
+        else:
+            out['bbox_head.conv_centerness.weight'] = rw[4:5].permute(0, 3, 1, 2)
+            out['bbox_head.conv_centerness.bias'] = rb[4:5]
         sc = self.tview('head.scales', tb)
         for i in range(5):
             out[f'bbox_head.scales.{i}.scale'] = sc[i]
@@ -440,9 +486,9 @@ class ParamStore:
             items, start = [], 0
             for name, (off, n) in lay.items():
                 if name == 'head.cls':
-                    w, co, cop, taps, cin, sc = self.tview('head.cls_w'), self.num_classes, self.cls_pad, 9, 256, None
+                    w, co, cop, taps, cin, sc = self.tview('head.cls_w'), self.cls_rows, self.cls_pad, 9, 256, None
                 elif name == 'head.regctr':
-                    w, co, cop, taps, cin, sc = self.tview('head.regctr_w'), 5, 64, 9, 256, None
+                    w, co, cop, taps, cin, sc = self.tview('head.regctr_w'), (4 if self.ctr_on_cls else 5), 64, 9, 256, None
                 else:
                     s = self.convs[name.split('#')[0]]
                     w, co, cop, taps, cin = self.tview(s.name + '.weight'), s.cout, s.cout_pad, s.k * s.k, s.cin_store

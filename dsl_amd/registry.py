@@ -96,6 +96,20 @@ def _wrap(v):
     return v
 
 
+def _merge_cfg(child, base):
+    """mmcv Config._merge_a_into_b for dict keys: child values win, dicts merge recursively unless the child's says `_delete_`."""
+    out = dict(base)
+    for k, v in child.items():
+        if isinstance(v, dict):
+            v = dict(v)
+            if not v.pop('_delete_', False) and isinstance(out.get(k), dict):
+                v = _merge_cfg(v, out[k])
+            else:
+                v = _merge_cfg(v, {})
+        out[k] = v
+    return out
+
+
 class Config:
     """Python-file configs, attribute access, dotted-key overrides."""
 
@@ -109,6 +123,18 @@ class Config:
         with open(path) as f:
             exec(compile(f.read(), path, 'exec'), g)
         d = {k: v for k, v in g.items() if not k.startswith('__') and not callable(v) and not isinstance(v, type(os))}
+        # mmcv Config._file2dict: `_base_` names one file or a list of files (relative to this one) whose keys this file's are merged
+        # into, dict by dict; a dict that carries `_delete_=True` replaces the inherited one instead
+        bases = d.pop('_base_', None)
+        if bases:
+            merged = {}
+            for b in ([bases] if isinstance(bases, str) else bases):
+                bd = Config.fromfile(os.path.join(os.path.dirname(os.path.abspath(path)), b))._cfg
+                dup = set(merged) & set(bd)
+                if dup:
+                    raise KeyError(f'{path}: duplicate keys in the _base_ files: {sorted(dup)}')
+                merged.update(bd)
+            d = _merge_cfg(d, merged)
         return Config(d, path)
 
     def merge_from_dict(self, options):

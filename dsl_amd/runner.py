@@ -321,17 +321,22 @@ class OptimizerHook(Hook):
 
 @HOOKS.register_module()
 class StepLrUpdaterHook(Hook):
-    """policy='step', by_epoch, gamma 0.1, linear warm-up from warmup_ratio over warmup_iters."""
+    """policy='step', by_epoch, gamma 0.1; warm-up over warmup_iters: 'linear' from warmup_ratio, or 'constant' at warmup_ratio
+    (mmcv LrUpdaterHook.get_warmup_lr; configs/fcos/fcos_r50_caffe_fpn_gn-head_1x_coco.py uses 'constant')."""
 
     def __init__(self, step, gamma=0.1, warmup=None, warmup_iters=0, warmup_ratio=0.1, by_epoch=True, **kw):
         self.step = [step] if isinstance(step, int) else list(step)
         self.gamma, self.warmup, self.warmup_iters, self.warmup_ratio = gamma, warmup, warmup_iters, warmup_ratio
+        if warmup not in (None, 'linear', 'constant'):
+            raise NotImplementedError(f"dsl_amd: lr warm-up {warmup!r} is not built (None, 'linear', 'constant')")
 
     def _factor(self, runner):
         f = self.gamma ** sum(1 for s in self.step if runner.epoch >= s)
         if self.warmup == 'linear' and runner.iter < self.warmup_iters:
             k = (1 - runner.iter / self.warmup_iters) * (1 - self.warmup_ratio)
             f = f * (1 - k)
+        elif self.warmup == 'constant' and runner.iter < self.warmup_iters:
+            f = f * self.warmup_ratio
         return f
 
     def before_train_iter(self, runner):

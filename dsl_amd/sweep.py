@@ -15,7 +15,7 @@ from . import _lib as L
 
 class DetectPlan:
     def __init__(self, n, sizes, strides, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05,
-                 iou_thr=0.5, ld_cls=80, ld_rc=8):
+                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None):
         d = L.DetDesc()
         d.nlvl, d.n = len(sizes), n
         d.h, d.w = L.seg5([s[0] for s in sizes]), L.seg5([s[1] for s in sizes])
@@ -23,6 +23,8 @@ class DetectPlan:
         d.num_classes, d.nms_pre, d.max_per_img = num_classes, nms_pre, max_per_img
         d.score_thr, d.iou_thr = score_thr, iou_thr
         d.ld_cls, d.ld_rc = ld_cls, ld_rc
+        d.head_flags = head_flags      # DSL_HEAD_EXP_DECODE: norm_on_bbox=False
+        self.ctr_col = ctr_col         # centerness_on_reg=False: the centerness logit is this column of the logits' rows
         self.dets = torch.zeros(n, max_per_img, 5, device=device)
         self.labels = torch.zeros(n, max_per_img, dtype=torch.int64, device=device)
         self.count = torch.zeros(n, dtype=torch.int32, device=device)
@@ -38,6 +40,8 @@ class DetectPlan:
 
     def bind(self, cls_logits, regctr, scales):
         self.desc.cls_logits, self.desc.regctr, self.desc.scales = L.ptr(cls_logits), L.ptr(regctr), L.ptr(scales)
+        if self.ctr_col is not None:
+            self.desc.ctr, self.desc.ld_ctr = self.desc.cls_logits + 4 * self.ctr_col, self.desc.ld_cls
         self._keep = [cls_logits, regctr, scales]
 
     def set_meta(self, img_shapes, scale_factors, rescale):
@@ -69,7 +73,8 @@ def detect_device(det, img, img_metas, rescale=False, store=None, single_stream=
         cfg = det.test_cfg or {}
         nms = cfg.get('nms', {})
         dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
-                        ld_cls=store.cls_ld, nms_pre=cfg.get('nms_pre', 1000),
+                        ld_cls=store.logit_ld, head_flags=store.head.flags() & L.HEAD_EXP_DECODE,
+                        ctr_col=store.cls_ld if store.ctr_on_cls else None, nms_pre=cfg.get('nms_pre', 1000),
                         max_per_img=cfg.get('max_per_img', 100), score_thr=cfg.get('score_thr', 0.05),
                         iou_thr=nms.get('iou_threshold', nms.get('iou_thr', 0.5)))
         dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))

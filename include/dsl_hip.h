@@ -484,7 +484,20 @@ typedef struct dsl_fcos_desc {
   size_t workspace_bytes;              /* are added up in a fixed order (bit-identical results from run to run) */
   float* logvec;                       /* NULL, or fp32 [5]: cls, bbox, centerness, [sisoft if soft_weight != 0,] their sum - the log
                                         * vector of BaseDetector._parse_losses (detectors/base.py:175-208) without a framework op */
+  /* Head options; all zero = the fcos_semi "tricks" head (center_sampling, norm_on_bbox, centerness_on_reg, GIoULoss) */
+  int32_t head_flags;                  /* DSL_HEAD_* below */
+  int32_t ld_ctr;                      /* row stride of ctr (floats) */
+  const float* ctr;                    /* NULL: the centerness logit is regctr[m][4].  Else ctr[m * ld_ctr] - centerness_on_reg=False
+                                        * (fcos_head.py:155-158): conv_centerness reads the classification tower, its logit is a column
+                                        * of the classification predictor's output; regctr then needs 4 columns only */
+  void* g_ctr;                         /* bf16, with ctr: the centerness gradient goes to g_ctr[m * ld_gctr], column 4 of g_rc gets 0 */
+  int32_t ld_gctr;                     /* row stride of g_ctr (bf16 elements); read only when g_ctr is set */
 } dsl_fcos_desc;
+#define DSL_HEAD_INSIDE_BOX 1   /* center_sampling=False: inside = min(l, t, r, b) > 0, radius unused (fcos_head.py:676-678) */
+#define DSL_HEAD_RAW_TARGETS 2  /* norm_on_bbox=False, assignment: bbox_targets stay in pixels (fcos_head.py:618) */
+#define DSL_HEAD_EXP_DECODE 4   /* norm_on_bbox=False, loss and detection: distances = exp(scale * x), no stride multiply
+                                 * (fcos_head.py:162-167); the gradient goes through exp into g_rc and g_scales */
+#define DSL_HEAD_IOU_LOSS 8     /* loss_bbox = IoULoss(linear=False, eps=1e-6): -log(clamp(iou, eps)) (losses/iou_loss.py:14-36) */
 size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d);
 
 int dsl_fcos_points(const dsl_fcos_desc* d, float* points /* [P][2] */, void* stream);
@@ -547,6 +560,9 @@ typedef struct dsl_det_desc {
   int64_t* det_labels;                       /* [n][max_per_img] */
   int32_t* det_count;                        /* [n] */
   void* workspace; size_t workspace_bytes;
+  int32_t head_flags;                        /* DSL_HEAD_EXP_DECODE: exp(scale x) without the stride (fcos_head.py:162-167); 0 = relu * stride */
+  int32_t ld_ctr;                            /* row stride of ctr (floats); read only when ctr is set */
+  const float* ctr;                          /* NULL: centerness logit = regctr[m][4]; else ctr[m * ld_ctr] (fcos_head.py:155-158) */
 } dsl_det_desc;
 size_t dsl_detect_workspace_bytes(const dsl_det_desc* d);
 int dsl_fcos_detect(const dsl_det_desc* d, void* stream);
