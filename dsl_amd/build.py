@@ -11,6 +11,9 @@ LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libdsl_hip.so')
 SOURCES = ['api.hip', 'conv.hip', 'wgrad.hip', 'misc.hip', 'fcos_loss.hip', 'optim.hip', 'detect.hip', 'rla.hip', 'datapath.hip', 'comm.hip', 'stem.hip', 'bneck.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-unused-value']
+# conv.hip only: its kernels carry a scalar hot header in front of their by-value parameter struct, which this makes the
+# compiler preload into user SGPRs (.amdhsa_user_sgpr_kernarg_preload_length; DESIGN.md section 3.1, "front end")
+EXTRA_FLAGS = {'conv.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=16']}
 
 
 def _hipcc():
@@ -37,7 +40,7 @@ def build_lib(force=False, verbose=True):
     def compile_one(so):
         s, o = so
         if force or _stale(o, [s] + hdrs):
-            cmd = [hipcc] + FLAGS + ['-c', s, '-o', o]
+            cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(os.path.basename(s), []) + ['-c', s, '-o', o]
             if verbose:
                 print(' '.join(cmd), flush=True)
             subprocess.check_call(cmd)

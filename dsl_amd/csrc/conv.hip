@@ -54,6 +54,17 @@ struct ConvK {
   const float* gnstats;               // [(segment, image)][cd / 8][mean, rstd] of the forward pass
 };
 
+// Hot header of conv_pipe_kernel / conv_f8_kernel: what a workgroup needs to find its tile and to address its first weight tile, as
+// leading scalar kernel parameters IN FRONT of the by-value ConvK.  Leading scalars are preloaded into user SGPRs at wave launch
+// (-mllvm -amdgpu-kernarg-preload-count, dsl_amd/build.py; a by-value struct is not), so the tile decode and the first weight DMA
+// wait for no scalar load.  2 + 2 + 10 = 14 SGPRs: with the kernarg pointer that is the whole user-SGPR budget of 16.  The kernels
+// read these fields from the parameters only, never from `p`; the launches pass them out of the same ConvK (CONV_HOT_ARGS).
+#define CONV_HOT_PARAMS                                                                                                   \
+  const uint16_t* h_wgt, const uint16_t* h_src, const int h_wrow, const int h_xcd_chunk, const int h_gx, const int h_gy, \
+      const int h_splits, const int h_kt_per_split, const int h_ktiles, const int h_kc, const int h_kw, const int h_lds
+#define CONV_HOT_ARGS(k) \
+  (k).wgt, (k).src, (int)(k).wrow, (k).xcd_chunk, (k).gx, (k).gy, (k).splits, (k).kt_per_split, (k).ktiles, (k).kc, (k).kw, (k).lds
+
 __device__ __forceinline__ u32x4 relu_bf16x8(u32x4 v) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -91,6 +102,32 @@ __device__ __forceinline__ void decode_pixel(const ConvK& p, int gp, int& seg, i
   x = rem - y * p.gw[seg];
 }
 
+// decode_pixel plus the pixel's source geometry for conv_pipe_kernel's prologue, with every table read at a compile-time index and
+// the segment's entries SELECTED per lane: constant indices are scalar loads (lgkmcnt), whereas a per-lane index into the kernel
+// arguments is a vector load - and the vmcnt wait on it would also wait for the first weight tile's DMA, which is in flight by
+// then (vmcnt retires in order).  Same integers as decode_pixel + p.sh[seg], p.sw[seg], (int)p.soff[seg].
+__device__ __forceinline__ void decode_pixel_src(const ConvK& p, int gp, int& img, int& y, int& x, int& sh, int& sw, int& soff) {
+  int ps = p.pxstart[0], gh = p.gh[0], gw = p.gw[0];
+  sh = p.sh[0];
+  sw = p.sw[0];
+  soff = (int)p.soff[0];
+#pragma unroll
+  for (int s = 1; s < DSL_MAX_SEG; ++s) {
+    const bool in = s < p.nseg && gp >= p.pxstart[s];
+    ps = in ? p.pxstart[s] : ps;
+    gh = in ? p.gh[s] : gh;
+    gw = in ? p.gw[s] : gw;
+    sh = in ? p.sh[s] : sh;
+    sw = in ? p.sw[s] : sw;
+    soff = in ? (int)p.soff[s] : soff;
+  }
+  const int q = gp - ps;
+  const int hw = gh * gw;
+  img = q / hw;
+  const int rem = q - img * hw;
+  y = rem / gw;
+  x = rem - y * gw;
+}
 
 // Epilogue for 4 consecutive output channels of one pixel (shared by every conv kernel).
 __device__ __forceinline__ void conv_epilogue4(const ConvK& p, long long dpix, long long apix, int co, float v[4]) {
@@ -347,17 +384,19 @@ __device__ __forceinline__ void conv_out_index(const ConvK& p, int gp, long long
 }
 
 // split-K second pass: sum the fp32 partial tiles and run the epilogue
-__global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const ConvK p) {
-  const int totpx = p.pxstart[p.nseg];
-  const int c4 = p.cd_pad / 4;
+// (hot header as in conv_pipe_kernel: the partial-sum loads need only these five, preloaded, values)
+__global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const float* h_ws, const int h_totpx, const int h_cd_pad, const int h_cd,
+                                                                   const int h_splits, const ConvK p) {
+  const int totpx = h_totpx;
+  const int c4 = h_cd_pad / 4;
   const long long total = (long long)totpx * c4;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int gp = (int)(i / c4);
     const int co = (int)(i - (long long)gp * c4) * 4;
-    if (co >= p.cd) continue;
+    if (co >= h_cd) continue;
     f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    for (int sp = 0; sp < p.splits; ++sp)
-      s += *reinterpret_cast<const f32x4*>(p.ws + ((long long)sp * totpx + gp) * p.cd_pad + co);
+    for (int sp = 0; sp < h_splits; ++sp)
+      s += *reinterpret_cast<const f32x4*>(h_ws + ((long long)sp * totpx + gp) * h_cd_pad + co);
     long long dpix, apix;
     conv_out_index(p, gp, dpix, apix);
     float v[4] = {s[0], s[1], s[2], s[3]};
@@ -1202,7 +1241,7 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvK& p, f32x16 (&acc)
 }
 
 template <int BCO, int BPX, int WCO, int WPX, int NST, bool SMC = false, bool GNB = false>
-__global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p) {
+__global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(CONV_HOT_PARAMS, const ConvK p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int T = 64 * WCO * WPX;
   constexpr int RPP = T / 8;                 // tile rows filled per pass (8 lanes per 128-byte row)
@@ -1225,71 +1264,83 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
 #ifdef DSL_ABLATE_BUILD
   if (p.dbg & 128) return;                   // launch + dispatch floor
 #endif
-  const int wi = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= p.xcd_chunk || wi >= p.gx * p.gy * p.splits) return;
-  const int bz = wi / (p.gx * p.gy);
-  const int rem_t = wi - bz * (p.gx * p.gy);
-  const int by = rem_t / p.gx;
-  const int co0 = (rem_t - by * p.gx) * BCO;
+  const int wi = (int)(blockIdx.x & 7) * h_xcd_chunk + (int)(blockIdx.x >> 3);
+  if ((int)(blockIdx.x >> 3) >= h_xcd_chunk || wi >= h_gx * h_gy * h_splits) return;
+  const int bz = wi / (h_gx * h_gy);
+  const int rem_t = wi - bz * (h_gx * h_gy);
+  const int by = rem_t / h_gx;
+  const int co0 = (rem_t - by * h_gx) * BCO;
   const int px0 = by * BPX;
-  const int totpx = p.pxstart[p.nseg];
   const int dt = tid, dwave = wave;
   const int lrow = dt >> 3;
   const int chunk = (dt & 7) ^ ((dt >> 4) & 7);       // source chunk that belongs in LDS slot (dt & 7) of this row
 
   // buffer resources: base shifted back by `margin` so that every VALID tap has a non-negative per-lane offset
   // (the hardware range-checks the per-lane offset, not the scalar one)
-  const unsigned margin = (unsigned)(p.kw * p.lds * 2);
+  const unsigned margin = (unsigned)(h_kw * h_lds * 2);
   const __amdgpu_buffer_rsrc_t rs_src =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const unsigned char*>(p.src) - margin), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wgt = __builtin_amdgcn_make_buffer_rsrc((void*)p.wgt, 0, 0x7fffffff, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const unsigned char*>(h_src) - margin), 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_wgt = __builtin_amdgcn_make_buffer_rsrc((void*)h_wgt, 0, 0x7fffffff, 0x00020000);
 
-  const int kt0 = bz * p.kt_per_split;
+  const int kt0 = bz * h_kt_per_split;
 #ifdef DSL_ABLATE_BUILD
-  const int kt1 = (p.dbg & 8) ? kt0 + 1 : min(kt0 + p.kt_per_split, p.ktiles);
+  const int kt1 = (p.dbg & 8) ? kt0 + 1 : min(kt0 + h_kt_per_split, h_ktiles);
 #else
-  const int kt1 = min(kt0 + p.kt_per_split, p.ktiles);
+  const int kt1 = min(kt0 + h_kt_per_split, h_ktiles);
 #endif
-  int cidx = kt0 % p.kc;
-  int tap_r = (kt0 / p.kc) / p.kw, tap_s = (kt0 / p.kc) % p.kw;
+  // ---- weights first: tile kt0's WPASS weight pieces need nothing but the hot header (rs_wgt, w_voff, w_pass, w_soff below are
+  // header arithmetic), so they are issued HERE, into ring slot 0, in front of the pixel decode: the segment tables' scalar loads
+  // and the two integer divisions per pixel pass then run under a DMA that is already in flight.  The tile's XPASS pixel pieces
+  // follow after the decode (the first pieces() call of the prologue below skips the weight pieces).
+  const unsigned w_voff = (unsigned)(lrow * h_wrow + chunk * 8) * 2u;
+  const unsigned w_pass = (unsigned)(RPP * h_wrow) * 2u;
+  unsigned w_soff = (unsigned)(co0 * h_wrow + kt0 * BK) * 2u;
+#pragma unroll
+  for (int i = 0; i < WPASS; ++i) {
+#ifdef DSL_ABLATE_BUILD
+    if (p.dbg & 2) continue;
+#endif
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_wgt, (lptr_t)(smem + (i * RPP + dwave * 8) * 128), 16, w_voff, w_soff + i * w_pass, 0, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);                  // (the decode below is not to be scheduled in front of the DMA issue)
+
+  const int totpx = p.pxstart[p.nseg];
+  int cidx = kt0 % h_kc;
+  int tap_r = (kt0 / h_kc) / h_kw, tap_s = (kt0 / h_kc) % h_kw;
 
   unsigned r_cur[XPASS], r_step[XPASS], r_mask[XPASS];
   int r_y[XPASS], r_x[XPASS], r_hw[XPASS];            // SMC: top-left source pixel of the window, source size
 #pragma unroll
   for (int i = 0; i < XPASS; ++i) {
     const int gp = px0 + lrow + RPP * i;
-    int seg = 0, img = 0, y = 0, x = 0;
+    int img, y, x, sh, sw, soff;
     const bool ok = gp < totpx;
-    if (ok) decode_pixel(p, gp, seg, img, y, x);
-    const int sh = p.sh[seg], sw = p.sw[seg];
+    decode_pixel_src(p, ok ? gp : 0, img, y, x, sh, sw, soff);   // (past the end: pixel 0 of segment 0, every tap masked off below)
     if (SMC) {
       r_y[i] = ok ? y * p.stride - p.pad : -100000;    // not ok: every tap fails the bounds test
       r_x[i] = x * p.stride - p.pad;
       r_hw[i] = (sh << 16) | sw;
-      r_cur[i] = (unsigned)(((int)(p.soff[seg]) + img * sh * sw + r_y[i] * sw + r_x[i]) * 16) + margin;
+      r_cur[i] = (unsigned)((soff + img * sh * sw + r_y[i] * sw + r_x[i]) * 16) + margin;
       r_step[i] = r_mask[i] = 0;
       continue;
     }
     const int row0 = p.mode == 0 ? y * p.stride - p.pad : y + p.pad;               // source row of tap r = 0
-    const int col0 = p.mode == 0 ? x * p.stride - p.pad : x + p.pad - (p.kw - 1);  // leftmost source column
+    const int col0 = p.mode == 0 ? x * p.stride - p.pad : x + p.pad - (h_kw - 1);  // leftmost source column
     unsigned m = 0;
     for (int r = 0; r < p.kh; ++r) {
       const int sy = p.mode == 0 ? row0 + r : row0 - r;
       if (ok && (unsigned)sy < (unsigned)sh) m |= 1u << r;
     }
-    for (int s_ = 0; s_ < p.kw; ++s_) {
+    for (int s_ = 0; s_ < h_kw; ++s_) {
       const int sx = p.mode == 0 ? col0 + s_ : x + p.pad - s_;
       if (ok && (unsigned)sx < (unsigned)sw) m |= 0x100u << s_;
     }
     r_mask[i] = m;
-    const unsigned pitch = (unsigned)(sw * p.lds * 2);
+    const unsigned pitch = (unsigned)(sw * h_lds * 2);
     r_step[i] = p.mode == 0 ? pitch : 0u - pitch;
-    const unsigned base = (unsigned)(((int)(p.soff[seg]) + img * sh * sw + row0 * sw + col0) * p.lds + chunk * 8) * 2u + margin;
+    const unsigned base = (unsigned)((soff + img * sh * sw + row0 * sw + col0) * h_lds + chunk * 8) * 2u + margin;
     r_cur[i] = base + (unsigned)tap_r * r_step[i];
   }
-  const unsigned w_voff = (unsigned)(lrow * (int)p.wrow + chunk * 8) * 2u;
-  const unsigned w_pass = (unsigned)(RPP * (int)p.wrow) * 2u;
-  unsigned w_soff = (unsigned)(co0 * (int)p.wrow + kt0 * BK) * 2u;
 
   // ---- DMA of one K tile = LPT "pieces" per thread (XPASS pixel passes, then WPASS weight passes), issued a few at
   // a time between the MFMAs: a burst of all pieces right after the barrier fills the CU's address queue and
@@ -1305,15 +1356,17 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
   // SALU instructions per K tile and wave, and these in-order waves with 8 MFMAs per K tile (the 128 x 128 / 128 x 64 tiles) are
   // bound by their own instruction count (probe: + 32 SALU or VALU per K tile = + 9 ... 12 % on the layer2-4 shapes).
   unsigned t_sel = (1u << tap_r) | (0x100u << tap_s);
-  unsigned t_soff = (unsigned)((p.mode == 0 ? tap_s : p.kw - 1 - tap_s) * p.lds * 2 + cidx * 128);
+  unsigned t_soff = (unsigned)((p.mode == 0 ? tap_s : h_kw - 1 - tap_s) * h_lds * 2 + cidx * 128);
   unsigned t_wv = w_voff;
-  int c_left = p.kc - cidx;        // tiles until the channel blocks wrap (tap advance)
+  int c_left = h_kc - cidx;        // tiles until the channel blocks wrap (tap advance)
   unsigned r_v[XPASS];             // this lane's source offsets for the CURRENT tap (out of range where the tap leaves the image):
 #pragma unroll                     // they change with the tap only, so the per-piece mask test moves into the tap advance
   for (int i = 0; i < XPASS; ++i) r_v[i] = (r_mask[i] & t_sel) == t_sel ? r_cur[i] : 0x80000000u;
   // ld_off: byte offset of the ring slot being filled (the K loop derives it from the slot it reads: no second ring counter)
-  auto pieces = [&](auto lo_c, auto hi_c, const unsigned ld_off) {
+  // skipw_c: the prologue's first tile, whose weight pieces went out in front of the pixel decode (the tile still counts LPT pieces)
+  auto pieces_of = [&](auto lo_c, auto hi_c, const unsigned ld_off, auto skipw_c) {
     constexpr int LO = decltype(lo_c)::value, HI = decltype(hi_c)::value;
+    constexpr bool SKIPW = decltype(skipw_c)::value;
     unsigned char* stage = smem + ld_off;
     const bool live = kt_next < kt1;      // (used by the 8-channel-source variant only)
     const unsigned s_off = t_soff;
@@ -1322,9 +1375,9 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
     bool s_ok = false;
     if (SMC) {                    // this lane's tap of the K tile
       const int tap = kt_next * 8 + chunk;
-      s_tr = tap / p.kw;
-      s_ts = tap - s_tr * p.kw;
-      s_ok = live && tap < p.kh * p.kw;
+      s_tr = tap / h_kw;
+      s_ts = tap - s_tr * h_kw;
+      s_ok = live && tap < p.kh * h_kw;
     }
 #pragma unroll
     for (int j = LO; j < HI; ++j) {
@@ -1343,7 +1396,7 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
           so = s_off;
         }
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_src, (lptr_t)(stage + TILE_W + (j * RPP + dwave * 8) * 128), 16, v, so, 0, 0);
-      } else {
+      } else if (!SKIPW) {
         const int i = j - XPASS;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_wgt, (lptr_t)(stage + (i * RPP + dwave * 8) * 128), 16, wv,
                                                  w_soff + i * w_pass, 0, 0);
@@ -1355,8 +1408,8 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
       if (--c_left != 0) {
         t_soff += 128;             // same tap, next 64-channel block
       } else {                     // tap advance: every kc-th tile (uniform branch)
-        c_left = p.kc;
-        const bool s_wrap = tap_s + 1 == p.kw;
+        c_left = h_kc;
+        const bool s_wrap = tap_s + 1 == h_kw;
         tap_s = s_wrap ? 0 : tap_s + 1;
         if (s_wrap) {
           ++tap_r;
@@ -1364,7 +1417,7 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
           for (int i = 0; i < XPASS; ++i) r_cur[i] += r_step[i];
         }
         t_sel = (1u << tap_r) | (0x100u << tap_s);
-        t_soff = (unsigned)((p.mode == 0 ? tap_s : p.kw - 1 - tap_s) * p.lds * 2);
+        t_soff = (unsigned)((p.mode == 0 ? tap_s : h_kw - 1 - tap_s) * h_lds * 2);
 #pragma unroll
         for (int i = 0; i < XPASS; ++i) r_v[i] = (r_mask[i] & t_sel) == t_sel ? r_cur[i] : 0x80000000u;
       }
@@ -1377,13 +1430,17 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
       }
     }
   };
+  auto pieces = [&](auto lo_c, auto hi_c, const unsigned ld_off) { pieces_of(lo_c, hi_c, ld_off, std::false_type{}); };
   using c0_t = std::integral_constant<int, 0>;
   using cp0_t = std::integral_constant<int, P0>;
   using cp1_t = std::integral_constant<int, P1>;
   using clpt_t = std::integral_constant<int, LPT>;
 
 #ifdef DSL_ABLATE_BUILD
-  if (p.dbg & 256) return;                   // + kernel-argument loads and the per-pixel decode
+  if (p.dbg & 256) {                         // + kernel-argument loads and the per-pixel decode (and the first tile's weight DMA,
+    wait_vmcnt<0>();                         // which is in flight by now)
+    return;
+  }
 #endif
   f32x16 acc[CT][PT];
 #pragma unroll
@@ -1446,9 +1503,17 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
   // Static priority for the second-dispatched half of an 8-wave workgroup: on each SIMD the younger wave otherwise loses every
   // issue arbitration to its partner and reaches the K loop's barrier ~750 cycles late (tools/trace_conv.py); measured + 0.75 % on the step.
   if (WCO * WPX == 8 && wave >= 4) __builtin_amdgcn_s_setprio(1);
-  // prologue: NST-1 whole tiles + the first pieces of the NST-th
+  // prologue: NST-1 whole tiles + the first pieces of the NST-th.  Tile kt0 went out weights first: its WPASS weight pieces in
+  // front of the decode, its XPASS pixel pieces here - still all LPT of them before any piece of tile kt0 + 1.
+  // vmcnt ledger at the wait below, per thread, in issue order (the counter retires these loads in order):
+  //   tile kt0                   WPASS + XPASS = LPT pieces   <- must have landed
+  //   tiles kt0+1 .. kt0+NST-2   (NST - 2) * LPT pieces       <- may stay in flight
+  //   tile kt0+NST-1             P0 pieces                    <- may stay in flight
+  // so "at most (NST - 2) * LPT + P0 outstanding" is exactly "tile kt0 complete", whatever the order inside tile kt0.
+  static_assert(NST >= 2, "the prologue issues tile kt0 on its own");
+  pieces_of(c0_t{}, clpt_t{}, 0u, std::true_type{});
 #pragma unroll
-  for (int s = 0; s < NST - 1; ++s) pieces(c0_t{}, clpt_t{}, (unsigned)(s * STAGE));
+  for (int s = 1; s < NST - 1; ++s) pieces(c0_t{}, clpt_t{}, (unsigned)(s * STAGE));
   pieces(c0_t{}, cp0_t{}, (unsigned)((NST - 1) * STAGE));
   wait_vmcnt<(NST - 2) * LPT + P0>();
   __builtin_amdgcn_s_barrier();
@@ -1556,7 +1621,7 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
   if (p.dbg & 16) return;
 #endif
 
-  if (p.splits > 1) {                      // split-K: raw fp32 partial tile -> workspace [split][pixel][cd_pad]
+  if (h_splits > 1) {                      // split-K: raw fp32 partial tile -> workspace [split][pixel][cd_pad]
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) {
       const int gp = px0 + wave_px * (32 * PT) + pt * 32 + (lane & 31);
@@ -1596,7 +1661,7 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_pipe_kernel(const ConvK p
 // ================================================================================================
 typedef int v8i32 __attribute__((ext_vector_type(8)));
 template <int BCO, int BPX, int WCO, int WPX, int NST>
-__global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) {
+__global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(CONV_HOT_PARAMS, const ConvK p) {
   constexpr bool SMC = false;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int T = 64 * WCO * WPX;
@@ -1614,12 +1679,12 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) 
   // XCD-aware tile order (workgroups are dealt round-robin to the XCDs: equal b % 8 = same XCD): every XCD owns a contiguous run of tiles in (cout tile
   // fastest, then pixel tile, then K split) order, so neighbouring pixel tiles - which share their halo rows - and
   // the cout tiles of one pixel range hit the same L2 instead of being fetched into up to three of them.
-  const int wi = (int)(blockIdx.x & 7) * p.xcd_chunk + (int)(blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= p.xcd_chunk || wi >= p.gx * p.gy * p.splits) return;
-  const int bz = wi / (p.gx * p.gy);
-  const int rem_t = wi - bz * (p.gx * p.gy);
-  const int by = rem_t / p.gx;
-  const int co0 = (rem_t - by * p.gx) * BCO;
+  const int wi = (int)(blockIdx.x & 7) * h_xcd_chunk + (int)(blockIdx.x >> 3);
+  if ((int)(blockIdx.x >> 3) >= h_xcd_chunk || wi >= h_gx * h_gy * h_splits) return;
+  const int bz = wi / (h_gx * h_gy);
+  const int rem_t = wi - bz * (h_gx * h_gy);
+  const int by = rem_t / h_gx;
+  const int co0 = (rem_t - by * h_gx) * BCO;
   const int px0 = by * BPX;
   const int totpx = p.pxstart[p.nseg];
   const int lrow = tid >> 3;
@@ -1627,15 +1692,15 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) 
 
   // buffer resources: base shifted back by `margin` so that every VALID tap has a non-negative per-lane offset
   // (the hardware range-checks the per-lane offset, not the scalar one)
-  const unsigned margin = (unsigned)(p.kw * p.lds);            // (1-byte elements)
+  const unsigned margin = (unsigned)(h_kw * h_lds);            // (1-byte elements)
   const __amdgpu_buffer_rsrc_t rs_src =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const unsigned char*>(p.src) - margin), 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_wgt = __builtin_amdgcn_make_buffer_rsrc((void*)p.wgt, 0, 0x7fffffff, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)(reinterpret_cast<const unsigned char*>(h_src) - margin), 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_wgt = __builtin_amdgcn_make_buffer_rsrc((void*)h_wgt, 0, 0x7fffffff, 0x00020000);
 
-  const int kt0 = bz * p.kt_per_split;
-  const int kt1 = min(kt0 + p.kt_per_split, p.ktiles);
-  int cidx = kt0 % p.kc;
-  int tap_r = (kt0 / p.kc) / p.kw, tap_s = (kt0 / p.kc) % p.kw;
+  const int kt0 = bz * h_kt_per_split;
+  const int kt1 = min(kt0 + h_kt_per_split, h_ktiles);
+  int cidx = kt0 % h_kc;
+  int tap_r = (kt0 / h_kc) / h_kw, tap_s = (kt0 / h_kc) % h_kw;
 
   unsigned r_cur[XPASS], r_step[XPASS], r_mask[XPASS];
   int r_y[XPASS], r_x[XPASS], r_hw[XPASS];            // SMC: top-left source pixel of the window, source size
@@ -1655,25 +1720,25 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) 
       continue;
     }
     const int row0 = p.mode == 0 ? y * p.stride - p.pad : y + p.pad;               // source row of tap r = 0
-    const int col0 = p.mode == 0 ? x * p.stride - p.pad : x + p.pad - (p.kw - 1);  // leftmost source column
+    const int col0 = p.mode == 0 ? x * p.stride - p.pad : x + p.pad - (h_kw - 1);  // leftmost source column
     unsigned m = 0;
     for (int r = 0; r < p.kh; ++r) {
       const int sy = p.mode == 0 ? row0 + r : row0 - r;
       if (ok && (unsigned)sy < (unsigned)sh) m |= 1u << r;
     }
-    for (int s_ = 0; s_ < p.kw; ++s_) {
+    for (int s_ = 0; s_ < h_kw; ++s_) {
       const int sx = p.mode == 0 ? col0 + s_ : x + p.pad - s_;
       if (ok && (unsigned)sx < (unsigned)sw) m |= 0x100u << s_;
     }
     r_mask[i] = m;
-    const unsigned pitch = (unsigned)(sw * p.lds);
+    const unsigned pitch = (unsigned)(sw * h_lds);
     r_step[i] = p.mode == 0 ? pitch : 0u - pitch;
-    const unsigned base = (unsigned)(((int)(p.soff[seg]) + img * sh * sw + row0 * sw + col0) * p.lds + chunk * 16) + margin;
+    const unsigned base = (unsigned)(((int)(p.soff[seg]) + img * sh * sw + row0 * sw + col0) * h_lds + chunk * 16) + margin;
     r_cur[i] = base + (unsigned)tap_r * r_step[i];
   }
-  const unsigned w_voff = (unsigned)(lrow * (int)p.wrow + chunk * 16);
-  const unsigned w_pass = (unsigned)(RPP * (int)p.wrow);
-  unsigned w_soff = (unsigned)(co0 * (int)p.wrow + kt0 * 128);
+  const unsigned w_voff = (unsigned)(lrow * h_wrow + chunk * 16);
+  const unsigned w_pass = (unsigned)(RPP * h_wrow);
+  unsigned w_soff = (unsigned)(co0 * h_wrow + kt0 * 128);
 
   // ---- DMA of one K tile = LPT "pieces" per thread (XPASS pixel passes, then WPASS weight passes), issued a few at
   // a time between the MFMAs: a burst of all pieces right after the barrier fills the CU's address queue and
@@ -1690,15 +1755,15 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) 
     unsigned char* stage = smem + ld_slot * STAGE;
     const bool live = kt_next < kt1;
     const unsigned sel = live ? ((1u << tap_r) | (0x100u << tap_s)) : 0xffffffffu;
-    const unsigned s_off = (unsigned)((p.mode == 0 ? tap_s : p.kw - 1 - tap_s) * p.lds + cidx * 128);
+    const unsigned s_off = (unsigned)((p.mode == 0 ? tap_s : h_kw - 1 - tap_s) * h_lds + cidx * 128);
     const unsigned wv = live ? w_voff : 0x80000000u;
     int s_tr = 0, s_ts = 0;
     bool s_ok = false;
     if (SMC) {                    // this lane's tap of the K tile
       const int tap = kt_next * 8 + chunk;
-      s_tr = tap / p.kw;
-      s_ts = tap - s_tr * p.kw;
-      s_ok = live && tap < p.kh * p.kw;
+      s_tr = tap / h_kw;
+      s_ts = tap - s_tr * h_kw;
+      s_ok = live && tap < p.kh * h_kw;
     }
 #pragma unroll
     for (int j = LO; j < HI; ++j) {
@@ -1724,8 +1789,8 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) 
       ++kt_next;
       ld_slot = (ld_slot + 1 == NST) ? 0 : ld_slot + 1;
       w_soff += BK * 2;
-      const bool c_wrap = cidx + 1 == p.kc;
-      const bool s_wrap = c_wrap && tap_s + 1 == p.kw;
+      const bool c_wrap = cidx + 1 == h_kc;
+      const bool s_wrap = c_wrap && tap_s + 1 == h_kw;
       cidx = c_wrap ? 0 : cidx + 1;
       tap_s = s_wrap ? 0 : (c_wrap ? tap_s + 1 : tap_s);
       tap_r += s_wrap ? 1 : 0;
@@ -1814,7 +1879,7 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(const ConvK p) 
   }
   wait_vmcnt<0>();                         // the out-of-range tail DMAs still write (zeros) into the ring
 
-  if (p.splits > 1) {                      // split-K: raw fp32 partial tile -> workspace [split][pixel][cd_pad]
+  if (h_splits > 1) {                      // split-K: raw fp32 partial tile -> workspace [split][pixel][cd_pad]
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) {
       const int gp = px0 + wave_px * (32 * PT) + pt * 32 + (lane & 31);
@@ -2121,7 +2186,7 @@ extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
                           (int)lds);                                                                          \
       attr_set3 = true;                                                                                       \
     }                                                                                                         \
-    hipLaunchKernelGGL((conv_pipe_kernel<A, B, C_, D, S_>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, k); \
+    hipLaunchKernelGGL((conv_pipe_kernel<A, B, C_, D, S_>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, CONV_HOT_ARGS(k), k); \
   } while (0)
 #define LAUNCH3G(A, B, C_, D, S_)                                                                              \
   do {                                                                                                        \
@@ -2131,7 +2196,7 @@ extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
                           (int)lds);                                                                          \
       attr_set3g = true;                                                                                      \
     }                                                                                                         \
-    hipLaunchKernelGGL((conv_pipe_kernel<A, B, C_, D, S_, false, true>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, k); \
+    hipLaunchKernelGGL((conv_pipe_kernel<A, B, C_, D, S_, false, true>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, CONV_HOT_ARGS(k), k); \
   } while (0)
     if (fp8) {
       DSL_CHECK(!force_v2_kernel && (pick == 0 || pick == 1 || pick == 3), "dsl_conv2d: no fp8 kernel for this shape (tile config %d)", pick);
@@ -2143,7 +2208,7 @@ extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
                           (int)lds);                                                                          \
       attr_8 = true;                                                                                          \
     }                                                                                                         \
-    hipLaunchKernelGGL((conv_f8_kernel<A, B, C_, D, S_>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, k); \
+    hipLaunchKernelGGL((conv_f8_kernel<A, B, C_, D, S_>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, CONV_HOT_ARGS(k), k); \
   } while (0)
       switch (pick) {
         case 0: LAUNCH8(256, 192, 4, 2, 2); break;
@@ -2172,7 +2237,7 @@ extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
           if (smallc) {
             static bool a4 = false;
             if (!a4) { hipFuncSetAttribute((const void*)conv_pipe_kernel<64, 256, 1, 8, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a4 = true; }
-            hipLaunchKernelGGL((conv_pipe_kernel<64, 256, 1, 8, 2, true>), dim3(8 * k.xcd_chunk), dim3(512), lds, st, k);
+            hipLaunchKernelGGL((conv_pipe_kernel<64, 256, 1, 8, 2, true>), dim3(8 * k.xcd_chunk), dim3(512), lds, st, CONV_HOT_ARGS(k), k);
           } else {
             LAUNCH3(64, 256, 1, 8, 2);
           }
@@ -2190,7 +2255,7 @@ extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
       const long long total = (long long)px * (d->cd_pad / 4);
       int blocks = (int)((total + 255) / 256);
       if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, k);
+      hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, k.ws, k.pxstart[k.nseg], k.cd_pad, k.cd, k.splits, k);
     }
     DSL_LAUNCH_CHECK("conv_glds_kernel");
     return 0;

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 python -c "from dsl_amd.build import build_lib; build_lib(verbose=False)" 2>/dev/null
 mkdir -p dsl_amd/lib/ablate
 for f in conv wgrad bneck; do      # the three sources that carry ablation knobs (bneck: DSL_BNECK_DBG = 1 / 2, phase cut-offs)
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -DDSL_ABLATE_BUILD -Iinclude -c dsl_amd/csrc/$f.hip -o dsl_amd/lib/ablate/$f.o 2>/dev/null &
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -DDSL_ABLATE_BUILD $([ $f = conv ] && echo -mllvm -amdgpu-kernarg-preload-count=16) -Iinclude -c dsl_amd/csrc/$f.hip -o dsl_amd/lib/ablate/$f.o 2>/dev/null &
 done
 wait
 objs=$(ls dsl_amd/lib/*.o | grep -v "/conv.o\|/wgrad.o\|/bneck.o")

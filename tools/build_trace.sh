@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/.."
 python -c "from dsl_amd.build import build_lib; build_lib(verbose=False)" 2>/dev/null
 mkdir -p dsl_amd/lib/trace
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -DDSL_TRACE_BUILD -Iinclude -c dsl_amd/csrc/conv.hip -o dsl_amd/lib/trace/conv.o 2>/dev/null
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -DDSL_TRACE_BUILD -mllvm -amdgpu-kernarg-preload-count=16 -Iinclude -c dsl_amd/csrc/conv.hip -o dsl_amd/lib/trace/conv.o 2>/dev/null
 objs=$(ls dsl_amd/lib/*.o | grep -v "/conv.o")
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs dsl_amd/lib/trace/conv.o -o dsl_amd/lib/libdsl_hip_trace.so
 echo built dsl_amd/lib/libdsl_hip_trace.so
