@@ -106,6 +106,7 @@ class FcosDesc(C.Structure):
 
 # dsl_fcos_desc.head_flags / dsl_det_desc.head_flags (0 = the fcos_semi "tricks" head)
 HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
+MAX_AUG = 16      # DSL_MAX_AUG: views merged by dsl_fcos_detect_collect / dsl_fcos_detect_finish
 
 
 class DetDesc(C.Structure):
@@ -191,6 +192,8 @@ if hasattr(lib, 'dsl_groupnorm_workspace_bytes'):
     lib.dsl_groupnorm_workspace_bytes.restype = C.c_size_t
 if hasattr(lib, 'dsl_detect_workspace_bytes'):
     lib.dsl_detect_workspace_bytes.restype = C.c_size_t
+if hasattr(lib, 'dsl_detect_aug_workspace_bytes'):
+    lib.dsl_detect_aug_workspace_bytes.restype = C.c_size_t
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
 _SIGS = {
     'dsl_conv2d': [_vp, _vp], 'dsl_conv2d_workspace_bytes': [_vp], 'dsl_conv2d_gn_fusable': [_vp], 'dsl_conv2d_wgrad': [_vp, _vp], 'dsl_wgrad_splits': [_vp],
@@ -222,6 +225,8 @@ _SIGS = {
     'dsl_ema_lerp': [_vp, _vp, _l, _f, _vp], 'dsl_ema_lerp_bf16': [_vp, _vp, _vp, _l, _f, _vp], 'dsl_cast_bf16': [_vp, _vp, _l, _vp],
     'dsl_pack_dgrad': [_vp, _vp, _vp, _i, _i, _i, _i, _vp], 'dsl_pack_dgrad_batched': [_vp, _i, _i, _vp],
     'dsl_detect_workspace_bytes': [_vp], 'dsl_fcos_detect': [_vp, _vp],
+    'dsl_detect_aug_workspace_bytes': [_vp, _i], 'dsl_fcos_detect_collect': [_vp, _vp, _i, _i, _i, _vp, C.c_size_t, _vp],
+    'dsl_fcos_detect_finish': [_vp, _i, _i, _vp, C.c_size_t, _vp],
     'dsl_pseudo_label_fuse': [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
     'dsl_comm_unique_id': [_vp],
     'dsl_comm_init_rank': [_vp, _i, _vp, _i],

@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void image_prep_kernel(const PrepK p) {
     return;
   }
   // undo RandomFlip, then PatchShuffle: position in the resized image
-  int xr = it.flip ? it.new_w - 1 - x : x, yr = y;
+  int xr = (it.flip & 1) ? it.new_w - 1 - x : x, yr = (it.flip & 2) ? it.new_h - 1 - y : y;      // bit 0 horizontal, bit 1 vertical
   if (it.ps_mode == 1) xr = xr < it.new_w - it.ps_crop ? xr + it.ps_crop : xr - (it.new_w - it.ps_crop);
   if (it.ps_mode == 2) yr = yr < it.new_h - it.ps_crop ? yr + it.ps_crop : yr - (it.new_h - it.ps_crop);
   int v[3];

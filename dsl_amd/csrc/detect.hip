@@ -6,6 +6,11 @@
 // un-vendored: class-offset trick boxes + label*(max+1), suppress IoU > thr, offset 0, scores sorted
 // descending) of the reference, replacing the GPU->CPU numpy->JSON round trip of
 // mmdet/runner/hooks/unlabel_pred_hook.py:194-293.
+//
+// Test-time augmentation (BBoxTestMixin.aug_test_bboxes / merge_aug_bboxes, dense_heads/dense_test_mixins.py:38-108, 173-200;
+// bbox_mapping_back / bbox_flip, core/bbox/transforms.py:5-55) splits the same work where the reference's with_nms=False
+// returns: dsl_fcos_detect_collect does a view's top-k, decode, clip and map-back into a pool of candidate rows,
+// dsl_fcos_detect_finish the threshold, compaction, sort, NMS and cut over the pool of all views.
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -27,6 +32,19 @@ struct DetK {
   float* dets; long long* det_labels; int* det_count;
   // workspace
   float* keys; int* sel; int* selcnt; float* cbox; float* cscore; int* clabel; int* ccount; float* pairscore;
+  // merged views (dsl_fcos_detect_finish): candidate rows [box 4, centerness, num_classes scores] of pool_ld floats, row =
+  // pair index / num_classes; `nlvl` then counts (view, level) groups and the per-level arrays above are not read
+  const float* pool; int pool_ld;
+};
+
+// what dsl_fcos_detect_collect adds to a view's DetK
+constexpr int AUG_MAGIC = 0x41554731;
+struct AugK {
+  int view, flip;              // DSL_FLIP_*
+  float* rows; int ld;         // the pool's rows; this view's start at (view * nlvl) * nms_pre
+  int* rec;                    // the pool's record per view [view][4]: AUG_MAGIC, nlvl, nms_pre, num_classes of its collect
+  int* selcnt;                 // the pool's valid rows per (view, level)
+  float* sf;                   // the pool's copy of every view's scale factor [view][4]
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
@@ -219,16 +237,8 @@ __global__ void det_pairscore_kernel(const DetK p) {
   p.pairscore[((long long)img * p.nlvl + lvl) * p.nms_pre * p.num_classes + t] = out;
 }
 
-// one candidate: decode the box of pair i (level, slot, class) and store it in candidate slot `out`
-__device__ __forceinline__ void det_emit(const DetK& p, int img, const float* ps, int i, unsigned out) {
-  if (out >= (unsigned)CAND_CAP) return;
-  const float f = ps[i];
-  const int c = i % p.num_classes;
-  const int slot = (i / p.num_classes) % p.nms_pre;
-  const int lvl = i / (p.num_classes * p.nms_pre);
-  const int P = p.h[lvl] * p.w[lvl];
-  const int loc = p.sel[((long long)img * p.nlvl + lvl) * p.nms_pre + slot];
-  const int m = p.mstart[lvl] + img * P + loc;
+// the box of location `loc` of (image, level), row m of the head outputs: decode and clip to the image's img_shape
+__device__ __forceinline__ void det_decode(const DetK& p, int img, int lvl, int loc, int m, float* b) {
   const float* rc = p.rc + (long long)m * p.ld_rc;
   const int s = p.stride[lvl];
   const int y = loc / p.w[lvl], x = loc - y * p.w[lvl];
@@ -238,11 +248,29 @@ __device__ __forceinline__ void det_emit(const DetK& p, int img, const float* ps
 #pragma unroll
   for (int e = 0; e < 4; ++e) d[e] = p.exp_decode ? expf(rc[e] * sc) : fmaxf(rc[e] * sc, 0.f) * (float)s;      // fcos_head.py:159-167 (eval)
   const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
-  float b[4] = {px - d[0], py - d[1], px + d[2], py + d[3]};
+  b[0] = px - d[0]; b[1] = py - d[1]; b[2] = px + d[2]; b[3] = py + d[3];
   b[0] = fminf(fmaxf(b[0], 0.f), W);                    // distance2bbox clip (transforms.py:150-160)
   b[1] = fminf(fmaxf(b[1], 0.f), H);
   b[2] = fminf(fmaxf(b[2], 0.f), W);
   b[3] = fminf(fmaxf(b[3], 0.f), H);
+}
+
+// one candidate: decode the box of pair i (level, slot, class) and store it in candidate slot `out`
+__device__ __forceinline__ void det_emit(const DetK& p, int img, const float* ps, int i, unsigned out) {
+  if (out >= (unsigned)CAND_CAP) return;
+  const float f = ps[i];
+  const int c = i % p.num_classes;
+  float b[4];
+  if (p.pool) {          // merged views: the row holds the box, decoded and mapped back by its view's collect
+    const float* row = p.pool + (long long)(i / p.num_classes) * p.pool_ld;
+    b[0] = row[0]; b[1] = row[1]; b[2] = row[2]; b[3] = row[3];
+  } else {
+    const int slot = (i / p.num_classes) % p.nms_pre;
+    const int lvl = i / (p.num_classes * p.nms_pre);
+    const int P = p.h[lvl] * p.w[lvl];
+    const int loc = p.sel[((long long)img * p.nlvl + lvl) * p.nms_pre + slot];
+    det_decode(p, img, lvl, loc, p.mstart[lvl] + img * P + loc, b);
+  }
   if (p.scale_factors) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) b[e] = b[e] / p.scale_factors[4 * img + e];
@@ -318,6 +346,86 @@ __global__ __launch_bounds__(1024) void det_compact_kernel(const DetK p) {
       [&](int i) { const float f = ps[i]; return f > 0.f && __float_as_uint(f) == prefix; },
       [&](int i, unsigned out) { det_emit(p, img, ps, i, out); }, &s_total);
   if (threadIdx.x == 0) p.ccount[img] = min((int)s_total, CAND_CAP);
+}
+
+// ---- test-time augmentation: collect a view into the pool, finish over the pool ------------------------------------
+// One thread per (level, slot, column) of the view's selected locations (n == 1): column 0 decodes the box, clips it to the
+// view's img_shape (get_bboxes with rescale=False), maps it back - bbox_flip against img_shape (transforms.py:20-30), then the
+// division by the 4-element scale factor (:54) - and stores it with the centerness; column 1 + c stores sigmoid(cls c).
+__global__ void aug_collect_kernel(const DetK p, const AugK a) {
+  const int lvl = blockIdx.y;
+  const int cols = p.num_classes + 1;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nsel = p.selcnt[lvl];
+  if (t == 0) {
+    a.selcnt[a.view * p.nlvl + lvl] = nsel;
+    if (lvl == 0) {
+      for (int e = 0; e < 4; ++e) a.sf[4 * a.view + e] = p.scale_factors[e];
+      int* rec = a.rec + 4 * a.view;
+      rec[0] = AUG_MAGIC; rec[1] = p.nlvl; rec[2] = p.nms_pre; rec[3] = p.num_classes;
+    }
+  }
+  if (t >= p.nms_pre * cols) return;
+  const int slot = t / cols, col = t - slot * cols;
+  if (slot >= nsel) return;            // rows behind the count are never read
+  const int loc = p.sel[lvl * p.nms_pre + slot];
+  const int m = p.mstart[lvl] + loc;
+  float* row = a.rows + ((long long)(a.view * p.nlvl + lvl) * p.nms_pre + slot) * a.ld;
+  if (col > 0) {
+    row[4 + col] = sigmoidf_(p.cls[(long long)m * p.ld_cls + col - 1]);
+    return;
+  }
+  float b[4];
+  det_decode(p, 0, lvl, loc, m, b);
+  const float H = p.img_shapes[0], W = p.img_shapes[1];
+  if (a.flip & 1) { const float x1 = W - b[2], x2 = W - b[0]; b[0] = x1; b[2] = x2; }
+  if (a.flip & 2) { const float y1 = H - b[3], y2 = H - b[1]; b[1] = y1; b[3] = y2; }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) row[e] = b[e] / p.scale_factors[e];
+  row[4] = sigmoidf_(p.ctr[(long long)m * p.ld_ctr]);
+}
+
+// det_pairscore_kernel over the pool: pair = (view, level, slot, class) in that order, the order merge_aug_bboxes concatenates
+__device__ __forceinline__ bool aug_view_ok(const int* rec, int view, int nlvl, const DetK& p) {
+  const int* r = rec + 4 * view;
+  return r[0] == AUG_MAGIC && r[1] == nlvl && r[2] == p.nms_pre && r[3] == p.num_classes;
+}
+__global__ void aug_pairscore_kernel(const DetK p, const int* rec, int nlvl, const int* selcnt, long long npair) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= npair) return;
+  const long long r = t / p.num_classes;
+  const int c = (int)(t - r * p.num_classes);
+  const int slot = (int)(r % p.nms_pre), grp = (int)(r / p.nms_pre);
+  float out = -1.f;
+  // a view without this pool's record (not collected for this image, or with other nlvl / nms_pre / num_classes) gives no pair:
+  // its counts and rows are not read
+  if (aug_view_ok(rec, grp / nlvl, nlvl, p) && slot < selcnt[grp]) {
+    const float* row = p.pool + r * p.pool_ld;
+    const float score = row[5 + c];
+    if (score > p.score_thr) out = score * row[4];
+  }
+  p.pairscore[t] = out;
+}
+
+// rescale=False: the kept boxes in the FIRST view's coordinates (dense_test_mixins.py:99-104)
+__global__ void aug_scale_kernel(const DetK p, const float* sf) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= p.det_count[0] * 4) return;
+  p.dets[(t >> 2) * 5 + (t & 3)] *= sf[t & 3];
+}
+
+// last launch of finish: det_count = -1 when a view's record is missing or does not match, and the records are consumed, so that
+// the counts of this image cannot pass for the next image's in a reused pool
+__global__ void aug_status_kernel(const DetK p, int* rec, int nlvl, int nviews) {
+  bool ok = true;
+  for (int v = 0; v < nviews; ++v) ok = ok && aug_view_ok(rec, v, nlvl, p);
+  __syncthreads();                   // one block: every thread has read the records
+  if (!ok)                           // the boxes of the views that were there are not a result
+    for (int i = threadIdx.x; i < p.max_per_img * 5; i += blockDim.x) p.dets[i] = 0.f;
+  if (threadIdx.x == 0) {
+    for (int v = 0; v < nviews; ++v) rec[4 * v] = 0;
+    if (!ok) p.det_count[0] = -1;
+  }
 }
 
 __device__ __forceinline__ bool iou_gt(const float* a, const float* b, float thr) {
@@ -512,6 +620,72 @@ size_t ws_layout(const dsl_det_desc* d, size_t off[8]) {
   return o;
 }
 
+// the pool of `nviews` views: [0] per-view records and valid rows per (view, level), [1] scale factors, [2] rows, then what finish needs
+size_t aug_layout(const dsl_det_desc* d, int nviews, size_t off[9]) {
+  const size_t rows = (size_t)nviews * d->nlvl * d->nms_pre;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
+  off[0] = take((size_t)nviews * (4 + d->nlvl) * 4);             // per-view records [nviews][4], then the counts [nviews][nlvl]
+  off[1] = take((size_t)nviews * 16);
+  off[2] = take(rows * (d->num_classes + 5) * 4);
+  off[3] = take(rows * d->num_classes * 4);                      // pairscore
+  off[4] = take((size_t)CAND_CAP * 16);                           // cbox
+  off[5] = take((size_t)CAND_CAP * 4);                            // cscore
+  off[6] = take((size_t)CAND_CAP * 4);                            // clabel
+  off[7] = take((size_t)4 * (1 + DET_CB));                        // ccount
+  off[8] = o;
+  return o;
+}
+
+int aug_check(const dsl_det_desc* d, int nviews, const char* who) {
+  DSL_CHECK(d && d->nlvl >= 1 && d->nlvl <= DSL_MAX_SEG, "%s: bad descriptor", who);
+  DSL_CHECK(nviews >= 1 && nviews <= DSL_MAX_AUG, "%s: %d views, at most DSL_MAX_AUG = %d are merged", who, nviews, DSL_MAX_AUG);
+  DSL_CHECK(d->n == 1, "%s: one image per view (n == 1, as aug_test_bboxes), got n = %d", who, d->n);
+  DSL_CHECK(d->num_classes >= 1, "%s: num_classes must be >= 1, got %d", who, d->num_classes);
+  DSL_CHECK(d->nms_pre > 0, "%s: nms_pre must be > 0, got %d", who, d->nms_pre);
+  DSL_CHECK((long long)nviews * d->nlvl * d->nms_pre * d->num_classes < (1ll << 31), "%s: nms_pre * num_classes too large", who);
+  return 0;
+}
+
+void launch_nms(const DetK& k, int n, hipStream_t st) {
+  const size_t lds = (size_t)CAND_CAP * 8 + (size_t)k.max_per_img * 16;
+  static bool attr = false;
+  if (!attr) {
+    hipFuncSetAttribute((const void*)det_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)CAND_CAP * 8 + NMS_THREADS * 16));
+    attr = true;
+  }
+  hipLaunchKernelGGL(det_nms_kernel, dim3(n), dim3(NMS_THREADS), lds, st, k);
+}
+
+// fills the per-view part of a DetK (geometry, head outputs, the view's scratch)
+int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
+  size_t off[8];
+  const size_t need = ws_layout(d, off);
+  DSL_CHECK(d->workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, d->workspace_bytes, need);
+  memset(&k, 0, sizeof(k));
+  k.nlvl = d->nlvl; k.n = d->n; k.num_classes = d->num_classes; k.nms_pre = d->nms_pre; k.max_per_img = d->max_per_img;
+  int m = 0;
+  for (int l = 0; l < d->nlvl; ++l) {
+    k.h[l] = d->h[l]; k.w[l] = d->w[l]; k.stride[l] = d->stride[l];
+    k.mstart[l] = m;
+    m += d->n * d->h[l] * d->w[l];
+  }
+  k.mstart[d->nlvl] = m;
+  k.score_thr = d->score_thr; k.iou_thr = d->iou_thr;
+  k.cls = d->cls_logits; k.ld_cls = d->ld_cls; k.rc = d->regctr; k.ld_rc = d->ld_rc;
+  k.ctr = d->ctr ? d->ctr : d->regctr + 4; k.ld_ctr = d->ctr ? d->ld_ctr : d->ld_rc;
+  k.exp_decode = (d->head_flags & DSL_HEAD_EXP_DECODE) ? 1 : 0;
+  k.scales = d->scales; k.img_shapes = d->img_shapes; k.scale_factors = d->scale_factors;
+  k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;
+  unsigned char* ws = (unsigned char*)d->workspace;
+  k.keys = (float*)(ws + off[0]); k.sel = (int*)(ws + off[1]); k.selcnt = (int*)(ws + off[2]);
+  k.cbox = (float*)(ws + off[3]); k.cscore = (float*)(ws + off[4]); k.clabel = (int*)(ws + off[5]);
+  k.ccount = (int*)(ws + off[6]);
+  k.pairscore = (float*)(ws + off[7]);
+  m_out = m;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t dsl_detect_workspace_bytes(const dsl_det_desc* d) {
@@ -527,31 +701,9 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr ? 4 : 5),
             "dsl_fcos_detect: unsupported layout");
   DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS && d->nms_pre > 0, "dsl_fcos_detect: max_per_img must be in 1..%d", NMS_THREADS);
-  size_t off[8];
-  const size_t need = ws_layout(d, off);
-  DSL_CHECK(d->workspace_bytes >= need, "dsl_fcos_detect: workspace too small (%zu < %zu)", d->workspace_bytes, need);
   DetK k;
-  memset(&k, 0, sizeof(k));
-  k.nlvl = d->nlvl; k.n = d->n; k.num_classes = d->num_classes; k.nms_pre = d->nms_pre; k.max_per_img = d->max_per_img;
-  int m = 0, maxP = 0;
-  for (int l = 0; l < d->nlvl; ++l) {
-    k.h[l] = d->h[l]; k.w[l] = d->w[l]; k.stride[l] = d->stride[l];
-    k.mstart[l] = m;
-    m += d->n * d->h[l] * d->w[l];
-    maxP = max(maxP, d->h[l] * d->w[l]);
-  }
-  k.mstart[d->nlvl] = m;
-  k.score_thr = d->score_thr; k.iou_thr = d->iou_thr;
-  k.cls = d->cls_logits; k.ld_cls = d->ld_cls; k.rc = d->regctr; k.ld_rc = d->ld_rc;
-  k.ctr = d->ctr ? d->ctr : d->regctr + 4; k.ld_ctr = d->ctr ? d->ld_ctr : d->ld_rc;
-  k.exp_decode = (d->head_flags & DSL_HEAD_EXP_DECODE) ? 1 : 0;
-  k.scales = d->scales; k.img_shapes = d->img_shapes; k.scale_factors = d->scale_factors;
-  k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;
-  unsigned char* ws = (unsigned char*)d->workspace;
-  k.keys = (float*)(ws + off[0]); k.sel = (int*)(ws + off[1]); k.selcnt = (int*)(ws + off[2]);
-  k.cbox = (float*)(ws + off[3]); k.cscore = (float*)(ws + off[4]); k.clabel = (int*)(ws + off[5]);
-  k.ccount = (int*)(ws + off[6]);
-  k.pairscore = (float*)(ws + off[7]);
+  int m = 0;
+  if (view_detk(d, k, m, "dsl_fcos_detect")) return -1;
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(k.ccount, 0, sizeof(int) * d->n, st);
   hipMemsetAsync(d->dets, 0, sizeof(float) * 5 * d->n * d->max_per_img, st);
@@ -562,14 +714,84 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   hipLaunchKernelGGL(det_count_kernel, dim3(DET_CB, d->n), dim3(1024), 0, st, k);
   hipLaunchKernelGGL(det_scatter_kernel, dim3(DET_CB, d->n), dim3(1024), 0, st, k);
   hipLaunchKernelGGL(det_compact_kernel, dim3(d->n), dim3(1024), 0, st, k);
-  const size_t lds = (size_t)CAND_CAP * 8 + (size_t)d->max_per_img * 16;
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)det_nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)CAND_CAP * 8 + NMS_THREADS * 16));
-    attr = true;
-  }
-  hipLaunchKernelGGL(det_nms_kernel, dim3(d->n), dim3(NMS_THREADS), lds, st, k);
+  launch_nms(k, d->n, st);
   DSL_LAUNCH_CHECK("dsl_fcos_detect");
+  return 0;
+}
+
+extern "C" size_t dsl_detect_aug_workspace_bytes(const dsl_det_desc* d, int nviews) {
+  if (aug_check(d, nviews, "dsl_detect_aug_workspace_bytes")) return 0;
+  size_t off[9];
+  return aug_layout(d, nviews, off);
+}
+
+extern "C" int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc* pool_desc, int view, int nviews, int flip, void* pool,
+                                       size_t pool_bytes, void* stream) {
+  if (aug_check(d, nviews, "dsl_fcos_detect_collect")) return -1;
+  DSL_CHECK(pool_desc, "dsl_fcos_detect_collect: null pool descriptor");
+  // the pool is laid out by ITS nlvl / nms_pre / num_classes: a view that differs would write into other views' rows
+  DSL_CHECK(d->nlvl == pool_desc->nlvl && d->nms_pre == pool_desc->nms_pre && d->num_classes == pool_desc->num_classes,
+            "dsl_fcos_detect_collect: view %d has nlvl %d, nms_pre %d, num_classes %d, the pool %d, %d, %d", view, d->nlvl, d->nms_pre,
+            d->num_classes, pool_desc->nlvl, pool_desc->nms_pre, pool_desc->num_classes);
+  DSL_CHECK(view >= 0 && view < nviews, "dsl_fcos_detect_collect: view %d of %d", view, nviews);
+  DSL_CHECK(flip >= DSL_FLIP_NONE && flip <= DSL_FLIP_DIAGONAL, "dsl_fcos_detect_collect: flip must be a DSL_FLIP_* code, got %d", flip);
+  DSL_CHECK(d->cls_logits && d->regctr && d->scales && d->img_shapes && d->scale_factors && d->workspace && pool,
+            "dsl_fcos_detect_collect: null pointer (the map-back needs img_shapes and scale_factors)");
+  DSL_CHECK(d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr ? 4 : 5), "dsl_fcos_detect_collect: unsupported layout");
+  size_t off[9];
+  const size_t need = aug_layout(pool_desc, nviews, off);
+  DSL_CHECK(pool_bytes >= need, "dsl_fcos_detect_collect: pool too small (%zu < %zu)", pool_bytes, need);
+  DetK k;
+  int m = 0;
+  if (view_detk(d, k, m, "dsl_fcos_detect_collect")) return -1;
+  unsigned char* pw = (unsigned char*)pool;
+  AugK a;
+  a.view = view; a.flip = flip;
+  a.rec = (int*)(pw + off[0]); a.selcnt = a.rec + 4 * nviews; a.sf = (float*)(pw + off[1]);
+  a.rows = (float*)(pw + off[2]); a.ld = d->num_classes + 5;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(det_key_kernel, dim3((m + 255) / 256), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(det_select_kernel, dim3(d->nlvl, 1), dim3(1024), 0, st, k);
+  const int per_lvl = d->nms_pre * (d->num_classes + 1);
+  hipLaunchKernelGGL(aug_collect_kernel, dim3((per_lvl + 255) / 256, d->nlvl), dim3(256), 0, st, k, a);
+  DSL_LAUNCH_CHECK("dsl_fcos_detect_collect");
+  return 0;
+}
+
+extern "C" int dsl_fcos_detect_finish(const dsl_det_desc* d, int nviews, int rescale, void* pool, size_t pool_bytes, void* stream) {
+  if (aug_check(d, nviews, "dsl_fcos_detect_finish")) return -1;
+  DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS, "dsl_fcos_detect_finish: max_per_img must be in 1..%d, got %d", NMS_THREADS,
+            d->max_per_img);
+  DSL_CHECK(d->dets && d->det_labels && d->det_count && pool, "dsl_fcos_detect_finish: null pointer");
+  size_t off[9];
+  const size_t need = aug_layout(d, nviews, off);
+  DSL_CHECK(pool_bytes >= need, "dsl_fcos_detect_finish: pool too small (%zu < %zu)", pool_bytes, need);
+  unsigned char* pw = (unsigned char*)pool;
+  DetK k;
+  memset(&k, 0, sizeof(k));
+  k.nlvl = nviews * d->nlvl;           // (view, level) groups: only nlvl * nms_pre * num_classes is formed from it
+  k.n = 1; k.num_classes = d->num_classes; k.nms_pre = d->nms_pre; k.max_per_img = d->max_per_img;
+  k.score_thr = d->score_thr; k.iou_thr = d->iou_thr;
+  k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;
+  k.pool = (const float*)(pw + off[2]); k.pool_ld = d->num_classes + 5;
+  k.pairscore = (float*)(pw + off[3]);
+  k.cbox = (float*)(pw + off[4]); k.cscore = (float*)(pw + off[5]); k.clabel = (int*)(pw + off[6]);
+  k.ccount = (int*)(pw + off[7]);
+  const long long npair = (long long)k.nlvl * k.nms_pre * k.num_classes;
+  hipStream_t st = (hipStream_t)stream;
+  hipMemsetAsync(k.ccount, 0, sizeof(int), st);
+  hipMemsetAsync(d->dets, 0, sizeof(float) * 5 * d->max_per_img, st);
+  int* rec = (int*)(pw + off[0]);
+  hipLaunchKernelGGL(aug_pairscore_kernel, dim3((unsigned)((npair + 255) / 256)), dim3(256), 0, st, k, (const int*)rec, d->nlvl,
+                     (const int*)(rec + 4 * nviews), npair);
+  hipLaunchKernelGGL(det_count_kernel, dim3(DET_CB, 1), dim3(1024), 0, st, k);
+  hipLaunchKernelGGL(det_scatter_kernel, dim3(DET_CB, 1), dim3(1024), 0, st, k);
+  hipLaunchKernelGGL(det_compact_kernel, dim3(1), dim3(1024), 0, st, k);
+  launch_nms(k, 1, st);
+  if (!rescale)
+    hipLaunchKernelGGL(aug_scale_kernel, dim3((4 * d->max_per_img + 255) / 256), dim3(256), 0, st, k, (const float*)(pw + off[1]));
+  hipLaunchKernelGGL(aug_status_kernel, dim3(1), dim3(64), 0, st, k, rec, d->nlvl, nviews);
+  DSL_LAUNCH_CHECK("dsl_fcos_detect_finish");
   return 0;
 }
 

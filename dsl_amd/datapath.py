@@ -5,12 +5,13 @@ dozen numbers per image - on the host, exactly as the reference computes it.
 Mirrors, by name and argument meaning (configs/fcos_semi/RLA_*.py:68-82; mmdet/datasets/pipelines/transforms.py):
   Resize(img_scale, multiscale_mode='value'|'range', keep_ratio=True)   :41-332
   PatchShuffle(ratio, ranges, mode)                                     :2143-2248
-  RandomFlip(flip_ratio)  (horizontal)                                  :334-470
+  RandomFlip(flip_ratio)  (drawn: horizontal; forced: any direction)    :334-470
   Normalize(mean, std, to_rgb)                                          :652-690
   Pad(size_divisor)                                                     :581-650
   MultiDataLoader._merge_data2one_batch (pad to the batch's largest)    mmdet/datasets/builder.py:236-267
   RandomAugmentBBox_Fast(aug_type='affine'|'default')                  mmdet/datasets/pipelines/semi_aug.py:344-531
   UBAug()                                                               :2098-2140
+  MultiScaleFlipAug(transforms, img_scale, flip, flip_direction)        mmdet/datasets/pipelines/test_time_aug.py:10-120
 A transform's __call__(results) only DRAWS its random parameters and updates boxes / meta; `GpuBatchPipeline` then renders all
 images of the batch: one launch for the labeled stream, and for the unlabeled stream (the last two transforms) one launch per
 augmentation pass over uint8 canvases (dsl_image_prep_u8 -> dsl_image_aug ... -> dsl_image_normalize).  UBAug's colour,
@@ -21,6 +22,7 @@ test infrastructure).
 """
 import ctypes as C
 import random
+import warnings
 
 import numpy as np
 import torch
@@ -135,6 +137,9 @@ class PatchShuffle:
         return r
 
 
+FLIP_BITS = {'horizontal': 1, 'vertical': 2, 'diagonal': 3}      # dsl_image_prep_item.flip: bit 0 mirrors x, bit 1 mirrors y
+
+
 @PIPELINES.register_module()
 class RandomFlip:
     def __init__(self, flip_ratio=None, direction='horizontal'):
@@ -145,13 +150,21 @@ class RandomFlip:
         if 'flip' not in r:
             r['flip'] = bool(self.flip_ratio is not None and np.random.rand() < self.flip_ratio)
             r['flip_direction'] = 'horizontal' if r['flip'] else None
+        elif r.get('flip_direction') is None:         # forced (MultiScaleFlipAug gives the direction as well)
+            r['flip_direction'] = 'horizontal' if r['flip'] else None
         if r['flip']:
-            w = r['img_shape'][1]
-            for key in r.get('bbox_fields', []):
+            d = r['flip_direction']
+            assert d in FLIP_BITS, f'flip_direction {d!r}'
+            h, w = r['img_shape'][:2]
+            for key in r.get('bbox_fields', []):          # bbox_flip (:401-432)
                 b = r[key]
                 f = b.copy()
-                f[..., 0::4] = w - b[..., 2::4]
-                f[..., 2::4] = w - b[..., 0::4]
+                if FLIP_BITS[d] & 1:
+                    f[..., 0::4] = w - b[..., 2::4]
+                    f[..., 2::4] = w - b[..., 0::4]
+                if FLIP_BITS[d] & 2:
+                    f[..., 1::4] = h - b[..., 3::4]
+                    f[..., 3::4] = h - b[..., 1::4]
                 r[key] = f
         return r
 
@@ -346,6 +359,8 @@ def blur_box_radius(radius, passes=3):
     return float(np.float32(l_ + a))
 
 
+META_KEYS = ('filename', 'ori_filename', 'ori_shape', 'img_shape', 'pad_shape', 'scale_factor', 'scale_idx', 'flip',
+             'flip_direction', 'img_norm_cfg', 'PS', 'PS_place', 'PS_mode')
 _SKIP = ('LoadImageFromFile', 'LoadAnnotations', 'DefaultFormatBundle', 'Collect', 'ImageToTensor')
 
 
@@ -367,6 +382,29 @@ class GpuBatchPipeline:
         assert len(norm) == 1, 'the pipeline needs exactly one Normalize'
         self.norm = norm[0]
 
+    def draw(self, s, h, w):
+        """Host side of one sample of size h x w: every transform draws its parameters and updates boxes / meta; no image work."""
+        r = dict(filename=s.get('filename'), ori_filename=s.get('filename'), ori_shape=(h, w, 3), img_shape=(h, w, 3),
+                 gt_bboxes=np.asarray(s.get('gt_bboxes', np.zeros((0, 4))), np.float32).reshape(-1, 4),
+                 gt_labels=np.asarray(s.get('gt_labels', np.zeros((0,))), np.int64).reshape(-1),
+                 gt_bboxes_ignore=np.asarray(s.get('gt_bboxes_ignore', np.zeros((0, 4))), np.float32).reshape(-1, 4),
+                 bbox_fields=['gt_bboxes_ignore', 'gt_bboxes'], scale_factor=np.ones(4, np.float32))
+        for k in ('scale', 'flip', 'flip_direction'):          # forced parameters (tests; the test pipeline's MultiScaleFlipAug)
+            if k in s:
+                r[k] = s[k]
+        for t in self.transforms:
+            r = t(r)
+        r.setdefault('pad_shape', r['img_shape'])
+        r.setdefault('flip', False)
+        r.setdefault('flip_direction', None)
+        return r
+
+    @staticmethod
+    def meta(r, hc, wc):
+        m = {k: r.get(k) for k in META_KEYS}
+        m['batch_input_shape'] = (hc, wc)
+        return m
+
     def __call__(self, samples):
         n = len(samples)
         results, srcs = [], []
@@ -375,21 +413,7 @@ class GpuBatchPipeline:
             img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
             assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
             srcs.append(img.to(self.device, non_blocking=True).contiguous())
-            h, w = img.shape[:2]
-            r = dict(filename=s.get('filename'), ori_filename=s.get('filename'), ori_shape=(h, w, 3), img_shape=(h, w, 3),
-                     gt_bboxes=np.asarray(s.get('gt_bboxes', np.zeros((0, 4))), np.float32).reshape(-1, 4),
-                     gt_labels=np.asarray(s.get('gt_labels', np.zeros((0,))), np.int64).reshape(-1),
-                     gt_bboxes_ignore=np.asarray(s.get('gt_bboxes_ignore', np.zeros((0, 4))), np.float32).reshape(-1, 4),
-                     bbox_fields=['gt_bboxes_ignore', 'gt_bboxes'], scale_factor=np.ones(4, np.float32))
-            for k in ('scale', 'flip'):          # forced parameters (tests; the test pipeline's MultiScaleFlipAug)
-                if k in s:
-                    r[k] = s[k]
-            for t in self.transforms:
-                r = t(r)
-            r.setdefault('pad_shape', r['img_shape'])
-            r.setdefault('flip', False)
-            r.setdefault('flip_direction', None)
-            results.append(r)
+            results.append(self.draw(s, *img.shape[:2]))
         hc, wc = max(r['pad_shape'][0] for r in results), max(r['pad_shape'][1] for r in results)       # merge/pad
         items = (L.ImagePrepItem * n)()
         inv = (1.0 / self.norm.std.astype(np.float64)).astype(np.float32)
@@ -397,7 +421,7 @@ class GpuBatchPipeline:
             it = items[i]
             it.src, it.src_h, it.src_w = src.data_ptr(), src.shape[0], src.shape[1]
             it.new_h, it.new_w = r['img_shape'][0], r['img_shape'][1]
-            it.flip, it.to_rgb = int(bool(r['flip'])), int(bool(self.norm.to_rgb))
+            it.flip, it.to_rgb = (FLIP_BITS[r['flip_direction'] or 'horizontal'] if r['flip'] else 0), int(bool(self.norm.to_rgb))
             it.ps_mode, it.ps_crop = r.get('_ps', (0, 0))
             for c in range(3):
                 it.mean[c], it.inv_std[c] = float(self.norm.mean[c]), float(inv[c])
@@ -449,13 +473,46 @@ class GpuBatchPipeline:
             srcs = srcs + keep
         self._keep = (srcs, tab)            # alive until the launch has run (stream order)
         self.last_passes = [list(r.get('_aug', ())) for r in results]      # what was rendered (tests replay it on the oracle)
-        meta_keys = ('filename', 'ori_filename', 'ori_shape', 'img_shape', 'pad_shape', 'scale_factor', 'scale_idx', 'flip',
-                     'flip_direction', 'img_norm_cfg', 'PS', 'PS_place', 'PS_mode')
-        metas = []
-        for r in results:
-            m = {k: r.get(k) for k in meta_keys}
-            m['batch_input_shape'] = (hc, wc)
-            metas.append(m)
+        metas = [self.meta(r, hc, wc) for r in results]
         return dict(img=out, img_metas=metas, gt_bboxes=[torch.from_numpy(r['gt_bboxes']) for r in results],
                     gt_labels=[torch.from_numpy(r['gt_labels']) for r in results],
                     gt_bboxes_ignore=[torch.from_numpy(r['gt_bboxes_ignore']) for r in results])
+
+
+@PIPELINES.register_module()
+class MultiScaleFlipAug:
+    """test_time_aug.py:10-120: one view per (scale, flip) of ONE image - scales outer, flip_args = [(False, None)] + [(True, d)
+    for d in flip_direction] inner.  `views(h, w)` is the host side alone (the metas, in that order); __call__(sample) renders
+    them and returns the reference's dict of lists, batched for forward_test: img = [view][1, 3, Hc, Wc], img_metas = [view][1]."""
+
+    def __init__(self, transforms, img_scale=None, scale_factor=None, flip=False, flip_direction='horizontal', device='cuda'):
+        assert img_scale is not None and scale_factor is None, 'the configs give img_scale'
+        many = isinstance(img_scale, (list, tuple)) and len(img_scale) > 0 and isinstance(img_scale[0], (list, tuple))
+        self.img_scale = [tuple(s) for s in (img_scale if many else [img_scale])]      # a config loader may hand lists over
+        assert all(len(s) == 2 for s in self.img_scale), img_scale
+        self.flip = flip
+        self.flip_direction = list(flip_direction) if isinstance(flip_direction, (list, tuple)) else [flip_direction]
+        assert all(d in FLIP_BITS for d in self.flip_direction), self.flip_direction
+        if not self.flip and self.flip_direction != ['horizontal']:          # test_time_aug.py:76-82
+            warnings.warn('flip_direction has no effect when flip is set to False')
+        if self.flip and not any(t['type'] == 'RandomFlip' for t in transforms):
+            warnings.warn('flip has no effect when RandomFlip is not in transforms')
+        self.pipeline = GpuBatchPipeline(transforms, device=device)
+
+    def _forced(self, sample):
+        flip_args = [(False, None)] + ([(True, d) for d in self.flip_direction] if self.flip else [])
+        return [dict(sample, scale=scale, flip=flip, flip_direction=d) for scale in self.img_scale for flip, d in flip_args]
+
+    def views(self, h, w, filename=None):
+        out = []
+        for s in self._forced(dict(filename=filename)):
+            r = self.pipeline.draw(s, h, w)
+            out.append(self.pipeline.meta(r, *r['pad_shape'][:2]))
+        return out
+
+    def __call__(self, sample):
+        img = sample['img']
+        img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
+        sample = dict(sample, img=img.to(self.pipeline.device).contiguous())      # ONE upload: every view renders from the same device copy
+        data = [self.pipeline([s]) for s in self._forced(sample)]
+        return dict(img=[d['img'] for d in data], img_metas=[d['img_metas'] for d in data])

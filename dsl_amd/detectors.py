@@ -16,6 +16,7 @@ from collections import OrderedDict
 
 import ctypes
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -384,6 +385,9 @@ class FCOS(nn.Module):
         # SemiEpochBasedRunner(scale_invariant=True) may hand the batch over WITHOUT its half-scale third image: the stem kernel reads
         # it out of the second one (forward_train(half_scale_copy=True)); set it False and the runner builds the copy with framework ops
         self.half_scale_in_stem = True
+        # sweep.aug_test: store -> {(number of views, test_cfg values): AugMerge}.  Weak keys: a pool (13.6 MB at full size, four
+        # views) lives as long as its parameter store (this model's, a teacher's handed in by a caller) and goes with it
+        self._aug_merges = weakref.WeakKeyDictionary()
         self._onehot = {}          # cached gradient of the total loss w.r.t. the step's log vector (_TotalFn)
         # eager_backward True: INSIDE train_step the backward kernel lists are queued right behind the loss kernel (and the few
         # log-variable ops) instead of when `loss.backward()` reaches the autograd bridge.  The gradient of the summed loss is 1
@@ -734,8 +738,12 @@ class FCOS(nn.Module):
         return self.forward_test(img, img_metas, **kwargs)
 
     def forward_test(self, imgs, img_metas, **kwargs):
+        """detectors/base.py:116-153: one view -> simple_test, several (MultiScaleFlipAug) -> aug_test."""
         if isinstance(imgs, (list, tuple)):
-            assert len(imgs) == 1, 'test-time augmentation is out of scope'
+            if len(imgs) != len(img_metas):
+                raise ValueError(f'num of augmentations ({len(imgs)}) != num of image meta ({len(img_metas)})')
+            if len(imgs) > 1:
+                return self.aug_test(imgs, img_metas, **kwargs)
             imgs, img_metas = imgs[0], img_metas[0]
         return self.simple_test(imgs, img_metas, **kwargs)
 
@@ -743,6 +751,12 @@ class FCOS(nn.Module):
         from .sweep import simple_test
         self.store.wait_pending()          # a deferred head update of the last optimizer step (the training forward waits in its op list)
         return simple_test(self, img, img_metas, rescale)
+
+    def aug_test(self, imgs, img_metas, rescale=False):
+        """detectors/single_stage.py:109-135: `imgs` / `img_metas` hold one entry per view, each with ONE image."""
+        from .sweep import aug_test
+        self.store.wait_pending()
+        return aug_test(self, imgs, img_metas, rescale)
 
     def _parse_losses(self, losses):
         """detectors/base.py:175-208: total = sum of keys containing 'loss'; log vars averaged over ranks."""

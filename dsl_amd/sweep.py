@@ -4,7 +4,12 @@ Mirrors SingleStageDetector.simple_test (mmdet/models/detectors/single_stage.py:
 FCOSHead.get_bboxes (dense_heads/fcos_head.py:340-548) -> multiclass_nms (core/post_processing/
 bbox_nms.py:7-94) -> bbox2result (core/bbox/transforms.py:99-116) of the reference; the detections stay
 on the GPU (`detect_device`) for the pseudo-label refresh, and `simple_test` converts them to the
-reference's per-class numpy lists."""
+reference's per-class numpy lists.
+
+Test-time augmentation (`aug_test`) mirrors SingleStageDetector.aug_test (single_stage.py:109-135) ->
+BBoxTestMixin.aug_test_bboxes / merge_aug_bboxes (dense_heads/dense_test_mixins.py:38-108, 173-200): every view's candidates
+are mapped back to the original image on the device (dsl_fcos_detect_collect) into one pool, and one sort + NMS runs over the
+pool (dsl_fcos_detect_finish); nothing but the final detections crosses to the host."""
 import ctypes as C
 
 import numpy as np
@@ -60,6 +65,64 @@ class DetectPlan:
         L.check(L.lib.dsl_fcos_detect(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_detect')
 
 
+FLIP_CODES = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}      # DSL_FLIP_* (bit 0: x, bit 1: y)
+
+
+class AugMerge:
+    """The candidate pool of one original image over `nviews` views, and the merged detections ([1, max_per_img, 5] etc.).
+    `collect(view, dp, ...)` takes a view's bound DetectPlan (n == 1; its geometry may differ from the other views'),
+    `finish(rescale)` runs the score threshold, sort, class-offset NMS and max_per_img cut over the pool; count[0] = -1 says that a
+    view was missing from the pool (finish consumes the views' records: every image collects all of its views again)."""
+
+    def __init__(self, nviews, nlvl, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05, iou_thr=0.5):
+        if nviews > L.MAX_AUG:
+            raise ValueError(f'test-time augmentation: {nviews} views, at most {L.MAX_AUG} (DSL_MAX_AUG) are merged')
+        d = L.DetDesc()
+        d.nlvl, d.n = nlvl, 1
+        d.num_classes, d.nms_pre, d.max_per_img = num_classes, nms_pre, max_per_img
+        d.score_thr, d.iou_thr = score_thr, iou_thr
+        self.dets = torch.zeros(1, max_per_img, 5, device=device)
+        self.labels = torch.zeros(1, max_per_img, dtype=torch.int64, device=device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device)
+        d.dets, d.det_labels, d.det_count = L.ptr(self.dets), L.ptr(self.labels), L.ptr(self.count)
+        self.bytes = int(L.lib.dsl_detect_aug_workspace_bytes(C.byref(d), nviews))
+        if self.bytes == 0:
+            raise RuntimeError(f'dsl_detect_aug_workspace_bytes: {L.lib.dsl_last_error().decode()}')
+        self.pool = torch.empty(self.bytes, dtype=torch.uint8, device=device)
+        self.desc, self.nviews = d, nviews
+
+    def collect(self, view, dp, img_shape, scale_factor, flip=False, flip_direction=None):
+        if dp.n != 1:
+            raise ValueError(f'test-time augmentation takes one image per view (aug_test_bboxes: "only one image in the batch"), got {dp.n}')
+        dp.set_meta([img_shape], [scale_factor], True)          # the map-back always divides by the view's scale factor
+        code = FLIP_CODES[flip_direction or 'horizontal'] if flip else 0
+        L.check(L.lib.dsl_fcos_detect_collect(C.byref(dp.desc), C.byref(self.desc), view, self.nviews, code, L.ptr(self.pool), self.bytes,
+                                              L.stream_ptr()), 'dsl_fcos_detect_collect')
+
+    def finish(self, rescale):
+        L.check(L.lib.dsl_fcos_detect_finish(C.byref(self.desc), self.nviews, int(bool(rescale)), L.ptr(self.pool), self.bytes,
+                                             L.stream_ptr()), 'dsl_fcos_detect_finish')
+        return self.dets, self.labels, self.count
+
+
+def _test_cfg(det):
+    cfg = det.test_cfg or {}
+    nms = cfg.get('nms', {})
+    return dict(nms_pre=cfg.get('nms_pre', 1000), max_per_img=cfg.get('max_per_img', 100), score_thr=cfg.get('score_thr', 0.05),
+                iou_thr=nms.get('iou_threshold', nms.get('iou_thr', 0.5)))
+
+
+def _detplan(det, plan, store, N):
+    dp = getattr(plan, 'detplan', None)
+    if dp is None:
+        dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
+                        ld_cls=store.logit_ld, head_flags=store.head.flags() & L.HEAD_EXP_DECODE,
+                        ctr_col=store.cls_ld if store.ctr_on_cls else None, **_test_cfg(det))
+        dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
+        plan.detplan = dp
+    return dp
+
+
 def detect_device(det, img, img_metas, rescale=False, store=None, single_stream=False):
     """Forward + post-processing; returns (dets [N,100,5], labels [N,100], count [N]) on the GPU."""
     eng = det._get_engine()
@@ -68,17 +131,7 @@ def detect_device(det, img, img_metas, rescale=False, store=None, single_stream=
     plan = eng.plan(store, N, H, W, training=False, single_stream=single_stream)
     plan.bind_image(img)
     plan.fwd.run()
-    dp = getattr(plan, 'detplan', None)
-    if dp is None:
-        cfg = det.test_cfg or {}
-        nms = cfg.get('nms', {})
-        dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
-                        ld_cls=store.logit_ld, head_flags=store.head.flags() & L.HEAD_EXP_DECODE,
-                        ctr_col=store.cls_ld if store.ctr_on_cls else None, nms_pre=cfg.get('nms_pre', 1000),
-                        max_per_img=cfg.get('max_per_img', 100), score_thr=cfg.get('score_thr', 0.05),
-                        iou_thr=nms.get('iou_threshold', nms.get('iou_thr', 0.5)))
-        dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
-        plan.detplan = dp
+    dp = _detplan(det, plan, store, N)
     dp.set_meta([m['img_shape'] for m in img_metas], [m.get('scale_factor', 1.0) for m in img_metas], rescale)
     dp.run()
     return dp.dets, dp.labels, dp.count
@@ -95,3 +148,38 @@ def simple_test(det, img, img_metas, rescale=False, store=None):
     dets, labels, count = detect_device(det, img, img_metas, rescale, store)
     dets, labels, count = dets.cpu().numpy(), labels.cpu().numpy(), count.cpu().numpy()
     return [bbox2result(dets[i, :count[i]], labels[i, :count[i]], det.bbox_head.num_classes) for i in range(len(count))]
+
+
+def aug_test_device(det, imgs, img_metas, rescale=False, store=None):
+    """Per view: forward + collect into the image's pool; then one finish.  Returns (dets [1,100,5], labels [1,100], count [1])
+    on the GPU, in the original image's coordinates when `rescale`, else in the first view's (dense_test_mixins.py:99-104)."""
+    eng = det._get_engine()
+    store = store or det.store
+    nviews = len(imgs)
+    cfg = _test_cfg(det)
+    pools = det._aug_merges.setdefault(store, {})          # weakly keyed by the store object (an id() could be reused once it is freed)
+    key = (nviews, tuple(sorted(cfg.items())))
+    mg = pools.get(key)
+    if mg is None:
+        mg = pools[key] = AugMerge(nviews, len(det.bbox_head.strides), store.device, num_classes=store.num_classes, **cfg)
+    for v, (img, metas) in enumerate(zip(imgs, img_metas)):
+        N, _, H, W = img.shape
+        if N != 1 or len(metas) != 1:
+            raise ValueError(f'test-time augmentation takes one image per view (aug_test_bboxes: "only one image in the batch"), got {N}')
+        plan = eng.plan(store, N, H, W, training=False)
+        plan.bind_image(img)
+        plan.fwd.run()
+        m = metas[0]
+        mg.collect(v, _detplan(det, plan, store, N), m['img_shape'], m.get('scale_factor', 1.0), m.get('flip', False),
+                   m.get('flip_direction'))
+    return mg.finish(rescale)
+
+
+def aug_test(det, imgs, img_metas, rescale=False, store=None):
+    """SingleStageDetector.aug_test: a one-element list of per-class arrays."""
+    dets, labels, count = aug_test_device(det, imgs, img_metas, rescale, store)
+    dets, labels, k = dets.cpu().numpy(), labels.cpu().numpy(), int(count.cpu()[0])
+    if k < 0:
+        raise RuntimeError('dsl_fcos_detect_finish: a view of the pool was not collected for this image, or with another nlvl / nms_pre / '
+                           'num_classes than the pool\'s (det_count = -1)')
+    return [bbox2result(dets[0, :k], labels[0, :k], det.bbox_head.num_classes)]

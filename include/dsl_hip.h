@@ -255,7 +255,7 @@ typedef struct dsl_image_prep_item {
   const unsigned char* src;      /* [src_h][src_w][3] */
   int32_t src_h, src_w;
   int32_t new_h, new_w;          /* size after Resize (= src size: no resampling) */
-  int32_t flip;                  /* horizontal */
+  int32_t flip;                  /* bit 0: horizontal, bit 1: vertical (3: diagonal); 1 is RandomFlip's */
   int32_t ps_mode, ps_crop;      /* PatchShuffle: 0 none, 1 'flip' (columns [crop, w) first), 2 'flop' (rows [crop, h) first) */
   int32_t to_rgb;
   float mean[3], inv_std[3];     /* in output channel order */
@@ -566,6 +566,45 @@ typedef struct dsl_det_desc {
 } dsl_det_desc;
 size_t dsl_detect_workspace_bytes(const dsl_det_desc* d);
 int dsl_fcos_detect(const dsl_det_desc* d, void* stream);
+
+/* Test-time augmentation: BBoxTestMixin.aug_test_bboxes (mmdet/models/dense_heads/dense_test_mixins.py:38-108) over the views
+ * MultiScaleFlipAug made of ONE image.  dsl_fcos_detect split where the reference's with_nms=False returns; the candidates of
+ * all views meet in a caller-owned pool, and one sort + NMS runs over it.  At most DSL_MAX_AUG views.
+ *
+ * Pool (dsl_detect_aug_workspace_bytes; reads d->nlvl, nms_pre, num_classes, d->n == 1): a record per view (the nlvl, nms_pre and
+ * num_classes it was collected with), valid rows per (view, level), every view's scale factor, then nviews * nlvl * nms_pre candidate rows of 5 + num_classes floats - mapped-back box, sigmoid
+ * centerness, sigmoid class scores - view v's level l at row (v * nlvl + l) * nms_pre, and behind them the scratch of finish.
+ * The views may differ in their level sizes; nlvl, nms_pre and num_classes are the pool's and the same for all.  Returns 0
+ * (and sets dsl_last_error) for a descriptor or view count it refuses. */
+#define DSL_MAX_AUG 16
+#define DSL_FLIP_NONE 0
+#define DSL_FLIP_HORIZONTAL 1
+#define DSL_FLIP_VERTICAL 2
+#define DSL_FLIP_DIAGONAL 3   /* both */
+size_t dsl_detect_aug_workspace_bytes(const dsl_det_desc* d, int nviews);
+
+/* One view (replaces FCOSHead.get_bboxes(..., rescale=False, with_nms=False), fcos_head.py:340-548, and this view's turn of
+ * merge_aug_bboxes, dense_test_mixins.py:173-200): per level the nms_pre top-k by max_c(sigmoid(cls) * sigmoid(ctr)), the decode
+ * and the clip to img_shapes[0] (the view's img_shape), then bbox_mapping_back (core/bbox/transforms.py:46-55) in fp32 in the
+ * reference's order - bbox_flip against img_shape (:5-31) for `flip` = DSL_FLIP_*, then the division by scale_factors[0..3] -
+ * and the rows stored at view `view` of the pool.  `d` is the view's dsl_fcos_detect descriptor (n == 1; img_shapes and
+ * scale_factors are required; workspace as dsl_detect_workspace_bytes(d) says; dets / det_labels / det_count are not used).
+ * `pool_desc` is the descriptor the pool was sized with (the one finish takes): a view whose nlvl, nms_pre or num_classes differ
+ * from it is refused here, with the view's index in the message, before anything is written. */
+int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc* pool_desc, int view, int nviews, int flip, void* pool,
+                            size_t pool_bytes, void* stream);
+
+/* After every view 0 .. nviews-1 was collected on the same stream (replaces multiclass_nms(merged_bboxes, merged_scores,
+ * score_thr, nms, max_per_img, score_factors), dense_test_mixins.py:88-104, core/post_processing/bbox_nms.py:7-94): pairs with
+ * score > score_thr, final score = score * centerness, candidates in (view, level, slot, class) order - when more than 16 384
+ * are valid the best 16 384 by final score, as dsl_fcos_detect keeps them per image - sort, class-offset NMS, max_per_img
+ * (1..1024, checked here).  finish checks every view's record against its own nlvl / nms_pre / num_classes and consumes it:
+ * det_count[0] = -1 (and no detection) says that a view was not collected since the last finish, or with other values - a reused
+ * pool cannot pass the previous image's rows on.  In that case only det_count is meaningful: dets is zeroed, det_labels holds
+ * whatever the NMS wrote.
+ * rescale == 0: the kept boxes are multiplied by view 0's scale factor (:99-104).  Reads d->nlvl, num_classes, nms_pre,
+ * max_per_img, score_thr, iou_thr; writes d->dets [1][max_per_img][5], det_labels, det_count. */
+int dsl_fcos_detect_finish(const dsl_det_desc* d, int nviews, int rescale, void* pool, size_t pool_bytes, void* stream);
 
 /* The label-file step of the pseudo-label refresh (runner/hooks/unlabel_pred_hook.py:20-57,84-171 with
  * fuse_history=False) on the detections of dsl_fcos_detect, per image: keep score >= parse_thr, int()-truncate the
