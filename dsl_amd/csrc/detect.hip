@@ -88,7 +88,9 @@ __device__ void radix_select_block(const float* keys, int P, int k, unsigned* hi
       const float f = keys[i];
       const unsigned u = f > 0.f ? __float_as_uint(f) : 0u;
       // (non-positive keys all fall into bin 0 of the first pass: hundreds of thousands of atomics on one LDS word for the
-      // dense pair scores; the callers only select among positive keys, so they are left out of the histogram)
+      // dense pair scores, so they are left out of the histogram: with fewer positive keys than asked for the result is prefix 0
+      // and need = k - their number, and the callers' tie predicate decides which zeros count - all of a level's keys, only the
+      // valid pairs' zero scores)
       if (u != 0u && (u & mask) == prefix) atomicAdd(&hist[(u >> shifts[pass]) & (nb - 1)], 1u);
     }
     __syncthreads();
@@ -219,7 +221,12 @@ __global__ __launch_bounds__(1024) void det_select_kernel(const DetK p) {
 }
 
 // dense final scores of every (selected location, class) pair: score*centerness if score > score_thr
-// (bbox_nms.py:54: validity is tested BEFORE the centerness factor), else -1
+// (bbox_nms.py:54: validity is tested BEFORE the centerness factor), else -1.  A valid pair whose centerness sigmoid
+// underflows has final score 0 and stays a candidate, as in the reference: every consumer tests det_valid (>= 0), never > 0.
+__device__ __forceinline__ bool det_valid(float ps) { return ps >= 0.f; }
+// the radix select's view of a final score: the bit pattern of a positive one, 0 for a zero (and for the -1 of an invalid pair,
+// which det_valid keeps out first)
+__device__ __forceinline__ unsigned det_bits(float ps) { return ps > 0.f ? __float_as_uint(ps) : 0u; }
 __global__ void det_pairscore_kernel(const DetK p) {
   const int img = blockIdx.z, lvl = blockIdx.y;
   const int nsel = p.selcnt[img * p.nlvl + lvl];
@@ -301,7 +308,7 @@ __global__ __launch_bounds__(1024) void det_count_kernel(const DetK p) {
   if (threadIdx.x == 0) s_cnt = 0;
   __syncthreads();
   unsigned local = 0;
-  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) local += ps[i] > 0.f ? 1u : 0u;
+  for (int i = lo + threadIdx.x; i < hi; i += blockDim.x) local += det_valid(ps[i]) ? 1u : 0u;
   atomicAdd(&s_cnt, local);            // integer count: order-independent
   __syncthreads();
   if (threadIdx.x == 0) p.ccount[p.n + img * DET_CB + blockIdx.x] = (int)s_cnt;
@@ -323,7 +330,7 @@ __global__ __launch_bounds__(1024) void det_scatter_kernel(const DetK p) {
   det_chunk(p, lo, hi);
   if (cnt[blockIdx.x] == 0) return;
   ordered_compact(
-      hi - lo, 0u, s_wave, [&](int i) { return ps[lo + i] > 0.f; }, [&](int) { return false; },
+      hi - lo, 0u, s_wave, [&](int i) { return det_valid(ps[lo + i]); }, [&](int) { return false; },
       [&](int i, unsigned out) { det_emit(p, img, ps, lo + i, before + out); }, &s_total);
 }
 
@@ -342,8 +349,9 @@ __global__ __launch_bounds__(1024) void det_compact_kernel(const DetK p) {
   unsigned prefix = 0, need = 0;
   radix_select_block(ps, per_img, CAND_CAP, hist, s_tmp, prefix, need);
   ordered_compact(
-      per_img, need, s_wave, [&](int i) { const float f = ps[i]; return f > 0.f && __float_as_uint(f) > prefix; },
-      [&](int i) { const float f = ps[i]; return f > 0.f && __float_as_uint(f) == prefix; },
+      per_img, need, s_wave, [&](int i) { return det_bits(ps[i]) > prefix; },
+      // (fewer positive scores than CAND_CAP: prefix 0, and the valid zero scores are the tie group)
+      [&](int i) { const float f = ps[i]; return det_valid(f) && det_bits(f) == prefix; },
       [&](int i, unsigned out) { det_emit(p, img, ps, i, out); }, &s_total);
   if (threadIdx.x == 0) p.ccount[img] = min((int)s_total, CAND_CAP);
 }

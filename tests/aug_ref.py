@@ -50,7 +50,9 @@ def collect(cls, raw, ctr, img_shape, scale_factor, flip_direction, nms_pre, exp
         ys, xs = torch.meshgrid(torch.arange(h), torch.arange(w), indexing='ij')
         px, py = (xs.reshape(-1) * s + s // 2).float(), (ys.reshape(-1) * s + s // 2).float()
         if 0 < nms_pre < P:
-            idx = (sc * ce[:, None]).max(1)[0].topk(nms_pre)[1].sort()[0]
+            # the kernel's documented rule where torch.topk leaves the choice among equal keys open: the first nms_pre of a stable
+            # descending sort (ties: the lowest indices, zero keys included), back in index order
+            idx = (sc * ce[:, None]).max(1)[0].sort(descending=True, stable=True)[1][:nms_pre].sort()[0]
             sc, ce, d, px, py = sc[idx], ce[idx], d[idx], px[idx], py[idx]
         b = torch.stack([(px - d[:, 0]).clamp(0, W), (py - d[:, 1]).clamp(0, H), (px + d[:, 2]).clamp(0, W), (py + d[:, 3]).clamp(0, H)], 1)
         boxes.append(b)
@@ -64,14 +66,18 @@ def collect(cls, raw, ctr, img_shape, scale_factor, flip_direction, nms_pre, exp
     return b / torch.tensor(np.asarray(scale_factor, np.float32)), torch.cat(scores), torch.cat(cens)
 
 
-def finish(boxes, scores, cens, score_thr=0.05, iou_thr=0.5, max_per_img=100, cap=None):
-    """Returns dets [k, 5], labels [k], and the number of valid pairs."""
+def finish(boxes, scores, cens, score_thr=0.05, iou_thr=0.5, max_per_img=100, cap=None, cap_keeps='lowest'):
+    """Returns dets [k, 5], labels [k], and the number of valid pairs.  cap_keeps='highest' is NOT the kernel's rule: the cut through a
+    group of equal scores then keeps its highest candidate numbers - for tests that an input can tell the two cuts apart."""
     C = scores.shape[1]
     row, lab = torch.nonzero(scores > score_thr, as_tuple=True)           # (row, class) order
     final = (scores * cens[:, None])[row, lab]
     nvalid = len(row)
     if cap is not None and nvalid > cap:
-        keep = final.sort(descending=True, stable=True)[1][:cap].sort()[0]
+        if cap_keeps == 'lowest':
+            keep = final.sort(descending=True, stable=True)[1][:cap].sort()[0]
+        else:
+            keep = (nvalid - 1 - final.flip(0).sort(descending=True, stable=True)[1][:cap]).sort()[0]
         row, lab, final = row[keep], lab[keep], final[keep]
     b = boxes[row]
     if len(row) == 0:
@@ -95,12 +101,12 @@ def finish(boxes, scores, cens, score_thr=0.05, iou_thr=0.5, max_per_img=100, ca
     return torch.cat([b[kept], final[kept, None]], 1), lab[kept], nvalid
 
 
-def aug_test_bboxes(views, metas, nms_pre, exp_decode, rescale=True, cap=None, **nms):
+def aug_test_bboxes(views, metas, nms_pre, exp_decode, rescale=True, cap=None, cap_keeps='lowest', **nms):
     """views: [(cls, raw, ctr)] per view; metas: dicts with img_shape, scale_factor, flip, flip_direction."""
     parts = [collect(*v, m['img_shape'], m['scale_factor'], m['flip_direction'] if m['flip'] else None, nms_pre, exp_decode)
              for v, m in zip(views, metas)]
     dets, labels, nvalid = finish(torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]),
-                                  cap=cap, **nms)
+                                  cap=cap, cap_keeps=cap_keeps, **nms)
     if not rescale:
         dets = dets.clone()
         dets[:, :4] *= torch.tensor(np.asarray(metas[0]['scale_factor'], np.float32))
