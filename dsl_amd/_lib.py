@@ -106,6 +106,7 @@ class FcosDesc(C.Structure):
 
 # dsl_fcos_desc.head_flags / dsl_det_desc.head_flags (0 = the fcos_semi "tricks" head)
 HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
+NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 MAX_AUG = 16      # DSL_MAX_AUG: views merged by dsl_fcos_detect_collect / dsl_fcos_detect_finish
 
 
@@ -119,7 +120,8 @@ class DetDesc(C.Structure):
                 ('scales', C.c_void_p), ('img_shapes', C.c_void_p), ('scale_factors', C.c_void_p),
                 ('dets', C.c_void_p), ('det_labels', C.c_void_p), ('det_count', C.c_void_p),
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
-                ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p)]
+                ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p),
+                ('nms_method', C.c_int32), ('soft_sigma', C.c_float), ('soft_min_score', C.c_float)]
 
 
 class PackItem(C.Structure):

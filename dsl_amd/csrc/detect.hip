@@ -11,6 +11,10 @@
 // bbox_mapping_back / bbox_flip, core/bbox/transforms.py:5-55) splits the same work where the reference's with_nms=False
 // returns: dsl_fcos_detect_collect does a view's top-k, decode, clip and map-back into a pool of candidate rows,
 // dsl_fcos_detect_finish the threshold, compaction, sort, NMS and cut over the pool of all views.
+//
+// Soft-NMS (dsl_det_desc.nms_method != 0; mmcv's batched_nms with type='soft_nms', stated by the reference's
+// mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127) replaces the suppression stage of all three entry points: det_soft_kernel runs the
+// pick / decay loop per (image, class), det_soft_final_kernel pools the picks and keeps the best max_per_img.
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -35,6 +39,9 @@ struct DetK {
   // merged views (dsl_fcos_detect_finish): candidate rows [box 4, centerness, num_classes scores] of pool_ld floats, row =
   // pair index / num_classes; `nlvl` then counts (view, level) groups and the per-level arrays above are not read
   const float* pool; int pool_ld;
+  // Soft-NMS: DSL_NMS_* of the descriptor, and the current score per candidate slot (workspace): >= 0 while the candidate is in
+  // the running and once it is emitted, -1 when it is out
+  int nms_method; float soft_sigma, soft_min_score; float* sscore;
 };
 
 // what dsl_fcos_detect_collect adds to a view's DetK
@@ -446,6 +453,25 @@ __device__ __forceinline__ bool iou_gt(const float* a, const float* b, float thr
   return inter / (sa + sb - inter) > thr;
 }
 
+// descending bitonic sort of np2 (a power of two) keys in LDS by the whole workgroup; the keys are written and a barrier passed
+__device__ __forceinline__ void bitonic_desc(unsigned long long* keyidx, int np2) {
+  for (int k = 2; k <= np2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < np2; i += blockDim.x) {
+        const int ixj = i ^ j;
+        if (ixj > i) {
+          const unsigned long long a = keyidx[i], b = keyidx[ixj];
+          const bool desc = (i & k) == 0;
+          if (desc ? (a < b) : (a > b)) {
+            keyidx[i] = b;
+            keyidx[ixj] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
 // one block per image: sort candidates by score (bitonic, LDS), greedy class-aware NMS, keep max_per_img
 __global__ __launch_bounds__(NMS_THREADS) void det_nms_kernel(const DetK p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -478,21 +504,7 @@ __global__ __launch_bounds__(NMS_THREADS) void det_nms_kernel(const DetK p) {
     keyidx[i] = k;
   }
   __syncthreads();
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < np2; i += blockDim.x) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const unsigned long long a = keyidx[i], b = keyidx[ixj];
-          const bool desc = (i & k) == 0;
-          if (desc ? (a < b) : (a > b)) {
-            keyidx[i] = b;
-            keyidx[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_desc(keyidx, np2);
   if (threadIdx.x == 0) s_nkept = 0;
   __syncthreads();
   // greedy scan: candidate i survives iff no kept box (same label via the offset trick) has IoU > thr
@@ -518,6 +530,149 @@ __global__ __launch_bounds__(NMS_THREADS) void det_nms_kernel(const DetK p) {
     __syncthreads();
   }
   if (threadIdx.x == 0) p.det_count[img] = s_nkept;
+}
+
+// ---- Soft-NMS ------------------------------------------------------------------------------------------------------------------
+// The rule of soft_nms_cpu.pyx:39-125, per image and class (batched_nms's class offset keeps classes apart; here a workgroup only
+// ever sees one class): pick the highest current score (:52-56), emit it with that score (:59-64), multiply every other
+// remaining score of the class by w(IoU with the pick) (:98-111) and drop the candidates that fall below min_score (:115-123).
+// IoU is iou_gt's expression on the class-offset boxes, so that DSL_NMS_NAIVE decides exactly as det_nms_kernel does.
+constexpr int SOFT_T = 256;
+constexpr unsigned SOFT_OUT = 0x8000u;      // s_idx flag: emitted or dropped (candidate slots need 14 bits)
+
+__device__ __forceinline__ float iou_of(const float* a, const float* b) {
+  const float left = fmaxf(a[0], b[0]), right = fminf(a[2], b[2]);
+  const float top = fmaxf(a[1], b[1]), bottom = fminf(a[3], b[3]);
+  const float width = fmaxf(right - left, 0.f), height = fmaxf(bottom - top, 0.f);
+  const float inter = width * height;
+  const float sa = (a[2] - a[0]) * (a[3] - a[1]), sb = (b[2] - b[0]) * (b[3] - b[1]);
+  return inter / (sa + sb - inter);
+}
+
+// w of soft_nms_cpu.pyx:98-109.  0 / 0 of two zero-area boxes is no overlap, as in the hard NMS (`>` is false for a NaN)
+__device__ __forceinline__ float soft_weight(int method, float iou, float thr, float sigma) {
+  if (method == DSL_NMS_GAUSSIAN) return iou > 0.f ? expf(-(iou * iou) / sigma) : 1.f;
+  if (!(iou > thr)) return 1.f;
+  return method == DSL_NMS_LINEAR ? 1.f - iou : 0.f;
+}
+
+// One workgroup per (class, image).  The class's candidate slots are gathered into LDS in slot order; thread t owns list entries
+// t, t + T, ...: it alone reads and writes their flags and current scores, so the loop needs one barrier per pick, for the
+// arg-max across waves.  A list of at most 64 entries is run by wave 0 alone, without a barrier.  The arg-max key is (score bits,
+// ~slot): among equal current scores the lowest candidate slot wins - the order of det_nms_kernel's sort.
+__global__ __launch_bounds__(SOFT_T) void det_soft_kernel(const DetK p) {
+  __shared__ unsigned short s_idx[CAND_CAP];
+  __shared__ unsigned s_wave[34], s_total;
+  __shared__ float s_red[SOFT_T / 64];
+  __shared__ unsigned long long s_best[2][SOFT_T / 64];
+  const int cls = blockIdx.x, img = blockIdx.y;
+  int n = p.ccount[img];
+  if (n > CAND_CAP) n = CAND_CAP;
+  const float* cbox = p.cbox + (long long)img * CAND_CAP * 4;
+  const float* cscore = p.cscore + (long long)img * CAND_CAP;
+  const int* clabel = p.clabel + (long long)img * CAND_CAP;
+  float* cur = p.sscore + (long long)img * CAND_CAP;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the class offset of det_nms_kernel: label * (max coordinate over the image's candidates + 1)
+  float mx = -3.0e38f;
+  for (int i = threadIdx.x; i < n * 4; i += SOFT_T) mx = fmaxf(mx, cbox[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) s_red[wave] = mx;
+  __syncthreads();
+  mx = s_red[0];
+  for (int i = 1; i < SOFT_T / 64; ++i) mx = fmaxf(mx, s_red[i]);
+  const float off = (float)cls * (mx + 1.0f);
+  ordered_compact(
+      n, 0u, s_wave, [&](int i) { return clabel[i] == cls; }, [&](int) { return false; },
+      [&](int i, unsigned slot) { s_idx[slot] = (unsigned short)i; }, &s_total);
+  const int len = (int)s_total;
+  const bool wide = len > 64;
+  if (!wide && wave) return;
+  const int first = wide ? (int)threadIdx.x : lane, step = wide ? SOFT_T : 64;
+  for (int k = first; k < len; k += step) cur[s_idx[k]] = cscore[s_idx[k]];
+  // A class places at most max_per_img detections in the result and its picks come out in descending score order (a score only
+  // ever shrinks, and a pick is the maximum of what is left): the picks behind the first max_per_img cannot be among the image's
+  // best max_per_img, so stopping here is exact.
+  for (int it = 0; it < p.max_per_img; ++it) {
+    unsigned long long best = 0ull;                  // no entry left; an entry's key is never 0 (~slot != 0)
+    for (int k = first; k < len; k += step) {
+      const unsigned e = s_idx[k];
+      if (e & SOFT_OUT) continue;
+      const unsigned long long key = ((unsigned long long)__float_as_uint(cur[e]) << 32) | (0xffffffffu - e);
+      best = key > best ? key : best;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(best, o, 64);
+      best = other > best ? other : best;
+    }
+    if (wide) {
+      // two buffers by parity: a wave that is early for pick it + 1 writes the other buffer, and nobody writes this one again
+      // before every wave has passed the barrier of pick it + 1, behind its reads of pick it
+      if (lane == 0) s_best[it & 1][wave] = best;
+      __syncthreads();
+      best = s_best[it & 1][0];
+      for (int w = 1; w < SOFT_T / 64; ++w) best = s_best[it & 1][w] > best ? s_best[it & 1][w] : best;
+    }
+    if (best == 0ull) break;
+    const unsigned pick = 0xffffffffu - (unsigned)(best & 0xffffffffu);
+    const float bp[4] = {cbox[4 * pick] + off, cbox[4 * pick + 1] + off, cbox[4 * pick + 2] + off, cbox[4 * pick + 3] + off};
+    for (int k = first; k < len; k += step) {
+      const unsigned e = s_idx[k];
+      if (e & SOFT_OUT) continue;
+      if (e == pick) {                               // emitted with its current score, which stays in cur
+        s_idx[k] = (unsigned short)(e | SOFT_OUT);
+        continue;
+      }
+      const float be[4] = {cbox[4 * e] + off, cbox[4 * e + 1] + off, cbox[4 * e + 2] + off, cbox[4 * e + 3] + off};
+      float s = cur[e] * soft_weight(p.nms_method, iou_of(bp, be), p.iou_thr, p.soft_sigma);
+      if (s < p.soft_min_score) {
+        s_idx[k] = (unsigned short)(e | SOFT_OUT);
+        s = -1.f;
+      }
+      cur[e] = s;
+    }
+  }
+  for (int k = first; k < len; k += step)            // still in the running behind the class's last pick: not emitted
+    if (!(s_idx[k] & SOFT_OUT)) cur[s_idx[k]] = -1.f;
+}
+
+// one block per image: the emitted candidates of all classes by rescored score, descending (equal scores: ascending candidate
+// slot), the first max_per_img
+__global__ __launch_bounds__(NMS_THREADS) void det_soft_final_kernel(const DetK p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned long long* keyidx = reinterpret_cast<unsigned long long*>(smem);          // CAND_CAP * 8
+  __shared__ int s_count;
+  const int img = blockIdx.x;
+  int n = p.ccount[img];
+  if (n > CAND_CAP) n = CAND_CAP;
+  const float* cbox = p.cbox + (long long)img * CAND_CAP * 4;
+  const int* clabel = p.clabel + (long long)img * CAND_CAP;
+  const float* cur = p.sscore + (long long)img * CAND_CAP;
+  int np2 = 1;
+  while (np2 < n) np2 <<= 1;
+  for (int i = threadIdx.x; i < np2; i += blockDim.x) {
+    unsigned long long k = 0ull;                     // not emitted: behind every emitted one, whose key is never 0
+    if (i < n && cur[i] >= 0.f) k = ((unsigned long long)__float_as_uint(cur[i]) << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+    keyidx[i] = k;
+  }
+  if (threadIdx.x == 0) s_count = 0;
+  __syncthreads();
+  bitonic_desc(keyidx, np2);
+  const int maxk = p.max_per_img, lim = min(n, maxk);
+  for (int r = threadIdx.x; r < lim; r += blockDim.x) {
+    const unsigned long long key = keyidx[r];
+    if (key == 0ull) continue;
+    const int ci = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
+    float* o = p.dets + ((long long)img * maxk + r) * 5;
+    o[0] = cbox[4 * ci]; o[1] = cbox[4 * ci + 1]; o[2] = cbox[4 * ci + 2]; o[3] = cbox[4 * ci + 3];
+    o[4] = cur[ci];
+    p.det_labels[(long long)img * maxk + r] = clabel[ci];
+    if (r + 1 == lim || keyidx[r + 1] == 0ull) s_count = r + 1;          // the last emitted rank: one writer
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) p.det_count[img] = s_count;
 }
 
 // ---- pseudo-label fuse step of the refresh (unlabel_pred_hook.py:84-171) -----------------------------------------
@@ -612,7 +767,7 @@ __global__ __launch_bounds__(FUSE_T) void pseudo_fuse_kernel(const FuseK p) {
   if (threadIdx.x == 0) p.out_count[img] = nk;
 }
 
-size_t ws_layout(const dsl_det_desc* d, size_t off[8]) {
+size_t ws_layout(const dsl_det_desc* d, size_t off[9]) {
   long long M = 0;
   for (int l = 0; l < d->nlvl; ++l) M += (long long)d->n * d->h[l] * d->w[l];
   size_t o = 0;
@@ -625,11 +780,12 @@ size_t ws_layout(const dsl_det_desc* d, size_t off[8]) {
   off[5] = take((size_t)d->n * CAND_CAP * 4);                     // clabel
   off[6] = take((size_t)d->n * 4 * (1 + DET_CB));                 // ccount, then DET_CB chunk counts per image
   off[7] = take((size_t)d->n * d->nlvl * d->nms_pre * d->num_classes * 4);   // pairscore
+  off[8] = take(d->nms_method ? (size_t)d->n * CAND_CAP * 4 : 0);  // Soft-NMS: current scores (a zeroed field: the size as before)
   return o;
 }
 
 // the pool of `nviews` views: [0] per-view records and valid rows per (view, level), [1] scale factors, [2] rows, then what finish needs
-size_t aug_layout(const dsl_det_desc* d, int nviews, size_t off[9]) {
+size_t aug_layout(const dsl_det_desc* d, int nviews, size_t off[10]) {
   const size_t rows = (size_t)nviews * d->nlvl * d->nms_pre;
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) / 256 * 256; return r; };
@@ -641,7 +797,8 @@ size_t aug_layout(const dsl_det_desc* d, int nviews, size_t off[9]) {
   off[5] = take((size_t)CAND_CAP * 4);                            // cscore
   off[6] = take((size_t)CAND_CAP * 4);                            // clabel
   off[7] = take((size_t)4 * (1 + DET_CB));                        // ccount
-  off[8] = o;
+  off[8] = take(d->nms_method ? (size_t)CAND_CAP * 4 : 0);        // Soft-NMS: current scores
+  off[9] = o;
   return o;
 }
 
@@ -655,7 +812,26 @@ int aug_check(const dsl_det_desc* d, int nviews, const char* who) {
   return 0;
 }
 
+// the nms_method / soft_* fields of a descriptor (all zero: the hard NMS)
+int soft_check(const dsl_det_desc* d, const char* who) {
+  DSL_CHECK(d->nms_method >= DSL_NMS_HARD && d->nms_method <= DSL_NMS_NAIVE, "%s: nms_method must be a DSL_NMS_* code, got %d", who, d->nms_method);
+  DSL_CHECK(d->nms_method != DSL_NMS_GAUSSIAN || d->soft_sigma > 0.f, "%s: soft_sigma must be > 0 for DSL_NMS_GAUSSIAN, got %g", who,
+            (double)d->soft_sigma);
+  DSL_CHECK(d->nms_method == DSL_NMS_HARD || d->soft_min_score >= 0.f, "%s: soft_min_score must be >= 0, got %g", who, (double)d->soft_min_score);
+  return 0;
+}
+
 void launch_nms(const DetK& k, int n, hipStream_t st) {
+  if (k.nms_method != DSL_NMS_HARD) {
+    static bool soft_attr = false;
+    if (!soft_attr) {
+      hipFuncSetAttribute((const void*)det_soft_final_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)CAND_CAP * 8));
+      soft_attr = true;
+    }
+    hipLaunchKernelGGL(det_soft_kernel, dim3(k.num_classes, n), dim3(SOFT_T), 0, st, k);
+    hipLaunchKernelGGL(det_soft_final_kernel, dim3(n), dim3(NMS_THREADS), (size_t)CAND_CAP * 8, st, k);
+    return;
+  }
   const size_t lds = (size_t)CAND_CAP * 8 + (size_t)k.max_per_img * 16;
   static bool attr = false;
   if (!attr) {
@@ -667,7 +843,7 @@ void launch_nms(const DetK& k, int n, hipStream_t st) {
 
 // fills the per-view part of a DetK (geometry, head outputs, the view's scratch)
 int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
-  size_t off[8];
+  size_t off[9];
   const size_t need = ws_layout(d, off);
   DSL_CHECK(d->workspace_bytes >= need, "%s: workspace too small (%zu < %zu)", who, d->workspace_bytes, need);
   memset(&k, 0, sizeof(k));
@@ -690,6 +866,8 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
   k.cbox = (float*)(ws + off[3]); k.cscore = (float*)(ws + off[4]); k.clabel = (int*)(ws + off[5]);
   k.ccount = (int*)(ws + off[6]);
   k.pairscore = (float*)(ws + off[7]);
+  k.nms_method = d->nms_method; k.soft_sigma = d->soft_sigma; k.soft_min_score = d->soft_min_score;
+  k.sscore = (float*)(ws + off[8]);
   m_out = m;
   return 0;
 }
@@ -697,7 +875,7 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
 }  // namespace
 
 extern "C" size_t dsl_detect_workspace_bytes(const dsl_det_desc* d) {
-  size_t off[8];
+  size_t off[9];
   return ws_layout(d, off);
 }
 
@@ -709,6 +887,7 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr ? 4 : 5),
             "dsl_fcos_detect: unsupported layout");
   DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS && d->nms_pre > 0, "dsl_fcos_detect: max_per_img must be in 1..%d", NMS_THREADS);
+  if (soft_check(d, "dsl_fcos_detect")) return -1;
   DetK k;
   int m = 0;
   if (view_detk(d, k, m, "dsl_fcos_detect")) return -1;
@@ -729,7 +908,7 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
 
 extern "C" size_t dsl_detect_aug_workspace_bytes(const dsl_det_desc* d, int nviews) {
   if (aug_check(d, nviews, "dsl_detect_aug_workspace_bytes")) return 0;
-  size_t off[9];
+  size_t off[10];
   return aug_layout(d, nviews, off);
 }
 
@@ -737,6 +916,7 @@ extern "C" int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc
                                        size_t pool_bytes, void* stream) {
   if (aug_check(d, nviews, "dsl_fcos_detect_collect")) return -1;
   DSL_CHECK(pool_desc, "dsl_fcos_detect_collect: null pool descriptor");
+  if (soft_check(pool_desc, "dsl_fcos_detect_collect")) return -1;          // its nms_method sizes the pool's scratch (aug_layout)
   // the pool is laid out by ITS nlvl / nms_pre / num_classes: a view that differs would write into other views' rows
   DSL_CHECK(d->nlvl == pool_desc->nlvl && d->nms_pre == pool_desc->nms_pre && d->num_classes == pool_desc->num_classes,
             "dsl_fcos_detect_collect: view %d has nlvl %d, nms_pre %d, num_classes %d, the pool %d, %d, %d", view, d->nlvl, d->nms_pre,
@@ -746,7 +926,7 @@ extern "C" int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc
   DSL_CHECK(d->cls_logits && d->regctr && d->scales && d->img_shapes && d->scale_factors && d->workspace && pool,
             "dsl_fcos_detect_collect: null pointer (the map-back needs img_shapes and scale_factors)");
   DSL_CHECK(d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr ? 4 : 5), "dsl_fcos_detect_collect: unsupported layout");
-  size_t off[9];
+  size_t off[10];
   const size_t need = aug_layout(pool_desc, nviews, off);
   DSL_CHECK(pool_bytes >= need, "dsl_fcos_detect_collect: pool too small (%zu < %zu)", pool_bytes, need);
   DetK k;
@@ -771,7 +951,8 @@ extern "C" int dsl_fcos_detect_finish(const dsl_det_desc* d, int nviews, int res
   DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS, "dsl_fcos_detect_finish: max_per_img must be in 1..%d, got %d", NMS_THREADS,
             d->max_per_img);
   DSL_CHECK(d->dets && d->det_labels && d->det_count && pool, "dsl_fcos_detect_finish: null pointer");
-  size_t off[9];
+  if (soft_check(d, "dsl_fcos_detect_finish")) return -1;
+  size_t off[10];
   const size_t need = aug_layout(d, nviews, off);
   DSL_CHECK(pool_bytes >= need, "dsl_fcos_detect_finish: pool too small (%zu < %zu)", pool_bytes, need);
   unsigned char* pw = (unsigned char*)pool;
@@ -785,6 +966,8 @@ extern "C" int dsl_fcos_detect_finish(const dsl_det_desc* d, int nviews, int res
   k.pairscore = (float*)(pw + off[3]);
   k.cbox = (float*)(pw + off[4]); k.cscore = (float*)(pw + off[5]); k.clabel = (int*)(pw + off[6]);
   k.ccount = (int*)(pw + off[7]);
+  k.nms_method = d->nms_method; k.soft_sigma = d->soft_sigma; k.soft_min_score = d->soft_min_score;
+  k.sscore = (float*)(pw + off[8]);
   const long long npair = (long long)k.nlvl * k.nms_pre * k.num_classes;
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(k.ccount, 0, sizeof(int), st);

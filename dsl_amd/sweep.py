@@ -20,8 +20,9 @@ from . import _lib as L
 
 class DetectPlan:
     def __init__(self, n, sizes, strides, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05,
-                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None):
+                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0):
         d = L.DetDesc()
+        d.nms_method, d.soft_sigma, d.soft_min_score = nms_method, soft_sigma, soft_min_score      # L.NMS_*; all zero: the hard NMS
         d.nlvl, d.n = len(sizes), n
         d.h, d.w = L.seg5([s[0] for s in sizes]), L.seg5([s[1] for s in sizes])
         d.stride = L.seg5(strides)
@@ -71,13 +72,15 @@ FLIP_CODES = {None: 0, 'horizontal': 1, 'vertical': 2, 'diagonal': 3}      # DSL
 class AugMerge:
     """The candidate pool of one original image over `nviews` views, and the merged detections ([1, max_per_img, 5] etc.).
     `collect(view, dp, ...)` takes a view's bound DetectPlan (n == 1; its geometry may differ from the other views'),
-    `finish(rescale)` runs the score threshold, sort, class-offset NMS and max_per_img cut over the pool; count[0] = -1 says that a
+    `finish(rescale)` runs the score threshold, sort, class-offset NMS (or Soft-NMS, `nms_method`) and max_per_img cut over the pool; count[0] = -1 says that a
     view was missing from the pool (finish consumes the views' records: every image collects all of its views again)."""
 
-    def __init__(self, nviews, nlvl, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05, iou_thr=0.5):
+    def __init__(self, nviews, nlvl, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05, iou_thr=0.5,
+                 nms_method=0, soft_sigma=0.0, soft_min_score=0.0):
         if nviews > L.MAX_AUG:
             raise ValueError(f'test-time augmentation: {nviews} views, at most {L.MAX_AUG} (DSL_MAX_AUG) are merged')
         d = L.DetDesc()
+        d.nms_method, d.soft_sigma, d.soft_min_score = nms_method, soft_sigma, soft_min_score
         d.nlvl, d.n = nlvl, 1
         d.num_classes, d.nms_pre, d.max_per_img = num_classes, nms_pre, max_per_img
         d.score_thr, d.iou_thr = score_thr, iou_thr
@@ -105,11 +108,27 @@ class AugMerge:
         return self.dets, self.labels, self.count
 
 
+SOFT_METHODS = {'linear': L.NMS_LINEAR, 'gaussian': L.NMS_GAUSSIAN, 'naive': L.NMS_NAIVE}      # mmcv.ops.soft_nms's `method`
+
+
 def _test_cfg(det):
+    """test_cfg -> the keyword arguments of DetectPlan / AugMerge.  nms.type 'nms' (or absent): the hard NMS, iou_threshold 0.5;
+    'soft_nms': mmcv.ops.soft_nms's keys and defaults (iou_threshold 0.3, sigma 0.5, min_score 1e-3, method 'linear')."""
     cfg = det.test_cfg or {}
     nms = cfg.get('nms', {})
-    return dict(nms_pre=cfg.get('nms_pre', 1000), max_per_img=cfg.get('max_per_img', 100), score_thr=cfg.get('score_thr', 0.05),
-                iou_thr=nms.get('iou_threshold', nms.get('iou_thr', 0.5)))
+    kind = nms.get('type', 'nms')
+    if kind not in ('nms', 'soft_nms'):
+        raise NotImplementedError(f"test_cfg.nms.type={kind!r}: the detection post-processing builds 'nms' and 'soft_nms'")
+    soft = kind == 'soft_nms'
+    out = dict(nms_pre=cfg.get('nms_pre', 1000), max_per_img=cfg.get('max_per_img', 100), score_thr=cfg.get('score_thr', 0.05),
+               iou_thr=nms.get('iou_threshold', nms.get('iou_thr', 0.3 if soft else 0.5)), nms_method=L.NMS_HARD, soft_sigma=0.0,
+               soft_min_score=0.0)
+    if soft:
+        method = nms.get('method', 'linear')
+        if method not in SOFT_METHODS:
+            raise ValueError(f'test_cfg.nms.method={method!r}: soft_nms has {sorted(SOFT_METHODS)}')
+        out.update(nms_method=SOFT_METHODS[method], soft_sigma=float(nms.get('sigma', 0.5)), soft_min_score=float(nms.get('min_score', 1e-3)))
+    return out
 
 
 def _detplan(det, plan, store, N):

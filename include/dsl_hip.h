@@ -563,7 +563,22 @@ typedef struct dsl_det_desc {
   int32_t head_flags;                        /* DSL_HEAD_EXP_DECODE: exp(scale x) without the stride (fcos_head.py:162-167); 0 = relu * stride */
   int32_t ld_ctr;                            /* row stride of ctr (floats); read only when ctr is set */
   const float* ctr;                          /* NULL: centerness logit = regctr[m][4]; else ctr[m * ld_ctr] (fcos_head.py:155-158) */
+  int32_t nms_method;                        /* DSL_NMS_*; 0 = the hard NMS, and soft_sigma / soft_min_score are not read */
+  float soft_sigma;                          /* DSL_NMS_GAUSSIAN: w = exp(-iou^2 / soft_sigma), > 0 (mmcv: 0.5) */
+  float soft_min_score;                      /* Soft-NMS: a candidate whose decayed score is < soft_min_score is dropped, >= 0 (mmcv: 1e-3) */
 } dsl_det_desc;
+/* dsl_det_desc.nms_method.  Soft-NMS is mmcv's batched_nms with nms=dict(type='soft_nms', method=...) (stated by
+ * mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127), per image and class over the candidates the hard NMS would get: pick the highest current score
+ * (equal scores: the candidate that comes first in (level, slot, class) order - with views, (view, level, slot, class)), emit it
+ * with that score, multiply every other remaining score of the class by w, drop those that fall below soft_min_score, repeat;
+ * then the emitted detections of all classes by rescored score, the first max_per_img.  dets[..][4] is the RESCORED score.
+ * w with iou = IoU(pick, other), the hard NMS's expression on the class-offset boxes:
+ *   LINEAR 1 - iou if iou > iou_thr, else 1;  GAUSSIAN exp(-iou^2 / soft_sigma);  NAIVE 0 if iou > iou_thr, else 1.
+ * The workspace / pool sizes grow by 16 384 floats per image when nms_method != 0: query them with the field set. */
+#define DSL_NMS_HARD 0
+#define DSL_NMS_LINEAR 1
+#define DSL_NMS_GAUSSIAN 2
+#define DSL_NMS_NAIVE 3
 size_t dsl_detect_workspace_bytes(const dsl_det_desc* d);
 int dsl_fcos_detect(const dsl_det_desc* d, void* stream);
 
@@ -603,7 +618,7 @@ int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc* pool_desc
  * pool cannot pass the previous image's rows on.  In that case only det_count is meaningful: dets is zeroed, det_labels holds
  * whatever the NMS wrote.
  * rescale == 0: the kept boxes are multiplied by view 0's scale factor (:99-104).  Reads d->nlvl, num_classes, nms_pre,
- * max_per_img, score_thr, iou_thr; writes d->dets [1][max_per_img][5], det_labels, det_count. */
+ * max_per_img, score_thr, iou_thr, nms_method, soft_sigma, soft_min_score (Soft-NMS: one pass over the pooled views); writes d->dets [1][max_per_img][5], det_labels, det_count. */
 int dsl_fcos_detect_finish(const dsl_det_desc* d, int nviews, int rescale, void* pool, size_t pool_bytes, void* stream);
 
 /* The label-file step of the pseudo-label refresh (runner/hooks/unlabel_pred_hook.py:20-57,84-171 with
