@@ -107,6 +107,7 @@ class FcosDesc(C.Structure):
 # dsl_fcos_desc.head_flags / dsl_det_desc.head_flags (0 = the fcos_semi "tricks" head)
 HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
+EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
 MAX_AUG = 16      # DSL_MAX_AUG: views merged by dsl_fcos_detect_collect / dsl_fcos_detect_finish
 
 
@@ -196,6 +197,8 @@ if hasattr(lib, 'dsl_detect_workspace_bytes'):
     lib.dsl_detect_workspace_bytes.restype = C.c_size_t
 if hasattr(lib, 'dsl_detect_aug_workspace_bytes'):
     lib.dsl_detect_aug_workspace_bytes.restype = C.c_size_t
+if hasattr(lib, 'dsl_eval_match_workspace_bytes'):
+    lib.dsl_eval_match_workspace_bytes.restype = C.c_size_t
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
 _SIGS = {
     'dsl_conv2d': [_vp, _vp], 'dsl_conv2d_workspace_bytes': [_vp], 'dsl_conv2d_gn_fusable': [_vp], 'dsl_conv2d_wgrad': [_vp, _vp], 'dsl_wgrad_splits': [_vp],
@@ -230,6 +233,9 @@ _SIGS = {
     'dsl_detect_aug_workspace_bytes': [_vp, _i], 'dsl_fcos_detect_collect': [_vp, _vp, _i, _i, _i, _vp, C.c_size_t, _vp],
     'dsl_fcos_detect_finish': [_vp, _i, _i, _vp, C.c_size_t, _vp],
     'dsl_pseudo_label_fuse': [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp],
+    'dsl_eval_match_workspace_bytes': [_i, _i],
+    'dsl_eval_match': [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    'dsl_eval_accumulate': [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'dsl_comm_unique_id': [_vp],
     'dsl_comm_init_rank': [_vp, _i, _vp, _i],
     'dsl_comm_size': [_vp],

@@ -277,3 +277,30 @@ def set_ptrs(d, **tensors):
         setattr(d, k, L.ptr(t))
         d._keep[k] = t
     return d
+
+
+def eval_match(mode, num_cats, num_imgs, det_boxes, det_off, gt_boxes, gt_area, gt_crowd, gt_ignore, gt_off, max_gt_per_cell,
+               iou_thrs, area_ranges):
+    """dsl_eval_match over a packed evaluation set (evaluation.pack_eval_inputs): every array is device memory.  Returns
+    (out_a, out_b, npos): COCO matched / ignored [R, T, M] uint8 and npos [C, R] int32; VOC tp / fp [M] uint8 and None."""
+    M, G, T, R = det_boxes.shape[0], gt_boxes.shape[0], iou_thrs.numel(), area_ranges.shape[0]
+    dev = det_off.device
+    shape = (R, T, M) if mode == L.EVAL_COCO else (M,)
+    out_a = torch.zeros(shape, dtype=torch.uint8, device=dev)
+    out_b = torch.zeros(shape, dtype=torch.uint8, device=dev)
+    npos = torch.zeros(num_cats, R, dtype=torch.int32, device=dev) if mode == L.EVAL_COCO else None
+    need = int(lib.dsl_eval_match_workspace_bytes(G, int(max_gt_per_cell)))
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+    L.check(lib.dsl_eval_match(mode, num_cats, num_imgs, M, G, int(max_gt_per_cell), L.ptr(det_boxes), L.ptr(det_off), L.ptr(gt_boxes),
+                               L.ptr(gt_area), L.ptr(gt_crowd), L.ptr(gt_ignore), L.ptr(gt_off), L.ptr(iou_thrs), T, L.ptr(area_ranges), R,
+                               L.ptr(out_a), L.ptr(out_b), L.ptr(npos), L.ptr(ws), need, L.stream_ptr()), 'dsl_eval_match')
+    return out_a, out_b, npos
+
+
+def eval_accumulate(num_cats, num_imgs, matched, ignored, npos, det_off, perm, rec_thrs):
+    """dsl_eval_accumulate: prec [R, T, len(rec_thrs), C] float64 on the device."""
+    R, T, M = matched.shape
+    prec = torch.empty(R, T, rec_thrs.numel(), num_cats, dtype=torch.float64, device=det_off.device)
+    L.check(lib.dsl_eval_accumulate(num_cats, num_imgs, M, R, T, rec_thrs.numel(), L.ptr(matched), L.ptr(ignored), L.ptr(npos),
+                                    L.ptr(det_off), L.ptr(perm), L.ptr(rec_thrs), L.ptr(prec), L.stream_ptr()), 'dsl_eval_accumulate')
+    return prec

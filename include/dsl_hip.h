@@ -642,6 +642,43 @@ int dsl_pseudo_label_fuse_history(const float* dets, const int64_t* labels, cons
                                   int32_t* out_count, int max_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation on the device (dsl_amd/evaluation.py: coco_bbox_eval = the bbox protocol of COCOeval; tpfp_default of
+ * mmdet/core/evaluation/mean_ap.py).  The kernels restate the host path's fp64 / fp32 operation order and are compared with it
+ * bit for bit; they are compiled with floating-point contraction off.
+ *
+ * Cells: (category c, image i) -> cell c * num_imgs + i.  Detections are ordered by (category, image, rank within the cell:
+ * descending score, ties in array order) and already cut to max_dets per cell: det_boxes [num_det][4] fp32 xyxy.  Ground truth
+ * is ordered by (category, image, annotation order): gt_boxes [num_gt][4] fp64 - COCO: x, y, w, h; VOC: x1, y1, x2, y2 holding
+ * float32 values, regular boxes before ignore boxes - gt_area [num_gt] fp64, gt_crowd / gt_ignore [num_gt] bytes (VOC reads
+ * gt_ignore only).  det_off / gt_off [num_cats * num_imgs + 1] int32 delimit the cells.  iou_thrs [num_thrs] fp64, area_ranges
+ * [num_ranges][2] fp64 (lo, hi) are DEVICE arrays too; num_ranges * num_thrs <= 64 (one lane each).
+ *
+ *   DSL_EVAL_COCO  out_a = matched [num_ranges][num_thrs][num_det] bytes, out_b = ignored (same shape), npos [num_cats][num_ranges]
+ *                  int32 (zeroed here) = non-ignored ground truth (not crowd, not gt_ignore, area in [lo, hi]).
+ *   DSL_EVAL_VOC   num_ranges == 1 and num_thrs == 1 (else an error): out_a = tp [num_det] bytes, out_b = fp [num_det]; npos is
+ *                  not used.  The comparison is (double)max_iou >= iou_thrs[0].
+ * A cell with more ground truth than the LDS state holds (128) keeps its matched state in `workspace`
+ * (dsl_eval_match_workspace_bytes: 0 when max_gt_per_cell fits); max_gt_per_cell is the largest gt_off difference. */
+#define DSL_EVAL_COCO 0
+#define DSL_EVAL_VOC 1
+#define DSL_EVAL_MAX_THRS 16
+#define DSL_EVAL_MAX_RANGES 4
+size_t dsl_eval_match_workspace_bytes(int num_gt, int max_gt_per_cell);
+int dsl_eval_match(int mode, int num_cats, int num_imgs, int num_det, int num_gt, int max_gt_per_cell, const float* det_boxes,
+                   const int32_t* det_off, const double* gt_boxes, const double* gt_area, const uint8_t* gt_crowd,
+                   const uint8_t* gt_ignore, const int32_t* gt_off, const double* iou_thrs, int num_thrs, const double* area_ranges,
+                   int num_ranges, uint8_t* out_a, uint8_t* out_b, int32_t* npos, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* COCO accumulation per (category, range, threshold): `perm` [num_det] lists each category's detections (indices into the
+ * detection arrays, category c at det_off[c * num_imgs] .. det_off[(c + 1) * num_imgs]) by descending score, ties by (image,
+ * rank).  rec_thrs [num_rec <= 128] fp64 ascending, a device array filled by the host (np.linspace(0, 1, 101)).
+ * prec [num_ranges][num_thrs][num_rec][num_cats] fp64: the precision envelope at the first detection whose recall reaches
+ * rec_thrs[k], 0 past the last recall, -1 everywhere when npos == 0. */
+int dsl_eval_accumulate(int num_cats, int num_imgs, int num_det, int num_ranges, int num_thrs, int num_rec, const uint8_t* matched,
+                        const uint8_t* ignored, const int32_t* npos, const int32_t* det_off, const int32_t* perm,
+                        const double* rec_thrs, double* prec, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Data-parallel exchange (one process per GPU, RCCL over xGMI).  Stands where the reference has
  * MMDistributedDataParallel's gradient buckets (mmdet/apis/train.py:92-96) and reduce_mean
  * (mmdet/core/utils/dist_utils.py:63-69).  librccl.so.1 is bound at the first call (dlopen), not at
