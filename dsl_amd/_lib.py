@@ -101,11 +101,16 @@ class FcosDesc(C.Structure):
                 ('g_scales', C.c_void_p), ('losses', C.c_void_p),
                 ('soft_weight', C.c_float), ('grad_scale', C.c_float), ('inv_world', C.c_float),
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t), ('logvec', C.c_void_p),
-                ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p), ('g_ctr', C.c_void_p), ('ld_gctr', C.c_int32)]
+                ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p), ('g_ctr', C.c_void_p), ('ld_gctr', C.c_int32),
+                # loss family, read with HEAD_LOSS_EXT only (all zero = the default head's terms)
+                ('box_kind', C.c_int32), ('box_eps', C.c_float), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float),
+                ('w_cls', C.c_float), ('w_bbox', C.c_float), ('w_ctr', C.c_float)]
 
 
 # dsl_fcos_desc.head_flags / dsl_det_desc.head_flags (0 = the fcos_semi "tricks" head)
 HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
+HEAD_LOSS_EXT = 16      # dsl_fcos_desc only: box_kind .. w_ctr are set
+BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_DIOU, BOX_CIOU = range(5)      # DSL_BOX_*: dsl_fcos_desc.box_kind
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
 MAX_AUG = 16      # DSL_MAX_AUG: views merged by dsl_fcos_detect_collect / dsl_fcos_detect_finish

@@ -11,6 +11,16 @@
 // the IoU log loss (losses/iou_loss.py:14-36), and the centerness logit / gradient at a caller-given address
 // (centerness_on_reg=False, :155-158: it belongs to the classification tower's predictor then).
 //
+// Loss family (DSL_HEAD_LOSS_EXT, uniform per launch; the loss_kernel<., true> instantiation - the default head's instruction stream
+// is the kExt = false one, unchanged): loss_bbox of kind DSL_BOX_* - the linear IoU loss 1 - clamp(iou, eps) (losses/iou_loss.py:14-36),
+// DIoU (:105-157) and CIoU (:160-219) beside GIoU and the IoU log loss; the focal loss with gamma >= 0 and 0 <= alpha <= 1
+// (focal_loss.py:11-56); loss_weight of loss_cls / loss_bbox / loss_centerness (focal_loss.py:174, iou_loss.py:398,438,
+// cross_entropy_loss.py:203) on the reported terms and on their gradients.  Two deliberate deviations from the reference's fp32
+// arithmetic, both at their sites below: the CIoU aspect penalty v^2 / (1 - iou + v) and its gradient are 0 where v == 0 (the
+// reference gives 0/0 = NaN when prediction and target coincide; 0 is the fp64 value), and the focal gradient is formed as
+// -+alpha q^gamma (gamma p sp + q), which has no q^(gamma-1) and is finite where the reference's autograd returns NaN (gamma < 1 with
+// a sigmoid saturated to exactly 0 or 1; the kernel returns the limit, 0).
+//
 // The assignment must be BIT-identical to the reference's fp32 torch arithmetic, so this file is
 // compiled with floating-point contraction off and the comparisons are written exactly as there.
 #include "common.hpp"
@@ -38,6 +48,9 @@ struct FcK {
   const float* ctr; int ld_ctr;      // centerness logit of location m: ctr[m * ld_ctr]
   uint16_t* g_ctr; int ld_gctr;      // its gradient, when it does not live in column 4 of g_rc (else null)
   float* part;            // block records of the loss / assignment sums (fixed-order second pass, no float atomics)
+  // loss family (loss_kernel<., true> only): DSL_BOX_*, eps of DIoU / CIoU, focal gamma / alpha, the three loss weights
+  int box_kind;
+  float box_eps, gamma, alpha, w_cls, w_bbox, w_ctr;
 };
 
 __device__ __forceinline__ void decode_loc(const FcK& p, int m, int& lvl, int& img, int& y, int& x) {
@@ -151,7 +164,8 @@ __global__ __launch_bounds__(256) void assign_kernel(const FcK p) {
 constexpr int FIN_T = 256;
 __global__ __launch_bounds__(FIN_T) void fcos_finalize_kernel(const float* __restrict__ part, int nblocks, int V, float* out0,
                                                               int n0, float* out1, const float* norm, float inv_world,
-                                                              float soft_weight, int mode, float* logvec = nullptr) {
+                                                              float soft_weight, int mode, float* logvec = nullptr,
+                                                              float w_cls = 1.f, float w_bbox = 1.f, float w_ctr = 1.f) {
   __shared__ float sh[FIN_T];
   // thread (q, v): blocks q, q + Q, ... ; then thread v adds the Q partial sums in order
   const int Q = FIN_T / V;
@@ -169,10 +183,11 @@ __global__ __launch_bounds__(FIN_T) void fcos_finalize_kernel(const float* __res
     if (mode == 1) {           // loss records: [cls, sisoft, bbox, centerness, g_scale x 5] -> losses[4] + g_scales[5]
       const float num_pos = fmaxf(norm[0] * inv_world, 1.0f), denorm = fmaxf(norm[1] * inv_world, 1e-6f);
       float fv = t;
-      if (threadIdx.x == 0) out0[0] = fv = t / num_pos;
+      // (loss_weight * the mean, as the loss modules do; a weight of 1 leaves the bits as they are)
+      if (threadIdx.x == 0) out0[0] = fv = t / num_pos * w_cls;
       else if (threadIdx.x == 1) out0[3] = fv = t * soft_weight;
-      else if (threadIdx.x == 2) out0[1] = fv = t / denorm;
-      else if (threadIdx.x == 3) out0[2] = fv = t / num_pos;
+      else if (threadIdx.x == 2) out0[1] = fv = t / denorm * w_bbox;
+      else if (threadIdx.x == 3) out0[2] = fv = t / num_pos * w_ctr;
       else if (threadIdx.x - 4 < n0) out1[threadIdx.x - 4] = t;
       if (threadIdx.x < 4) sh[threadIdx.x] = fv;          // (slot x of sh is read by thread x only, above)
     } else if (threadIdx.x < n0) {
@@ -231,9 +246,116 @@ __device__ __forceinline__ void focal_fb(float x, bool t, float& loss, float& gr
 __device__ __forceinline__ float dmax_a(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
 __device__ __forceinline__ float dmin_a(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
 
+// ---- loss family (kExt) -------------------------------------------------------------------------------------------------------
+// focal loss and dloss/dx with gamma >= 0, 0 <= alpha <= 1 (focal_loss.py:34-40).  gamma == 2 keeps focal_fb's q * q sequence
+// (launch-uniform branch).  Otherwise q = 1 - p is formed as sigmoid(-x), without cancellation, and the gradient as
+// -+alpha q^gamma (gamma p sp + q): no q^(gamma-1), so it is finite for gamma < 1 at a saturated sigmoid, where the reference's autograd
+// (pow's backward, 0 * inf) returns NaN - the value here is the limit, 0.  powf(0, 0) is 1, as torch's pow.
+__device__ __forceinline__ void focal_fb_ext(float x, bool t, float gamma, float alpha, bool gamma2, float& loss, float& grad) {
+  const float e = __expf(-fabsf(x));
+  const float l1p = log1pf(e);
+  const float inv = 1.f / (1.f + e);
+  const float pp = x >= 0.f ? inv : e * inv;   // sigmoid(x)
+  if (gamma2) {
+    const float q = 1.f - pp;
+    if (t) {
+      const float sp = fmaxf(-x, 0.f) + l1p;      // -log p
+      loss = alpha * q * q * sp;
+      grad = -alpha * q * q * (2.f * pp * sp + q);
+    } else {
+      const float sp = fmaxf(x, 0.f) + l1p;       // -log(1-p)
+      loss = (1.f - alpha) * pp * pp * sp;
+      grad = (1.f - alpha) * pp * pp * (2.f * q * sp + pp);
+    }
+    return;
+  }
+  const float q = x >= 0.f ? e * inv : inv;     // sigmoid(-x)
+  if (t) {
+    const float sp = fmaxf(-x, 0.f) + l1p;
+    const float mod = powf(q, gamma);
+    loss = alpha * mod * sp;
+    grad = -alpha * mod * (gamma * pp * sp + q);
+  } else {
+    const float sp = fmaxf(x, 0.f) + l1p;
+    const float mod = powf(pp, gamma);
+    loss = (1.f - alpha) * mod * sp;
+    grad = (1.f - alpha) * mod * (gamma * q * sp + pp);
+  }
+}
+
+// One positive location's box loss of kind DSL_BOX_IOU_LINEAR / DIOU / CIOU on the decoded boxes (prediction x, target X) and
+// dl[k] = dloss / d(x1, y1, x2, y2), written as the reference's torch lines so that the subgradients are autograd's (max / min ties
+// split 0.5, clamp(min=0) passes the gradient at 0).
+__device__ __forceinline__ float box_loss_ext(int kind, float eps, float x1, float y1, float x2, float y2, float X1, float Y1,
+                                              float X2, float Y2, float dl[4]) {
+  const float a1 = (x2 - x1) * (y2 - y1), a2 = (X2 - X1) * (Y2 - Y1);
+  const float ltx = fmaxf(x1, X1), lty = fmaxf(y1, Y1), rbx = fminf(x2, X2), rby = fminf(y2, Y2);
+  const float w0 = rbx - ltx, h0 = rby - lty;
+  const float iw = fmaxf(w0, 0.f), ih = fmaxf(h0, 0.f);
+  const float ov = iw * ih;
+  const float u0 = a1 + a2 - ov;
+  const float cw = w0 >= 0.f ? 1.f : 0.f, chh = h0 >= 0.f ? 1.f : 0.f;
+  const float dov[4] = {ih * (-dmax_a(x1, X1) * cw), iw * (-dmax_a(y1, Y1) * chh), ih * (dmin_a(x2, X2) * cw), iw * (dmin_a(y2, Y2) * chh)};
+  const float da1[4] = {-(y2 - y1), -(x2 - x1), (y2 - y1), (x2 - x1)};
+  if (kind == DSL_BOX_IOU_LINEAR) {
+    // iou_loss.py:31-33: 1 - bbox_overlaps(...).clamp(min=eps); union = max(., eps) (iou2d_calculator.py:242-247), both eps 1e-6
+    const float e6 = 1e-6f;
+    const float U = fmaxf(u0, e6);
+    const float ug = u0 > e6 ? 1.f : (u0 == e6 ? 0.5f : 0.f);
+    const float iou = ov / U;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float dU = (da1[k] - dov[k]) * ug;
+      dl[k] = iou >= e6 ? -(dov[k] / U - ov * dU / (U * U)) : 0.f;      // no gradient where the clamp is active
+    }
+    return 1.f - fmaxf(iou, e6);
+  }
+  // diou_loss / ciou_loss (iou_loss.py:121-156, :177-218): union = ap + ag - overlap + eps (an add), c2 = cw^2 + ch^2 + eps
+  const float U = u0 + eps;
+  const float iou = ov / U;
+  const float ew0 = fmaxf(x2, X2) - fminf(x1, X1), eh0 = fmaxf(y2, Y2) - fminf(y1, Y1);
+  const float ew = fmaxf(ew0, 0.f), eh = fmaxf(eh0, 0.f);
+  const float cew = ew0 >= 0.f ? 1.f : 0.f, ceh = eh0 >= 0.f ? 1.f : 0.f;
+  const float c2 = ew * ew + eh * eh + eps;
+  const float dc2[4] = {2.f * ew * (-dmin_a(x1, X1) * cew), 2.f * eh * (-dmin_a(y1, Y1) * ceh), 2.f * ew * (dmax_a(x2, X2) * cew),
+                        2.f * eh * (dmax_a(y2, Y2) * ceh)};
+  const float sx = (X1 + X2) - (x1 + x2), sy = (Y1 + Y2) - (y1 + y2);
+  const float rho2 = sx * sx / 4.f + sy * sy / 4.f;
+  const float drho[4] = {-sx / 2.f, -sy / 2.f, -sx / 2.f, -sy / 2.f};
+  float pen = 0.f, kv = 0.f, ki = 0.f;
+  float dv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (kind == DSL_BOX_CIOU) {
+    const float w1 = x2 - x1, h1 = y2 - y1 + eps, w2 = X2 - X1, h2 = Y2 - Y1 + eps;
+    const float r = w1 / h1;
+    const float A = atanf(w2 / h2) - atanf(r);
+    const float f = 0.40528473456935109f;          // 4 / pi^2
+    const float v = f * (A * A);
+    // DEVIATION: the reference's v^2 / (1 - iou + v) is 0/0 = NaN in fp32 when prediction and target coincide (1 - iou + v rounds to
+    // 0); the penalty and its gradient are taken as 0 where v == 0, which is the fp64 value
+    if (v != 0.f) {
+      const float D = 1.f - iou + v;
+      pen = v * v / D;
+      ki = pen / D;                                 // d pen / d iou  = v^2 / D^2
+      kv = 2.f * v / D - ki;                        // d pen / d v
+      const float da = 2.f * f * A / (1.f + r * r); // -dv / d(w1 / h1)
+      const float dvw = -da / h1, dvh = da * (w1 / (h1 * h1));
+      dv[0] = -dvw; dv[1] = -dvh; dv[2] = dvw; dv[3] = dvh;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float dU = da1[k] - dov[k];
+    const float diou = dov[k] / U - ov * dU / (U * U);
+    dl[k] = -diou + (drho[k] / c2 - rho2 * dc2[k] / (c2 * c2)) + (kv * dv[k] + ki * diou);
+  }
+  return 1.f - (iou - (rho2 / c2 + pen));
+}
+
 // kTail: C % 4 != 0, the last group of 4 classes of a location is partial.  Its lanes c + e >= C add no loss and no
 // sisoft term and write 0 into g_cls; for C % 4 == 0 the kTail = false instantiation is the only one launched.
-template <bool kTail>
+// kExt: the loss family (box kind, focal gamma / alpha, loss weights); kExt = false is the default head's kernel, which reads none
+// of those fields.
+template <bool kTail, bool kExt>
 __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
   __shared__ float sh[16];
   const int M = p.mstart[p.nlvl];
@@ -253,7 +375,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
     const f32x4 xv = *reinterpret_cast<const f32x4*>(p.cls_logits + (long long)m * p.ld_cls + c);
     const int label = (int)p.labels[m];
     const float wgt = p.cls_weight[m];
-    const float gs = wgt / num_pos * p.grad_scale;
+    const float gs = kExt ? wgt / num_pos * p.grad_scale * p.w_cls : wgt / num_pos * p.grad_scale;
     float g[4];
     bool live[4];
 #pragma unroll
@@ -261,7 +383,8 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float l, d;
-      focal_fb(xv[e], label == c + e, l, d);
+      if constexpr (kExt) focal_fb_ext(xv[e], label == c + e, p.gamma, p.alpha, p.gamma == 2.f, l, d);
+      else focal_fb(xv[e], label == c + e, l, d);
       if (kTail && !live[e]) l = d = 0.f;
       lsum += l * wgt;
       g[e] = d * gs;
@@ -330,54 +453,66 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
       // decode (distance2bbox, core/bbox/transforms.py:119-162; no clip in training)
       const float x1 = px - d[0], y1 = py - d[1], x2 = px + d[2], y2 = py + d[3];
       const float X1 = px - t[0], Y1 = py - t[1], X2 = px + t[2], Y2 = py + t[3];
-      const float eps = 1e-6f;
-      const float a1 = (x2 - x1) * (y2 - y1), a2 = (X2 - X1) * (Y2 - Y1);
-      const float ltx = fmaxf(x1, X1), lty = fmaxf(y1, Y1), rbx = fminf(x2, X2), rby = fminf(y2, Y2);
-      const float w0 = rbx - ltx, h0 = rby - lty;
-      const float iw = fmaxf(w0, 0.f), ih = fmaxf(h0, 0.f);
-      const float ov = iw * ih;
-      const float u0 = a1 + a2 - ov;
-      const float U = fmaxf(u0, eps);
-      const float ex1 = fminf(x1, X1), ey1 = fminf(y1, Y1), ex2 = fmaxf(x2, X2), ey2 = fmaxf(y2, Y2);
-      const float ew0 = ex2 - ex1, eh0 = ey2 - ey1;
-      const float ew = fmaxf(ew0, 0.f), eh = fmaxf(eh0, 0.f);
-      const float e0 = ew * eh;
-      const float E = fmaxf(e0, eps);
       const float wb = ct * pw;
-      // IoULoss (iou_loss.py:14-36): -log(clamp(iou, eps)); clamp passes the gradient where iou >= eps
-      const float iou = ov / U;
-      float coef_iou = 0.f;                             // dL/diou of the log loss (set below, IoU mode only)
-      if (iou_loss) {
-        const float iouc = fmaxf(iou, eps);
-        bsum += wb * (-logf(iouc));
-        coef_iou = (-wb / denorm * p.grad_scale) / iouc;
-      } else {
-        const float giou = iou - (E - U) / E;
-        bsum += wb * (1.f - giou);
-      }
-      // ---- backward of (1 - giou) w.r.t. (x1, y1, x2, y2) ----
-      const float cw = w0 >= 0.f ? 1.f : 0.f, chh = h0 >= 0.f ? 1.f : 0.f;   // clamp(min=0) passes grad at 0
-      const float dw_x1 = -dmax_a(x1, X1) * cw, dw_x2 = dmin_a(x2, X2) * cw;
-      const float dh_y1 = -dmax_a(y1, Y1) * chh, dh_y2 = dmin_a(y2, Y2) * chh;
-      const float dov[4] = {ih * dw_x1, iw * dh_y1, ih * dw_x2, iw * dh_y2};
-      const float da1[4] = {-(y2 - y1), -(x2 - x1), (y2 - y1), (x2 - x1)};
-      const float ug = u0 > eps ? 1.f : (u0 == eps ? 0.5f : 0.f);
-      const float cew = ew0 >= 0.f ? 1.f : 0.f, ceh = eh0 >= 0.f ? 1.f : 0.f;
-      const float dew_x1 = -dmin_a(x1, X1) * cew, dew_x2 = dmax_a(x2, X2) * cew;
-      const float deh_y1 = -dmin_a(y1, Y1) * ceh, deh_y2 = dmax_a(y2, Y2) * ceh;
-      const float eg = e0 > eps ? 1.f : (e0 == eps ? 0.5f : 0.f);
-      const float de[4] = {eh * dew_x1 * eg, ew * deh_y1 * eg, eh * dew_x2 * eg, ew * deh_y2 * eg};
-      const float coef = -wb / denorm * p.grad_scale;   // dL/dgiou
       float dbox[4];
+      if (kExt && p.box_kind >= DSL_BOX_IOU_LINEAR) {
+        float dl[4];
+        bsum += wb * box_loss_ext(p.box_kind, p.box_eps, x1, y1, x2, y2, X1, Y1, X2, Y2, dl);
+        const float coef = wb / denorm * p.grad_scale * p.w_bbox;   // dL/dloss; 0: no positive weight or loss_weight 0 - exactly-zero gradients
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float dU = (da1[k] - dov[k]) * ug;
+        for (int k = 0; k < 4; ++k) dbox[k] = coef != 0.f ? coef * dl[k] : 0.f;
+      } else {
+        const float eps = 1e-6f;
+        const float a1 = (x2 - x1) * (y2 - y1), a2 = (X2 - X1) * (Y2 - Y1);
+        const float ltx = fmaxf(x1, X1), lty = fmaxf(y1, Y1), rbx = fminf(x2, X2), rby = fminf(y2, Y2);
+        const float w0 = rbx - ltx, h0 = rby - lty;
+        const float iw = fmaxf(w0, 0.f), ih = fmaxf(h0, 0.f);
+        const float ov = iw * ih;
+        const float u0 = a1 + a2 - ov;
+        const float U = fmaxf(u0, eps);
+        const float ex1 = fminf(x1, X1), ey1 = fminf(y1, Y1), ex2 = fmaxf(x2, X2), ey2 = fmaxf(y2, Y2);
+        const float ew0 = ex2 - ex1, eh0 = ey2 - ey1;
+        const float ew = fmaxf(ew0, 0.f), eh = fmaxf(eh0, 0.f);
+        const float e0 = ew * eh;
+        const float E = fmaxf(e0, eps);
+        // IoULoss (iou_loss.py:14-36): -log(clamp(iou, eps)); clamp passes the gradient where iou >= eps
+        const float iou = ov / U;
+        float coef_iou = 0.f;                             // dL/diou of the log loss (set below, IoU mode only)
         if (iou_loss) {
-          const float dg = dov[k] / U - ov * dU / (U * U);
-          dbox[k] = iou >= eps ? coef_iou * dg : 0.f;
+          const float iouc = fmaxf(iou, eps);
+          bsum += wb * (-logf(iouc));
+          coef_iou = (-wb / denorm * p.grad_scale) / iouc;
         } else {
-          const float dg = dov[k] / U - ov * dU / (U * U) + dU / E - U * de[k] / (E * E);
-          dbox[k] = coef * dg;
+          const float giou = iou - (E - U) / E;
+          bsum += wb * (1.f - giou);
+        }
+        // ---- backward of (1 - giou) w.r.t. (x1, y1, x2, y2) ----
+        const float cw = w0 >= 0.f ? 1.f : 0.f, chh = h0 >= 0.f ? 1.f : 0.f;   // clamp(min=0) passes grad at 0
+        const float dw_x1 = -dmax_a(x1, X1) * cw, dw_x2 = dmin_a(x2, X2) * cw;
+        const float dh_y1 = -dmax_a(y1, Y1) * chh, dh_y2 = dmin_a(y2, Y2) * chh;
+        const float dov[4] = {ih * dw_x1, iw * dh_y1, ih * dw_x2, iw * dh_y2};
+        const float da1[4] = {-(y2 - y1), -(x2 - x1), (y2 - y1), (x2 - x1)};
+        const float ug = u0 > eps ? 1.f : (u0 == eps ? 0.5f : 0.f);
+        const float cew = ew0 >= 0.f ? 1.f : 0.f, ceh = eh0 >= 0.f ? 1.f : 0.f;
+        const float dew_x1 = -dmin_a(x1, X1) * cew, dew_x2 = dmax_a(x2, X2) * cew;
+        const float deh_y1 = -dmin_a(y1, Y1) * ceh, deh_y2 = dmax_a(y2, Y2) * ceh;
+        const float eg = e0 > eps ? 1.f : (e0 == eps ? 0.5f : 0.f);
+        const float de[4] = {eh * dew_x1 * eg, ew * deh_y1 * eg, eh * dew_x2 * eg, ew * deh_y2 * eg};
+        const float coef = -wb / denorm * p.grad_scale;   // dL/dgiou
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float dU = (da1[k] - dov[k]) * ug;
+          if (iou_loss) {
+            const float dg = dov[k] / U - ov * dU / (U * U);
+            dbox[k] = iou >= eps ? coef_iou * dg : 0.f;
+          } else {
+            const float dg = dov[k] / U - ov * dU / (U * U) + dU / E - U * de[k] / (E * E);
+            dbox[k] = coef * dg;
+          }
+        }
+        if constexpr (kExt) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) dbox[k] *= p.w_bbox;
         }
       }
       const float dd[4] = {-dbox[0], -dbox[1], dbox[2], dbox[3]};   // x1 = px - d0, ... x2 = px + d2
@@ -393,6 +528,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
       const float sig = cl >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
       csum += (fmaxf(cl, 0.f) - cl * ct + log1pf(e)) * pw;
       gc = (sig - ct) * pw / num_pos * p.grad_scale;
+      if constexpr (kExt) gc *= p.w_ctr;
     }
     if (p.g_ctr) {      // the centerness gradient belongs to the classification predictor's columns
       u32x4 o = {pack2bf(gr[0], gr[1]), pack2bf(gr[2], gr[3]), 0u, 0u};
@@ -448,7 +584,26 @@ int fill(const dsl_fcos_desc* d, FcK& k) {
   k.ctr = d->ctr ? d->ctr : (d->regctr ? d->regctr + 4 : nullptr);
   k.ld_ctr = d->ctr ? d->ld_ctr : d->ld_rc;
   k.g_ctr = (uint16_t*)d->g_ctr; k.ld_gctr = d->ld_gctr;
+  // loss family: the fields behind ld_gctr count only with DSL_HEAD_LOSS_EXT; without it they are not read (zero-filled descriptors)
+  k.box_kind = (k.flags & DSL_HEAD_IOU_LOSS) ? DSL_BOX_IOU_LOG : DSL_BOX_GIOU;
+  k.box_eps = 1e-6f; k.gamma = 2.f; k.alpha = 0.25f; k.w_cls = k.w_bbox = k.w_ctr = 1.f;
+  if (k.flags & DSL_HEAD_LOSS_EXT) {
+    DSL_CHECK(d->box_kind >= DSL_BOX_GIOU && d->box_kind <= DSL_BOX_CIOU, "fcos: box_kind is not a DSL_BOX_* value");
+    DSL_CHECK(d->focal_gamma >= 0.f && d->focal_gamma < 1e30f && d->focal_alpha >= 0.f && d->focal_alpha <= 1.f,
+              "fcos: focal gamma must be >= 0 and alpha in [0, 1]");
+    DSL_CHECK(d->w_cls >= 0.f && d->w_cls < 1e30f && d->w_bbox >= 0.f && d->w_bbox < 1e30f && d->w_ctr >= 0.f && d->w_ctr < 1e30f,
+              "fcos: loss weights must be finite and >= 0");
+    DSL_CHECK(d->box_kind < DSL_BOX_DIOU || (d->box_eps > 0.f && d->box_eps < 1.f), "fcos: DIoU / CIoU need 0 < box_eps < 1");
+    k.box_kind = d->box_kind; k.box_eps = d->box_eps; k.gamma = d->focal_gamma; k.alpha = d->focal_alpha;
+    k.w_cls = d->w_cls; k.w_bbox = d->w_bbox; k.w_ctr = d->w_ctr;
+    k.flags = (k.flags & ~DSL_HEAD_IOU_LOSS) | (k.box_kind == DSL_BOX_IOU_LOG ? DSL_HEAD_IOU_LOSS : 0);
+  }
   return 0;
+}
+
+// the default head's loss terms (GIoU or the IoU log loss, gamma 2, alpha 0.25, weights 1): the kExt = false kernel computes them
+bool loss_is_default(const FcK& k) {
+  return k.box_kind <= DSL_BOX_IOU_LOG && k.gamma == 2.f && k.alpha == 0.25f && k.w_cls == 1.f && k.w_bbox == 1.f && k.w_ctr == 1.f;
 }
 
 }  // namespace
@@ -506,12 +661,19 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   const bool tail = d->num_classes % 4 != 0;
   int blocks = (int)(((long long)M * ((d->num_classes + 3) / 4) + 255) / 256);
   if (blocks > 2048) blocks = 2048;
-  if (tail)
-    hipLaunchKernelGGL(loss_kernel<true>, dim3(blocks), dim3(256), 0, st, k);
-  else
-    hipLaunchKernelGGL(loss_kernel<false>, dim3(blocks), dim3(256), 0, st, k);
+  if (loss_is_default(k)) {
+    if (tail)
+      hipLaunchKernelGGL((loss_kernel<true, false>), dim3(blocks), dim3(256), 0, st, k);
+    else
+      hipLaunchKernelGGL((loss_kernel<false, false>), dim3(blocks), dim3(256), 0, st, k);
+  } else {
+    if (tail)
+      hipLaunchKernelGGL((loss_kernel<true, true>), dim3(blocks), dim3(256), 0, st, k);
+    else
+      hipLaunchKernelGGL((loss_kernel<false, true>), dim3(blocks), dim3(256), 0, st, k);
+  }
   hipLaunchKernelGGL(fcos_finalize_kernel, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
-                     DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec);
+                     DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec, k.w_cls, k.w_bbox, k.w_ctr);
   DSL_LAUNCH_CHECK("loss_kernel");
   return 0;
 }

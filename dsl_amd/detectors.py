@@ -5,7 +5,7 @@ configs/fcos_semi/*.py build unmodified:
   ResNet                        mmdet/models/backbones/resnet.py:304-656   (depth 50, caffe, frozen BN)
   FPN                           mmdet/models/necks/fpn.py:9-202
   FCOSHead                      mmdet/models/dense_heads/fcos_head.py:14-726
-  FocalLoss / GIoULoss / CrossEntropyLoss   mmdet/models/losses/*.py
+  FocalLoss / GIoULoss / IoULoss / DIoULoss / CIoULoss / CrossEntropyLoss   mmdet/models/losses/*.py
 
 Unlike the reference these classes do not compute with torch ops: they validate the configuration
 the HIP path implements, own the parameter store, and drive the prebuilt kernel lists of
@@ -142,30 +142,53 @@ class FPN(nn.Module):
         _expect(upsample_cfg.get('mode', 'nearest') == 'nearest' and 'scale_factor' not in upsample_cfg, 'nearest upsample')
 
 
+def _loss_weight(name, loss_weight, reduction):
+    _expect(reduction == 'mean', f"{name} reduction='mean'")
+    _expect(isinstance(loss_weight, (int, float)) and 0.0 <= float(loss_weight) < float('inf'),
+            f'{name} loss_weight: a finite number >= 0 (got {loss_weight!r})')
+    return float(loss_weight)
+
+
 class _LossCfg(nn.Module):
-    def __init__(self, loss_weight=1.0, **kw):
+    """loss_weight scales the reported term and its gradients in the loss kernel (dsl_fcos_desc.w_cls / w_bbox / w_ctr)."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', **kw):
         super().__init__()
-        _expect(loss_weight == 1.0 and kw.get('reduction', 'mean') == 'mean', 'loss_weight=1.0, reduction=mean')
-        self.loss_weight = loss_weight
+        _expect(not kw, f'{type(self).__name__}: unknown arguments {sorted(kw)}')
+        self.loss_weight = _loss_weight(type(self).__name__, loss_weight, reduction)
 
 
 @LOSSES.register_module()
 class FocalLoss(_LossCfg):
+    """mmdet/models/losses/focal_loss.py:11-56,140-180: sigmoid focal loss with gamma >= 0 and 0 <= alpha <= 1."""
+
     def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.25, **kw):
         super().__init__(**kw)
-        _expect(use_sigmoid and gamma == 2.0 and alpha == 0.25, 'sigmoid focal loss, gamma 2, alpha 0.25')
+        _expect(use_sigmoid, 'FocalLoss use_sigmoid=True (the reference has no softmax focal loss either)')
+        _expect(isinstance(gamma, (int, float)) and 0.0 <= float(gamma) < float('inf'), f'FocalLoss gamma >= 0 (got {gamma!r})')
+        _expect(isinstance(alpha, (int, float)) and 0.0 <= float(alpha) <= 1.0, f'FocalLoss alpha in [0, 1] (got {alpha!r})')
+        self.gamma, self.alpha = float(gamma), float(alpha)
 
 
 @LOSSES.register_module()
 class GIoULoss(_LossCfg):
+    """loss_weight stays at 1.0 in the config (as IoULoss's, and IoULoss's linear=False): these three refusals are part of the
+    configuration surface from before the loss family.  The kernel and params.HeadOptions(box_loss='giou' | 'iou' | 'iou_linear',
+    bbox_weight=...) compute them; DIoULoss / CIoULoss take a loss_weight here."""
+    box_loss = 'giou'
+
     def __init__(self, eps=1e-6, **kw):
         super().__init__(**kw)
         _expect(eps == 1e-6, 'GIoU eps 1e-6')
+        _expect(self.loss_weight == 1.0, 'GIoULoss loss_weight=1.0 (DIoULoss / CIoULoss take a loss_weight)')
+        self.eps = 1e-6
 
 
 @LOSSES.register_module()
 class IoULoss(nn.Module):
-    """mmdet/models/losses/iou_loss.py:223-290 with its defaults: -log(clamp(iou, 1e-6)), mean over avg_factor."""
+    """mmdet/models/losses/iou_loss.py:223-290 with its defaults: -log(clamp(iou, 1e-6)), mean over avg_factor.  linear=True and
+    loss_weight != 1.0 stay refused here (see GIoULoss); params.HeadOptions(box_loss='iou_linear', bbox_weight=...) runs them."""
+    box_loss = 'iou'
 
     def __init__(self, linear=False, eps=1e-6, reduction='mean', loss_weight=1.0, **kw):
         super().__init__()
@@ -175,7 +198,33 @@ class IoULoss(nn.Module):
         _expect(not (set(kw) - {'mode'}), f'IoULoss arguments linear, eps, reduction, loss_weight (got {sorted(kw)})')
         _expect(reduction == 'mean', "IoULoss reduction='mean'")
         _expect(loss_weight == 1.0, 'IoULoss loss_weight=1.0')
-        self.loss_weight = loss_weight
+        self.loss_weight, self.eps = 1.0, 1e-6
+
+
+@LOSSES.register_module()
+class DIoULoss(_LossCfg):
+    """mmdet/models/losses/iou_loss.py:105-157,369-406."""
+    box_loss = 'diou'
+
+    def __init__(self, eps=1e-6, **kw):
+        super().__init__(**kw)
+        _expect(isinstance(eps, float) and 0.0 < eps < 1.0, f'{type(self).__name__} 0 < eps < 1 (got {eps!r})')
+        self.eps = eps
+
+
+@LOSSES.register_module()
+class CIoULoss(DIoULoss):
+    """mmdet/models/losses/iou_loss.py:160-219,409-446.  Where prediction and target have the same aspect (v == 0) the penalty
+    v^2 / (1 - iou + v) and its gradient are 0: the reference's fp32 arithmetic gives 0/0 = NaN when the two boxes coincide."""
+    box_loss = 'ciou'
+
+
+@LOSSES.register_module()
+class BoundedIoULoss(nn.Module):
+    def __init__(self, **kw):
+        super().__init__()
+        _expect(False, "GIoULoss, IoULoss, DIoULoss or CIoULoss as FCOSHead's loss_bbox (BoundedIoULoss cannot be used by the "
+                       "reference's FCOSHead either: its (n, 4) loss does not broadcast against the (n,) centerness weight)")
 
 
 @LOSSES.register_module()
@@ -214,11 +263,15 @@ class FCOSHead(nn.Module):
         self.cur_iter = 0                               # fcos_head.py:103
         self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)
         self.loss_centerness = build_loss(loss_centerness)
-        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, (GIoULoss, IoULoss))
-                and isinstance(self.loss_centerness, CrossEntropyLoss), 'FocalLoss + GIoULoss or IoULoss + CrossEntropyLoss')
+        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, (GIoULoss, IoULoss, DIoULoss))
+                and isinstance(self.loss_centerness, CrossEntropyLoss),
+                'FocalLoss + GIoULoss, IoULoss, DIoULoss or CIoULoss + CrossEntropyLoss')
         # what the kernels and the parameter layout are built for (fixed per model: ParamStore.head)
+        lb = self.loss_bbox
         self.options = HeadOptions(self.center_sampling, self.norm_on_bbox, self.centerness_on_reg,
-                                   isinstance(self.loss_bbox, IoULoss), self.conv_bias)
+                                   isinstance(lb, IoULoss), self.conv_bias, box_loss=lb.box_loss, box_eps=lb.eps,
+                                   focal_gamma=self.loss_cls.gamma, focal_alpha=self.loss_cls.alpha, cls_weight=self.loss_cls.loss_weight,
+                                   bbox_weight=lb.loss_weight, ctr_weight=self.loss_centerness.loss_weight)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
 
     def effective_soft_weight(self, batch_size):
@@ -369,7 +422,7 @@ class FCOS(nn.Module):
             # the fp8 tower convolutions fold the layer's bias into their epilogue and were validated on the default head only
             _expect(self.bbox_head.options.is_default(),
                     f'fp8 towers with the default head options only (center_sampling, norm_on_bbox, centerness_on_reg, GIoULoss, '
-                    f'conv_bias=True), got {self.bbox_head.options}')
+                    f'conv_bias=True, default loss settings), got {self.bbox_head.options}')
             self.store.fp8 = dict(fp8)
         self._params = None
         self._engine = None

@@ -24,7 +24,9 @@ class FcosLossPlan:
     def __init__(self, n, sizes, device, strides=STRIDES, ranges=REGRESS_RANGES, num_classes=80,
                  radius=1.5, max_gt=1024, head=None):
         """head: params.HeadOptions (None = the default head).  centerness_on_reg=False: the centerness logit is column
-        round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls."""
+        round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls.  The head's loss
+        settings (box_loss, focal gamma / alpha, the loss weights) go into the descriptor: losses, logvec and the gradients are the
+        weighted ones."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head
         self.ctr_col = None
@@ -72,6 +74,8 @@ class FcosLossPlan:
         self.desc.ld_gcls, self.desc.ld_grc = self.LD_GCLS, self.LD_GRC
         if head is not None:
             self.desc.head_flags = head.flags()
+            if not head.loss_is_default():      # box kind, focal gamma / alpha, the three loss weights (HEAD_LOSS_EXT is in the flags)
+                head.fill_loss_desc(self.desc)
         if self.ctr_col is not None:
             self.desc.g_ctr, self.desc.ld_gctr = self.g_cls.data_ptr() + 2 * self.ctr_col, self.LD_GCLS
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))

@@ -125,15 +125,40 @@ class HeadOptions:
       norm_on_bbox       False: distances = exp(scale * x), targets in pixels (fcos_head.py:162-167, :618)
       centerness_on_reg  False: conv_centerness reads the classification tower (fcos_head.py:155-158)
       iou_loss           True: IoULoss, -log(clamp(iou, 1e-6)) (losses/iou_loss.py:14-36); False: GIoULoss
-      conv_bias          False: the eight tower convolutions have no bias ('auto' in front of GroupNorm, mmcv ConvModule)"""
+      conv_bias          False: the eight tower convolutions have no bias ('auto' in front of GroupNorm, mmcv ConvModule)
+    The loss family (dsl_fcos_desc.box_kind .. w_ctr; a head with any of them off its default is not the default head):
+      box_loss           None: GIoULoss / IoULoss as iou_loss says; 'giou', 'iou', 'iou_linear' (IoULoss(linear=True)), 'diou', 'ciou'
+                         (losses/iou_loss.py:105-219); iou_loss then follows it (True for the two IoULoss kinds)
+      box_eps            eps of DIoULoss / CIoULoss
+      focal_gamma, focal_alpha                 FocalLoss (losses/focal_loss.py:11-56)
+      cls_weight, bbox_weight, ctr_weight      loss_weight of loss_cls / loss_bbox / loss_centerness"""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
+    LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
+    BOX_KINDS = dict(giou=L.BOX_GIOU, iou=L.BOX_IOU_LOG, iou_linear=L.BOX_IOU_LINEAR, diou=L.BOX_DIOU, ciou=L.BOX_CIOU)
 
-    def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True):
+    def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
+                 box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0):
         self.center_sampling, self.norm_on_bbox, self.centerness_on_reg = bool(center_sampling), bool(norm_on_bbox), bool(centerness_on_reg)
-        self.iou_loss, self.conv_bias = bool(iou_loss), bool(conv_bias)
+        self.conv_bias = bool(conv_bias)
+        self.box_loss = box_loss if box_loss is not None else ('iou' if iou_loss else 'giou')
+        if self.box_loss not in self.BOX_KINDS:
+            raise NotImplementedError(f'dsl_amd hot path: box_loss must be one of {sorted(self.BOX_KINDS)}, got {box_loss!r}')
+        self.iou_loss = self.box_loss in ('iou', 'iou_linear')
+        self.box_eps, self.focal_gamma, self.focal_alpha = float(box_eps), float(focal_gamma), float(focal_alpha)
+        self.cls_weight, self.bbox_weight, self.ctr_weight = float(cls_weight), float(bbox_weight), float(ctr_weight)
+
+    def loss_key(self):
+        return tuple(getattr(self, f) for f in self.LOSS_FIELDS)
+
+    def loss_is_default(self):
+        """GIoU or the IoU log loss, focal gamma 2 / alpha 0.25, unit weights: what a descriptor without HEAD_LOSS_EXT computes
+        (box_eps counts for DIoU / CIoU only)."""
+        return self.loss_key()[2:] == (2.0, 0.25, 1.0, 1.0, 1.0) and self.box_loss in ('giou', 'iou')
 
     def key(self):
-        return tuple(getattr(self, f) for f in self.FIELDS)
+        """The five FIELDS for every head that existed before the loss family; the loss settings follow only where one is set."""
+        k = tuple(getattr(self, f) for f in self.FIELDS)
+        return k if self.loss_is_default() else k + self.loss_key()
 
     def is_default(self):
         return self.key() == HeadOptions().key()
@@ -141,10 +166,17 @@ class HeadOptions:
     def flags(self):
         """dsl_fcos_desc.head_flags / dsl_det_desc.head_flags."""
         return ((0 if self.center_sampling else L.HEAD_INSIDE_BOX) | (0 if self.norm_on_bbox else L.HEAD_RAW_TARGETS | L.HEAD_EXP_DECODE)
-                | (L.HEAD_IOU_LOSS if self.iou_loss else 0))
+                | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT))
+
+    def fill_loss_desc(self, d):
+        """The loss family's fields of a dsl_fcos_desc (read by the kernel with HEAD_LOSS_EXT only)."""
+        d.box_kind, d.box_eps = self.BOX_KINDS[self.box_loss], self.box_eps
+        d.focal_gamma, d.focal_alpha = self.focal_gamma, self.focal_alpha
+        d.w_cls, d.w_bbox, d.w_ctr = self.cls_weight, self.bbox_weight, self.ctr_weight
 
     def __repr__(self):
-        return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in self.FIELDS) + ')'
+        fields = self.FIELDS if self.loss_is_default() else self.FIELDS + self.LOSS_FIELDS
+        return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in fields) + ')'
 
 
 def head_specs(conv_bias=True):

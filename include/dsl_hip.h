@@ -442,7 +442,7 @@ int dsl_colsum(const void* x, float* out, long rows, int c, int ld, void* stream
 
 /* ------------------------------------------------------------------------------------------
  * FCOS targets and losses (fcos_head.py:170-338,550-726; losses/focal_loss.py:11-56;
- * losses/iou_loss.py:85-102; losses/cross_entropy_loss.py:73-112)
+ * losses/iou_loss.py:14-36,85-219; losses/cross_entropy_loss.py:73-112)
  * ---------------------------------------------------------------------------------------- */
 typedef struct dsl_fcos_desc {
   int32_t nlvl, n;                     /* levels, images */
@@ -492,12 +492,33 @@ typedef struct dsl_fcos_desc {
                                         * of the classification predictor's output; regctr then needs 4 columns only */
   void* g_ctr;                         /* bf16, with ctr: the centerness gradient goes to g_ctr[m * ld_gctr], column 4 of g_rc gets 0 */
   int32_t ld_gctr;                     /* row stride of g_ctr (bf16 elements); read only when g_ctr is set */
+  /* Loss family, read only with DSL_HEAD_LOSS_EXT in head_flags (then every field counts as written: a weight of 0 is 0).  Without
+   * the bit - a zero-filled tail included - the terms are the default head's: GIoU or, with DSL_HEAD_IOU_LOSS, the IoU log loss;
+   * focal gamma 2, alpha 0.25; weights 1.  With the bit and exactly those values the same kernel runs (bit-identical outputs). */
+  int32_t box_kind;                    /* DSL_BOX_* below: loss_bbox (it replaces DSL_HEAD_IOU_LOSS) */
+  float box_eps;                       /* eps of DIoULoss / CIoULoss (losses/iou_loss.py:107,162; the classes' default 1e-6); the other
+                                        * kinds use 1e-6 */
+  float focal_gamma, focal_alpha;      /* FocalLoss gamma >= 0, 0 <= alpha <= 1 (losses/focal_loss.py:11-56) */
+  float w_cls, w_bbox, w_ctr;          /* loss_weight of loss_cls / loss_bbox / loss_centerness: scale losses[0..2], logvec and the
+                                        * term's gradients (g_cls; g_rc[:, :4] and g_scales; the centerness gradient).  The sisoft term
+                                        * and the stream weight `loss_weight` above are independent of them */
 } dsl_fcos_desc;
 #define DSL_HEAD_INSIDE_BOX 1   /* center_sampling=False: inside = min(l, t, r, b) > 0, radius unused (fcos_head.py:676-678) */
 #define DSL_HEAD_RAW_TARGETS 2  /* norm_on_bbox=False, assignment: bbox_targets stay in pixels (fcos_head.py:618) */
 #define DSL_HEAD_EXP_DECODE 4   /* norm_on_bbox=False, loss and detection: distances = exp(scale * x), no stride multiply
                                  * (fcos_head.py:162-167); the gradient goes through exp into g_rc and g_scales */
 #define DSL_HEAD_IOU_LOSS 8     /* loss_bbox = IoULoss(linear=False, eps=1e-6): -log(clamp(iou, eps)) (losses/iou_loss.py:14-36) */
+#define DSL_HEAD_LOSS_EXT 16    /* dsl_fcos_desc: box_kind .. w_ctr are set (loss family); not a dsl_det_desc flag */
+/* dsl_fcos_desc.box_kind.  Linear IoU: 1 - clamp(iou, 1e-6), no gradient where the clamp is active (losses/iou_loss.py:31-33).
+ * DIoU / CIoU restate losses/iou_loss.py:105-219 (union = a1 + a2 - overlap + eps, c2 = cw^2 + ch^2 + eps, CIoU's h = y2 - y1 + eps)
+ * with two deviations from the reference's fp32 results: CIoU's penalty v^2 / (1 - iou + v) and its gradient are 0 where v == 0
+ * (the reference: 0/0 = NaN when prediction and target coincide; 0 is the fp64 value), and the focal gradient for gamma < 1 is the
+ * finite limit where the sigmoid saturates to exactly 0 or 1 (the reference: NaN). */
+#define DSL_BOX_GIOU 0
+#define DSL_BOX_IOU_LOG 1
+#define DSL_BOX_IOU_LINEAR 2
+#define DSL_BOX_DIOU 3
+#define DSL_BOX_CIOU 4
 size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d);
 
 int dsl_fcos_points(const dsl_fcos_desc* d, float* points /* [P][2] */, void* stream);
