@@ -39,6 +39,7 @@ MAX_MULTI = 16
 SLOT_TAIL, SLOT_PREFIX = 13, 14     # pipelined frozen prefix: 'previous backward's data-gradient chain done', 'prefix of this step done'
 SLOT_PACKS = 15      # named event: the data-gradient weight packs of the last optimizer step are complete
 SUMSQ_PARTS = 256
+ACC_SET, ACC_ADD, ACC_FOLD = 0, 1, 2      # DSL_ACC_*: dsl_grad_accumulate's mode
 SLOT_UPD = 8         # named events 8 .. 11: gradient bucket 0 .. 3 of the last optimizer step is updated (late exchange)
 SLOT_HEADW = 12      # named event: the head + FPN bucket of the last optimizer step is updated (deferred head update)
 (RLA_AVGPOOL, RLA_AVGPOOL_BWD, RLA_BN_TANH, RLA_BN_TANH_BWD, RLA_BN_FOLD, RLA_BN_POST, RLA_REC_SUM, RLA_TAIL_FWD, RLA_TAIL_BWD) = range(2, 11)
@@ -232,6 +233,7 @@ _SIGS = {
     'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
+    'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],
     'dsl_ema_lerp': [_vp, _vp, _l, _f, _vp], 'dsl_ema_lerp_bf16': [_vp, _vp, _vp, _l, _f, _vp], 'dsl_cast_bf16': [_vp, _vp, _l, _vp],
     'dsl_pack_dgrad': [_vp, _vp, _vp, _i, _i, _i, _i, _vp], 'dsl_pack_dgrad_batched': [_vp, _i, _i, _vp],
     'dsl_detect_workspace_bytes': [_vp], 'dsl_fcos_detect': [_vp, _vp],

@@ -151,6 +151,22 @@ __global__ __launch_bounds__(256) void pack_dgrad_batched_kernel(const dsl_pack_
   }
 }
 
+// Gradient accumulation (FlatSGD.accumulate / the fold in front of a window's closing update): plain fp32 adds, one rounding per
+// element per micro-step, every element owned by one thread - no atomics, the sum's order is the micro-steps' order.  16-byte
+// accesses, grid-stride; HBM-bound (SET 8, ADD / FOLD 12 bytes per element).
+template <int MODE>
+__global__ __launch_bounds__(256) void grad_acc_kernel(float* __restrict__ acc, float* __restrict__ g, long long n4) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 4 * i);
+    if (MODE == DSL_ACC_SET) {
+      *reinterpret_cast<f32x4*>(acc + 4 * i) = gv;
+    } else {
+      const f32x4 s = *reinterpret_cast<const f32x4*>(acc + 4 * i) + gv;
+      *reinterpret_cast<f32x4*>((MODE == DSL_ACC_ADD ? acc : g) + 4 * i) = s;
+    }
+  }
+}
+
 int nblocks(long long n4, int cap) {
   long long b = (n4 + 255) / 256;
   if (b > cap) b = cap;
@@ -184,6 +200,22 @@ extern "C" int dsl_sgd_step(float* p, const float* g, float* m, void* p16, const
                      (uint16_t*)p16, group, (long long)n, lr, momentum, wd, bias_lr_mult, bias_decay_mult, gnorm_sq,
                      max_norm, first_step);
   DSL_LAUNCH_CHECK("sgd_kernel");
+  return 0;
+}
+
+extern "C" int dsl_grad_accumulate(float* acc, float* g, long n, int mode, void* stream) {
+  DSL_CHECK(acc && g, "dsl_grad_accumulate: null pointer (acc=%p g=%p)", (void*)acc, (void*)g);
+  DSL_CHECK(n > 0 && n % 4 == 0, "dsl_grad_accumulate: n=%ld must be positive and a multiple of 4", n);
+  DSL_CHECK(((uintptr_t)acc | (uintptr_t)g) % 16 == 0, "dsl_grad_accumulate: pointers must be 16-byte aligned (acc=%p g=%p)", (void*)acc,
+            (void*)g);
+  DSL_CHECK(mode >= DSL_ACC_SET && mode <= DSL_ACC_FOLD, "dsl_grad_accumulate: mode=%d is none of DSL_ACC_SET / _ADD / _FOLD", mode);
+  const long long n4 = n / 4;
+  const dim3 grid(nblocks(n4, 2048)), block(256);      // memory-bound: at most 8 blocks per CU, the rest by grid stride
+  const hipStream_t st = (hipStream_t)stream;
+  if (mode == DSL_ACC_SET) hipLaunchKernelGGL(grad_acc_kernel<DSL_ACC_SET>, grid, block, 0, st, acc, g, n4);
+  else if (mode == DSL_ACC_ADD) hipLaunchKernelGGL(grad_acc_kernel<DSL_ACC_ADD>, grid, block, 0, st, acc, g, n4);
+  else hipLaunchKernelGGL(grad_acc_kernel<DSL_ACC_FOLD>, grid, block, 0, st, acc, g, n4);
+  DSL_LAUNCH_CHECK("grad_acc_kernel");
   return 0;
 }
 

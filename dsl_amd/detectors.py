@@ -471,6 +471,14 @@ class FCOS(nn.Module):
         # uses), 'torch' = a stream from torch's pool, as ProcessGroupNCCL runs its kernels on one of its own
         self.comm_proxy = None
         self._proxy_stream = None
+        # Gradient accumulation (FlatSGD.accumulate / set_closing, GradientCumulativeOptimizerHook).  accum_closing False: the next
+        # backward pass is a window's non-closing micro-step - it queues NO gradient collective (each rank banks its local gradient,
+        # the window's sum is exchanged once).  _fold_acc: the optimizer's bank while a window is open - the closing pass's
+        # exchange(info) folds it into the bucket (DSL_ACC_FOLD) in front of the collective and lists the bucket in _folded
+        self.accum_closing = True
+        self._fold_acc = None
+        self._folded = set()
+        self._bwd_exchanged = self._bwd_unexchanged = False
         self.clip_partials = None     # [buckets * SUMSQ_PARTS] floats: FlatSGD with grad_clip asks for the norm in pieces, per bucket
         self._partials_valid = False
         self._g16 = None
@@ -672,6 +680,12 @@ class FCOS(nn.Module):
         self._last_bwd_infos = [info for _, info in plan.bwd_segments]      # bucket ranges / event slots, for the optimizer
         proxy = self.comm_proxy if (self.comm_proxy and self.world_size == 1 and self.store.grad.is_cuda) else None
         ddp = (self.world_size > 1 and not self.comm_off) or proxy is not None
+        # a non-closing micro-step of an accumulation window exchanges nothing: _pending / _late_todo stay empty, no norm partials
+        closing = bool(getattr(self, 'accum_closing', True))
+        self._bwd_unexchanged = bool(ddp and not closing)
+        ddp = ddp and closing
+        self._bwd_exchanged = bool(ddp)
+        self._folded = set()
         on_gpu = self.store.grad.is_cuda
         if ddp and on_gpu and self._comm_stream is None:
             self._comm_stream = role_stream('comm', self.store.device)
@@ -691,7 +705,10 @@ class FCOS(nn.Module):
 
         def exchange(info):
             lo, hi = info['bucket']
+            acc = self._fold_acc
             if not on_gpu:            # host tensors (the gloo unit test of the bucket order): nothing to order against
+                if acc is not None:
+                    raise NotImplementedError('dsl_amd: gradient accumulation runs on the GPU only (dsl_grad_accumulate)')
                 self._pending.append(dist.all_reduce(self.store.grad[lo:hi], group=self.dist_group, async_op=True))
                 return
             from . import _lib as L
@@ -702,6 +719,11 @@ class FCOS(nn.Module):
             if info['main']:
                 cs.wait_stream(torch.cuda.current_stream())
             g = self.store.grad[lo:hi]
+            if acc is not None:
+                # the closing micro-step of an accumulation window: the bucket becomes the window's sum (bank + this pass) on the
+                # communication stream, behind the bucket's weight gradients and in front of everything that reads it from here on
+                L.check(L.lib.dsl_grad_accumulate(C_void(acc.data_ptr() + lo * 4), L.ptr(g), hi - lo, L.ACC_FOLD, csp), 'dsl_grad_accumulate')
+                self._folded.add((int(lo), int(hi)))
             if proxy is not None:
                 # the bucket's stand-in collective (no peer: the values stay): same stream, same event, same optimizer hand-over
                 L.check(L.lib.dsl_comm_proxy(L.ptr(g), (hi - lo) // 4 * 4, int(proxy.get('wgs', 32)), int(proxy.get('passes', 2)), csp),

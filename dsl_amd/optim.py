@@ -37,6 +37,8 @@ class FlatSGD:
         self.momentum_buf = None
         self.gnorm_sq = None
         self.steps = 0
+        self._acc = None          # gradient accumulation (accumulate()): the open window's running sum, laid out like store.grad
+        self.acc_count = 0        # micro-steps banked in the open window
         self.late_exchange = bool(late_exchange)      # data parallel without clipping: collectives behind the backward pass (see _sync_defer)
         self.defer_head_update = bool(defer_head_update)      # opt-in (measured slower on one GPU, LAB_NOTES: deferred head update)
         self._sync_defer()
@@ -106,6 +108,60 @@ class FlatSGD:
             fresh = True          # (copied into place on the caller's stream just now: the same ordering as for the zero fill)
         if self.gnorm_sq is None or self.gnorm_sq.device != st.device:
             self.gnorm_sq = torch.zeros(1, device=st.device)
+        if getattr(self.model, '_bwd_unexchanged', False):
+            raise RuntimeError('FlatSGD.step(): the last backward pass was declared non-closing (set_closing(False)) and queued no '
+                               'gradient exchange: call set_closing(True) in front of the train_step whose step() closes the window')
+        self._walk(True, fresh)
+        self.steps += 1
+        if self.acc_count:
+            self.acc_count = 0
+            self.model._fold_acc = None
+        self.set_closing(True)
+
+    def set_closing(self, closing):
+        """Gradient accumulation under data parallel: says whether the NEXT backward pass closes its window, i.e. is followed by
+        step() (True, the default) or by accumulate() (False: that pass queues no gradient collective - the window's sum is exchanged
+        once, by the closing pass).  Call it in front of train_step (the eager backward pass is queued in there);
+        GradientCumulativeOptimizerHook does so in before_train_iter.  step() sets it back to True."""
+        self.model.accum_closing = bool(closing)
+
+    def accumulate(self):
+        """Banks the gradient of the backward pass that has just run instead of applying it: step() with the update kernel swapped
+        for dsl_grad_accumulate - the same buckets on the same streams behind the same events (_walk), so the next backward pass
+        cannot overwrite a bucket this call still reads.  The next step() folds the bank into store.grad (DSL_ACC_FOLD) in front
+        of whatever reads each bucket first.  The bank is one fp32 tensor like store.grad, made at the first call."""
+        st, m = self.store, self.model
+        if not st.grad.is_cuda:
+            raise RuntimeError('FlatSGD.accumulate() runs on the GPU only (dsl_grad_accumulate; no host fallback)')
+        if getattr(m, '_bwd_exchanged', False) or getattr(m, '_pending', None) or getattr(m, '_late_todo', None):
+            raise RuntimeError('FlatSGD.accumulate(): the last backward pass queued its gradient exchange - a window is exchanged once, '
+                               'by its closing pass: call set_closing(False) in front of the train_step of a micro-step that accumulates')
+        fresh = False
+        if self._acc is None or self._acc.device != st.device or self._acc.shape != st.grad.shape:
+            # (from torch's allocator on the CALLER's stream, written on the walk's streams: they wait, as for the momentum's fill)
+            self._acc = torch.empty_like(st.grad)
+            self.acc_count = 0
+            fresh = True
+        self._walk(False, fresh)
+        self.acc_count += 1
+        m._fold_acc = self._acc          # (the detector folds it into each bucket in front of that bucket's exchange)
+
+    def _acc_launch(self, lo, hi, mode, tp):
+        L.check(L.lib.dsl_grad_accumulate(C.c_void_p(self._acc.data_ptr() + lo * 4), C.c_void_p(self.store.grad.data_ptr() + lo * 4),
+                                          hi - lo, mode, tp), 'dsl_grad_accumulate')
+
+    def _walk(self, update, fresh):
+        """The schedule shared by step() (update=True) and accumulate() (False): which stream touches which gradient bucket behind
+        which events.  accumulate() swaps dsl_sgd_step for dsl_grad_accumulate and leaves the data-gradient packs alone (the
+        weights did not move: SLOT_PACKS still stands for packs of the current weights); every wait and record is the same.
+        step() with banked micro-steps (acc_count > 0) folds the bank into each bucket first, unless that bucket's exchange did
+        (the detector lists those in model._folded)."""
+        st = self.store
+        window = update and self.acc_count > 0
+
+        def folded():          # (read when asked: the late exchanges run, and fold, inside this walk)
+            return getattr(self.model, '_folded', None) or ()
+        acc_mode = L.ACC_ADD if self.acc_count else L.ACC_SET
         sp = L.stream_ptr()
         lr = float(self.param_groups[0]['lr'])
         blr = float(self.param_groups[1]['lr']) / lr if lr != 0 else self.bias_lr_mult
@@ -167,6 +223,11 @@ class FlatSGD:
                 o4, o2, o1 = lo * 4, lo * 2, lo
                 if 'sgd' in skip_items():          # step-level ablation (tools/step_ablation.sh): timing only
                     continue
+                if not update:
+                    self._acc_launch(lo, hi, acc_mode, tp)
+                    continue
+                if window and (int(lo), int(hi)) not in folded():          # (no exchange in front of this bucket's update: the fold goes here)
+                    self._acc_launch(lo, hi, L.ACC_FOLD, tp)
                 L.check(L.lib.dsl_sgd_step(C.c_void_p(st.train.data_ptr() + o4), C.c_void_p(st.grad.data_ptr() + o4),
                                            C.c_void_p(self.momentum_buf.data_ptr() + o4), C.c_void_p(st.train16.data_ptr() + o2),
                                            C.c_void_p(st.group.data_ptr() + o1), hi - lo, lr, self.momentum, self.weight_decay, blr,
@@ -182,7 +243,8 @@ class FlatSGD:
                 st._pending_ev.record(self._side1)
                 # the data-gradient packs read every bucket: behind the caller's stream (its three updates) AND the deferred one,
                 # i.e. forked from the caller's stream onto the weight-gradient stream, in order behind the deferred update
-                st.repack_dgrad(sp, side=True)
+                if update:
+                    st.repack_dgrad(sp, side=True)
             elif late:
                 # nothing on the caller's stream waits: the next forward pass waits per stage (SLOT_UPD), every other reader of the
                 # parameters calls ParamStore.wait_pending; the data-gradient packs follow the last update on the optimizer's stream
@@ -192,14 +254,23 @@ class FlatSGD:
                 st.repack_dgrad(sp, side=True)
             else:
                 cur.wait_stream(os_)
-                st.repack_dgrad(sp, side=_PACK_SIDE)
-            self.steps += 1
+                if update:
+                    st.repack_dgrad(sp, side=_PACK_SIDE)
             return
         if hasattr(self.model, 'wait_grads'):
             self.model.wait_grads()
         for i in infos or []:
             if i.get('deferred'):        # a list built for the deferred head update left its last weight gradients unjoined
                 L.lib.dsl_stream_wait_slot(int(i['slot']), sp)
+        if not update:
+            self._acc_launch(0, st.n_train, acc_mode, sp)
+            return
+        if window:
+            # the buckets whose exchange folded them (data parallel) are done; the rest - one GPU: everything - in front of the norm
+            done = folded()
+            rest = [(0, st.n_train)] if not done else [i['bucket'] for i in infos or [] if (int(i['bucket'][0]), int(i['bucket'][1])) not in done]
+            for lo, hi in rest:
+                self._acc_launch(lo, hi, L.ACC_FOLD, sp)
         gptr = None
         if self.max_norm is not None:
             m = self.model
@@ -220,7 +291,6 @@ class FlatSGD:
                                    self.bias_decay_mult, L.ptr(gptr), self.max_norm or 0.0, int(self.steps == 0), sp),
                 'dsl_sgd_step')
         st.repack_dgrad(sp, side=_PACK_SIDE)
-        self.steps += 1
 
     def state_dict(self):
         # regions: where every named parameter lives in the flat momentum buffer - what load_state_dict / step remap by.
@@ -242,6 +312,8 @@ class FlatSGD:
             self._loaded_regions = {}          # (falsy, but makes step() run the size check once)
         self.gnorm_sq = None
         self._sumsq_ws = None
+        self.acc_count = 0          # (the accumulation window is not part of the state: a resume starts a fresh one)
+        self.model._fold_acc = None
 
 
 def build_optimizer(model, cfg, grad_clip=None):

@@ -538,6 +538,13 @@ int dsl_sumsq_det(const float* x, long n, float* out /* [1] */, float* workspace
 int dsl_sgd_step(float* p, const float* g, float* m, void* p16, const uint8_t* group, long n,
                  float lr, float momentum, float wd, float bias_lr_mult, float bias_decay_mult,
                  const float* gnorm_sq, float max_norm, int first_step, void* stream);
+/* Gradient accumulation over flat fp32 buffers (mmcv GradientCumulativeOptimizerHook): the gradient of one micro-step joins the
+ * window's running sum.  Plain fp32 adds in micro-step order - one rounding per element and call, no atomics, denormals kept - i.e.
+ * the bits of torch's `p.grad += g`.  n > 0, n % 4 == 0, both pointers 16-byte aligned (checked before anything is launched). */
+#define DSL_ACC_SET  0   /* acc[i]  = g[i]           first micro-step of a window (acc is not read) */
+#define DSL_ACC_ADD  1   /* acc[i] += g[i]           */
+#define DSL_ACC_FOLD 2   /* g[i]    = acc[i] + g[i]  closing micro-step: g then holds the window's sum; acc is left as is */
+int dsl_grad_accumulate(float* acc, float* g, long n, int mode, void* stream);
 int dsl_ema_lerp(float* teacher, const float* student, long n, float keep, void* stream);
 /* the same, and the teacher's bf16 forward copy written in the same pass (what dsl_cast_bf16 would re-read the result for) */
 int dsl_ema_lerp_bf16(float* teacher, const float* student, void* teacher_bf16, long n, float keep, void* stream);
