@@ -174,6 +174,51 @@ class AugItem(C.Structure):
  AUG_AUTOCONTRAST, AUG_EQUALIZE, AUG_SOLARIZE, AUG_POSTERIZE, AUG_SHARPNESS) = range(15)
 
 
+GEO_CROP, GEO_EXPAND, GEO_SHIFT, GEO_CUTOUT = 1, 2, 3, 4      # DSL_GEO_*: dsl_geo_step.kind
+GEO_MAX_STEPS = 32
+
+
+class GeoStep(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('a', C.c_int32 * 4), ('in_h', C.c_int32), ('in_w', C.c_int32), ('fill', C.c_uint8 * 4)]
+
+
+class GeoItem(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('src_h', C.c_int32), ('src_w', C.c_int32), ('src_ld', C.c_int32),
+                ('out_h', C.c_int32), ('out_w', C.c_int32), ('dst', C.c_void_p),
+                ('dst_h', C.c_int32), ('dst_w', C.c_int32), ('dst_ld', C.c_int32), ('nsteps', C.c_int32),
+                ('steps', GeoStep * GEO_MAX_STEPS)]
+
+
+def geo_out_size(steps, h, w):
+    """Size of an h x w image after the step list; a step is (kind, a[, fill]) (include/dsl_hip.h, dsl_geo_step)."""
+    for st in steps:
+        if st[0] == GEO_CROP:
+            h, w = st[1][3], st[1][2]
+        elif st[0] == GEO_EXPAND:
+            h, w = st[1][3], st[1][2]
+    return int(h), int(w)
+
+
+def geo_fill_item(it, steps, src, src_h, src_w, src_ld, dst, dst_h, dst_w, dst_ld):
+    """Fills one dsl_geo_item from a step list of (kind, a[, fill]) tuples: the sizes every step receives and out_h x out_w are
+    derived here.  len(steps) beyond GEO_MAX_STEPS is written as it is (nsteps says so; the entry refuses it)."""
+    it.src, it.src_h, it.src_w, it.src_ld = src, src_h, src_w, src_ld
+    it.dst, it.dst_h, it.dst_w, it.dst_ld = dst, dst_h, dst_w, dst_ld
+    it.nsteps = len(steps)
+    h, w = src_h, src_w
+    for k, st in enumerate(steps):
+        if k < GEO_MAX_STEPS:
+            s = it.steps[k]
+            s.kind, s.in_h, s.in_w = st[0], h, w
+            for q, v in enumerate(st[1]):
+                s.a[q] = int(v)
+            for q, v in enumerate(st[2] if len(st) > 2 else ()):
+                s.fill[q] = int(v)
+        h, w = geo_out_size([st], h, w)
+    it.out_h, it.out_w = h, w
+    return it
+
+
 class Op(C.Structure):
     _fields_ = [('kind', C.c_int32), ('i', C.c_int32 * 7), ('desc', C.c_void_p),
                 ('p', C.c_void_p * 4), ('l', C.c_int64 * 2)]
@@ -222,7 +267,7 @@ _SIGS = {
     'dsl_rla_tail_fwd': [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp], 'dsl_bn_tanh_bwd_workspace_bytes': [_l, _i],
     'dsl_bn_tanh_bwd': [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _f, _vp, _i, _vp, _vp, _vp, _l, _i, _vp],
     'dsl_image_prep_u8': [_vp, _i, _vp, _i, _i, _vp], 'dsl_image_aug': [_vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp], 'dsl_image_aug_scratch_bytes': [_i],
-    'dsl_image_normalize': [_vp, _vp, _i, _vp, _i, _i, _vp],
+    'dsl_image_normalize': [_vp, _vp, _i, _vp, _i, _i, _vp], 'dsl_image_geo': [_vp, _vp, _i, _i, _i, _vp],
     'dsl_quant_fp8': [_vp, _vp, _l, _i, _i, _f, _vp], 'dsl_absmax': [_vp, _l, _i, _i, _vp, _i, _vp],
     'dsl_quant_fp8_dyn': [_vp, _vp, _l, _i, _i, _vp, _i, _vp], 'dsl_fp8_comb': [_vp, _vp, _i, _vp, _i, _vp], 'dsl_fp8_prep': [_vp, _i, _i, _i, _f, _vp],
     'dsl_quant_fp8_delayed': [_vp, _vp, _l, _i, _i, _vp, _vp, _i, _vp], 'dsl_quant_fp8_weights': [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],

@@ -433,7 +433,96 @@ __global__ __launch_bounds__(256) void image_normalize_kernel(const PrepK p, con
   }
 }
 
+// ---- integer geometric steps (RandomCrop, MinIoURandomCrop, Expand, RandomShift, CutOut: transforms.py:693-873, 1113-1249,
+// 1021-1109, 491-577, 1850-1920) --------------------------------------------------------------------------------------------
+// One thread per pixel of an image's dst_h x dst_w rectangle (the grid of image_prep_kernel: x blocks x rows x images).  The pixel
+// walks the image's step list BACKWARDS to the position it comes from: a CROP adds its corner, an EXPAND subtracts its placement
+// and ends the walk with the fill on its border, a SHIFT subtracts its offset and ends the walk with 0 where that leaves the image,
+// a CUTOUT ends it with the fill inside its rectangle.  The list is the same for every thread of a block (scalar loads); no
+// floats, no atomics, dst is only written.  The lists were checked on the host (dsl_image_geo); the final read is guarded anyway.
+__global__ __launch_bounds__(256) void image_geo_kernel(const dsl_geo_item* __restrict__ items) {
+  const dsl_geo_item* __restrict__ it = items + blockIdx.z;
+  const int xo = blockIdx.x * blockDim.x + threadIdx.x, yo = blockIdx.y;
+  if (yo >= it->dst_h || xo >= it->dst_w) return;
+  int x = xo, y = yo;
+  int v0 = 0, v1 = 0, v2 = 0;
+  bool live = xo < it->out_w && yo < it->out_h;            // outside the image: the zero margin
+  const int ns = min(it->nsteps, DSL_GEO_MAX_STEPS);
+  for (int k = ns - 1; k >= 0 && live; --k) {
+    const dsl_geo_step* __restrict__ s = it->steps + k;
+    const int kind = s->kind;
+    if (kind == DSL_GEO_CROP) {
+      x += s->a[0]; y += s->a[1];
+    } else if (kind == DSL_GEO_EXPAND || kind == DSL_GEO_SHIFT) {
+      x -= s->a[0]; y -= s->a[1];
+      if (x < 0 || y < 0 || x >= s->in_w || y >= s->in_h) {
+        if (kind == DSL_GEO_EXPAND) { v0 = s->fill[0]; v1 = s->fill[1]; v2 = s->fill[2]; }
+        live = false;
+      }
+    } else if (kind == DSL_GEO_CUTOUT) {
+      if (x >= s->a[0] && x < s->a[2] && y >= s->a[1] && y < s->a[3]) {
+        v0 = s->fill[0]; v1 = s->fill[1]; v2 = s->fill[2];
+        live = false;
+      }
+    }
+  }
+  if (live && x >= 0 && y >= 0 && x < it->src_w && y < it->src_h) {
+    const unsigned char* s = it->src + ((long long)y * it->src_ld + x) * 3;
+    v0 = s[0]; v1 = s[1]; v2 = s[2];
+  }
+  unsigned char* d = it->dst + ((long long)yo * it->dst_ld + xo) * 3;
+  d[0] = (unsigned char)v0; d[1] = (unsigned char)v1; d[2] = (unsigned char)v2;
+}
+
 }  // namespace
+
+// the host-side check of one step list: every step inside the image it receives, the sizes chaining from src to out
+static const char* geo_item_error(const dsl_geo_item& it, int max_dst_h, int max_dst_w) {
+  if (!it.src || !it.dst) return "null image pointer";
+  if (it.src == it.dst) return "src == dst";
+  if (it.src_h <= 0 || it.src_w <= 0 || it.out_h <= 0 || it.out_w <= 0 || it.dst_h <= 0 || it.dst_w <= 0) return "non-positive size";
+  if (it.src_ld < it.src_w || it.dst_ld < it.dst_w) return "row pitch smaller than the width";
+  if (it.dst_h < it.out_h || it.dst_w < it.out_w) return "dst rectangle smaller than the output image";
+  if (it.dst_h > max_dst_h || it.dst_w > max_dst_w) return "dst rectangle larger than max_dst_h x max_dst_w";
+  if (it.nsteps < 0 || it.nsteps > DSL_GEO_MAX_STEPS) return "nsteps outside 0 .. DSL_GEO_MAX_STEPS (split a longer list over launches)";
+  long long h = it.src_h, w = it.src_w;
+  for (int k = 0; k < it.nsteps; ++k) {
+    const dsl_geo_step& s = it.steps[k];
+    const long long a0 = s.a[0], a1 = s.a[1], a2 = s.a[2], a3 = s.a[3];
+    if (s.in_h != h || s.in_w != w) return "a step's in_h x in_w is not the size the previous step leaves";
+    switch (s.kind) {
+      case DSL_GEO_CROP:
+        if (a0 < 0 || a1 < 0 || a2 <= 0 || a3 <= 0 || a0 + a2 > w || a1 + a3 > h) return "CROP outside its input";
+        w = a2; h = a3;
+        break;
+      case DSL_GEO_EXPAND:
+        if (a0 < 0 || a1 < 0 || a0 + w > a2 || a1 + h > a3) return "EXPAND does not hold its input";
+        w = a2; h = a3;
+        break;
+      case DSL_GEO_SHIFT:
+        if (a0 <= -w || a0 >= w || a1 <= -h || a1 >= h) return "SHIFT of at least the image size";
+        break;
+      case DSL_GEO_CUTOUT:
+        if (a0 < 0 || a1 < 0 || a2 < a0 || a3 < a1 || a2 > w || a3 > h) return "CUTOUT not clipped to its image";
+        break;
+      default: return "unknown step kind";
+    }
+  }
+  if (h != it.out_h || w != it.out_w) return "out_h x out_w is not the size the last step leaves";
+  return nullptr;
+}
+
+extern "C" int dsl_image_geo(const dsl_geo_item* items, const dsl_geo_item* items_dev, int n, int max_dst_h, int max_dst_w, void* stream) {
+  DSL_CHECK(items && items_dev && n > 0 && n <= 65535 && max_dst_h > 0 && max_dst_h <= 65535 && max_dst_w > 0,
+            "dsl_image_geo: bad arguments");
+  for (int i = 0; i < n; ++i) {
+    const char* why = geo_item_error(items[i], max_dst_h, max_dst_w);
+    DSL_CHECK(!why, "dsl_image_geo: item %d: %s", i, why);
+  }
+  hipLaunchKernelGGL(image_geo_kernel, dim3((max_dst_w + 255) / 256, max_dst_h, n), dim3(256), 0, (hipStream_t)stream, items_dev);
+  DSL_LAUNCH_CHECK("image_geo_kernel");
+  return 0;
+}
 
 extern "C" int dsl_image_prep(const dsl_image_prep_item* items_dev, int n, float* dst, int hc, int wc, void* stream) {
   DSL_CHECK(items_dev && dst && n > 0 && hc > 0 && wc > 0, "dsl_image_prep: bad arguments");

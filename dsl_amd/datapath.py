@@ -12,6 +12,18 @@ Mirrors, by name and argument meaning (configs/fcos_semi/RLA_*.py:68-82; mmdet/d
   RandomAugmentBBox_Fast(aug_type='affine'|'default')                  mmdet/datasets/pipelines/semi_aug.py:344-531
   UBAug()                                                               :2098-2140
   MultiScaleFlipAug(transforms, img_scale, flip, flip_direction)        mmdet/datasets/pipelines/test_time_aug.py:10-120
+  RandomShift(shift_ratio, max_shift_px, filter_thr_px)                 :491-577
+  Pad(size=(h, w))                                                      :581-650
+  RandomCrop(crop_size, crop_type, allow_negative_crop, bbox_clip_border)   :693-873
+  Expand(mean, to_rgb, ratio_range, prob)                               :1021-1109
+  MinIoURandomCrop(min_ious, min_crop_size, bbox_clip_border)           :1113-1249
+  CutOut(n_holes, cutout_shape | cutout_ratio, fill_in)                 :1850-1920
+The last five are integer geometry: they draw from np.random in the reference's call order (pinned to the reference's own classes,
+tests/golden/geo_transforms.json) and append (kind, a[, fill]) steps to r['_geo']; GpuBatchPipeline renders a sample's list with
+dsl_image_geo (one launch per batch, a list longer than 32 steps over successive launches) in one of two places: in front of Resize
+(SSD style: Expand -> MinIoURandomCrop -> Resize; the rendered images become dsl_image_prep's sources) or behind Resize / PatchShuffle
+/ RandomFlip and in front of the augmentations and Normalize (uint8 canvas -> uint8 canvas); any other position is refused at
+construction.  RandomCrop may reject a sample (None): __call__(samples, resample) asks for a replacement, SampleRejected otherwise.
 A transform's __call__(results) only DRAWS its random parameters and updates boxes / meta; `GpuBatchPipeline` then renders all
 images of the batch: one launch for the labeled stream, and for the unlabeled stream (the last two transforms) one launch per
 augmentation pass over uint8 canvases (dsl_image_prep_u8 -> dsl_image_aug ... -> dsl_image_normalize).  UBAug's colour,
@@ -182,15 +194,252 @@ class Normalize:
 @PIPELINES.register_module()
 class Pad:
     def __init__(self, size=None, size_divisor=None, pad_val=0):
-        assert size is None and size_divisor is not None and pad_val == 0, 'the configs pad to a multiple with zeros'
-        self.size_divisor = size_divisor
+        assert (size is None) != (size_divisor is None) and pad_val == 0, 'pads with zeros, to a multiple or to a fixed (h, w)'
+        self.size, self.size_divisor = (None if size is None else (int(size[0]), int(size[1]))), size_divisor
 
     def __call__(self, r):
         h, w = r['img_shape'][:2]
+        if self.size is not None:              # mmcv.impad(shape=size): the image must fit
+            assert self.size[0] >= h and self.size[1] >= w, f'Pad(size={self.size}) is smaller than the image {(h, w)}'
+            r['pad_shape'] = (self.size[0], self.size[1], 3)
+            r['pad_fixed_size'], r['pad_size_divisor'] = self.size, None
+            return r
         d = self.size_divisor
         r['pad_shape'] = (int(np.ceil(h / d)) * d, int(np.ceil(w / d)) * d, 3)
         r['pad_size_divisor'] = d
         return r
+
+
+# ---- the general geometric transforms (transforms.py:491-577, 693-873, 1021-1109, 1113-1249, 1850-1920) ------------------------
+# __call__ draws from np.random in the reference's call order, moves / filters boxes and labels, updates img_shape and appends the
+# image work to r['_geo'] as (kind, a[, fill]) steps (include/dsl_hip.h, dsl_geo_step); GpuBatchPipeline renders them with
+# dsl_image_geo.  Pinned to the reference's own classes (tests/golden/geo_transforms.json).
+_LABEL_OF = {'gt_bboxes': 'gt_labels', 'gt_bboxes_ignore': 'gt_labels_ignore'}
+
+
+def _u8(values):
+    """The bytes numpy stores when it assigns these values into a uint8 image (123.675 -> 123)."""
+    return tuple(int(v) for v in np.asarray(values, np.float64).astype(np.uint8).reshape(-1)[:3])
+
+
+@PIPELINES.register_module()
+class RandomShift:
+    def __init__(self, shift_ratio=0.5, max_shift_px=32, filter_thr_px=1):
+        assert 0 <= shift_ratio <= 1
+        assert max_shift_px >= 0
+        self.shift_ratio, self.max_shift_px, self.filter_thr_px = shift_ratio, max_shift_px, int(filter_thr_px)
+
+    def __call__(self, r):
+        if not np.random.random() < self.shift_ratio:
+            return r
+        h, w = r['img_shape'][:2]
+        dx = np.random.randint(-self.max_shift_px, self.max_shift_px)        # numpy's randint: the upper bound is exclusive
+        dy = np.random.randint(-self.max_shift_px, self.max_shift_px)
+        for key in r.get('bbox_fields', []):
+            b = r[key].copy()
+            b[..., 0::2] += dx
+            b[..., 1::2] += dy
+            b[..., 0::2] = np.clip(b[..., 0::2], 0, w)
+            b[..., 1::2] = np.clip(b[..., 1::2], 0, h)
+            valid = ((b[..., 2] - b[..., 0]) > self.filter_thr_px) & ((b[..., 3] - b[..., 1]) > self.filter_thr_px)
+            if key == 'gt_bboxes' and not valid.any():
+                return r           # no gt box survives: the image is not shifted either (fields visited before keep their shift)
+            r[key] = b[valid]
+            if _LABEL_OF.get(key) in r:
+                r[_LABEL_OF[key]] = r[_LABEL_OF[key]][valid]
+        if abs(int(dx)) >= w or abs(int(dy)) >= h:
+            raise ValueError(f'RandomShift: drawn shift {(int(dx), int(dy))} is not smaller than the image {(h, w)}')
+        r.setdefault('_geo', []).append((L.GEO_SHIFT, (int(dx), int(dy))))
+        return r
+
+
+@PIPELINES.register_module()
+class RandomCrop:
+    def __init__(self, crop_size, crop_type='absolute', allow_negative_crop=False, bbox_clip_border=True):
+        if crop_type not in ('relative_range', 'relative', 'absolute', 'absolute_range'):
+            raise ValueError(f'Invalid crop_type {crop_type}.')
+        if crop_type in ('absolute', 'absolute_range'):
+            assert crop_size[0] > 0 and crop_size[1] > 0
+            assert isinstance(crop_size[0], int) and isinstance(crop_size[1], int)
+        else:
+            assert 0 < crop_size[0] <= 1 and 0 < crop_size[1] <= 1
+        self.crop_size, self.crop_type = crop_size, crop_type
+        self.allow_negative_crop, self.bbox_clip_border = allow_negative_crop, bbox_clip_border
+
+    def _get_crop_size(self, h, w):
+        cs = self.crop_size
+        if self.crop_type == 'absolute':
+            return min(cs[0], h), min(cs[1], w)
+        if self.crop_type == 'absolute_range':
+            assert cs[0] <= cs[1]
+            crop_h = np.random.randint(min(h, cs[0]), min(h, cs[1]) + 1)
+            crop_w = np.random.randint(min(w, cs[0]), min(w, cs[1]) + 1)
+            return crop_h, crop_w
+        if self.crop_type == 'relative':
+            return int(h * cs[0] + 0.5), int(w * cs[1] + 0.5)
+        cs = np.asarray(cs, dtype=np.float32)                   # relative_range
+        rh, rw = cs + np.random.rand(2) * (1 - cs)
+        return int(h * rh + 0.5), int(w * rw + 0.5)
+
+    def __call__(self, r):
+        h, w = r['img_shape'][:2]
+        ch, cw = self._get_crop_size(h, w)
+        assert ch > 0 and cw > 0
+        off_h = int(np.random.randint(0, max(h - ch, 0) + 1))
+        off_w = int(np.random.randint(0, max(w - cw, 0) + 1))
+        new_h, new_w = min(off_h + int(ch), h) - off_h, min(off_w + int(cw), w) - off_w      # what the slice yields
+        off = np.array([off_w, off_h, off_w, off_h], dtype=np.float32)
+        for key in r.get('bbox_fields', []):
+            b = r[key] - off
+            if self.bbox_clip_border:
+                b[:, 0::2] = np.clip(b[:, 0::2], 0, new_w)
+                b[:, 1::2] = np.clip(b[:, 1::2], 0, new_h)
+            valid = (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+            if key == 'gt_bboxes' and not valid.any() and not self.allow_negative_crop:
+                return None        # a crop without gt area: the caller draws another sample
+            r[key] = b[valid, :]
+            if _LABEL_OF.get(key) in r:
+                r[_LABEL_OF[key]] = r[_LABEL_OF[key]][valid]
+        r['img_shape'] = (new_h, new_w, 3)
+        if (new_h, new_w) != (h, w):
+            r.setdefault('_geo', []).append((L.GEO_CROP, (off_w, off_h, new_w, new_h)))
+        return r
+
+
+@PIPELINES.register_module()
+class Expand:
+    def __init__(self, mean=(0, 0, 0), to_rgb=True, ratio_range=(1, 4), seg_ignore_label=None, prob=0.5):
+        self.to_rgb, self.ratio_range = to_rgb, ratio_range
+        self.mean = mean[::-1] if to_rgb else mean              # the image is BGR
+        self.min_ratio, self.max_ratio = ratio_range
+        self.seg_ignore_label, self.prob = seg_ignore_label, prob
+
+    def __call__(self, r):
+        if np.random.uniform(0, 1) > self.prob:
+            return r
+        h, w = r['img_shape'][:2]
+        ratio = np.random.uniform(self.min_ratio, self.max_ratio)
+        big_h, big_w = int(h * ratio), int(w * ratio)
+        left = int(np.random.uniform(0, w * ratio - w))
+        top = int(np.random.uniform(0, h * ratio - h))
+        for key in r.get('bbox_fields', []):
+            r[key] = r[key] + np.tile((left, top), 2).astype(r[key].dtype)
+        r['img_shape'] = (big_h, big_w, 3)
+        if (big_h, big_w) != (h, w):
+            r.setdefault('_geo', []).append((L.GEO_EXPAND, (left, top, big_w, big_h), _u8(self.mean)))
+        return r
+
+
+def _patch_overlaps(patch, boxes, eps=1e-6):
+    """IoU of one patch with every box in float32, the union floored at eps (mmdet/core/evaluation/bbox_overlaps.py)."""
+    p, b = patch.astype(np.float32), boxes.astype(np.float32).reshape(-1, 4)
+    if b.shape[0] == 0:
+        return np.zeros((0,), np.float32)
+    area_p = (p[2] - p[0]) * (p[3] - p[1])
+    area_b = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    inter = np.maximum(np.minimum(p[2], b[:, 2]) - np.maximum(p[0], b[:, 0]), 0) * \
+        np.maximum(np.minimum(p[3], b[:, 3]) - np.maximum(p[1], b[:, 1]), 0)
+    union = np.maximum(area_p + area_b - inter, eps)
+    return (inter / union).astype(np.float32)
+
+
+def _centre_in_patch(boxes, patch):
+    c = (boxes[:, :2] + boxes[:, 2:]) / 2
+    return (c[:, 0] > patch[0]) * (c[:, 1] > patch[1]) * (c[:, 0] < patch[2]) * (c[:, 1] < patch[3])
+
+
+@PIPELINES.register_module()
+class MinIoURandomCrop:
+    def __init__(self, min_ious=(0.1, 0.3, 0.5, 0.7, 0.9), min_crop_size=0.3, bbox_clip_border=True):
+        self.min_ious = min_ious
+        self.sample_mode = (1, *min_ious, 0)           # 1: return the image as it is
+        self.min_crop_size, self.bbox_clip_border = min_crop_size, bbox_clip_border
+
+    def __call__(self, r):
+        assert 'bbox_fields' in r
+        boxes = np.concatenate([r[key] for key in r['bbox_fields']], 0)
+        h, w = r['img_shape'][:2]
+        while True:
+            mode = np.random.choice(self.sample_mode)
+            self.mode = mode
+            if mode == 1:
+                return r
+            for _ in range(50):
+                new_w = np.random.uniform(self.min_crop_size * w, w)
+                new_h = np.random.uniform(self.min_crop_size * h, h)
+                if new_h / new_w < 0.5 or new_h / new_w > 2:
+                    continue
+                left = np.random.uniform(low=w - new_w, high=1.0)       # the reference's one-argument uniform(w - new_w)
+                top = np.random.uniform(low=h - new_h, high=1.0)
+                patch = np.array((int(left), int(top), int(left + new_w), int(top + new_h)))
+                if patch[2] == patch[0] or patch[3] == patch[1]:
+                    continue
+                overlaps = _patch_overlaps(patch, boxes)
+                if len(overlaps) > 0 and overlaps.min() < mode:
+                    continue
+                if len(overlaps) > 0:
+                    if not _centre_in_patch(boxes, patch).any():
+                        continue
+                    for key in r.get('bbox_fields', []):
+                        b = r[key].copy()
+                        mask = _centre_in_patch(b, patch)
+                        b = b[mask]
+                        if self.bbox_clip_border:
+                            b[:, 2:] = b[:, 2:].clip(max=patch[2:])
+                            b[:, :2] = b[:, :2].clip(min=patch[:2])
+                        b -= np.tile(patch[:2], 2)
+                        r[key] = b
+                        if _LABEL_OF.get(key) in r:
+                            r[_LABEL_OF[key]] = r[_LABEL_OF[key]][mask]
+                x0, y0 = int(patch[0]), int(patch[1])
+                x1, y1 = min(int(patch[2]), w), min(int(patch[3]), h)
+                r['img_shape'] = (y1 - y0, x1 - x0, 3)
+                if (y1 - y0, x1 - x0) != (h, w):
+                    r.setdefault('_geo', []).append((L.GEO_CROP, (x0, y0, x1 - x0, y1 - y0)))
+                return r
+
+
+@PIPELINES.register_module()
+class CutOut:
+    def __init__(self, n_holes, cutout_shape=None, cutout_ratio=None, fill_in=(0, 0, 0)):
+        assert (cutout_shape is None) ^ (cutout_ratio is None), 'Either cutout_shape or cutout_ratio should be specified.'
+        assert isinstance(cutout_shape, (list, tuple)) or isinstance(cutout_ratio, (list, tuple))
+        if isinstance(n_holes, tuple):
+            assert len(n_holes) == 2 and 0 <= n_holes[0] < n_holes[1]
+        else:
+            n_holes = (n_holes, n_holes)
+        self.n_holes, self.fill_in = n_holes, fill_in
+        self.with_ratio = cutout_ratio is not None
+        self.candidates = cutout_ratio if self.with_ratio else cutout_shape
+        if not isinstance(self.candidates, list):
+            self.candidates = [self.candidates]
+
+    def __call__(self, r):
+        h, w = r['img_shape'][:2]
+        steps = r.setdefault('_geo', [])
+        for _ in range(np.random.randint(self.n_holes[0], self.n_holes[1] + 1)):
+            x1 = np.random.randint(0, w)
+            y1 = np.random.randint(0, h)
+            index = np.random.randint(0, len(self.candidates))
+            if not self.with_ratio:
+                cut_w, cut_h = self.candidates[index]
+            else:
+                cut_w, cut_h = int(self.candidates[index][0] * w), int(self.candidates[index][1] * h)
+            x2, y2 = np.clip(x1 + cut_w, 0, w), np.clip(y1 + cut_h, 0, h)
+            if x2 > x1 and y2 > y1:
+                steps.append((L.GEO_CUTOUT, (int(x1), int(y1), int(x2), int(y2)), _u8(self.fill_in)))
+        return r
+
+
+GEO_TRANSFORMS = (RandomShift, RandomCrop, Expand, MinIoURandomCrop, CutOut)
+
+
+class SampleRejected(Exception):
+    """A transform returned None for sample `index` (RandomCrop without gt area) and no `resample` was given."""
+
+    def __init__(self, index):
+        super().__init__(f'sample {index} was rejected by its pipeline and there is no resample callback')
+        self.index = index
 
 
 def _affine_forward(kind, value, w, h):
@@ -381,9 +630,52 @@ class GpuBatchPipeline:
         norm = [t for t in self.transforms if isinstance(t, Normalize)]
         assert len(norm) == 1, 'the pipeline needs exactly one Normalize'
         self.norm = norm[0]
+        self._geo_split = self._place_geo()
+
+    def _place_geo(self):
+        """Where the geometric transforms render.  In front of Resize their steps run from the uploads into per-sample images that
+        become dsl_image_prep's sources; after Resize / PatchShuffle / RandomFlip and in front of the augmentations and Normalize
+        they run between two uint8 canvases.  Returns the index of the first transform behind the front group (None: the pipeline
+        lists no geometric transform and renders as it always did); any other position is refused here."""
+        if not any(isinstance(t, GEO_TRANSFORMS) for t in self.transforms):
+            return None
+        stage, last_geo = 0, None      # 0 start, 1 after Resize, 2 after PatchShuffle / RandomFlip, 3 after a geometric transform
+        names = {4: 'the augmentation passes', 5: 'Normalize'}      # behind those, 4 / 5 after the augmentations / Normalize
+        split = next(i for i, t in enumerate(self.transforms) if not isinstance(t, GEO_TRANSFORMS))      # (Normalize is there)
+        for i, t in enumerate(self.transforms):
+            name = type(t).__name__
+            if isinstance(t, Resize):
+                if any(isinstance(u, Resize) for u in self.transforms[:i]):
+                    raise NotImplementedError(f'{name} at position {i}: a second Resize in a pipeline with geometric transforms is not rendered')
+                if stage != 0:
+                    raise NotImplementedError(f'{name} at position {i}: with geometric transforms Resize comes before PatchShuffle / RandomFlip '
+                                              'and the augmentations')
+                stage = 1
+            elif isinstance(t, (PatchShuffle, RandomFlip)):
+                if stage == 3:
+                    raise NotImplementedError(f'{last_geo[1]} at position {last_geo[0]}: a geometric transform between Resize and {name} '
+                                              f'(position {i}) is not rendered; put it before Resize or after RandomFlip')
+                if stage > 3:
+                    raise NotImplementedError(f'{name} at position {i}: after {names[stage]} is not rendered')
+                stage = 2
+            elif isinstance(t, GEO_TRANSFORMS):
+                if stage >= 4:
+                    raise NotImplementedError(f'{name} at position {i}: a geometric transform after {names[stage]} is not rendered; put it '
+                                              'before Resize, or after RandomFlip and before the augmentations and Normalize')
+                if stage == 0 and i > split:
+                    raise NotImplementedError(f'{name} at position {i}: a geometric transform before Resize goes in front of every '
+                                              f'other transform ({type(self.transforms[split]).__name__} at position {split} precedes it)')
+                if stage >= 1:
+                    stage, last_geo = 3, (i, name)
+            elif isinstance(t, (RandomAugmentBBox_Fast, UBAug)):
+                stage = max(stage, 4)
+            elif isinstance(t, Normalize):
+                stage = 5
+        return split
 
     def draw(self, s, h, w):
-        """Host side of one sample of size h x w: every transform draws its parameters and updates boxes / meta; no image work."""
+        """Host side of one sample of size h x w: every transform draws its parameters and updates boxes / meta; no image work.
+        None when a transform rejects the sample (RandomCrop without gt area)."""
         r = dict(filename=s.get('filename'), ori_filename=s.get('filename'), ori_shape=(h, w, 3), img_shape=(h, w, 3),
                  gt_bboxes=np.asarray(s.get('gt_bboxes', np.zeros((0, 4))), np.float32).reshape(-1, 4),
                  gt_labels=np.asarray(s.get('gt_labels', np.zeros((0,))), np.int64).reshape(-1),
@@ -392,8 +684,17 @@ class GpuBatchPipeline:
         for k in ('scale', 'flip', 'flip_direction'):          # forced parameters (tests; the test pipeline's MultiScaleFlipAug)
             if k in s:
                 r[k] = s[k]
-        for t in self.transforms:
+        split = self._geo_split
+        for i, t in enumerate(self.transforms):
+            if split is not None:
+                if i == split:                      # the steps drawn in front of Resize render from the upload
+                    r['_geo_pre'], r['_geo'] = r.pop('_geo', []), []
+                elif i > split and isinstance(t, GEO_TRANSFORMS):
+                    r.setdefault('_prep_shape', r['img_shape'])      # what dsl_image_prep renders: the size in front of the first step
             r = t(r)
+            if r is None:
+                return None
+        r.setdefault('_prep_shape', r['img_shape'])
         r.setdefault('pad_shape', r['img_shape'])
         r.setdefault('flip', False)
         r.setdefault('flip_direction', None)
@@ -405,78 +706,171 @@ class GpuBatchPipeline:
         m['batch_input_shape'] = (hc, wc)
         return m
 
-    def __call__(self, samples):
-        n = len(samples)
-        results, srcs = [], []
-        for s in samples:
-            img = s['img']
-            img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
-            assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
-            srcs.append(img.to(self.device, non_blocking=True).contiguous())
-            results.append(self.draw(s, *img.shape[:2]))
-        hc, wc = max(r['pad_shape'][0] for r in results), max(r['pad_shape'][1] for r in results)       # merge/pad
-        items = (L.ImagePrepItem * n)()
+    def _render_geo(self, jobs):
+        """dsl_image_geo over jobs = dicts(src, src_h, src_w, src_ld, steps, dst, dst_h, dst_w, dst_ld) (device addresses): one launch,
+        or, where a list is longer than GEO_MAX_STEPS, successive launches that ping-pong two buffers holding the images in between.
+        Returns the tensors that must stay alive until the launches have run."""
+        M = L.GEO_MAX_STEPS
+        chunks = [max(1, (len(j['steps']) + M - 1) // M) for j in jobs]
+        offs, total = {}, 0
+        for q, j in enumerate(jobs):
+            if chunks[q] > 1:
+                sizes = [L.geo_out_size(j['steps'][:M * (c + 1)], j['src_h'], j['src_w']) for c in range(chunks[q] - 1)]
+                j['_mid'] = sizes
+                offs[q], total = total, total + max(h * w for h, w in sizes) * 3
+        tmp = [torch.empty(total, dtype=torch.uint8, device=self.device) for _ in range(2)] if total else []
+        keep = list(tmp)
+        for k in range(max(chunks)):
+            live = [q for q in range(len(jobs)) if chunks[q] > k]
+            its = (L.GeoItem * len(live))()
+            for it, q in zip(its, live):
+                j = jobs[q]
+                if k == 0:
+                    src = (j['src'], j['src_h'], j['src_w'], j['src_ld'])
+                else:
+                    mh, mw = j['_mid'][k - 1]
+                    src = (tmp[(k - 1) % 2].data_ptr() + offs[q], mh, mw, mw)
+                if k == chunks[q] - 1:
+                    dst = (j['dst'], j['dst_h'], j['dst_w'], j['dst_ld'])
+                else:
+                    mh, mw = j['_mid'][k]
+                    dst = (tmp[k % 2].data_ptr() + offs[q], mh, mw, mw)
+                L.geo_fill_item(it, j['steps'][M * k:M * (k + 1)], *src, *dst)
+            tab = torch.frombuffer(bytearray(bytes(its)), dtype=torch.uint8).to(self.device)
+            keep.append(tab)
+            L.check(L.lib.dsl_image_geo(C.cast(its, C.c_void_p), L.ptr(tab), len(live), max(it.dst_h for it in its),
+                                        max(it.dst_w for it in its), L.stream_ptr()), 'dsl_image_geo')
+        return keep
+
+    def _prep_table(self, results, srcs, shape_key):
+        """The dsl_image_prep_item table: srcs = (address, h, w) per sample, new_h x new_w = r[shape_key]."""
+        items = (L.ImagePrepItem * len(results))()
         inv = (1.0 / self.norm.std.astype(np.float64)).astype(np.float32)
         for i, (r, src) in enumerate(zip(results, srcs)):
             it = items[i]
-            it.src, it.src_h, it.src_w = src.data_ptr(), src.shape[0], src.shape[1]
-            it.new_h, it.new_w = r['img_shape'][0], r['img_shape'][1]
+            it.src, it.src_h, it.src_w = src
+            it.new_h, it.new_w = r[shape_key][0], r[shape_key][1]
             it.flip, it.to_rgb = (FLIP_BITS[r['flip_direction'] or 'horizontal'] if r['flip'] else 0), int(bool(self.norm.to_rgb))
             it.ps_mode, it.ps_crop = r.get('_ps', (0, 0))
             for c in range(3):
                 it.mean[c], it.inv_std[c] = float(self.norm.mean[c]), float(inv[c])
-        tab = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device)
+        return torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.device)
+
+    def draw_batch(self, samples, resample=None):
+        """Host side of a batch: (uint8 image tensors, drawn results).  resample(i): a replacement for sample i when a transform
+        rejects it (the reference's dataset loop draws another index the same way, datasets/custom.py:193-198); without it a
+        rejection raises SampleRejected."""
+        imgs, results = [], []
+        for i, s in enumerate(samples):
+            while True:
+                img = s['img']
+                img = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
+                assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3
+                r = self.draw(s, *img.shape[:2])
+                if r is not None:
+                    break
+                if resample is None:
+                    raise SampleRejected(i)
+                s = resample(i)
+            imgs.append(img)
+            results.append(r)
+        return imgs, results
+
+    def __call__(self, samples, resample=None):
+        n = len(samples)
+        imgs, results = self.draw_batch(samples, resample)
+        srcs = [img.to(self.device, non_blocking=True).contiguous() for img in imgs]
+        hc, wc = max(r['pad_shape'][0] for r in results), max(r['pad_shape'][1] for r in results)       # merge/pad
+        keep = []
+        prep_src = [(src.data_ptr(), src.shape[0], src.shape[1]) for src in srcs]
+        pre = [i for i, r in enumerate(results) if r.get('_geo_pre')]
+        if pre:
+            # the steps in front of Resize: one launch from the uploads into one allocation of per-sample images, which become
+            # dsl_image_prep's sources (a sample without steps keeps pointing at its upload)
+            sizes = {i: L.geo_out_size(results[i]['_geo_pre'], *srcs[i].shape[:2]) for i in pre}
+            buf = torch.empty(sum(h * w for h, w in sizes.values()) * 3, dtype=torch.uint8, device=self.device)
+            jobs, off = [], 0
+            for i in pre:
+                h, w = sizes[i]
+                jobs.append(dict(src=srcs[i].data_ptr(), src_h=srcs[i].shape[0], src_w=srcs[i].shape[1], src_ld=srcs[i].shape[1],
+                                 steps=results[i]['_geo_pre'], dst=buf.data_ptr() + off, dst_h=h, dst_w=w, dst_ld=w))
+                prep_src[i] = (buf.data_ptr() + off, h, w)
+                off += h * w * 3
+            keep += [buf] + self._render_geo(jobs)
+        post = any(r.get('_geo') for r in results) and self._geo_split is not None
+        tab = self._prep_table(results, prep_src, '_prep_shape' if post else 'img_shape')
         out = torch.empty(n, 3, hc, wc, dtype=torch.float32, device=self.device)
         n_pass = max(len(r.get('_aug', ())) for r in results)
-        if n_pass == 0:
+        if n_pass == 0 and not post:
             L.check(L.lib.dsl_image_prep(L.ptr(tab), n, L.ptr(out), hc, wc, L.stream_ptr()), 'dsl_image_prep')
         else:
             # the unlabeled stream (RandomAugmentBBox_Fast, UBAug): Resize / PatchShuffle / Flip into uint8 canvases, one launch per
             # augmentation pass over the batch (an image with fewer passes is copied), then Normalize / Pad
             a = torch.empty(n, hc, wc, 3, dtype=torch.uint8, device=self.device)
-            b = torch.empty_like(a)
-            sums = torch.empty(int(L.lib.dsl_image_aug_scratch_bytes(n)) // 8, dtype=torch.int64, device=self.device)
-            L.check(L.lib.dsl_image_prep_u8(L.ptr(tab), n, L.ptr(a), hc, wc, L.stream_ptr()), 'dsl_image_prep_u8')
-            # every pass's item table in ONE host -> device copy
-            its = (L.AugItem * (n * n_pass))()
-            need_mean = [0] * n_pass
-            for k in range(n_pass):
-                for i, r in enumerate(results):
-                    it, ps = its[k * n + i], r.get('_aug', ())
-                    it.h, it.w = r['img_shape'][0], r['img_shape'][1]
-                    if k >= len(ps):
-                        continue
-                    ps_k = ps[k]
-                    it.kind = ps_k['kind']
-                    need_mean[k] |= int(it.kind == L.AUG_CONTRAST) | 2 * int(it.kind in (L.AUG_AUTOCONTRAST, L.AUG_EQUALIZE))
-                    it.f[0] = float(ps_k.get('f', 0.0))
-                    if it.kind == L.AUG_AFFINE:
-                        x0, y0, x1, y1 = ps_k['roi']
-                        Mi = np.linalg.inv(ps_k['M'])
-                        for q in range(6):
-                            it.m[q] = float(Mi[q // 3, q % 3])
-                        it.roi[0], it.roi[1], it.roi[2], it.roi[3] = x0, y0, x1, y1
-                        it.order, it.cval = int(ps_k['order']), 125
-                    if it.kind == L.AUG_ERASE:
-                        it.seed = ps_k['seed']
-                        for q, rc in enumerate(ps_k['rects'][:3]):
-                            for e in range(4):
-                                it.rect[q][e] = int(rc[e])
-            at = torch.frombuffer(bytearray(bytes(its)), dtype=torch.uint8).to(self.device)
-            keep = [a, b, sums, at]
-            isz = C.sizeof(L.AugItem)
-            for k in range(n_pass):
-                L.check(L.lib.dsl_image_aug(at.data_ptr() + k * n * isz, n, L.ptr(a), L.ptr(b), hc, wc, L.ptr(sums), need_mean[k],
-                                            L.stream_ptr()), 'dsl_image_aug')
-                a, b = b, a
-            L.check(L.lib.dsl_image_normalize(L.ptr(a), L.ptr(tab), n, L.ptr(out), hc, wc, L.stream_ptr()), 'dsl_image_normalize')
-            srcs = srcs + keep
-        self._keep = (srcs, tab)            # alive until the launch has run (stream order)
+            keep.append(a)
+            tab_n = tab
+            if post:
+                # the steps behind Resize / PatchShuffle / RandomFlip: those render into a canvas sized by the largest resized image,
+                # dsl_image_geo moves that into the final canvas; the later stages see the final img_shape
+                h1, w1 = max(r['_prep_shape'][0] for r in results), max(r['_prep_shape'][1] for r in results)
+                a1 = torch.empty(n, h1, w1, 3, dtype=torch.uint8, device=self.device)
+                L.check(L.lib.dsl_image_prep_u8(L.ptr(tab), n, L.ptr(a1), h1, w1, L.stream_ptr()), 'dsl_image_prep_u8')
+                jobs = [dict(src=a1.data_ptr() + i * h1 * w1 * 3, src_h=r['_prep_shape'][0], src_w=r['_prep_shape'][1], src_ld=w1,
+                             steps=r.get('_geo', []), dst=a.data_ptr() + i * hc * wc * 3, dst_h=hc, dst_w=wc, dst_ld=wc)
+                        for i, r in enumerate(results)]
+                tab_n = self._prep_table(results, prep_src, 'img_shape')
+                keep += [a1, tab_n] + self._render_geo(jobs)
+            else:
+                L.check(L.lib.dsl_image_prep_u8(L.ptr(tab), n, L.ptr(a), hc, wc, L.stream_ptr()), 'dsl_image_prep_u8')
+            if n_pass:
+                a = self._render_aug(results, n_pass, a, hc, wc, keep)
+            L.check(L.lib.dsl_image_normalize(L.ptr(a), L.ptr(tab_n), n, L.ptr(out), hc, wc, L.stream_ptr()), 'dsl_image_normalize')
+        self._keep = (srcs + keep, tab)            # alive until the launch has run (stream order)
         self.last_passes = [list(r.get('_aug', ())) for r in results]      # what was rendered (tests replay it on the oracle)
+        self.last_geo = [(list(r.get('_geo_pre', ())), list(r.get('_geo', ()))) for r in results]      # (front of Resize, behind it)
         metas = [self.meta(r, hc, wc) for r in results]
         return dict(img=out, img_metas=metas, gt_bboxes=[torch.from_numpy(r['gt_bboxes']) for r in results],
                     gt_labels=[torch.from_numpy(r['gt_labels']) for r in results],
                     gt_bboxes_ignore=[torch.from_numpy(r['gt_bboxes_ignore']) for r in results])
+
+    def _render_aug(self, results, n_pass, a, hc, wc, keep):
+        """One dsl_image_aug launch per pass from canvas a into a second one and back; returns the canvas holding the result."""
+        n = len(results)
+        b = torch.empty_like(a)
+        sums = torch.empty(int(L.lib.dsl_image_aug_scratch_bytes(n)) // 8, dtype=torch.int64, device=self.device)
+        # every pass's item table in ONE host -> device copy
+        its = (L.AugItem * (n * n_pass))()
+        need_mean = [0] * n_pass
+        for k in range(n_pass):
+            for i, r in enumerate(results):
+                it, ps = its[k * n + i], r.get('_aug', ())
+                it.h, it.w = r['img_shape'][0], r['img_shape'][1]
+                if k >= len(ps):
+                    continue
+                ps_k = ps[k]
+                it.kind = ps_k['kind']
+                need_mean[k] |= int(it.kind == L.AUG_CONTRAST) | 2 * int(it.kind in (L.AUG_AUTOCONTRAST, L.AUG_EQUALIZE))
+                it.f[0] = float(ps_k.get('f', 0.0))
+                if it.kind == L.AUG_AFFINE:
+                    x0, y0, x1, y1 = ps_k['roi']
+                    Mi = np.linalg.inv(ps_k['M'])
+                    for q in range(6):
+                        it.m[q] = float(Mi[q // 3, q % 3])
+                    it.roi[0], it.roi[1], it.roi[2], it.roi[3] = x0, y0, x1, y1
+                    it.order, it.cval = int(ps_k['order']), 125
+                if it.kind == L.AUG_ERASE:
+                    it.seed = ps_k['seed']
+                    for q, rc in enumerate(ps_k['rects'][:3]):
+                        for e in range(4):
+                            it.rect[q][e] = int(rc[e])
+        at = torch.frombuffer(bytearray(bytes(its)), dtype=torch.uint8).to(self.device)
+        keep += [b, sums, at]
+        isz = C.sizeof(L.AugItem)
+        for k in range(n_pass):
+            L.check(L.lib.dsl_image_aug(at.data_ptr() + k * n * isz, n, L.ptr(a), L.ptr(b), hc, wc, L.ptr(sums), need_mean[k],
+                                        L.stream_ptr()), 'dsl_image_aug')
+            a, b = b, a
+        return a
 
 
 @PIPELINES.register_module()

@@ -305,6 +305,37 @@ int dsl_image_aug(const dsl_aug_item* items_dev, int n, const unsigned char* src
 int dsl_image_normalize(const unsigned char* src_u8, const dsl_image_prep_item* items_dev, int n, float* dst, int hc, int wc,
                         void* stream);
 
+/* Integer (non-resampling) geometric steps on uint8 BGR images, one launch per batch: the image work of the reference's RandomCrop,
+ * MinIoURandomCrop, Expand, RandomShift and CutOut (mmdet/datasets/pipelines/transforms.py:693-873, 1113-1249, 1021-1109, 491-577,
+ * 1850-1920).  The host draws the parameters and moves the boxes; an image's ordered step list maps (src_h, src_w) to (out_h, out_w):
+ *   CROP    a = x0, y0, cw, ch          -> ch x cw: img[y0 : y0 + ch, x0 : x0 + cw]
+ *   EXPAND  a = left, top, W, H; fill   -> H x W: fill everywhere, the input at (top, left)
+ *   SHIFT   a = dx, dy                  -> unchanged: out[y, x] = in[y - dy, x - dx], zero where that falls outside (|dx| < w, |dy| < h)
+ *   CUTOUT  a = x1, y1, x2, y2; fill    -> unchanged: the rectangle [y1, y2) x [x1, x2), already clipped to the image, set to fill
+ * in_h / in_w: the size of the image the step receives (the kernel walks the list backwards from each output pixel and has no other
+ * way to know it).  Every pixel of the dst_h x dst_w rectangle is written once: zero outside out_h x out_w. */
+enum { DSL_GEO_CROP = 1, DSL_GEO_EXPAND = 2, DSL_GEO_SHIFT = 3, DSL_GEO_CUTOUT = 4 };
+#define DSL_GEO_MAX_STEPS 32
+typedef struct dsl_geo_step {
+  int32_t kind;
+  int32_t a[4];
+  int32_t in_h, in_w;
+  uint8_t fill[4];               /* EXPAND / CUTOUT: B, G, R (fill[3] unused) */
+} dsl_geo_step;
+typedef struct dsl_geo_item {
+  const unsigned char* src;      /* [src_h] rows of src_ld pixels, src_w of them the image */
+  int32_t src_h, src_w, src_ld;
+  int32_t out_h, out_w;          /* size of the image after the last step (= src size for an empty list: a copy) */
+  unsigned char* dst;            /* [dst_h] rows of dst_ld pixels; dst != src */
+  int32_t dst_h, dst_w, dst_ld;  /* rectangle written, >= out_h x out_w */
+  int32_t nsteps;                /* 0 .. DSL_GEO_MAX_STEPS; a longer list is split over launches by the caller */
+  dsl_geo_step steps[DSL_GEO_MAX_STEPS];
+} dsl_geo_item;
+/* items: the n items in HOST memory - every list is checked here before anything runs (pointers, sizes, each step inside the image it
+ * receives, the sizes chaining up to out_h x out_w, dst_h <= max_dst_h, dst_w <= max_dst_w); items_dev: the same n items on the
+ * device, which the kernel reads.  The library allocates nothing and does not copy the table. */
+int dsl_image_geo(const dsl_geo_item* items, const dsl_geo_item* items_dev, int n, int max_dst_h, int max_dst_w, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Memory-bound fused layers
  * ---------------------------------------------------------------------------------------- */
