@@ -60,6 +60,12 @@ class ConvDesc(C.Structure):
                 ('gn_stats', C.c_void_p)]
 
 
+class ConvPlan(C.Structure):      # dsl_conv_plan: what dsl_conv2d would launch for a descriptor (dsl_conv2d_plan, host only)
+    _fields_ = [('kernel', C.c_int32), ('cfg', C.c_int32), ('bco', C.c_int32), ('bpx', C.c_int32), ('threads', C.c_int32),
+                ('splits', C.c_int32), ('grid', C.c_int32 * 3), ('ident', C.c_int32), ('addfast', C.c_int32),
+                ('lds_bytes', C.c_size_t), ('workspace_bytes', C.c_size_t)]
+
+
 class WgradDesc(C.Structure):
     _fields_ = [('nseg', C.c_int32), ('n', C.c_int32),
                 ('gh', I5), ('gw', I5), ('sh', I5), ('sw', I5),
@@ -252,7 +258,7 @@ if hasattr(lib, 'dsl_eval_match_workspace_bytes'):
     lib.dsl_eval_match_workspace_bytes.restype = C.c_size_t
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
 _SIGS = {
-    'dsl_conv2d': [_vp, _vp], 'dsl_conv2d_workspace_bytes': [_vp], 'dsl_conv2d_gn_fusable': [_vp], 'dsl_conv2d_wgrad': [_vp, _vp], 'dsl_wgrad_splits': [_vp],
+    'dsl_conv2d': [_vp, _vp], 'dsl_conv2d_workspace_bytes': [_vp], 'dsl_conv2d_gn_fusable': [_vp], 'dsl_conv2d_plan': [_vp, _vp], 'dsl_conv2d_wgrad': [_vp, _vp], 'dsl_wgrad_splits': [_vp],
     'dsl_wgrad_workspace_bytes': [_vp], 'dsl_wgrad_pixtab_bytes': [_vp], 'dsl_wgrad_pixtab_fill': [_vp, _vp, C.c_size_t, _vp], 'dsl_wgrad_group_workspace_bytes': [_vp, _i], 'dsl_conv2d_wgrad_group': [_vp, _i, _vp],
     'dsl_wgrad_multi_config': [_vp], 'dsl_wgrad_multi_table_bytes': [], 'dsl_wgrad_multi_workspace_bytes': [_vp, _vp, _i],
     'dsl_wgrad_multi_build': [_vp, _vp, _i, _vp, C.c_size_t, _vp, C.c_size_t], 'dsl_conv2d_wgrad_multi': [_vp, _vp, _vp], 'dsl_wgrad_multi_info': [_vp, _vp, _vp, _vp, _vp, _vp],

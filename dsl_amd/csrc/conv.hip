@@ -65,6 +65,42 @@ struct ConvK {
 #define CONV_HOT_ARGS(k) \
   (k).wgt, (k).src, (int)(k).wrow, (k).xcd_chunk, (k).gx, (k).gy, (k).splits, (k).kt_per_split, (k).ktiles, (k).kc, (k).kw, (k).lds
 
+// THE tile table of the DMA-to-LDS kernels: one row per tile configuration (forced by the test hook as row + 1).  BCO couts x BPX
+// pixels per workgroup, an NST-deep LDS ring of 64-element K stages, OCC workgroups per CU; `eff` is the cost model's per-row
+// efficiency of the K loop (conv_cost_us; the 8-wave 128x128 tile keeps 2 waves per SIMD even alone on a CU; rows 6, 7: measured
+// best on one shape of tools/bench_conv.py only), `prof` the dsl_prof_* class of its launches.  gen[]: the WCO x WPX wave layout
+// with which each kernel generation is instantiated for the row, {} where it is not - the small tiles (rows 5-7, for the layers
+// with few pixels: enough workgroups to use every CU without split-K partials, several resident per CU) exist for the pipelined
+// kernel only, the backward GroupNorm records for the 256-cout tiles, the 8-channel-source variant for 64x256.  The planner
+// (conv_cfg_ok), LDS sizes (conv_lds_bytes) and conv_dispatch, which instantiates the kernels, all read these rows.
+enum ConvGen { kGenV1 = 0, kGenGlds, kGenPipe, kGenPipeGn, kGenPipeSmallC, kGenF8, kNumConvGen };     // = dsl_conv_plan.kernel
+struct ConvWaves { int wco, wpx; };
+struct ConvTile {
+  int bco, bpx, nst, occ;
+  double eff;
+  int prof;
+  ConvWaves gen[kNumConvGen];      // ([kGenV1] unused: conv_gemm_kernel has its own fixed tile)
+};
+constexpr ConvTile kConvTiles[] = {
+    // bco bpx nst occ  eff  prof        glds    pipe    pipe+GN SMALL_C  fp8
+    {256, 192, 2, 1, 1.0,  1, {{}, {4, 2}, {4, 2}, {4, 2}, {},     {4, 2}}},
+    {256, 128, 3, 1, 1.0,  2, {{}, {4, 2}, {4, 2}, {4, 2}, {},     {4, 2}}},
+    {128, 256, 3, 1, 1.0,  2, {{}, {2, 4}, {2, 4}, {},     {},     {}}},
+    {128, 128, 2, 2, 0.7,  0, {{}, {2, 2}, {2, 4}, {},     {},     {2, 4}}},
+    {64,  256, 2, 2, 0.95, 2, {{}, {1, 4}, {1, 8}, {},     {1, 8}, {}}},
+    {128, 64,  3, 2, 0.9,  2, {{}, {},     {2, 2}, {},     {},     {}}},
+    {64,  64,  3, 3, 1.3,  2, {{}, {},     {1, 2}, {},     {},     {}}},
+    {64,  128, 3, 2, 1.25, 2, {{}, {},     {1, 4}, {},     {},     {}}},
+};
+constexpr int kNumConvTiles = sizeof(kConvTiles) / sizeof(kConvTiles[0]);
+// dynamic LDS of one workgroup: the stage ring (weight tile + pixel tile per stage, 128-byte rows).  conv_glds_kernel stages its
+// epilogue inside the ring; the pipelined kernels' staging (32 * wpx pixel rows of fp32 + pad) may be the larger of the two
+constexpr size_t conv_lds_bytes(int bco, int bpx, int wpx, int nst, bool glds) {
+  const size_t ring = (size_t)nst * (bco + bpx) * 128, stg = (size_t)32 * wpx * (bco * 4 + 16);
+  return glds || ring > stg ? ring : stg;
+}
+constexpr size_t conv_lds_bytes(const ConvTile& t, int gen) { return conv_lds_bytes(t.bco, t.bpx, t.gen[gen].wpx, t.nst, gen == kGenGlds); }
+
 __device__ __forceinline__ u32x4 relu_bf16x8(u32x4 v) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -743,7 +779,8 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_glds_kernel(const ConvK p
   constexpr int ROWB = BCO * 4 + 16;            // fp32 row + 16 B pad: conflict-free ds_write_b128 down a column
   constexpr int CPX = 32 * WPX;                 // pixels per chunk
   constexpr int GPR = BCO / 8;                  // 8-channel groups per pixel row
-  static_assert(CPX * ROWB <= NST * STAGE, "epilogue staging must fit in the stage memory");
+  static_assert(NST * STAGE == conv_lds_bytes(BCO, BPX, WPX, NST, true) && CPX * ROWB <= NST * STAGE,
+                "epilogue staging must fit in the stage memory: the host sizes the launch's LDS with conv_lds_bytes");
 #pragma unroll
   for (int pt = 0; pt < PT; ++pt) {
     lds_barrier();                            // previous chunk fully read (first pass: all MFMA operands consumed)
@@ -818,7 +855,9 @@ __device__ __forceinline__ void conv_tile_epilogue(const ConvK& p, f32x16 (&acc)
   constexpr int ROWB = BCO * 4 + 16;
   constexpr int CPX = 32 * WPX;
   constexpr int GPR = BCO / 8;
-  static_assert(CPX * ROWB <= 160 * 1024, "epilogue staging must fit in LDS (the host sizes LDS as max(ring, staging))");
+  static_assert(CPX * ROWB <= conv_lds_bytes(BCO, BPX, WPX, RING / ((BCO + BPX) * 128), false) &&
+                conv_lds_bytes(BCO, BPX, WPX, RING / ((BCO + BPX) * 128), false) <= 160 * 1024,
+                "epilogue staging must fit in LDS: the host sizes the launch's LDS with conv_lds_bytes, max(ring, staging)");
   static_assert(T % GPR == 0, "a thread keeps its channel group across the staged rows");
   const Affine8 aff = conv_affine8(p, co0 + (tid % GPR) * 8);     // (issued here: the loads fly during the first staging round)
   const EpiFast ef = conv_epi_fast(p, co0 + (tid % GPR) * 8);
@@ -1907,35 +1946,26 @@ __global__ __launch_bounds__(64 * WCO * WPX) void conv_f8_kernel(CONV_HOT_PARAMS
 // host side
 // ================================================================================================
 namespace {
-// DMA-to-LDS tile configurations {BCO, BPX, workgroups per CU, ring depth}
-struct TileCfg { int bco, bpx, occ, nst, wpx; };     // wpx: pixel-waves of the pipelined kernel (epilogue staging = 32*wpx pixels)
-constexpr int kNumCfg = 8;
-const TileCfg kCfgs[kNumCfg] = {{256, 192, 1, 2, 2}, {256, 128, 1, 3, 2}, {128, 256, 1, 3, 4}, {128, 128, 2, 2, 4}, {64, 256, 2, 2, 8},
-                                {128, 64, 2, 3, 2},
-                                // small tiles for the layers with few pixels (layer3/4: 8 400 / 2 100 pixels at N = 2): enough
-                                // workgroups to use every CU without split-K partials, several resident per CU
-                                {64, 64, 3, 3, 2}, {64, 128, 2, 3, 4}};
+const char* const kConvGenNames[kNumConvGen] = {"conv_gemm_kernel", "conv_glds_kernel", "conv_pipe_kernel", "conv_pipe_kernel (backward GroupNorm records)",
+                                                "conv_pipe_kernel (SMALL_C)", "conv_f8_kernel"};
 
 // strided data-gradients gather with per-tap divisibility tests: only the v2 kernel's general address path does that
 inline bool conv_v2_only(const dsl_conv_desc* d) { return d->mode == 1 && d->stride > 1; }
 
-// Launch-time cost model (microseconds) of one (tile config, split-K factor) choice.  Calibrated on MI355X
-// (tools/ablate_pipe.py, tools/bench_conv.py; the constants were fitted to the forced-config sweep of
+// Launch-time cost model (microseconds) of one (tile row, split-K factor) choice.  Calibrated on MI355X
+// (tools/ablate_pipe.py, tools/bench_conv.py; the constants were fitted to the forced-row sweep of
 // `tools/bench_conv.py 2 0,1,2,3,4,5,6`: the model picks the measured-best tile on 12 of its 13 shapes, 1.9 us total
 // regret): per K tile a workgroup needs bco*bpx/32 MFMA cycles of its CU and
 // (bco+bpx)*128 B through the CU's 64 B/clk vector-memory path (~54 B/clk measured); co-resident workgroups share
 // both; the two overlap imperfectly.  Output and split-K partial traffic are HBM-rate terms.
-double conv_cost_us(int ci, long long px, int cd_pad, int ktiles, int sp, bool out_f32) {
-  const TileCfg& c = kCfgs[ci];
-  // per-config efficiency of the K loop (the 8-wave 128x128 tile keeps 2 waves per SIMD even alone on a CU)
-  static const double kEff[kNumCfg] = {1.0, 1.0, 1.0, 0.7, 0.95, 0.9, 1.3, 1.25};     // 6, 7: measured best on one shape of tools/bench_conv.py only
+double conv_cost_us(const ConvTile& c, long long px, int cd_pad, int ktiles, int sp, bool out_f32) {
   const long long wgs = (long long)(cd_pad / c.bco) * ((px + c.bpx - 1) / c.bpx) * sp;
   const long long slots = 256LL * c.occ;
   const long long rounds = (wgs + slots - 1) / slots;
   const long long per_cu = (wgs + 255) / 256;
   const double share = (double)(per_cu < c.occ ? per_cu : c.occ);     // workgroups sharing a CU in a round
   const double mfma = c.bco * c.bpx / 32.0, dma = (c.bco + c.bpx) * 128 / 54.0;
-  const double tile = share * (1.15 * (mfma > dma ? mfma : dma) + 0.5 * (mfma > dma ? dma : mfma)) * kEff[ci];
+  const double tile = share * (1.15 * (mfma > dma ? mfma : dma) + 0.5 * (mfma > dma ? dma : mfma)) * c.eff;
   // per-workgroup fill + epilogue: grows with the tile, and co-resident workgroups overlap each other's
   const double fixed = (1000.0 + 0.05 * c.bco * c.bpx) * (share > 1.0 ? share / 2.0 : share);
   const int kt = (ktiles + sp - 1) / sp;
@@ -1945,10 +1975,23 @@ double conv_cost_us(int ci, long long px, int cd_pad, int ktiles, int sp, bool o
   return t;
 }
 
-// picks the tile configuration (-1 = v1 kernel) and the split-K factor for a conv
+// May `d` run on tile row c?  The row divides the padded couts, is the forced one if the test hook forces one (1..8; 9..14 force
+// nothing), and is instantiated for every kernel generation the descriptor asks for.  every_gen = false asks for the
+// general-gather generation only (conv_choose's second pass).
+bool conv_cfg_ok(const dsl_conv_desc* d, int c, bool every_gen = true) {
+  const ConvTile& T = kConvTiles[c];
+  const int force = (d->flags >> 8) & 15;
+  if (d->cd_pad % T.bco || (force >= 1 && force <= kNumConvTiles && force - 1 != c)) return false;
+  if (conv_v2_only(d) && !T.gen[kGenGlds].wco) return false;
+  if (!every_gen) return true;
+  return !(d->gn_x && !T.gen[kGenPipeGn].wco) && !((d->flags & DSL_CONV_SMALL_C) && !T.gen[kGenPipeSmallC].wco) &&
+         !((d->flags & DSL_CONV_FP8) && !T.gen[kGenF8].wco);
+}
+
+// picks the tile row (-1 = v1 kernel) and the split-K factor for a conv
 void conv_choose(const dsl_conv_desc* d, long long px, int ktiles, int* pick_out, int* splits_out) {
-  const bool smallc = (d->flags & DSL_CONV_SMALL_C) != 0;
-  const int force = (d->flags >> 8) & 15;          // test hook: 1..8 = tile config, 15 = v1 kernel
+  const bool smallc = (d->flags & DSL_CONV_SMALL_C) != 0, fp8 = (d->flags & DSL_CONV_FP8) != 0;
+  const int force = (d->flags >> 8) & 15;          // test hook: 1..8 = tile row, 15 = v1 kernel
   const int force_split = (d->flags >> 12) & 15;   // test hook: split-K factor
   int pick = -1, splits = 1;
   long long src_px = 0;
@@ -1957,34 +2000,23 @@ void conv_choose(const dsl_conv_desc* d, long long px, int ktiles, int* pick_out
   const long long lds_ = d->lds > 0 ? d->lds : d->cs;
   const bool dma_ok = conv_v2_only(d) || (d->kh <= 8 && d->kw <= 8 && src_px * lds_ * 2 + (long long)d->kw * lds_ * 2 < 0x7fff0000LL);
   const bool smallc_pipe = smallc && d->cd_pad % 64 == 0;    // stem: pipelined kernel, 64-cout tile
-  const bool v1_only = ((smallc && !smallc_pipe) || (d->flags & DSL_CONV_RELU_IN) || !dma_ok) && !(d->flags & DSL_CONV_FP8);
-  if (!v1_only && force != 15) {
-    double best = 1e300;
-    const bool out_f32 = (d->flags & DSL_CONV_OUT_F32) != 0;
-    for (int c = 0; c < kNumCfg; ++c) {
-      if (d->cd_pad % kCfgs[c].bco) continue;
-      if (force >= 1 && force <= kNumCfg && force - 1 != c) continue;
-      if (c >= 5 && conv_v2_only(d)) continue;       // the small tiles exist for the pipelined kernel only
-      if (d->gn_x && c > 1) continue;                // backward GroupNorm records: the 256-cout tiles carry them (conv_gn_ok)
-      if (smallc && c != 4) continue;                // the 8-channel-source variant is instantiated for the 64x256 tile
-      if ((d->flags & DSL_CONV_FP8) && c != 0 && c != 1 && c != 3) continue;     // fp8: instantiated for 256x192, 256x128, 128x128
-      for (int sp = 1; sp <= 16; ++sp) {
-        if (sp > 1 && (smallc || (d->flags & DSL_CONV_FP8) || d->gn_ws)) break;
+  const bool v1_only = ((smallc && !smallc_pipe) || (d->flags & DSL_CONV_RELU_IN) || !dma_ok) && !fp8;
+  const bool out_f32 = (d->flags & DSL_CONV_OUT_F32) != 0;
+  double best = 1e300;
+  // Second pass: a forced split that no row can honour is ignored.  That pass filters the rows by the general-gather generation only
+  // (as it always did): a forced row that the GroupNorm-record, SMALL_C or fp8 generation lacks comes back from it when a split is
+  // forced as well, and the launch refuses it or runs the plain pipelined kernel.  tests/golden/conv_plan.json pins those answers.
+  for (int pass = 0; pass < 2 && pick < 0 && !v1_only && force != 15 && (pass == 0 || force_split > 1); ++pass)
+    for (int c = 0; c < kNumConvTiles; ++c) {
+      if (!conv_cfg_ok(d, c, pass == 0)) continue;
+      for (int sp = 1; sp <= (pass ? 1 : 16); ++sp) {
+        if (sp > 1 && (smallc || fp8 || d->gn_ws)) break;
         if (sp > 1 && (!d->workspace || sp > ktiles / 2 || (size_t)sp * px * d->cd_pad * 4 > d->workspace_bytes)) break;
-        if (force_split > 1 && sp != force_split) continue;
-        const double t = conv_cost_us(c, px, d->cd_pad, ktiles, sp, out_f32);
+        if (!pass && force_split > 1 && sp != force_split) continue;
+        const double t = conv_cost_us(kConvTiles[c], px, d->cd_pad, ktiles, sp, out_f32);
         if (t < best) { best = t; pick = c; splits = sp; }
       }
     }
-    if (pick < 0 && force_split > 1) {               // forced split not feasible: ignore it
-      for (int c = 0; c < kNumCfg; ++c) {
-        if (d->cd_pad % kCfgs[c].bco || (force >= 1 && force <= kNumCfg && force - 1 != c)) continue;
-        if (c >= 5 && conv_v2_only(d)) continue;
-        const double t = conv_cost_us(c, px, d->cd_pad, ktiles, 1, out_f32);
-        if (t < best) { best = t; pick = c; splits = 1; }
-      }
-    }
-  }
   *pick_out = pick;
   *splits_out = splits;
 }
@@ -2017,6 +2049,12 @@ long long conv_pixels(const dsl_conv_desc* d) {
   return px;
 }
 
+// THE K-tile rule: 128-byte LDS rows, i.e. 64 bf16 or 128 fp8 channels of one tap, or 8 taps of the 8-channel (NHWC8) stem source
+int conv_ktiles(const dsl_conv_desc* d) {
+  if (d->flags & DSL_CONV_SMALL_C) return (d->kh * d->kw + 7) / 8;
+  return d->kh * d->kw * (d->cs / ((d->flags & DSL_CONV_FP8) ? 128 : 64));
+}
+
 // Would a launch of `d` with gn_ws set leave the GroupNorm records?  Only the pipelined kernel's in-register ("pure") epilogue
 // writes them: bf16 output on the compute grid's own pixels, nothing added, one launch (no split-K).
 bool conv_gn_ok(const dsl_conv_desc* d) {
@@ -2031,15 +2069,199 @@ bool conv_gn_ok(const dsl_conv_desc* d) {
   dsl_conv_desc t = *d;
   t.gn_ws = (void*)1;
   int pick, splits;
-  conv_choose(&t, conv_pixels(d), d->kh * d->kw * (d->cs / 64), &pick, &splits);
+  conv_choose(&t, conv_pixels(d), conv_ktiles(d), &pick, &splits);
   if (pick < 0 || splits != 1) return false;
-  if (d->gn_x) {      // the backward records: instantiated for the 256-cout tiles only (256 x 192, 256 x 128).  Their workgroups own a
-    // CU anyway (114 / 147 KB of LDS); the 128 x 128 tile with the ~60 extra registers (158) keeps ONE workgroup per CU instead of
-    // two and the launch takes twice as long (N = 3 head: 100 -> 212 us, profiles/r04_rla_timeline.txt) - there the separate pass stays
-    if (pick != 0 && pick != 1) return false;
-    if (d->ldd != d->cd) return false;
+  // the backward records: instantiated for the 256-cout tiles only (kConvTiles: 256 x 192, 256 x 128).  Their workgroups own a
+  // CU anyway (114 / 147 KB of LDS); the 128 x 128 tile with the ~60 extra registers (158) keeps ONE workgroup per CU instead of
+  // two and the launch takes twice as long (N = 3 head: 100 -> 212 us, profiles/r04_rla_timeline.txt) - there the separate pass stays
+  if (d->gn_x && (!kConvTiles[pick].gen[kGenPipeGn].wco || d->ldd != d->cd)) return false;
+  return true;
+}
+
+int conv_validate(const dsl_conv_desc* d) {
+  DSL_CHECK(d != nullptr, "dsl_conv2d: null descriptor");
+  DSL_CHECK(d->nseg >= 1 && d->nseg <= DSL_MAX_SEG, "dsl_conv2d: nseg=%d out of range", d->nseg);
+  DSL_CHECK(d->src && d->wgt && d->dst, "dsl_conv2d: null tensor pointer");
+  const bool fp8 = (d->flags & DSL_CONV_FP8) != 0;
+  if (d->flags & DSL_CONV_SMALL_C)
+    DSL_CHECK(d->cs == 8 && d->mode == 0, "dsl_conv2d: SMALL_C needs cs == 8, forward mode");
+  else if (fp8)
+    DSL_CHECK(d->cs % 128 == 0 && d->cs > 0 && d->mode == 0 && !(d->flags & DSL_CONV_RELU_IN) && d->scale,
+              "dsl_conv2d: FP8 needs forward mode, cs %% 128 == 0 (cs=%d) and the dequantisation `scale` vector", d->cs);
+  else
+    DSL_CHECK(d->cs % 64 == 0 && d->cs > 0, "dsl_conv2d: source channels %d not a multiple of 64", d->cs);
+  DSL_CHECK(d->cd_pad % 64 == 0 && d->cd <= d->cd_pad && d->cd > 0, "dsl_conv2d: bad cd=%d cd_pad=%d", d->cd, d->cd_pad);
+  DSL_CHECK(d->ldd % 4 == 0 && d->ldd >= d->cd, "dsl_conv2d: ldd=%d must be a multiple of 4 and >= cd", d->ldd);
+  DSL_CHECK(d->stride >= 1 && d->os >= 1 && d->kh >= 1 && d->kw >= 1, "dsl_conv2d: bad stride/os/kernel");
+  DSL_CHECK(!(d->addend) || d->lda % 4 == 0, "dsl_conv2d: lda must be a multiple of 4");
+  DSL_CHECK(!(d->mask) || d->ldm % 4 == 0, "dsl_conv2d: ldm must be a multiple of 4");
+  for (int s = 0; s < d->nseg; ++s) {
+    DSL_CHECK(d->gh[s] > 0 && d->gw[s] > 0 && d->sh[s] > 0 && d->sw[s] > 0 && d->dh[s] > 0 && d->dw[s] > 0,
+              "dsl_conv2d: empty segment %d", s);
+    DSL_CHECK((d->gh[s] - 1) * d->os < d->dh[s] && (d->gw[s] - 1) * d->os < d->dw[s],
+              "dsl_conv2d: compute grid x os exceeds destination in segment %d", s);
+  }
+  const int lds = d->lds > 0 ? d->lds : d->cs;
+  DSL_CHECK(lds >= d->cs && lds % (fp8 ? 16 : 8) == 0, "dsl_conv2d: lds=%d must be >= cs=%d and a multiple of 16 bytes", lds, d->cs);
+  DSL_CHECK(!d->gn_ws || conv_gn_ok(d), "dsl_conv2d: gn_ws is set but this launch cannot write GroupNorm records "
+            "(ask dsl_conv2d_gn_fusable first)");
+  if (d->gn_ws && d->gn_x)
+    DSL_CHECK(d->gn_gamma && d->gn_beta && d->gn_stats && d->ldd == d->cd, "dsl_conv2d: backward GroupNorm records need gn_gamma, "
+              "gn_beta, gn_stats and a dense destination (ldd=%d cd=%d)", d->ldd, d->cd);
+  return 0;
+}
+
+// the kernels' view of a validated descriptor; the planner's fields (splits .. xcd_chunk, ws) stay zero until conv_plan
+void conv_fill_k(const dsl_conv_desc* d, ConvK& k) {
+  memset(&k, 0, sizeof(k));
+  const bool fp8 = (d->flags & DSL_CONV_FP8) != 0, up = (d->flags & DSL_CONV_ADD_UPSAMPLE) != 0;
+  k.nseg = d->nseg;
+  k.n = d->n;
+  long long so = 0, dof = 0, ao = 0;
+  int px = 0;
+  bool identd = d->os == 1;               // destination pixel == compute-grid pixel (whatever the addend's grid is)
+  for (int s = 0; s < d->nseg; ++s) {
+    k.gh[s] = d->gh[s]; k.gw[s] = d->gw[s];
+    k.sh[s] = d->sh[s]; k.sw[s] = d->sw[s];
+    k.dh[s] = d->dh[s]; k.dw[s] = d->dw[s];
+    k.ah[s] = up ? d->ah[s] : d->dh[s];
+    k.aw[s] = up ? d->aw[s] : d->dw[s];
+    if (d->gh[s] != d->dh[s] || d->gw[s] != d->dw[s]) identd = false;
+    k.pxstart[s] = px;
+    k.soff[s] = so; k.doff[s] = dof; k.aoff[s] = ao;
+    px += d->n * d->gh[s] * d->gw[s];
+    so += (long long)d->n * d->sh[s] * d->sw[s];
+    dof += (long long)d->n * d->dh[s] * d->dw[s];
+    ao += (long long)d->n * k.ah[s] * k.aw[s];
+  }
+  k.pxstart[d->nseg] = px;
+  k.ident = identd && !up;
+  k.cs = d->cs; k.cd = d->cd; k.ldd = d->ldd; k.lda = d->lda; k.ldm = d->ldm;
+  // the in-register addend epilogue (conv_tile_epilogue): the addend tile goes to LDS by DMA with 32-bit buffer offsets
+  k.addfast = (d->addend && identd && !(d->flags & DSL_CONV_EPI_STAGED) && d->lda % 8 == 0 && d->ldd % 8 == 0 &&
+               (!d->mask || d->ldm % 8 == 0) && ((uintptr_t)d->addend & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 &&
+               (dof > ao ? dof : ao) * (long long)d->lda * 2 < 0x7fff0000LL) ? (up ? 2 : 1) : 0;
+  k.lds = d->lds > 0 ? d->lds : d->cs;
+  k.kh = d->kh; k.kw = d->kw; k.stride = d->stride; k.pad = d->pad; k.mode = d->mode; k.os = d->os;
+  k.flags = d->flags;
+  k.ktiles = conv_ktiles(d);
+  k.kc = (d->flags & DSL_CONV_SMALL_C) ? 1 : d->cs / (fp8 ? 128 : 64);
+  k.wrow = (long long)k.ktiles * (fp8 ? 128 : BK);     // (a K tile is 128 one-byte elements in fp8: the same 128-byte LDS rows)
+  k.src = (const uint16_t*)d->src; k.wgt = (const uint16_t*)d->wgt; k.dst = d->dst;
+  k.scale = d->scale; k.bias = d->bias;
+  k.addend = (const uint16_t*)d->addend; k.mask = (const uint16_t*)d->mask;
+  k.gnws = (float*)d->gn_ws;
+  if (d->gn_ws && d->gn_x) { k.gnx = (const uint16_t*)d->gn_x; k.gngamma = d->gn_gamma; k.gnbeta = d->gn_beta; k.gnstats = d->gn_stats; }
+}
+
+// Kernel generation, tile row, grid, block and LDS size of the launch of `d`, and the planner's fields of k.  No HIP call: dsl_conv2d_plan
+// answers from here, and conv_launch launches exactly what this says.
+int conv_plan(const dsl_conv_desc* d, ConvK& k, dsl_conv_plan& p) {
+  const int px = k.pxstart[k.nseg];
+  int pick, splits;
+  conv_choose(d, px, k.ktiles, &pick, &splits);
+  memset(&p, 0, sizeof(p));
+  p.cfg = pick; p.splits = splits; p.ident = k.ident; p.addfast = k.addfast;
+  if (pick < 0) {                          // the v1 kernel: 128 pixels x 128 or 64 couts, two K stages
+    p.kernel = kGenV1; p.bco = (d->cd_pad % 128 == 0) ? 128 : 64; p.bpx = BPX; p.threads = 256;
+    p.grid[0] = d->cd_pad / p.bco; p.grid[1] = (px + BPX - 1) / BPX; p.grid[2] = 1;
+    p.lds_bytes = 2 * (size_t)(p.bco + BPX) * BK * 2;
+    return 0;
+  }
+  const ConvTile& T = kConvTiles[pick];
+  p.kernel = (d->flags & DSL_CONV_FP8) ? kGenF8 : conv_v2_only(d) ? kGenGlds : k.gnx ? kGenPipeGn
+             : ((d->flags & DSL_CONV_SMALL_C) && T.gen[kGenPipeSmallC].wco) ? kGenPipeSmallC : kGenPipe;
+  const ConvWaves W = T.gen[p.kernel];
+  if (p.kernel == kGenF8) DSL_CHECK(W.wco, "dsl_conv2d: no fp8 kernel for this shape (tile config %d)", pick);
+  DSL_CHECK(W.wco, "dsl_conv2d: no %s for tile config %d", kConvGenNames[p.kernel], pick);
+  p.bco = T.bco; p.bpx = T.bpx; p.threads = 64 * W.wco * W.wpx;
+  p.lds_bytes = conv_lds_bytes(T, p.kernel);
+  p.workspace_bytes = splits > 1 ? (size_t)splits * px * d->cd_pad * 4 : 0;
+  k.splits = splits;
+  k.kt_per_split = (k.ktiles + splits - 1) / splits;
+  k.cd_pad = d->cd_pad;
+  k.ws = (float*)d->workspace;
+  k.gx = d->cd_pad / T.bco;
+  k.gy = (px + T.bpx - 1) / T.bpx;
+  k.xcd_chunk = (int)(((unsigned)k.gx * k.gy * splits + 7) / 8);
+  if (p.kernel == kGenGlds) { p.grid[0] = k.gx; p.grid[1] = k.gy; p.grid[2] = splits; }
+  else { p.grid[0] = 8 * k.xcd_chunk; p.grid[1] = p.grid[2] = 1; }      // the pipelined kernels: the 1-D XCD-aware grid
+  return 0;
+}
+
+// Calls f(std::integral_constant<int, row>) if the kConvTiles row has a kernel of generation `gen`: the caller instantiates its kernel
+// from the row that the plan's block and LDS size come from.  False: no such kernel.
+template <class F>
+bool conv_dispatch(int row, int gen, F&& f) {
+  if (row < 0 || row >= kNumConvTiles || gen <= kGenV1 || gen >= kNumConvGen || !kConvTiles[row].gen[gen].wco) return false;
+  switch (row) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 7>{}); break;
   }
   return true;
+}
+static_assert(kNumConvTiles == 8, "conv_dispatch lists every row");
+#define CONV_TILE_ARGS(T, G) T.bco, T.bpx, T.gen[G].wco, T.gen[G].wpx, T.nst
+
+// launches a kernel as planned; its first launch raises the kernel's dynamic-LDS limit to the plan's size
+template <auto KERNEL, class... Args>
+void conv_run(const dsl_conv_plan& p, size_t lds, hipStream_t st, const Args&... args) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3(p.grid[0], p.grid[1], p.grid[2]), dim3(p.threads), lds, st, args...);
+}
+
+int conv_launch(const dsl_conv_desc* d, ConvK& k, const dsl_conv_plan& p, hipStream_t st) {
+  const int px = k.pxstart[k.nseg];
+  size_t lds = p.lds_bytes;
+  if (p.kernel != kGenV1) {                // the instrumented builds of tools/ (never the shipped library)
+#ifdef DSL_ABLATE_BUILD
+    { const char* e = getenv("DSL_ABLATE"); k.dbg = e ? atoi(e) : 0; }
+#endif
+#ifdef DSL_TRACE_BUILD
+    { const char* e = getenv("DSL_TRACE_WG"); k.dbg = e ? atoi(e) : -1; }
+    lds += 8 * 40 * 8 * 8 + 8 * 16 * 8;    // the stamp area behind the ring
+#endif
+  }
+  int prof = -1;
+  if (dsl_prof_active())
+    prof = dsl_prof_begin(p.kernel == kGenV1 ? 2 : kConvTiles[p.cfg].prof, conv_algo_flops(d, px), st, conv_algo_bytes(d, px));
+  if (p.kernel == kGenV1) {
+    const bool smallc = (d->flags & DSL_CONV_SMALL_C) != 0;
+    if (p.bco == 128) smallc ? conv_run<conv_gemm_kernel<128, true>>(p, lds, st, k) : conv_run<conv_gemm_kernel<128, false>>(p, lds, st, k);
+    else smallc ? conv_run<conv_gemm_kernel<64, true>>(p, lds, st, k) : conv_run<conv_gemm_kernel<64, false>>(p, lds, st, k);
+  } else {
+    conv_dispatch(p.cfg, p.kernel, [&](auto row) {      // (`if constexpr`: only the generations the row is instantiated for exist)
+      constexpr ConvTile T = kConvTiles[decltype(row)::value];
+      if (p.kernel == kGenPipe) conv_run<conv_pipe_kernel<CONV_TILE_ARGS(T, kGenPipe)>>(p, lds, st, CONV_HOT_ARGS(k), k);
+      if constexpr (T.gen[kGenGlds].wco != 0)
+        if (p.kernel == kGenGlds) conv_run<conv_glds_kernel<CONV_TILE_ARGS(T, kGenGlds)>>(p, lds, st, k);
+      if constexpr (T.gen[kGenPipeGn].wco != 0)
+        if (p.kernel == kGenPipeGn) conv_run<conv_pipe_kernel<CONV_TILE_ARGS(T, kGenPipeGn), false, true>>(p, lds, st, CONV_HOT_ARGS(k), k);
+      if constexpr (T.gen[kGenPipeSmallC].wco != 0)
+        if (p.kernel == kGenPipeSmallC) conv_run<conv_pipe_kernel<CONV_TILE_ARGS(T, kGenPipeSmallC), true>>(p, lds, st, CONV_HOT_ARGS(k), k);
+      if constexpr (T.gen[kGenF8].wco != 0)
+        if (p.kernel == kGenF8) conv_run<conv_f8_kernel<CONV_TILE_ARGS(T, kGenF8)>>(p, lds, st, CONV_HOT_ARGS(k), k);
+    });
+  }
+  dsl_prof_end(prof, st);
+  if (p.splits > 1) {
+    const long long total = (long long)px * (k.cd_pad / 4);
+    int blocks = (int)((total + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, k.ws, px, k.cd_pad, k.cd, k.splits, k);
+  }
+  DSL_LAUNCH_CHECK(kConvGenNames[p.kernel]);
+  return 0;
 }
 }  // namespace
 
@@ -2052,240 +2274,26 @@ extern "C" size_t dsl_conv2d_workspace_bytes(const dsl_conv_desc* d) {
   t.workspace_bytes = (size_t)1 << 40;
   int pick, splits;
   const long long px = conv_pixels(d);
-  conv_choose(&t, px, d->kh * d->kw * (d->cs / 64), &pick, &splits);
+  conv_choose(&t, px, conv_ktiles(d), &pick, &splits);
   return splits > 1 ? (size_t)splits * px * d->cd_pad * 4 : 0;
 }
 
-extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
-  DSL_CHECK(d != nullptr, "dsl_conv2d: null descriptor");
-  DSL_CHECK(d->nseg >= 1 && d->nseg <= DSL_MAX_SEG, "dsl_conv2d: nseg=%d out of range", d->nseg);
-  DSL_CHECK(d->src && d->wgt && d->dst, "dsl_conv2d: null tensor pointer");
-  const bool smallc = (d->flags & DSL_CONV_SMALL_C) != 0;
-  const bool fp8 = (d->flags & DSL_CONV_FP8) != 0;
-  if (smallc)
-    DSL_CHECK(d->cs == 8 && d->mode == 0, "dsl_conv2d: SMALL_C needs cs == 8, forward mode");
-  else if (fp8)
-    DSL_CHECK(d->cs % 128 == 0 && d->cs > 0 && d->mode == 0 && !(d->flags & DSL_CONV_RELU_IN) && d->scale,
-              "dsl_conv2d: FP8 needs forward mode, cs %% 128 == 0 (cs=%d) and the dequantisation `scale` vector", d->cs);
-  else
-    DSL_CHECK(d->cs % 64 == 0 && d->cs > 0, "dsl_conv2d: source channels %d not a multiple of 64", d->cs);
-  DSL_CHECK(d->cd_pad % 64 == 0 && d->cd <= d->cd_pad && d->cd > 0, "dsl_conv2d: bad cd=%d cd_pad=%d", d->cd, d->cd_pad);
-  DSL_CHECK(d->ldd % 4 == 0 && d->ldd >= d->cd, "dsl_conv2d: ldd=%d must be a multiple of 4 and >= cd", d->ldd);
-  DSL_CHECK(d->stride >= 1 && d->os >= 1 && d->kh >= 1 && d->kw >= 1, "dsl_conv2d: bad stride/os/kernel");
-  DSL_CHECK(!(d->addend) || d->lda % 4 == 0, "dsl_conv2d: lda must be a multiple of 4");
-  DSL_CHECK(!(d->mask) || d->ldm % 4 == 0, "dsl_conv2d: ldm must be a multiple of 4");
+extern "C" int dsl_conv2d_plan(const dsl_conv_desc* d, dsl_conv_plan* out) {
+  DSL_CHECK(out != nullptr, "dsl_conv2d_plan: null plan");
+  if (int rc = conv_validate(d)) return rc;
   ConvK k;
-  memset(&k, 0, sizeof(k));
-  k.nseg = d->nseg;
-  k.n = d->n;
-  long long so = 0, dof = 0, ao = 0;
-  int px = 0;
-  for (int s = 0; s < d->nseg; ++s) {
-    k.gh[s] = d->gh[s]; k.gw[s] = d->gw[s];
-    k.sh[s] = d->sh[s]; k.sw[s] = d->sw[s];
-    k.dh[s] = d->dh[s]; k.dw[s] = d->dw[s];
-    const bool up = (d->flags & DSL_CONV_ADD_UPSAMPLE) != 0;
-    k.ah[s] = up ? d->ah[s] : d->dh[s];
-    k.aw[s] = up ? d->aw[s] : d->dw[s];
-    DSL_CHECK(d->gh[s] > 0 && d->gw[s] > 0 && d->sh[s] > 0 && d->sw[s] > 0 && d->dh[s] > 0 && d->dw[s] > 0,
-              "dsl_conv2d: empty segment %d", s);
-    DSL_CHECK((d->gh[s] - 1) * d->os < d->dh[s] && (d->gw[s] - 1) * d->os < d->dw[s],
-              "dsl_conv2d: compute grid x os exceeds destination in segment %d", s);
-    k.pxstart[s] = px;
-    k.soff[s] = so; k.doff[s] = dof; k.aoff[s] = ao;
-    px += d->n * d->gh[s] * d->gw[s];
-    so += (long long)d->n * d->sh[s] * d->sw[s];
-    dof += (long long)d->n * d->dh[s] * d->dw[s];
-    ao += (long long)d->n * k.ah[s] * k.aw[s];
-  }
-  k.pxstart[d->nseg] = px;
-  k.ident = (d->os == 1 && !(d->flags & DSL_CONV_ADD_UPSAMPLE)) ? 1 : 0;
-  for (int s = 0; s < d->nseg; ++s)
-    if (d->gh[s] != d->dh[s] || d->gw[s] != d->dw[s]) k.ident = 0;
-  k.cs = d->cs; k.cd = d->cd; k.ldd = d->ldd; k.lda = d->lda; k.ldm = d->ldm;
-  // the in-register addend epilogue (conv_tile_epilogue): the addend tile goes to LDS by DMA with 32-bit buffer offsets
-  bool identd = d->os == 1;               // destination pixel == compute-grid pixel (whatever the addend's grid is)
-  for (int s = 0; s < d->nseg; ++s)
-    if (d->gh[s] != d->dh[s] || d->gw[s] != d->dw[s]) identd = false;
-  k.addfast = (d->addend && identd && !(d->flags & DSL_CONV_EPI_STAGED) && d->lda % 8 == 0 && d->ldd % 8 == 0 &&
-               (!d->mask || d->ldm % 8 == 0) && ((uintptr_t)d->addend & 15) == 0 && ((uintptr_t)d->dst & 15) == 0 &&
-               (dof > ao ? dof : ao) * (long long)d->lda * 2 < 0x7fff0000LL) ? ((d->flags & DSL_CONV_ADD_UPSAMPLE) ? 2 : 1) : 0;
-  k.lds = d->lds > 0 ? d->lds : d->cs;
-  DSL_CHECK(k.lds >= d->cs && k.lds % (fp8 ? 16 : 8) == 0, "dsl_conv2d: lds=%d must be >= cs=%d and a multiple of 16 bytes", k.lds, d->cs);
-  k.kh = d->kh; k.kw = d->kw; k.stride = d->stride; k.pad = d->pad; k.mode = d->mode; k.os = d->os;
-  k.flags = d->flags;
-  if (smallc) {
-    k.ktiles = (d->kh * d->kw + 7) / 8;
-    k.kc = 1;
-  } else if (fp8) {
-    k.kc = d->cs / 128;                 // a K tile is 128 one-byte elements: the same 128-byte LDS rows
-    k.ktiles = d->kh * d->kw * k.kc;
-  } else {
-    k.kc = d->cs / 64;
-    k.ktiles = d->kh * d->kw * k.kc;
-  }
-  k.wrow = (long long)k.ktiles * (fp8 ? 128 : BK);
-  k.src = (const uint16_t*)d->src; k.wgt = (const uint16_t*)d->wgt; k.dst = d->dst;
-  k.scale = d->scale; k.bias = d->bias;
-  k.addend = (const uint16_t*)d->addend; k.mask = (const uint16_t*)d->mask;
-  DSL_CHECK(!d->gn_ws || conv_gn_ok(d), "dsl_conv2d: gn_ws is set but this launch cannot write GroupNorm records "
-            "(ask dsl_conv2d_gn_fusable first)");
-  k.gnws = (float*)d->gn_ws;
-  if (d->gn_ws && d->gn_x) {
-    DSL_CHECK(d->gn_gamma && d->gn_beta && d->gn_stats && d->ldd == d->cd, "dsl_conv2d: backward GroupNorm records need gn_gamma, "
-              "gn_beta, gn_stats and a dense destination (ldd=%d cd=%d)", d->ldd, d->cd);
-    k.gnx = (const uint16_t*)d->gn_x; k.gngamma = d->gn_gamma; k.gnbeta = d->gn_beta; k.gnstats = d->gn_stats;
-  }
-
-  hipStream_t st = (hipStream_t)stream;
-  // ---- kernel / tile selection -------------------------------------------------------------------
-  int pick, splits;
-  conv_choose(d, px, k.ktiles, &pick, &splits);
-  if (pick >= 0) {
-    const TileCfg& c = kCfgs[pick];
-    k.splits = splits;
-    k.kt_per_split = (k.ktiles + splits - 1) / splits;
-    k.cd_pad = d->cd_pad;
-    k.ws = (float*)d->workspace;
-#ifdef DSL_ABLATE_BUILD
-    { const char* e = getenv("DSL_ABLATE"); k.dbg = e ? atoi(e) : 0; }
-#endif
-#ifdef DSL_TRACE_BUILD
-    { const char* e = getenv("DSL_TRACE_WG"); k.dbg = e ? atoi(e) : -1; }
-#endif
-    dim3 grid(d->cd_pad / c.bco, (px + c.bpx - 1) / c.bpx, splits);
-    const bool force_v2_kernel = conv_v2_only(d);
-    k.gx = (int)grid.x;
-    k.gy = (int)grid.y;
-    k.xcd_chunk = (int)((grid.x * grid.y * grid.z + 7) / 8);
-    size_t lds = (size_t)c.nst * (c.bco + c.bpx) * 128;
-    if (!force_v2_kernel) {                // the pipelined kernel stages its epilogue in LDS: 32*wpx pixel rows of fp32
-      const size_t stg = (size_t)32 * c.wpx * (c.bco * 4 + 16);
-      if (stg > lds) lds = stg;
-    }
-#ifdef DSL_TRACE_BUILD
-    lds += 8 * 40 * 8 * 8 + 8 * 16 * 8;    // the stamp area behind the ring
-#endif
-    int prof = -1;
-    if (dsl_prof_active()) prof = dsl_prof_begin(pick == 3 ? 0 : (pick == 0 ? 1 : 2), conv_algo_flops(d, px), st, conv_algo_bytes(d, px));
-#define LAUNCH2(A, B, C_, D, S_)                                                                               \
-  do {                                                                                                        \
-    static bool attr_set = false;                                                                             \
-    if (!attr_set) {                                                                                          \
-      hipFuncSetAttribute((const void*)conv_glds_kernel<A, B, C_, D, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                          (int)lds);                                                                          \
-      attr_set = true;                                                                                        \
-    }                                                                                                         \
-    hipLaunchKernelGGL((conv_glds_kernel<A, B, C_, D, S_>), grid, dim3(64 * C_ * D), lds, st, k);              \
-  } while (0)
-#define LAUNCH3(A, B, C_, D, S_)                                                                               \
-  do {                                                                                                        \
-    static bool attr_set3 = false;                                                                            \
-    if (!attr_set3) {                                                                                         \
-      hipFuncSetAttribute((const void*)conv_pipe_kernel<A, B, C_, D, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                          (int)lds);                                                                          \
-      attr_set3 = true;                                                                                       \
-    }                                                                                                         \
-    hipLaunchKernelGGL((conv_pipe_kernel<A, B, C_, D, S_>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, CONV_HOT_ARGS(k), k); \
-  } while (0)
-#define LAUNCH3G(A, B, C_, D, S_)                                                                              \
-  do {                                                                                                        \
-    static bool attr_set3g = false;                                                                           \
-    if (!attr_set3g) {                                                                                        \
-      hipFuncSetAttribute((const void*)conv_pipe_kernel<A, B, C_, D, S_, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                          (int)lds);                                                                          \
-      attr_set3g = true;                                                                                      \
-    }                                                                                                         \
-    hipLaunchKernelGGL((conv_pipe_kernel<A, B, C_, D, S_, false, true>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, CONV_HOT_ARGS(k), k); \
-  } while (0)
-    if (fp8) {
-      DSL_CHECK(!force_v2_kernel && (pick == 0 || pick == 1 || pick == 3), "dsl_conv2d: no fp8 kernel for this shape (tile config %d)", pick);
-#define LAUNCH8(A, B, C_, D, S_)                                                                               \
-  do {                                                                                                        \
-    static bool attr_8 = false;                                                                               \
-    if (!attr_8) {                                                                                            \
-      hipFuncSetAttribute((const void*)conv_f8_kernel<A, B, C_, D, S_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                          (int)lds);                                                                          \
-      attr_8 = true;                                                                                          \
-    }                                                                                                         \
-    hipLaunchKernelGGL((conv_f8_kernel<A, B, C_, D, S_>), dim3(8 * k.xcd_chunk), dim3(64 * C_ * D), lds, st, CONV_HOT_ARGS(k), k); \
-  } while (0)
-      switch (pick) {
-        case 0: LAUNCH8(256, 192, 4, 2, 2); break;
-        case 1: LAUNCH8(256, 128, 4, 2, 3); break;
-        default: LAUNCH8(128, 128, 2, 4, 2); break;
-      }
-#undef LAUNCH8
-    } else if (force_v2_kernel) {
-      switch (pick) {
-        case 0: LAUNCH2(256, 192, 4, 2, 2); break;
-        case 1: LAUNCH2(256, 128, 4, 2, 3); break;
-        case 2: LAUNCH2(128, 256, 2, 4, 3); break;
-        case 3: LAUNCH2(128, 128, 2, 2, 2); break;
-        default: LAUNCH2(64, 256, 1, 4, 2); break;
-      }
-    } else {
-      if (k.gnx) {                   // (conv_gn_ok: one of the two tiles below)
-        if (pick == 0) LAUNCH3G(256, 192, 4, 2, 2); else LAUNCH3G(256, 128, 4, 2, 3);
-      } else
-      switch (pick) {
-        case 0: LAUNCH3(256, 192, 4, 2, 2); break;
-        case 1: LAUNCH3(256, 128, 4, 2, 3); break;
-        case 2: LAUNCH3(128, 256, 2, 4, 3); break;
-        case 3: LAUNCH3(128, 128, 2, 4, 2); break;
-        case 4:
-          if (smallc) {
-            static bool a4 = false;
-            if (!a4) { hipFuncSetAttribute((const void*)conv_pipe_kernel<64, 256, 1, 8, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); a4 = true; }
-            hipLaunchKernelGGL((conv_pipe_kernel<64, 256, 1, 8, 2, true>), dim3(8 * k.xcd_chunk), dim3(512), lds, st, CONV_HOT_ARGS(k), k);
-          } else {
-            LAUNCH3(64, 256, 1, 8, 2);
-          }
-          break;
-        case 5: LAUNCH3(128, 64, 2, 2, 3); break;
-        case 6: LAUNCH3(64, 64, 1, 2, 3); break;
-        default: LAUNCH3(64, 128, 1, 4, 3); break;
-      }
-    }
-#undef LAUNCH2
-#undef LAUNCH3
-#undef LAUNCH3G
-    dsl_prof_end(prof, st);
-    if (splits > 1) {
-      const long long total = (long long)px * (d->cd_pad / 4);
-      int blocks = (int)((total + 255) / 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel, dim3(blocks), dim3(256), 0, st, k.ws, k.pxstart[k.nseg], k.cd_pad, k.cd, k.splits, k);
-    }
-    DSL_LAUNCH_CHECK("conv_glds_kernel");
-    return 0;
-  }
-  const int bco = (d->cd_pad % 128 == 0) ? 128 : 64;
-  dim3 grid(d->cd_pad / bco, (px + BPX - 1) / BPX);
-  const size_t lds = 2 * (size_t)(bco + BPX) * BK * 2;
-#define LAUNCH(BCO_, SC_)                                                                         \
-  do {                                                                                            \
-    static bool attr_set = false;                                                                 \
-    if (!attr_set) {                                                                              \
-      hipFuncSetAttribute((const void*)conv_gemm_kernel<BCO_, SC_>,                               \
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                  \
-      attr_set = true;                                                                            \
-    }                                                                                             \
-    hipLaunchKernelGGL((conv_gemm_kernel<BCO_, SC_>), grid, dim3(256), lds, st, k);               \
-  } while (0)
-  int prof = -1;
-  if (dsl_prof_active()) prof = dsl_prof_begin(2, conv_algo_flops(d, px), st, conv_algo_bytes(d, px));
-  if (bco == 128) {
-    if (smallc) LAUNCH(128, true); else LAUNCH(128, false);
-  } else {
-    if (smallc) LAUNCH(64, true); else LAUNCH(64, false);
-  }
-  dsl_prof_end(prof, st);
-#undef LAUNCH
-  DSL_LAUNCH_CHECK("conv_gemm_kernel");
-  return 0;
+  conv_fill_k(d, k);
+  return conv_plan(d, k, *out);
 }
 
+extern "C" int dsl_conv2d(const dsl_conv_desc* d, void* stream) {
+  if (int rc = conv_validate(d)) return rc;
+  ConvK k;
+  dsl_conv_plan p;
+  conv_fill_k(d, k);
+  if (int rc = conv_plan(d, k, p)) return rc;
+  return conv_launch(d, k, p, (hipStream_t)stream);
+}
 
 #ifdef DSL_TRACE_BUILD
 // tools/trace_conv.py: the s_memtime stamps of the traced workgroup (DSL_TRACE_WG) of the last conv_pipe launch

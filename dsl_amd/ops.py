@@ -108,6 +108,26 @@ def conv_workspace_bytes(d):
     return lib.dsl_conv2d_workspace_bytes(C.byref(d))
 
 
+def conv_plan(d):
+    """What dsl_conv2d would launch for `d` (L.ConvPlan; host only, no launch)."""
+    p = L.ConvPlan()
+    L.check(lib.dsl_conv2d_plan(C.byref(d), C.byref(p)), 'dsl_conv2d_plan')
+    return p
+
+
+def conv_forced_rows(d):
+    """The values of the `force` test hook (dsl_conv_desc.flags bits 8-11) that put `d` on the tile row they name: the library's
+    tile table is asked, nothing here mirrors it."""
+    f0, rows = d.flags, []
+    for f in range(1, 15):
+        d.flags = (f0 & ~0xf00) | (f << 8)
+        p = L.ConvPlan()
+        if lib.dsl_conv2d_plan(C.byref(d), C.byref(p)) == 0 and p.cfg == f - 1:
+            rows.append(f)
+    d.flags = f0
+    return rows
+
+
 def conv2d(*a, **k):
     d = conv_desc(*a, **k)
     L.check(lib.dsl_conv2d(C.byref(d), L.stream_ptr()), 'dsl_conv2d')

@@ -115,6 +115,18 @@ int dsl_conv2d_gn_fusable(const dsl_conv_desc* d);
 size_t dsl_conv2d_workspace_bytes(const dsl_conv_desc* d);
 int dsl_conv2d(const dsl_conv_desc* d, void* stream);
 
+/* What dsl_conv2d(d) would launch, from the function the launch itself takes its numbers from.  Host only: no HIP call, works
+ * without a device (tools, tests/test_conv_plan_cpu.py).  Returns what dsl_conv2d would return for a descriptor it refuses. */
+typedef struct dsl_conv_plan {
+  int32_t kernel;        /* 0 v1 gemm, 1 glds, 2 pipe, 3 pipe + backward GN records, 4 pipe SMALL_C, 5 fp8 */
+  int32_t cfg;           /* tile table row, -1 for the v1 kernel */
+  int32_t bco, bpx, threads, splits;
+  int32_t grid[3];       /* as passed to the launch */
+  int32_t ident, addfast;
+  size_t lds_bytes, workspace_bytes;
+} dsl_conv_plan;
+int dsl_conv2d_plan(const dsl_conv_desc* d, dsl_conv_plan* out);
+
 /* Weight gradient: dW[co][r][s][ci] = scale[co] * sum_p dY[p][co] * X[p@(r,s)][ci]  (fp32, KRSC).
  * Split-K over pixels into a caller-owned workspace, then a reduce pass.  Optionally also
  * db[co] = sum_p dY[p][co].  Replaces the autograd backward of the same F.conv2d calls. */

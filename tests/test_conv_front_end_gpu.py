@@ -14,7 +14,7 @@ from test_kernels_gpu import _multiseg, bf, from_nhwc, nhwc, pack_w, pack_w_dgra
 
 pytestmark = pytest.mark.gpu
 
-BCO = {1: 256, 2: 256, 3: 128, 4: 128, 5: 64, 6: 128, 7: 64, 8: 64}        # cout tile of forced configuration 1..8 (kCfgs, conv.hip)
+BCO = {1: 256, 2: 256, 3: 128, 4: 128, 5: 64, 6: 128, 7: 64, 8: 64}        # cout tile of forced configuration 1..8 (kConvTiles, conv.hip)
 
 
 def forces(cd_pad):

@@ -303,7 +303,9 @@ def test_conv_fpn_lateral_upsample_add(K):
 
 
 DGRAD_CASES = [('3x3_s1', 2, 128, 64, 11, 13, 3, 1, 1), ('3x3_s2', 1, 128, 128, 13, 21, 3, 2, 1),
-               ('1x1_s1', 2, 256, 128, 7, 9, 1, 1, 0), ('3x3_s1_pad80', 1, 256, 80, 9, 9, 3, 1, 1)]
+               ('1x1_s1', 2, 256, 128, 7, 9, 1, 1, 0), ('3x3_s1_pad80', 1, 256, 80, 9, 9, 3, 1, 1),
+               # 256 output channels on a strided data gradient: the general-gather kernel's two 256-cout tiles (forced rows 1, 2)
+               ('3x3_s2_c256', 1, 256, 64, 13, 21, 3, 2, 1)]
 
 
 @pytest.mark.parametrize('force', [0, 1, 2, 3, 4, 5, 6, 7, 8, 15])

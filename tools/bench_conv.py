@@ -46,12 +46,11 @@ def bench(name, ci, co, k, s, sizes_in):
     import ctypes as C
     res = [f'{name:28s}']
     for force in FORCE:
-        bco = {1: 256, 2: 256, 3: 128, 4: 128, 5: 64, 6: 128, 7: 64, 8: 64, 9: 256, 10: 256}.get(force & 15)
-        if bco and co % bco:
-            res.append(f'f{force}: n/a')
-            continue
         dfw = ops.conv_desc(x, w, y, n=N, grid=sizes_out, src_hw=sizes_in, dst_hw=sizes_out, cs=ci, cd=co, cd_pad=co,
                             ldd=co, kh=k, kw=k, stride=s, pad=p, flags=L.CONV_RELU_OUT | ((force & 15) << 8), workspace=WS if force < 16 else None)
+        if 1 <= (force & 15) <= 14 and (force & 15) not in ops.conv_forced_rows(dfw):      # no such row, or it does not divide cout
+            res.append(f'f{force}: n/a')
+            continue
         t_f = timeit(lambda: L.lib.dsl_conv2d(C.byref(dfw), L.stream_ptr()))
         res.append(f'f{force}: {t_f*1e6:6.1f}us {flops/t_f/1e12:5.0f}TF')
     if s == 1:

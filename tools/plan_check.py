@@ -9,7 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
 from dsl_amd import _lib as L
-from dsl_amd import detectors  # noqa: F401
+from dsl_amd import detectors, ops  # noqa: F401
 from dsl_amd.optim import FlatSGD
 from dsl_amd.registry import build_detector
 
@@ -59,7 +59,7 @@ for lname, ol in lists:
         t0 = timeit(op)
         best = (t0, 0, 0)
         alts = []
-        for cfg in range(1, 9):
+        for cfg in ops.conv_forced_rows(d):
             for sp in (1, 2, 4, 8):
                 d.flags = (f0 & ~0xff00) | (cfg << 8) | ((sp if sp > 1 else 0) << 12)
                 t = timeit(op, reps=6)
