@@ -111,12 +111,20 @@ class FcosDesc(C.Structure):
                 ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p), ('g_ctr', C.c_void_p), ('ld_gctr', C.c_int32),
                 # loss family, read with HEAD_LOSS_EXT only (all zero = the default head's terms)
                 ('box_kind', C.c_int32), ('box_eps', C.c_float), ('focal_gamma', C.c_float), ('focal_alpha', C.c_float),
-                ('w_cls', C.c_float), ('w_bbox', C.c_float), ('w_ctr', C.c_float)]
+                ('w_cls', C.c_float), ('w_bbox', C.c_float), ('w_ctr', C.c_float),
+                ('atss', C.c_void_p)]      # const dsl_atss_desc*, read with HEAD_ATSS only
+
+
+class AtssDesc(C.Structure):      # dsl_atss_desc: what an ATSS head adds to dsl_fcos_desc / dsl_det_desc
+    _fields_ = [('topk', C.c_int32), ('max_gt', C.c_int32), ('anchor_scale', C.c_float), ('delta_stds', C.c_float * 4),
+                ('pad_shapes', C.c_void_p), ('npos', C.c_void_p)]
 
 
 # dsl_fcos_desc.head_flags / dsl_det_desc.head_flags (0 = the fcos_semi "tricks" head)
 HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
 HEAD_LOSS_EXT = 16      # dsl_fcos_desc only: box_kind .. w_ctr are set
+HEAD_ATSS = 32          # ATSSHead: anchor-delta decode, ATSS targets and normalisers; the descriptor's `atss` is set
+ATSS_MAX_TOPK = 16
 BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_DIOU, BOX_CIOU = range(5)      # DSL_BOX_*: dsl_fcos_desc.box_kind
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
@@ -135,6 +143,10 @@ class DetDesc(C.Structure):
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
                 ('head_flags', C.c_int32), ('ld_ctr', C.c_int32), ('ctr', C.c_void_p),
                 ('nms_method', C.c_int32), ('soft_sigma', C.c_float), ('soft_min_score', C.c_float)]
+
+
+class DetAtssDesc(C.Structure):      # dsl_det_atss_desc: the detection descriptor of an ATSS head (HEAD_ATSS in det.head_flags)
+    _fields_ = [('det', DetDesc), ('atss', C.c_void_p)]
 
 
 class PackItem(C.Structure):
@@ -281,7 +293,7 @@ _SIGS = {
     'dsl_rec_sum_multi': [_vp, _i, _i, _vp],
     'dsl_groupnorm_relu_fwd': [_vp, _vp], 'dsl_groupnorm_relu_bwd': [_vp, _vp], 'dsl_groupnorm_workspace_bytes': [_vp],
     'dsl_sum2x2': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], 'dsl_colsum': [_vp, _vp, _l, _i, _i, _vp],
-    'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
+    'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_atss_assign': [_vp, _vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
     'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],

@@ -15,6 +15,10 @@
 // Soft-NMS (dsl_det_desc.nms_method != 0; mmcv's batched_nms with type='soft_nms', stated by the reference's
 // mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127) replaces the suppression stage of all three entry points: det_soft_kernel runs the
 // pick / decay loop per (image, class), det_soft_final_kernel pools the picks and keeps the best max_per_img.
+//
+// ATSSHead (DSL_HEAD_ATSS in head_flags, the descriptor then being a dsl_det_atss_desc; ATSSHead._get_bboxes,
+// mmdet/models/dense_heads/atss_head.py:420-495): det_decode decodes anchor deltas (delta2bbox,
+// core/bbox/coder/delta_xywh_bbox_coder.py:144-269, clipped to img_shape) instead of distances; every stage behind it is shared.
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -32,6 +36,8 @@ struct DetK {
   const float* rc; int ld_rc;
   const float* ctr; int ld_ctr;      // centerness logit of location m: ctr[m * ld_ctr] (column 4 of rc, or the classification predictor's)
   int exp_decode;                    // norm_on_bbox=False: exp(scale x), no stride multiply (fcos_head.py:162-167)
+  int atss;                          // DSL_HEAD_ATSS: delta2bbox against the location's anchor (atss_head.py:420-495)
+  float anchor_scale, stds[4];
   const float* scales; const float* img_shapes; const float* scale_factors;
   float* dets; long long* det_labels; int* det_count;
   // workspace
@@ -258,10 +264,24 @@ __device__ __forceinline__ void det_decode(const DetK& p, int img, int lvl, int 
   const int y = loc / p.w[lvl], x = loc - y * p.w[lvl];
   const float px = (float)x * (float)s + (float)(s / 2), py = (float)y * (float)s + (float)(s / 2);
   const float sc = p.scales[lvl];
+  const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
+  if (p.atss) {
+    // anchor centre (x s, y s), side a = anchor_scale * s; delta2bbox with max_shape = img_shape (delta_xywh_bbox_coder.py:209-269):
+    // d = scale * x * stds, dw / dh clamped to +-|log(16 / 1000)|
+    const float mr = 4.135166556742356f;
+    const float a = p.anchor_scale * (float)s;
+    const float d0 = rc[0] * sc * p.stds[0], d1 = rc[1] * sc * p.stds[1], d2 = rc[2] * sc * p.stds[2], d3 = rc[3] * sc * p.stds[3];
+    const float gw = a * expf(fminf(fmaxf(d2, -mr), mr)), gh = a * expf(fminf(fmaxf(d3, -mr), mr));
+    const float gx = (float)x * (float)s + a * d0, gy = (float)y * (float)s + a * d1;
+    b[0] = fminf(fmaxf(gx - gw * 0.5f, 0.f), W);
+    b[1] = fminf(fmaxf(gy - gh * 0.5f, 0.f), H);
+    b[2] = fminf(fmaxf(gx + gw * 0.5f, 0.f), W);
+    b[3] = fminf(fmaxf(gy + gh * 0.5f, 0.f), H);
+    return;
+  }
   float d[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) d[e] = p.exp_decode ? expf(rc[e] * sc) : fmaxf(rc[e] * sc, 0.f) * (float)s;      // fcos_head.py:159-167 (eval)
-  const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
   b[0] = px - d[0]; b[1] = py - d[1]; b[2] = px + d[2]; b[3] = py + d[3];
   b[0] = fminf(fmaxf(b[0], 0.f), W);                    // distance2bbox clip (transforms.py:150-160)
   b[1] = fminf(fmaxf(b[1], 0.f), H);
@@ -859,6 +879,16 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
   k.cls = d->cls_logits; k.ld_cls = d->ld_cls; k.rc = d->regctr; k.ld_rc = d->ld_rc;
   k.ctr = d->ctr ? d->ctr : d->regctr + 4; k.ld_ctr = d->ctr ? d->ld_ctr : d->ld_rc;
   k.exp_decode = (d->head_flags & DSL_HEAD_EXP_DECODE) ? 1 : 0;
+  if (d->head_flags & DSL_HEAD_ATSS) {
+    const dsl_atss_desc* a = reinterpret_cast<const dsl_det_atss_desc*>(d)->atss;      // the flag says: d is a dsl_det_atss_desc's first member
+    DSL_CHECK(a && a->anchor_scale > 0.f && a->anchor_scale < 1e30f, "%s: DSL_HEAD_ATSS needs a dsl_det_atss_desc whose atss has anchor_scale > 0", who);
+    DSL_CHECK(!k.exp_decode && !d->ctr, "%s: DSL_HEAD_ATSS goes with no other decode flag and centerness on the regression tower", who);
+    k.atss = 1; k.anchor_scale = a->anchor_scale;
+    for (int e = 0; e < 4; ++e) {
+      DSL_CHECK(a->delta_stds[e] > 0.f && a->delta_stds[e] < 1e30f, "%s: delta_stds must be finite and > 0", who);
+      k.stds[e] = a->delta_stds[e];
+    }
+  }
   k.scales = d->scales; k.img_shapes = d->img_shapes; k.scale_factors = d->scale_factors;
   k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;
   unsigned char* ws = (unsigned char*)d->workspace;

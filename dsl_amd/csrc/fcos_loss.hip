@@ -21,6 +21,12 @@
 // -+alpha q^gamma (gamma p sp + q), which has no q^(gamma-1) and is finite where the reference's autograd returns NaN (gamma < 1 with
 // a sigmoid saturated to exactly 0 or 1; the kernel returns the limit, 0).
 //
+// ATSS (DSL_HEAD_ATSS, uniform per launch): dsl_atss_assign restates mmdet/core/bbox/assigners/atss_assigner.py:66-178 over the
+// anchors of core/anchor/anchor_generator.py:99-143,287-412 (one square anchor per location, valid flags with allowed_border = -1) and
+// the target step of mmdet/models/dense_heads/atss_head.py:569-684; the loss_kernel<., true, true> instantiation restates
+// atss_head.py:142-215,268-309 with delta2bbox of core/bbox/coder/delta_xywh_bbox_coder.py:144-266.  Tie rules and the two deliberate
+// simplifications (the stored ground-truth box stands for decode(encode(gt))) are stated in include/dsl_hip.h and at their sites.
+//
 // The assignment must be BIT-identical to the reference's fp32 torch arithmetic, so this file is
 // compiled with floating-point contraction off and the comparisons are written exactly as there.
 #include "common.hpp"
@@ -51,6 +57,12 @@ struct FcK {
   // loss family (loss_kernel<., true> only): DSL_BOX_*, eps of DIoU / CIoU, focal gamma / alpha, the three loss weights
   int box_kind;
   float box_eps, gamma, alpha, w_cls, w_bbox, w_ctr;
+  // ATSS (DSL_HEAD_ATSS: the atss_* kernels and loss_kernel<., true, true> only)
+  float anchor_scale, stds[4];
+  int topk;
+  const int* pad_shapes;            // [n][2] (pad_h, pad_w)
+  unsigned long long* akeys;        // [M] (IoU bits << 32 | ~gt index) of the winning box, 0 = none (workspace)
+  int* npos;                        // [n] positives per image
 };
 
 __device__ __forceinline__ void decode_loc(const FcK& p, int m, int& lvl, int& img, int& y, int& x) {
@@ -160,8 +172,186 @@ __global__ __launch_bounds__(256) void assign_kernel(const FcK p) {
   }
 }
 
+// ---- ATSS assignment (atss_assigner.py:66-178, atss_head.py:569-684; semantics and tie rules: include/dsl_hip.h) ---------------
+constexpr int ATSS_T = 256;
+constexpr int ATSS_MAXC = DSL_MAX_SEG * DSL_ATSS_MAX_TOPK;
+constexpr float kMaxRatio = 4.135166556742356f;      // |log(16 / 1000)|, wh_ratio_clip of delta2bbox (delta_xywh_bbox_coder.py:227)
+
+// the anchor of location (x, y): AnchorGenerator's base anchor [-0.5 ws, 0.5 ws] (center_offset 0) shifted by (x s, y s)
+// (anchor_generator.py:99-143,287-352)
+__device__ __forceinline__ void atss_anchor(const FcK& p, int lvl, int x, int y, float a[4]) {
+  const float s = (float)p.stride[lvl];
+  const float hw = 0.5f * (s * p.anchor_scale);
+  const float sx = (float)x * s, sy = (float)y * s;
+  a[0] = sx + (0.f - hw); a[1] = sy + (0.f - hw); a[2] = sx + hw; a[3] = sy + hw;
+}
+
+// valid extent of a level in image img: valid_flags with allowed_border = -1 (anchor_generator.py:354-412)
+__device__ __forceinline__ void atss_valid(const FcK& p, int lvl, int img, int& vh, int& vw) {
+  const int s = p.stride[lvl];
+  const int ph = p.pad_shapes[2 * img], pw = p.pad_shapes[2 * img + 1];
+  vh = min(max((ph + s - 1) / s, 0), p.h[lvl]);
+  vw = min(max((pw + s - 1) / s, 0), p.w[lvl]);
+}
+
+// BboxOverlaps2D, mode 'iou' (iou2d_calculator.py:212-260)
+__device__ __forceinline__ float atss_iou(const float a[4], float x1, float y1, float x2, float y2) {
+  const float a1 = (a[2] - a[0]) * (a[3] - a[1]), a2 = (x2 - x1) * (y2 - y1);
+  const float w = fmaxf(fminf(a[2], x2) - fmaxf(a[0], x1), 0.f), h = fmaxf(fminf(a[3], y2) - fmaxf(a[1], y1), 0.f);
+  const float ov = w * h;
+  return ov / fmaxf(a1 + a2 - ov, 1e-6f);
+}
+
+__global__ __launch_bounds__(ATSS_T) void atss_zero_kernel(const FcK p) {
+  const int M = p.mstart[p.nlvl];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < M) p.akeys[i] = 0ull;
+  if (i < p.n) p.npos[i] = 0;
+}
+
+// One workgroup per ground-truth box: its candidates level by level (topk rounds of "the smallest (distance, index) above the last
+// one" over every valid anchor of the level), the IoU threshold, and the positives' claims on their anchors.
+__global__ __launch_bounds__(ATSS_T) void atss_cand_kernel(const FcK p) {
+  __shared__ unsigned long long red[ATSS_T];
+  __shared__ int c_idx[ATSS_MAXC], c_lvl[ATSS_MAXC];
+  __shared__ float c_iou[ATSS_MAXC];
+  __shared__ float s_thr;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (g >= p.gt_off[p.n]) return;
+  int img = 0;
+  for (int i = 1; i < p.n; ++i)
+    if (g >= p.gt_off[i]) img = i;
+  const float x1 = p.gt_boxes[4 * g], y1 = p.gt_boxes[4 * g + 1], x2 = p.gt_boxes[4 * g + 2], y2 = p.gt_boxes[4 * g + 3];
+  const float gcx = (x1 + x2) / 2.0f, gcy = (y1 + y2) / 2.0f;
+  int ncand = 0;
+  for (int lvl = 0; lvl < p.nlvl; ++lvl) {
+    int vh, vw;
+    atss_valid(p, lvl, img, vh, vw);
+    const int nvalid = vh * vw, W = p.w[lvl];
+    const int k = min(p.topk, nvalid);
+    unsigned long long last = 0ull;
+    for (int r = 0; r < k; ++r) {
+      unsigned long long best = ~0ull;
+      for (int i = tid; i < nvalid; i += ATSS_T) {
+        const int y = i / vw, x = i - y * vw;
+        float a[4];
+        atss_anchor(p, lvl, x, y, a);
+        const float dx = (a[0] + a[2]) / 2.0f - gcx, dy = (a[1] + a[3]) / 2.0f - gcy;
+        const float d = sqrtf(dx * dx + dy * dy);
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)(y * W + x);
+        if ((r == 0 || key > last) && key < best) best = key;
+      }
+      red[tid] = best;
+      __syncthreads();
+      for (int o = ATSS_T / 2; o > 0; o >>= 1) {
+        if (tid < o && red[tid + o] < red[tid]) red[tid] = red[tid + o];
+        __syncthreads();
+      }
+      last = red[0];
+      __syncthreads();
+      if (tid == 0) {
+        c_idx[ncand + r] = (int)(unsigned)last;
+        c_lvl[ncand + r] = lvl;
+      }
+    }
+    ncand += k;
+  }
+  __syncthreads();
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  int m = 0;
+  if (tid < ncand) {
+    const int lvl = c_lvl[tid], W = p.w[lvl];
+    const int y = c_idx[tid] / W, x = c_idx[tid] - y * W;
+    atss_anchor(p, lvl, x, y, a);
+    m = p.mstart[lvl] + (img * p.h[lvl] + y) * W + x;
+    c_iou[tid] = atss_iou(a, x1, y1, x2, y2);
+  }
+  __syncthreads();
+  if (tid == 0) {      // mean + unbiased std, in (level, rank) order (atss_assigner.py:131-134)
+    float sum = 0.f;
+    for (int c = 0; c < ncand; ++c) sum += c_iou[c];
+    const float mean = sum / (float)ncand;
+    float ss = 0.f;
+    for (int c = 0; c < ncand; ++c) ss += (c_iou[c] - mean) * (c_iou[c] - mean);
+    s_thr = mean + sqrtf(ss / (float)(ncand - 1));      // one candidate: 0 / 0 = NaN, no positive (torch.std of one element)
+  }
+  __syncthreads();
+  if (tid < ncand) {
+    const float cx = (a[0] + a[2]) / 2.0f, cy = (a[1] + a[3]) / 2.0f;
+    const float inside = fminf(fminf(cx - x1, cy - y1), fminf(x2 - cx, y2 - cy));
+    const float iou = c_iou[tid];
+    if (iou >= s_thr && inside > 0.01f)      // the highest IoU wins an anchor, equal IoUs the lower box (atss_assigner.py:156-166)
+      atomicMax(p.akeys + m, ((unsigned long long)__float_as_uint(iou) << 32) | (unsigned)~(unsigned)(g - p.gt_off[img]));
+  }
+}
+
+// one thread per anchor: the outputs of dsl_fcos_assign from the winning claim; block records [positives, centerness targets]
+__global__ __launch_bounds__(ATSS_T) void atss_write_kernel(const FcK p) {
+  __shared__ float sh[16];
+  const int M = p.mstart[p.nlvl];
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  float is_pos = 0.f, ctr = 0.f;
+  if (m < M) {
+    int lvl, img, y, x, vh, vw;
+    decode_loc(p, m, lvl, img, y, x);
+    atss_valid(p, lvl, img, vh, vw);
+    const bool valid = y < vh && x < vw;
+    const unsigned long long key = p.akeys[m];
+    long long label = p.num_classes;
+    int aidx = -1;
+    f32x4 t = {0.f, 0.f, 0.f, 0.f};
+    if (valid && key != 0ull) {
+      aidx = (int)~(unsigned)key;
+      const int g = p.gt_off[img] + aidx;
+      label = p.gt_labels[g];
+      t = *reinterpret_cast<const f32x4*>(p.gt_boxes + 4ll * g);
+      float a[4];
+      atss_anchor(p, lvl, x, y, a);
+      // centerness target (atss_head.py:293-309) from the anchor centre and the ground-truth box itself; the reference uses
+      // decode(encode(gt)), which differs from gt by rounding only
+      const float cx = (a[2] + a[0]) / 2, cy = (a[3] + a[1]) / 2;
+      const float l = cx - t[0], tp = cy - t[1], r = t[2] - cx, b = t[3] - cy;
+      ctr = sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(tp, b) / fmaxf(tp, b)));
+      is_pos = 1.f;
+      atomicAdd(p.npos + img, 1);
+    }
+    p.labels[m] = label;
+    p.assign_idx[m] = aidx;
+    *reinterpret_cast<f32x4*>(p.bbox_targets + 4ll * m) = t;
+    p.cls_weight[m] = valid ? 1.f : 0.f;
+    p.pos_weight[m] = 1.f;
+  }
+  const float np = block_sum(is_pos, sh);
+  const float cs = block_sum(ctr, sh);
+  if (threadIdx.x == 0) {
+    p.part[2 * blockIdx.x] = np;
+    p.part[2 * blockIdx.x + 1] = cs;
+  }
+}
+
+// stats[0] = sum_i max(npos_i, 1) (atss_head.py:554), stats[1] = the block records' centerness sums in block order, stats[2..7] = 0
+__global__ __launch_bounds__(ATSS_T) void atss_finalize_kernel(const FcK p, int nblocks) {
+  __shared__ float sh[ATSS_T];
+  float a = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += ATSS_T) a += p.part[2 * b + 1];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < ATSS_T; ++k) t += sh[k];
+    int tot = 0;
+    for (int i = 0; i < p.n; ++i) tot += max(p.npos[i], 1);
+    p.stats[0] = (float)tot;
+    p.stats[1] = t;
+  } else if (threadIdx.x < 8 && threadIdx.x >= 2) {
+    p.stats[threadIdx.x] = 0.f;
+  }
+}
+
 // fixed-order sum of per-block records: out[v] = sum_b part[b * V + v] * scale(v); one workgroup
 constexpr int FIN_T = 256;
+// kAtss: loss_bbox's normaliser is clamped at 1 (atss_head.py:286), not at 1e-6
+template <bool kAtss = false>
 __global__ __launch_bounds__(FIN_T) void fcos_finalize_kernel(const float* __restrict__ part, int nblocks, int V, float* out0,
                                                               int n0, float* out1, const float* norm, float inv_world,
                                                               float soft_weight, int mode, float* logvec = nullptr,
@@ -181,7 +371,7 @@ __global__ __launch_bounds__(FIN_T) void fcos_finalize_kernel(const float* __res
     float t = 0.f;
     for (int k = 0; k < Q; ++k) t += sh[k * V + threadIdx.x];
     if (mode == 1) {           // loss records: [cls, sisoft, bbox, centerness, g_scale x 5] -> losses[4] + g_scales[5]
-      const float num_pos = fmaxf(norm[0] * inv_world, 1.0f), denorm = fmaxf(norm[1] * inv_world, 1e-6f);
+      const float num_pos = fmaxf(norm[0] * inv_world, 1.0f), denorm = fmaxf(norm[1] * inv_world, kAtss ? 1.0f : 1e-6f);
       float fv = t;
       // (loss_weight * the mean, as the loss modules do; a weight of 1 leaves the bits as they are)
       if (threadIdx.x == 0) out0[0] = fv = t / num_pos * w_cls;
@@ -355,14 +545,16 @@ __device__ __forceinline__ float box_loss_ext(int kind, float eps, float x1, flo
 // sisoft term and write 0 into g_cls; for C % 4 == 0 the kTail = false instantiation is the only one launched.
 // kExt: the loss family (box kind, focal gamma / alpha, loss weights); kExt = false is the default head's kernel, which reads none
 // of those fields.
-template <bool kTail, bool kExt>
+// kAtss (with kExt): DSL_HEAD_ATSS - delta2bbox decode against the location's anchor, the stored ground-truth box as target, the
+// normaliser of loss_bbox clamped at 1 (atss_head.py:142-215,268-287); the kAtss = false instantiations are the FCOS kernels, unchanged.
+template <bool kTail, bool kExt, bool kAtss = false>
 __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
   __shared__ float sh[16];
   const int M = p.mstart[p.nlvl];
   const int C = p.num_classes;
   const int c4 = kTail ? (C + 3) / 4 : C / 4;
   const float num_pos = fmaxf(p.norm[0] * p.inv_world, 1.0f);
-  const float denorm = fmaxf(p.norm[1] * p.inv_world, 1e-6f);
+  const float denorm = fmaxf(p.norm[1] * p.inv_world, kAtss ? 1.0f : 1e-6f);
   const bool sisoft = (p.soft_weight != 0.f) && (p.n % 2 != 0) && p.n >= 3;
 
   // ---------------- classification: one thread per 4 consecutive classes of one location ----------
@@ -445,14 +637,32 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
       for (int k = 0; k < 4; ++k) {
         raw[k] = rc[k];
         const float z = raw[k] * sc;
-        d[k] = exp_dec ? expf(z) : fmaxf(z, 0.f);      // fcos_head.py:162-167
+        if constexpr (kAtss) d[k] = z * p.stds[k];      // denorm_deltas = deltas * stds + means, means 0 (delta_xywh_bbox_coder.py:209)
+        else d[k] = exp_dec ? expf(z) : fmaxf(z, 0.f);      // fcos_head.py:162-167
       }
       const f32x4 t = *reinterpret_cast<const f32x4*>(p.bbox_targets + 4ll * m);
       const float pw = p.pos_weight[m];
-      const float ct = sqrtf((fminf(t[0], t[2]) / fmaxf(t[0], t[2])) * (fminf(t[1], t[3]) / fmaxf(t[1], t[3])));
-      // decode (distance2bbox, core/bbox/transforms.py:119-162; no clip in training)
-      const float x1 = px - d[0], y1 = py - d[1], x2 = px + d[2], y2 = py + d[3];
-      const float X1 = px - t[0], Y1 = py - t[1], X2 = px + t[2], Y2 = py + t[3];
+      float ct, x1, y1, x2, y2, X1, Y1, X2, Y2;
+      float aw = 0.f, gw = 0.f, gh = 0.f;      // kAtss: anchor side, decoded width / height
+      if constexpr (kAtss) {
+        // the anchor's centre (x s, y s) and side a = anchor_scale * s; delta2bbox (delta_xywh_bbox_coder.py:209-246), no clip in training
+        const float acx = (float)x * (float)s, acy = (float)y * (float)s;
+        aw = p.anchor_scale * (float)s;
+        gw = aw * expf(fminf(fmaxf(d[2], -kMaxRatio), kMaxRatio));
+        gh = aw * expf(fminf(fmaxf(d[3], -kMaxRatio), kMaxRatio));
+        const float gx = acx + aw * d[0], gy = acy + aw * d[1];
+        x1 = gx - gw * 0.5f; y1 = gy - gh * 0.5f; x2 = gx + gw * 0.5f; y2 = gy + gh * 0.5f;
+        // target: the stored ground-truth box.  The reference decodes encode(gt) (atss_head.py:194-195), which differs from gt by
+        // rounding only; the centerness target (:293-309) likewise, from the anchor centre
+        X1 = t[0]; Y1 = t[1]; X2 = t[2]; Y2 = t[3];
+        const float l = acx - X1, tp = acy - Y1, r = X2 - acx, b = Y2 - acy;
+        ct = sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(tp, b) / fmaxf(tp, b)));
+      } else {
+        ct = sqrtf((fminf(t[0], t[2]) / fmaxf(t[0], t[2])) * (fminf(t[1], t[3]) / fmaxf(t[1], t[3])));
+        // decode (distance2bbox, core/bbox/transforms.py:119-162; no clip in training)
+        x1 = px - d[0]; y1 = py - d[1]; x2 = px + d[2]; y2 = py + d[3];
+        X1 = px - t[0]; Y1 = py - t[1]; X2 = px + t[2]; Y2 = py + t[3];
+      }
       const float wb = ct * pw;
       float dbox[4];
       if (kExt && p.box_kind >= DSL_BOX_IOU_LINEAR) {
@@ -515,12 +725,25 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
           for (int k = 0; k < 4; ++k) dbox[k] *= p.w_bbox;
         }
       }
-      const float dd[4] = {-dbox[0], -dbox[1], dbox[2], dbox[3]};   // x1 = px - d0, ... x2 = px + d2
+      if constexpr (kAtss) {
+        // x1 = gx - gw / 2, x2 = gx + gw / 2 with gx = acx + a d0, gw = a exp(clamp(d2)): no gradient through an active clamp
+        // (torch.clamp passes it on the closed interval), then d[k] = scale * raw[k] * stds[k]
+        const float dz[4] = {(dbox[0] + dbox[2]) * aw, (dbox[1] + dbox[3]) * aw,
+                             (d[2] >= -kMaxRatio && d[2] <= kMaxRatio) ? 0.5f * (dbox[2] - dbox[0]) * gw : 0.f,
+                             (d[3] >= -kMaxRatio && d[3] <= kMaxRatio) ? 0.5f * (dbox[3] - dbox[1]) * gh : 0.f};
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float on = exp_dec ? d[k] : ((raw[k] * sc > 0.f) ? 1.f : 0.f);     // d exp(z) / dz = exp(z); relu's gate
-        gr[k] = dd[k] * on * sc;
-        gsc[lvl] += dd[k] * on * raw[k];
+        for (int k = 0; k < 4; ++k) {
+          gr[k] = dz[k] * p.stds[k] * sc;
+          gsc[lvl] += dz[k] * p.stds[k] * raw[k];
+        }
+      } else {
+        const float dd[4] = {-dbox[0], -dbox[1], dbox[2], dbox[3]};   // x1 = px - d0, ... x2 = px + d2
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float on = exp_dec ? d[k] : ((raw[k] * sc > 0.f) ? 1.f : 0.f);     // d exp(z) / dz = exp(z); relu's gate
+          gr[k] = dd[k] * on * sc;
+          gsc[lvl] += dd[k] * on * raw[k];
+        }
       }
       // centerness BCE-with-logits (cross_entropy_loss.py:73-112)
       const float cl = p.ctr[(long long)m * p.ld_ctr];
@@ -598,8 +821,24 @@ int fill(const dsl_fcos_desc* d, FcK& k) {
     k.w_cls = d->w_cls; k.w_bbox = d->w_bbox; k.w_ctr = d->w_ctr;
     k.flags = (k.flags & ~DSL_HEAD_IOU_LOSS) | (k.box_kind == DSL_BOX_IOU_LOG ? DSL_HEAD_IOU_LOSS : 0);
   }
+  if (k.flags & DSL_HEAD_ATSS) {
+    const dsl_atss_desc* a = d->atss;
+    DSL_CHECK(a, "fcos: DSL_HEAD_ATSS needs dsl_fcos_desc.atss");
+    DSL_CHECK(a->anchor_scale > 0.f && a->anchor_scale < 1e30f, "atss: anchor_scale must be finite and > 0");
+    for (int e = 0; e < 4; ++e) {
+      DSL_CHECK(a->delta_stds[e] > 0.f && a->delta_stds[e] < 1e30f, "atss: delta_stds must be finite and > 0");
+      k.stds[e] = a->delta_stds[e];
+    }
+    DSL_CHECK((k.flags & (DSL_HEAD_INSIDE_BOX | DSL_HEAD_RAW_TARGETS | DSL_HEAD_EXP_DECODE)) == 0 && !d->ctr,
+              "atss: DSL_HEAD_ATSS goes with no other assignment / decode flag and centerness on the regression tower");
+    DSL_CHECK(d->loss_weight == 1.0f && d->soft_weight == 0.f, "atss: no DSL stream weight / sisoft term");
+    k.anchor_scale = a->anchor_scale;
+  }
   return 0;
 }
+
+// ATSS workspace: the block records of atss_write_kernel, then one 64-bit claim per anchor
+size_t atss_assign_bytes(long long M) { return ((size_t)((M + ATSS_T - 1) / ATSS_T) * 2 * sizeof(float) + 15) / 16 * 16 + (size_t)M * 8; }
 
 // the default head's loss terms (GIoU or the IoU log loss, gamma 2, alpha 0.25, weights 1): the kExt = false kernel computes them
 bool loss_is_default(const FcK& k) {
@@ -613,7 +852,9 @@ extern "C" size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d) {
   long long M = 0;
   for (int l = 0; l < d->nlvl; ++l) M += (long long)d->n * d->h[l] * d->w[l];
   const size_t assign_rec = (size_t)((M + 255) / 256) * 2, loss_rec = 2048 * 16;
-  return (assign_rec > loss_rec ? assign_rec : loss_rec) * sizeof(float);
+  const size_t need = (assign_rec > loss_rec ? assign_rec : loss_rec) * sizeof(float);
+  if (d->head_flags & DSL_HEAD_ATSS) return need > atss_assign_bytes(M) ? need : atss_assign_bytes(M);
+  return need;
 }
 
 extern "C" int dsl_fcos_points(const dsl_fcos_desc* d, float* points, void* stream) {
@@ -633,15 +874,41 @@ extern "C" int dsl_fcos_assign(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(d->gt_boxes && d->gt_labels && d->gt_off && d->labels && d->bbox_targets && d->assign_idx &&
                 d->cls_weight && d->pos_weight && d->stats,
             "dsl_fcos_assign: null pointer");
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_ATSS), "dsl_fcos_assign: a DSL_HEAD_ATSS descriptor is assigned by dsl_atss_assign");
   hipStream_t st = (hipStream_t)stream;
   const int M = k.mstart[k.nlvl];
   const int nb = (M + 255) / 256;
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d), "dsl_fcos_assign: workspace too small");
   hipLaunchKernelGGL(assign_kernel, dim3(nb), dim3(256), 0, st, k);
   // stats[0] = num_pos, stats[1] = sum of centerness targets (this rank), stats[2..7] = 0: block records added in block order
-  hipLaunchKernelGGL(fcos_finalize_kernel, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, nb, 2, d->stats, 2, (float*)nullptr,
+  hipLaunchKernelGGL(fcos_finalize_kernel<false>, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, nb, 2, d->stats, 2, (float*)nullptr,
                      (const float*)nullptr, 1.f, 0.f, 0);
   DSL_LAUNCH_CHECK("assign_kernel");
+  return 0;
+}
+
+extern "C" int dsl_atss_assign(const dsl_fcos_desc* d, const dsl_atss_desc* a, void* stream) {
+  FcK k;
+  DSL_CHECK(d && a && d->atss == a && (d->head_flags & DSL_HEAD_ATSS), "dsl_atss_assign: DSL_HEAD_ATSS and d->atss == a are required");
+  if (fill(d, k)) return -1;
+  DSL_CHECK(d->gt_boxes && d->gt_labels && d->gt_off && d->labels && d->bbox_targets && d->assign_idx && d->cls_weight &&
+                d->pos_weight && d->stats && a->pad_shapes && a->npos,
+            "dsl_atss_assign: null pointer");
+  DSL_CHECK(a->topk >= 1 && a->topk <= DSL_ATSS_MAX_TOPK, "dsl_atss_assign: topk must be in 1..16");
+  DSL_CHECK(a->max_gt >= 1 && a->max_gt <= 65535, "dsl_atss_assign: max_gt must be in 1..65535");
+  DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d) && ((uintptr_t)d->workspace & 15) == 0,
+            "dsl_atss_assign: workspace too small or not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int M = k.mstart[k.nlvl];
+  const int nb = (M + ATSS_T - 1) / ATSS_T;
+  k.topk = a->topk; k.pad_shapes = a->pad_shapes; k.npos = a->npos;
+  k.akeys = (unsigned long long*)((char*)d->workspace + (atss_assign_bytes(M) - (size_t)M * 8));
+  const int nz = (M > d->n ? M : d->n);
+  hipLaunchKernelGGL(atss_zero_kernel, dim3((nz + ATSS_T - 1) / ATSS_T), dim3(ATSS_T), 0, st, k);
+  hipLaunchKernelGGL(atss_cand_kernel, dim3(a->max_gt), dim3(ATSS_T), 0, st, k);
+  hipLaunchKernelGGL(atss_write_kernel, dim3(nb), dim3(ATSS_T), 0, st, k);
+  hipLaunchKernelGGL(atss_finalize_kernel, dim3(1), dim3(ATSS_T), 0, st, k, nb);
+  DSL_LAUNCH_CHECK("atss_assign");
   return 0;
 }
 
@@ -661,6 +928,16 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   const bool tail = d->num_classes % 4 != 0;
   int blocks = (int)(((long long)M * ((d->num_classes + 3) / 4) + 255) / 256);
   if (blocks > 2048) blocks = 2048;
+  if (k.flags & DSL_HEAD_ATSS) {      // (always the loss family's kernel: with the default settings it computes the default terms)
+    if (tail)
+      hipLaunchKernelGGL((loss_kernel<true, true, true>), dim3(blocks), dim3(256), 0, st, k);
+    else
+      hipLaunchKernelGGL((loss_kernel<false, true, true>), dim3(blocks), dim3(256), 0, st, k);
+    hipLaunchKernelGGL(fcos_finalize_kernel<true>, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
+                       DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec, k.w_cls, k.w_bbox, k.w_ctr);
+    DSL_LAUNCH_CHECK("loss_kernel");
+    return 0;
+  }
   if (loss_is_default(k)) {
     if (tail)
       hipLaunchKernelGGL((loss_kernel<true, false>), dim3(blocks), dim3(256), 0, st, k);
@@ -672,7 +949,7 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
     else
       hipLaunchKernelGGL((loss_kernel<false, true>), dim3(blocks), dim3(256), 0, st, k);
   }
-  hipLaunchKernelGGL(fcos_finalize_kernel, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
+  hipLaunchKernelGGL(fcos_finalize_kernel<false>, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
                      DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec, k.w_cls, k.w_bbox, k.w_ctr);
   DSL_LAUNCH_CHECK("loss_kernel");
   return 0;

@@ -5,6 +5,8 @@ configs/fcos_semi/*.py build unmodified:
   ResNet                        mmdet/models/backbones/resnet.py:304-656   (depth 50, caffe, frozen BN)
   FPN                           mmdet/models/necks/fpn.py:9-202
   FCOSHead                      mmdet/models/dense_heads/fcos_head.py:14-726
+  ATSS / ATSSHead               mmdet/models/detectors/atss.py, mmdet/models/dense_heads/atss_head.py:14-684 with
+                                core/bbox/assigners/atss_assigner.py, core/anchor/anchor_generator.py, core/bbox/coder/delta_xywh_bbox_coder.py
   FocalLoss / GIoULoss / IoULoss / DIoULoss / CIoULoss / CrossEntropyLoss   mmdet/models/losses/*.py
 
 Unlike the reference these classes do not compute with torch ops: they validate the configuration
@@ -137,8 +139,9 @@ class FPN(nn.Module):
         super().__init__()
         _expect(list(in_channels) == [256, 512, 1024, 2048] and out_channels == 256 and num_outs == 5 and start_level == 1,
                 'FPN 256ch, start_level=1, 5 outputs')
-        _expect(add_extra_convs == 'on_output' and relu_before_extra_convs and norm_cfg is None and act_cfg is None,
-                "add_extra_convs='on_output', relu_before_extra_convs=True, no norm/act")
+        _expect(add_extra_convs == 'on_output' and norm_cfg is None and act_cfg is None, "add_extra_convs='on_output', no norm/act")
+        # False (the class default; configs/atss): P7 = fpn_convs[4](P6) without the ReLU in front (fpn.py:196-199)
+        self.relu_before_extra_convs = bool(relu_before_extra_convs)
         _expect(upsample_cfg.get('mode', 'nearest') == 'nearest' and 'scale_factor' not in upsample_cfg, 'nearest upsample')
 
 
@@ -286,6 +289,93 @@ class FCOSHead(nn.Module):
         return w
 
 
+def _cfg_get(cfg, key, default=None):
+    return cfg.get(key, default) if hasattr(cfg, 'get') else getattr(cfg, key, default)
+
+
+@HEADS.register_module()
+class ATSSHead(nn.Module):
+    """mmdet/models/dense_heads/atss_head.py:14-684 on AnchorHead (anchor_head.py:36-100): the FCOS network (GN-32 towers without
+    conv bias, class predictor, box predictor with centerness on the regression tower, one Scale per level) with ATSSAssigner's
+    targets (dsl_atss_assign) and DeltaXYWHBBoxCoder boxes against one square anchor per location (DSL_HEAD_ATSS).  The signature
+    is the reference's; what the kernels do not build is refused, naming the option."""
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0), init_cfg=None,
+                 feat_channels=256,
+                 anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]),
+                 bbox_coder=dict(type='DeltaXYWHBBoxCoder', clip_border=True, target_means=(.0, .0, .0, .0), target_stds=(1.0, 1.0, 1.0, 1.0)),
+                 reg_decoded_bbox=False, loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None, **kw):
+        super().__init__()
+        class_layout(num_classes)
+        for k in ('soft_weight', 'soft_warm_up', 'loss_weight'):
+            _expect(k not in kw, f'ATSSHead: no DSL key {k} (the scale-invariant soft term and the per-stream loss_weight are FCOSHead options)')
+        _expect(not kw, f'ATSSHead: unknown arguments {sorted(kw)}')
+        _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
+        _expect(stacked_convs == 4, 'stacked_convs=4')
+        _expect(conv_cfg is None, 'conv_cfg=None (no DCN)')
+        _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers (norm_cfg)')
+        _expect(not reg_decoded_bbox, 'reg_decoded_bbox=False')
+        ag = dict(anchor_generator)
+        _expect(ag.pop('type', None) == 'AnchorGenerator', "anchor_generator type='AnchorGenerator'")
+        _expect(list(ag.pop('ratios', [])) == [1.0], 'anchor_generator ratios=[1.0] (one square anchor per location)')
+        _expect(ag.pop('scales_per_octave', None) == 1 and ag.get('scales') is None, 'anchor_generator scales_per_octave=1 (no scales list)')
+        obs = ag.pop('octave_base_scale', None)
+        _expect(isinstance(obs, (int, float)) and 0.0 < float(obs) < float('inf'), f'anchor_generator octave_base_scale > 0 (got {obs!r})')
+        _expect(list(ag.pop('strides', [])) == [8, 16, 32, 64, 128], 'anchor_generator strides 8..128')
+        _expect(float(ag.pop('center_offset', 0.0)) == 0.0, 'anchor_generator center_offset=0')
+        ag.pop('scales', None)
+        _expect(ag.pop('base_sizes', None) is None and ag.pop('centers', None) is None and ag.pop('scale_major', True),
+                'anchor_generator default base_sizes / centers / scale_major')
+        _expect(not ag, f'anchor_generator: unknown arguments {sorted(ag)}')
+        bc = dict(bbox_coder)
+        _expect(bc.pop('type', None) == 'DeltaXYWHBBoxCoder', "bbox_coder type='DeltaXYWHBBoxCoder'")
+        _expect(all(float(v) == 0.0 for v in bc.pop('target_means', (0., 0., 0., 0.))), 'bbox_coder target_means all 0')
+        stds = tuple(float(v) for v in bc.pop('target_stds', (1., 1., 1., 1.)))
+        _expect(len(stds) == 4 and all(0.0 < v < float('inf') for v in stds), f'bbox_coder target_stds: four numbers > 0 (got {stds})')
+        _expect(bc.pop('clip_border', True) and not bc.pop('add_ctr_clamp', False), 'bbox_coder clip_border=True, add_ctr_clamp=False')
+        bc.pop('ctr_clamp', None)
+        _expect(not bc, f'bbox_coder: unknown arguments {sorted(bc)}')
+        topk = 9
+        if train_cfg is not None:
+            asg = dict(_cfg_get(train_cfg, 'assigner') or {})
+            _expect(asg.pop('type', None) == 'ATSSAssigner', "train_cfg.assigner type='ATSSAssigner'")
+            topk = asg.pop('topk', None)
+            _expect(isinstance(topk, int) and 1 <= topk <= 16, f'train_cfg.assigner topk in 1..16 (got {topk!r})')
+            _expect(float(asg.pop('ignore_iof_thr', -1)) <= 0, 'train_cfg.assigner ignore_iof_thr <= 0 (gt_bboxes_ignore is not read)')
+            ic = asg.pop('iou_calculator', dict(type='BboxOverlaps2D'))
+            _expect(dict(ic) == dict(type='BboxOverlaps2D'), 'train_cfg.assigner iou_calculator BboxOverlaps2D')
+            _expect(not asg, f'train_cfg.assigner: unknown arguments {sorted(asg)}')
+            _expect(_cfg_get(train_cfg, 'allowed_border', -1) == -1, 'train_cfg.allowed_border=-1')
+            _expect(_cfg_get(train_cfg, 'pos_weight', -1) <= 0, 'train_cfg.pos_weight=-1')
+        self.num_classes, self.strides = num_classes, (8, 16, 32, 64, 128)
+        self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
+        self.loss_cls = build_loss(loss_cls)
+        # GIoULoss / IoULoss keep refusing a loss_weight in their own constructors (FCOSHead's configuration surface); here the weight
+        # of configs/atss (GIoULoss(loss_weight=2.0)) is taken off the dict and goes to the kernel as dsl_fcos_desc.w_bbox
+        lb = dict(loss_bbox)
+        wb = 1.0
+        if lb.get('type') in ('GIoULoss', 'IoULoss'):
+            wb = _loss_weight(lb['type'], lb.pop('loss_weight', 1.0), lb.get('reduction', 'mean'))
+        self.loss_bbox = build_loss(lb)
+        self.loss_centerness = build_loss(loss_centerness)
+        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, (GIoULoss, IoULoss, DIoULoss))
+                and isinstance(self.loss_centerness, CrossEntropyLoss),
+                'FocalLoss + GIoULoss, IoULoss, DIoULoss or CIoULoss + CrossEntropyLoss')
+        lbm = self.loss_bbox
+        wb = wb if isinstance(lbm, (GIoULoss, IoULoss)) else lbm.loss_weight
+        self.bbox_weight = wb
+        self.options = HeadOptions(box_loss=lbm.box_loss, box_eps=lbm.eps, focal_gamma=self.loss_cls.gamma, focal_alpha=self.loss_cls.alpha,
+                                   cls_weight=self.loss_cls.loss_weight, bbox_weight=wb, ctr_weight=self.loss_centerness.loss_weight,
+                                   assigner='atss', atss_topk=topk, anchor_scale=float(obs), delta_stds=stds)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    def effective_soft_weight(self, batch_size):
+        return 0.0
+
+
 # One stream per ROLE and device for the whole process, not per model instance (round 4).  Streams are dealt onto four hardware
 # queues in creation order; which streams share a queue moves the step by up to 20 % (DESIGN 3.2i: 350 vs 427 img/s for one stream
 # created too early).  The first detector of a process creates the streams in the order the measured layout came about; every later
@@ -416,6 +506,7 @@ class FCOS(nn.Module):
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
         self.store = ParamStore(self.bbox_head.num_classes, 'cpu', backbone=getattr(self.backbone, 'backbone_kind', 'resnet'),
                                 head=self.bbox_head.options)
+        self.store.fpn_relu_extra = bool(getattr(self.neck, 'relu_before_extra_convs', True))      # engine.Plan: P7's input
         self.store.init_reference_style(0)
         if fp8:
             assert str(fp8.get('layers', 'towers')) == 'towers', "fp8: only layers='towers' is built"
@@ -621,10 +712,12 @@ class FCOS(nn.Module):
             fwd = plan.fwd
         plan.fp8_warm(fwd)
         work = None
+        # an ATSS head's valid anchors come from each image's pad_shape (atss_head.py:615-617); absent: the batch tensor's size
+        pad = [tuple(m.get('pad_shape', (H, W)))[:2] for m in img_metas] if lp.atss is not None else None
         if ws > 1:
             # target assignment first: the reduce_mean of (num_pos, sum centerness targets) - one 2-float all-reduce
             # (fcos_head.py:264-274) - then runs under the forward pass
-            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore)
+            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
             plan.assign_ops.run()
             work = None if self.comm_off else self._all_reduce_async(lp.stats[:2], after_current=True)
             fwd.run()
@@ -634,7 +727,7 @@ class FCOS(nn.Module):
             # one process: target upload + assignment go behind the forward pass on the caller's stream, into the time it
             # would otherwise spend waiting for the regression tower on the side stream
             fwd.run()
-            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore)
+            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
             plan.assign_ops.run()
         plan.loss_ops.run()
         eager_now = False
@@ -894,3 +987,13 @@ class FCOS(nn.Module):
 
     def val_step(self, data, optimizer=None):
         return self.train_step(data, optimizer)
+
+
+@DETECTORS.register_module()
+class ATSS(FCOS):
+    """mmdet/models/detectors/atss.py:5-18: SingleStageDetector with an ATSSHead, on the FCOS detector's machinery (the same
+    network; assignment, box decode and loss normalisers are the head's)."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
+        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'ATSSHead', "ATSS with bbox_head type='ATSSHead'")
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)

@@ -144,8 +144,9 @@ class OpList:
     def gn_bwd(self, d, side=False):
         self._add(L.OP_GN_BWD, d, i=(0, 0, 0, 0, 0, 0, int(side)))
 
-    def assign(self, d):
-        self._add(L.OP_ASSIGN, d)
+    def assign(self, d, atss=None):
+        """atss: the head's dsl_atss_desc (dsl_atss_assign), None = dsl_fcos_assign."""
+        self._add(L.OP_ASSIGN, d, p=(C.addressof(atss),) if atss is not None else ())
 
     def loss(self, d):
         self._add(L.OP_LOSS, d)
@@ -218,7 +219,7 @@ class Plan:
             self.lossplan.bind_outputs(self.bufs['cls_logits'], self.bufs['regctr'], store.t32_ptr('head.scales'))
             # scale gradients go straight into the flat gradient buffer
             self.lossplan.desc.g_scales = store.t32_ptr('head.scales', store.grad)
-            self.assign_ops.assign(self.lossplan.desc)
+            self.assign_ops.assign(self.lossplan.desc, self.lossplan.atss)
             if self._fside:             # the regression tower's side stream: joined here, not at the end of the forward list,
                 self.loss_ops.join(self._fside)       # so that target upload + assignment run while it finishes
             self.loss_ops.prof(4, 1)
@@ -307,14 +308,17 @@ class Plan:
             # also orders this step's head, which overwrites the towers' activations, behind the weight gradients that read them
             f.wait(L.SLOT_HEADW, stream=0)
         fc = [cv[f'neck.fpn_convs.{i}.conv'] for i in range(5)]
-        p6r = self.buf('p6r', N, hw6[0], hw6[1], 256)
+        # FPN(relu_before_extra_convs=False) (fpn.py:196-199): P7 reads P6 itself, there is no relu(P6) copy
+        self.p6_relu = bool(getattr(st, 'fpn_relu_extra', True))
+        p6r = self.buf('p6r', N, hw6[0], hw6[1], 256) if self.p6_relu else self.feat_seg[3]
         f.conv(self._conv(lc[2], c5, lat[2], N, [hw5], [hw5], lds=ld5))
         if BR:
             f.fork(BR)
         # P5 -> P6 -> P7: five tiny launches, beside the P4 / P3 path
         f.conv(br(self._conv(fc[2], lat[2], self.feat_seg[2], N, [hw5], [hw5])), side=BR)
         f.conv(br(self._conv(fc[3], self.feat_seg[2], self.feat_seg[3], N, [hw5], [hw6])), side=BR)      # P6 (no relu)
-        f.conv(br(self._conv(fc[3], self.feat_seg[2], p6r, N, [hw5], [hw6], relu=True)), side=BR)        # relu(P6)
+        if self.p6_relu:
+            f.conv(br(self._conv(fc[3], self.feat_seg[2], p6r, N, [hw5], [hw6], relu=True)), side=BR)    # relu(P6)
         f.conv(br(self._conv(fc[4], p6r, self.feat_seg[4], N, [hw6], [hw7])), side=BR)                   # P7
         f.conv(self._conv(lc[1], c4, lat[1], N, [hw4], [hw4], addend=lat[2], add_hw=[hw5], lds=ld4))
         if BR:
@@ -784,7 +788,7 @@ class Plan:
         hw3, hw4, hw5, hw6, hw7 = ls
         gseg = [g_feats.data_ptr() + self.seg_off[i] * 256 * 2 for i in range(5)]
         lat = [self.bufs[f'lat{i}'] for i in range(3)]
-        p6r = self.bufs['p6r']
+        p6r = self.bufs['p6r'] if self.p6_relu else self.feat_seg[3]
         g_p6 = self.buf('g_p6', N, hw6[0], hw6[1], 256)
         g_p5 = self.buf('g_p5', N, hw5[0], hw5[1], 256)
         g_lat = [self.buf(f'g_lat{i}', N, hw[0], hw[1], 256) for i, hw in enumerate((hw3, hw4, hw5))]
@@ -807,9 +811,9 @@ class Plan:
         ol.conv(br_ws(self._dgrad(fc[1].name, gseg[1], g_lat[1], N, [hw4], [hw4], cs=256, cd=256, k=3, stride=1, pad=1,
                                   addend=s0)), side=BB)
         ol.sum2x2(g_lat[1], s1, N, hw5[0], hw5[1], hw4[0], hw4[1], 256, side=BB)
-        # P7 = fpn4(relu(P6))
+        # P7 = fpn4(relu(P6)); relu_before_extra_convs=False: P7 = fpn4(P6), its data gradient reaches P6 unmasked
         ol.conv(self._dgrad(fc[4].name, gseg[4], g_p6, N, [hw7], [hw6], cs=256, cd=256, k=3, stride=2, pad=1,
-                            addend=gseg[3], mask=p6r, mask_first=True))
+                            addend=gseg[3], mask=p6r if self.p6_relu else None, mask_first=self.p6_relu))
         # P6 = fpn3(P5)
         ol.conv(self._dgrad(fc[3].name, g_p6, g_p5, N, [hw6], [hw5], cs=256, cd=256, k=3, stride=2, pad=1,
                             addend=gseg[2]))

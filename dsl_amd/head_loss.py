@@ -26,7 +26,8 @@ class FcosLossPlan:
         """head: params.HeadOptions (None = the default head).  centerness_on_reg=False: the centerness logit is column
         round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls.  The head's loss
         settings (box_loss, focal gamma / alpha, the loss weights) go into the descriptor: losses, logvec and the gradients are the
-        weighted ones."""
+        weighted ones.  An ATSS head (head.assigner == 'atss'): the assignment is dsl_atss_assign, fed the images' pad_shape
+        (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554)."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head
         self.ctr_col = None
@@ -61,7 +62,8 @@ class FcosLossPlan:
         pin = torch.cuda.is_available()
         self._slots = [dict(boxes=torch.zeros(2, max_gt, 4, dtype=torch.float32, pin_memory=pin),
                             labels=torch.zeros(max_gt, dtype=torch.int64, pin_memory=pin),
-                            off=torch.zeros(2, n + 1, dtype=torch.int32, pin_memory=pin), ev=None) for _ in range(4)]
+                            off=torch.zeros(2, n + 1, dtype=torch.int32, pin_memory=pin),
+                            pad=torch.zeros(n, 2, dtype=torch.int32, pin_memory=pin), ev=None) for _ in range(4)]
         self._slot_i = 0
         self.desc = ops.fcos_desc(n=n, sizes=self.sizes, strides=strides, ranges=ranges, radius=radius,
                                   num_classes=num_classes)
@@ -78,13 +80,25 @@ class FcosLossPlan:
                 head.fill_loss_desc(self.desc)
         if self.ctr_col is not None:
             self.desc.g_ctr, self.desc.ld_gctr = self.g_cls.data_ptr() + 2 * self.ctr_col, self.LD_GCLS
+        self.atss = head.atss_desc() if head is not None else None
+        if self.atss is not None:
+            self.pad_shapes = torch.zeros(n, 2, dtype=torch.int32, device=dev)
+            self.npos = torch.zeros(n, dtype=torch.int32, device=dev)
+            self.atss.max_gt, self.atss.pad_shapes, self.atss.npos = max_gt, L.ptr(self.pad_shapes), L.ptr(self.npos)
+            self.desc.atss = C.addressof(self.atss)
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         self.desc.workspace, self.desc.workspace_bytes = L.ptr(self.ws), need
 
     # -- ground truth upload (host lists -> one pinned staging copy) --------------------------------
-    def set_targets(self, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+    def set_targets(self, gt_bboxes, gt_labels, gt_bboxes_ignore=None, pad_shapes=None):
+        """pad_shapes: (pad_h, pad_w) per image, required by an ATSS head (its valid anchors, atss_head.py:615-617) and not read
+        otherwise; ATSS does not read gt_bboxes_ignore (ignore_iof_thr = -1)."""
         assert len(gt_bboxes) == self.n == len(gt_labels)
+        if self.atss is not None:
+            if pad_shapes is None or len(pad_shapes) != self.n:
+                raise ValueError('an ATSS head needs the pad_shape of every image (set_targets(pad_shapes=...))')
+            gt_bboxes_ignore = None
         slot = self._slots[self._slot_i]
         self._slot_i = (self._slot_i + 1) % len(self._slots)
         if slot['ev'] is not None:
@@ -119,6 +133,10 @@ class FcosLossPlan:
 
         stage(gt_bboxes, 0, self.gt_boxes, gt_labels)
         self.gt_off.copy_(slot['off'][0], non_blocking=True)
+        if self.atss is not None:
+            for i, ps in enumerate(pad_shapes):
+                slot['pad'][i, 0], slot['pad'][i, 1] = int(ps[0]), int(ps[1])
+            self.pad_shapes.copy_(slot['pad'], non_blocking=True)
         if gt_bboxes_ignore is not None:
             assert len(gt_bboxes_ignore) == self.n
             stage(gt_bboxes_ignore, 1, self.ig_boxes)
@@ -140,6 +158,9 @@ class FcosLossPlan:
             self.desc.ctr, self.desc.ld_ctr = self.desc.cls_logits + 4 * self.ctr_col, self.LD_CLS
 
     def assign(self):
+        if self.atss is not None:
+            L.check(L.lib.dsl_atss_assign(C.byref(self.desc), C.byref(self.atss), L.stream_ptr()), 'dsl_atss_assign')
+            return
         L.check(L.lib.dsl_fcos_assign(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_assign')
 
     def loss(self):

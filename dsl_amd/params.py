@@ -131,13 +131,34 @@ class HeadOptions:
                          (losses/iou_loss.py:105-219); iou_loss then follows it (True for the two IoULoss kinds)
       box_eps            eps of DIoULoss / CIoULoss
       focal_gamma, focal_alpha                 FocalLoss (losses/focal_loss.py:11-56)
-      cls_weight, bbox_weight, ctr_weight      loss_weight of loss_cls / loss_bbox / loss_centerness"""
+      cls_weight, bbox_weight, ctr_weight      loss_weight of loss_cls / loss_bbox / loss_centerness
+    The assigner ('fcos'; 'atss' = ATSSHead, mmdet/models/dense_heads/atss_head.py, dsl_atss_desc of include/dsl_hip.h): an ATSS head has
+    the parameter layout of centerness_on_reg=True, conv_bias=False - both are forced, as are the two FCOS assignment options, which it
+    does not read - and the reference's predictor names (atss_cls, atss_reg, atss_centerness):
+      atss_topk          ATSSAssigner(topk), 1..16
+      anchor_scale       AnchorGenerator(octave_base_scale): the one square anchor of a location has side anchor_scale * stride
+      delta_stds         DeltaXYWHBBoxCoder(target_stds); the means are 0"""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
     BOX_KINDS = dict(giou=L.BOX_GIOU, iou=L.BOX_IOU_LOG, iou_linear=L.BOX_IOU_LINEAR, diou=L.BOX_DIOU, ciou=L.BOX_CIOU)
+    ATSS_FIELDS = ('assigner', 'atss_topk', 'anchor_scale', 'delta_stds')
 
     def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
-                 box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0):
+                 box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0,
+                 assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2)):
+        if assigner not in ('fcos', 'atss'):
+            raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
+        self.assigner = assigner
+        self.atss_topk, self.anchor_scale = int(atss_topk), float(anchor_scale)
+        self.delta_stds = tuple(float(v) for v in delta_stds)
+        if assigner == 'atss':
+            if not 1 <= self.atss_topk <= L.ATSS_MAX_TOPK:
+                raise NotImplementedError(f'dsl_amd hot path: atss_topk must be in 1..{L.ATSS_MAX_TOPK}, got {atss_topk!r}')
+            if not (0.0 < self.anchor_scale < float('inf')):
+                raise NotImplementedError(f'dsl_amd hot path: anchor_scale must be a finite number > 0, got {anchor_scale!r}')
+            if len(self.delta_stds) != 4 or not all(0.0 < v < float('inf') for v in self.delta_stds):
+                raise NotImplementedError(f'dsl_amd hot path: delta_stds must be four finite numbers > 0, got {delta_stds!r}')
+            center_sampling, norm_on_bbox, centerness_on_reg, conv_bias = True, True, True, False
         self.center_sampling, self.norm_on_bbox, self.centerness_on_reg = bool(center_sampling), bool(norm_on_bbox), bool(centerness_on_reg)
         self.conv_bias = bool(conv_bias)
         self.box_loss = box_loss if box_loss is not None else ('iou' if iou_loss else 'giou')
@@ -158,7 +179,8 @@ class HeadOptions:
     def key(self):
         """The five FIELDS for every head that existed before the loss family; the loss settings follow only where one is set."""
         k = tuple(getattr(self, f) for f in self.FIELDS)
-        return k if self.loss_is_default() else k + self.loss_key()
+        k = k if self.loss_is_default() else k + self.loss_key()
+        return k + tuple(getattr(self, f) for f in self.ATSS_FIELDS) if self.assigner == 'atss' else k
 
     def is_default(self):
         return self.key() == HeadOptions().key()
@@ -166,7 +188,18 @@ class HeadOptions:
     def flags(self):
         """dsl_fcos_desc.head_flags / dsl_det_desc.head_flags."""
         return ((0 if self.center_sampling else L.HEAD_INSIDE_BOX) | (0 if self.norm_on_bbox else L.HEAD_RAW_TARGETS | L.HEAD_EXP_DECODE)
-                | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT))
+                | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT)
+                | (L.HEAD_ATSS if self.assigner == 'atss' else 0))
+
+    def atss_desc(self):
+        """A dsl_atss_desc with the head's settings (None for an FCOS head); the caller fills max_gt, pad_shapes and npos."""
+        if self.assigner != 'atss':
+            return None
+        a = L.AtssDesc()
+        a.topk, a.anchor_scale = self.atss_topk, self.anchor_scale
+        for i, v in enumerate(self.delta_stds):
+            a.delta_stds[i] = v
+        return a
 
     def fill_loss_desc(self, d):
         """The loss family's fields of a dsl_fcos_desc (read by the kernel with HEAD_LOSS_EXT only)."""
@@ -176,6 +209,7 @@ class HeadOptions:
 
     def __repr__(self):
         fields = self.FIELDS if self.loss_is_default() else self.FIELDS + self.LOSS_FIELDS
+        fields += self.ATSS_FIELDS if self.assigner == 'atss' else ()
         return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in fields) + ')'
 
 
@@ -350,20 +384,28 @@ class ParamStore:
             bn(n)
         cw, cb = self.tview('head.cls_w', tb), self.tview('head.cls_b', tb)
         rw, rb = self.tview('head.regctr_w', tb), self.tview('head.regctr_b', tb)
-        out['bbox_head.conv_cls.weight'] = cw[:self.num_classes].permute(0, 3, 1, 2)
-        out['bbox_head.conv_cls.bias'] = cb[:self.num_classes]
-        out['bbox_head.conv_reg.weight'] = rw[:4].permute(0, 3, 1, 2)
-        out['bbox_head.conv_reg.bias'] = rb[:4]
+        # the predictors' names: FCOSHead's conv_*, ATSSHead's atss_* (atss_head.py:83-91)
+        pc, pr, pt = [f'bbox_head.{n}' for n in self.predictor_names()]
+        out[pc + '.weight'] = cw[:self.num_classes].permute(0, 3, 1, 2)
+        out[pc + '.bias'] = cb[:self.num_classes]
+        out[pr + '.weight'] = rw[:4].permute(0, 3, 1, 2)
+        out[pr + '.bias'] = rb[:4]
         if self.ctr_on_cls:       # (row 4 of the regression predictor is then zero and stays zero)
-            out['bbox_head.conv_centerness.weight'] = cw[self.cls_ld:self.cls_ld + 1].permute(0, 3, 1, 2)
-            out['bbox_head.conv_centerness.bias'] = cb[self.cls_ld:self.cls_ld + 1]
+            out[pt + '.weight'] = cw[self.cls_ld:self.cls_ld + 1].permute(0, 3, 1, 2)
+            out[pt + '.bias'] = cb[self.cls_ld:self.cls_ld + 1]
         else:
-            out['bbox_head.conv_centerness.weight'] = rw[4:5].permute(0, 3, 1, 2)
-            out['bbox_head.conv_centerness.bias'] = rb[4:5]
+            out[pt + '.weight'] = rw[4:5].permute(0, 3, 1, 2)
+            out[pt + '.bias'] = rb[4:5]
         sc = self.tview('head.scales', tb)
         for i in range(5):
             out[f'bbox_head.scales.{i}.scale'] = sc[i]
         return out
+
+    def predictor_names(self):
+        """Module names of the class, box and centerness predictors under bbox_head."""
+        if self.head.assigner == 'atss':
+            return 'atss_cls', 'atss_reg', 'atss_centerness'
+        return 'conv_cls', 'conv_reg', 'conv_centerness'
 
     def wait_pending(self):
         """Deferred head update (FlatSGD, Plan.defer): the last optimizer step may still be updating the head + FPN bucket on the
@@ -630,7 +672,7 @@ class ParamStore:
                     t = torch.zeros(shape)          # zero_init_last_bn (resnet_rla.py:251-256)
             else:
                 t = torch.zeros(shape)
-                if k == 'bbox_head.conv_cls.bias':
+                if k == f'bbox_head.{self.predictor_names()[0]}.bias':      # (atss_head.py:30-42: the same prior on atss_cls)
                     t = torch.full(shape, -math.log((1 - 0.01) / 0.01))
             sd[k] = t
         self.load_named(sd)

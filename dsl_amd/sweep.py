@@ -20,8 +20,14 @@ from . import _lib as L
 
 class DetectPlan:
     def __init__(self, n, sizes, strides, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05,
-                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0):
+                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, atss=None):
+        """atss: the dsl_atss_desc of an ATSS head (params.HeadOptions.atss_desc), with HEAD_ATSS in head_flags."""
         d = L.DetDesc()
+        self.atss = atss
+        if atss is not None:      # dsl_det_atss_desc: `d` is its first member (and keeps it alive)
+            self._ext = L.DetAtssDesc()
+            self._ext.atss = C.addressof(atss)
+            d = self._ext.det
         d.nms_method, d.soft_sigma, d.soft_min_score = nms_method, soft_sigma, soft_min_score      # L.NMS_*; all zero: the hard NMS
         d.nlvl, d.n = len(sizes), n
         d.h, d.w = L.seg5([s[0] for s in sizes]), L.seg5([s[1] for s in sizes])
@@ -29,7 +35,7 @@ class DetectPlan:
         d.num_classes, d.nms_pre, d.max_per_img = num_classes, nms_pre, max_per_img
         d.score_thr, d.iou_thr = score_thr, iou_thr
         d.ld_cls, d.ld_rc = ld_cls, ld_rc
-        d.head_flags = head_flags      # DSL_HEAD_EXP_DECODE: norm_on_bbox=False
+        d.head_flags = head_flags      # DSL_HEAD_EXP_DECODE: norm_on_bbox=False; DSL_HEAD_ATSS: anchor-delta decode
         self.ctr_col = ctr_col         # centerness_on_reg=False: the centerness logit is this column of the logits' rows
         self.dets = torch.zeros(n, max_per_img, 5, device=device)
         self.labels = torch.zeros(n, max_per_img, dtype=torch.int64, device=device)
@@ -135,7 +141,7 @@ def _detplan(det, plan, store, N):
     dp = getattr(plan, 'detplan', None)
     if dp is None:
         dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
-                        ld_cls=store.logit_ld, head_flags=store.head.flags() & L.HEAD_EXP_DECODE,
+                        ld_cls=store.logit_ld, head_flags=store.head.flags() & (L.HEAD_EXP_DECODE | L.HEAD_ATSS), atss=store.head.atss_desc(),
                         ctr_col=store.cls_ld if store.ctr_on_cls else None, **_test_cfg(det))
         dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
         plan.detplan = dp

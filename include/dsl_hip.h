@@ -487,6 +487,7 @@ int dsl_colsum(const void* x, float* out, long rows, int c, int ld, void* stream
  * FCOS targets and losses (fcos_head.py:170-338,550-726; losses/focal_loss.py:11-56;
  * losses/iou_loss.py:14-36,85-219; losses/cross_entropy_loss.py:73-112)
  * ---------------------------------------------------------------------------------------- */
+struct dsl_atss_desc;
 typedef struct dsl_fcos_desc {
   int32_t nlvl, n;                     /* levels, images */
   int32_t h[DSL_MAX_SEG], w[DSL_MAX_SEG], stride[DSL_MAX_SEG];
@@ -545,6 +546,7 @@ typedef struct dsl_fcos_desc {
   float w_cls, w_bbox, w_ctr;          /* loss_weight of loss_cls / loss_bbox / loss_centerness: scale losses[0..2], logvec and the
                                         * term's gradients (g_cls; g_rc[:, :4] and g_scales; the centerness gradient).  The sisoft term
                                         * and the stream weight `loss_weight` above are independent of them */
+  const struct dsl_atss_desc* atss;    /* read only with DSL_HEAD_ATSS: anchor_scale and delta_stds of the ATSS head (below) */
 } dsl_fcos_desc;
 #define DSL_HEAD_INSIDE_BOX 1   /* center_sampling=False: inside = min(l, t, r, b) > 0, radius unused (fcos_head.py:676-678) */
 #define DSL_HEAD_RAW_TARGETS 2  /* norm_on_bbox=False, assignment: bbox_targets stay in pixels (fcos_head.py:618) */
@@ -552,6 +554,7 @@ typedef struct dsl_fcos_desc {
                                  * (fcos_head.py:162-167); the gradient goes through exp into g_rc and g_scales */
 #define DSL_HEAD_IOU_LOSS 8     /* loss_bbox = IoULoss(linear=False, eps=1e-6): -log(clamp(iou, eps)) (losses/iou_loss.py:14-36) */
 #define DSL_HEAD_LOSS_EXT 16    /* dsl_fcos_desc: box_kind .. w_ctr are set (loss family); not a dsl_det_desc flag */
+#define DSL_HEAD_ATSS 32        /* ATSSHead (below): anchor-delta decode, the stored ground-truth box as target, ATSS normalisers */
 /* dsl_fcos_desc.box_kind.  Linear IoU: 1 - clamp(iou, 1e-6), no gradient where the clamp is active (losses/iou_loss.py:31-33).
  * DIoU / CIoU restate losses/iou_loss.py:105-219 (union = a1 + a2 - overlap + eps, c2 = cw^2 + ch^2 + eps, CIoU's h = y2 - y1 + eps)
  * with two deviations from the reference's fp32 results: CIoU's penalty v^2 / (1 - iou + v) and its gradient are 0 where v == 0
@@ -562,7 +565,50 @@ typedef struct dsl_fcos_desc {
 #define DSL_BOX_IOU_LINEAR 2
 #define DSL_BOX_DIOU 3
 #define DSL_BOX_CIOU 4
-size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d);
+size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d);   /* with DSL_HEAD_ATSS: also what dsl_atss_assign needs */
+
+/* ------------------------------------------------------------------------------------------
+ * ATSS: adaptive training sample selection (mmdet/core/bbox/assigners/atss_assigner.py:66-178,
+ * mmdet/models/dense_heads/atss_head.py:142-309,420-495,569-684, mmdet/core/anchor/anchor_generator.py:99-143,287-352,
+ * mmdet/core/bbox/coder/delta_xywh_bbox_coder.py:144-266, iou_calculators/iou2d_calculator.py:212-260), fp32, contraction off.
+ *
+ * Anchors: location (x, y) of a level with stride s has ONE square anchor [x s - a/2, y s - a/2, x s + a/2, y s + a/2],
+ * a = anchor_scale * s (AnchorGenerator(ratios=[1.0], scales_per_octave=1, octave_base_scale=anchor_scale), center_offset 0):
+ * its centre is (x s, y s), without FCOS's + s / 2.
+ * Valid anchors of image i (valid_flags with allowed_border = -1): x < min(ceil(pad_w_i / s), w_l), y < min(ceil(pad_h_i / s), h_l).
+ * An invalid anchor takes no part in the selection: label = num_classes, cls_weight = 0, assign_idx = -1.
+ *
+ * dsl_atss_assign: per ground-truth box and level the min(topk, valid anchors of the level) valid anchors with the smallest
+ * sqrt(dx^2 + dy^2) between anchor centre and box centre ((x1 + x2) / 2, (y1 + y2) / 2) - every valid anchor of the level is
+ * scanned.  TIE RULE: equal distances go to the lower anchor index (y * w_l + x); torch.topk leaves the order of ties unspecified.
+ * Threshold = mean + unbiased std (n - 1; NaN, i.e. no positive, for a single candidate) of the candidates' IoUs with the box,
+ * summed in ascending (level, rank) order; IoU as BboxOverlaps2D (union clamped at 1e-6).  A candidate is positive iff IoU >=
+ * threshold and min(cx - x1, cy - y1, x2 - cx, y2 - cy) > 0.01.  An anchor positive for several boxes takes the one with the highest
+ * IoU, equal IoUs the lower ground-truth index.  Every other valid anchor is background with cls_weight 1; an image without
+ * ground truth is all background.  ig_boxes / ig_off are not read (ignore_iof_thr = -1).
+ * Outputs are dsl_fcos_assign's; bbox_targets holds the assigned ground-truth box in pixels (x1, y1, x2, y2; zeros elsewhere),
+ * stats[0] = sum_i max(npos_i, 1) (atss_head.py:554), stats[1] = the sum of the centerness targets (block records added in
+ * block order), npos[i] = positives of image i.  No float atomics: conflicts are resolved by a 64-bit integer maximum of
+ * (IoU bits << 32 | ~ground-truth index) per anchor, the counts by integer adds - a second run is bit-identical.
+ *
+ * DSL_HEAD_ATSS in dsl_fcos_desc.head_flags (dsl_fcos_loss, `atss` set) and in dsl_det_desc.head_flags (dsl_fcos_detect, _collect;
+ * the descriptor is then a dsl_det_atss_desc): the box is delta2bbox of d = scale_l * x * delta_stds against the anchor - cx = acx + a dx, w = a exp(dw), dw / dh
+ * clamped to +-|log(16 / 1000)| (no gradient through an active clamp), corners at +- 0.5 w; detection clips to img_shapes.
+ * Loss: the target is the stored ground-truth box, the centerness target comes from the anchor centre and that box; loss_cls and
+ * loss_centerness are divided by max(norm[0] * inv_world, 1), loss_bbox - weighted by the centerness target - by
+ * max(norm[1] * inv_world, 1) (atss_head.py:268-287; FCOS clamps the latter at 1e-6).  The loss family applies unchanged.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct dsl_atss_desc {
+  int32_t topk;                        /* 1..16 (ATSSAssigner's 9) */
+  int32_t max_gt;                      /* capacity of gt_boxes: one workgroup per possible box is launched, >= gt_off[n] */
+  float anchor_scale;                  /* octave_base_scale (8), > 0 */
+  float delta_stds[4];                 /* DeltaXYWHBBoxCoder target_stds (0.1, 0.1, 0.2, 0.2), > 0; the means are 0 */
+  const int32_t* pad_shapes;           /* device [n][2]: (pad_h, pad_w) of every image (img_meta['pad_shape']) */
+  int32_t* npos;                       /* device [n], output of dsl_atss_assign: positives per image */
+} dsl_atss_desc;
+#define DSL_ATSS_MAX_TOPK 16
+/* `d` as for dsl_fcos_assign, with DSL_HEAD_ATSS in head_flags and a workspace of dsl_fcos_workspace_bytes(d) */
+int dsl_atss_assign(const dsl_fcos_desc* d, const dsl_atss_desc* a, void* stream);
 
 int dsl_fcos_points(const dsl_fcos_desc* d, float* points /* [P][2] */, void* stream);
 int dsl_fcos_assign(const dsl_fcos_desc* d, void* stream);
@@ -638,6 +684,13 @@ typedef struct dsl_det_desc {
   float soft_sigma;                          /* DSL_NMS_GAUSSIAN: w = exp(-iou^2 / soft_sigma), > 0 (mmcv: 0.5) */
   float soft_min_score;                      /* Soft-NMS: a candidate whose decayed score is < soft_min_score is dropped, >= 0 (mmcv: 1e-3) */
 } dsl_det_desc;
+/* An ATSS head's detection descriptor: with DSL_HEAD_ATSS in det.head_flags the dsl_det_desc handed to dsl_fcos_detect /
+ * dsl_fcos_detect_collect is the first member of one of these (dsl_det_desc itself keeps its layout), and `atss` supplies
+ * anchor_scale and delta_stds (atss_head.py:420-495). */
+typedef struct dsl_det_atss_desc {
+  dsl_det_desc det;
+  const struct dsl_atss_desc* atss;
+} dsl_det_atss_desc;
 /* dsl_det_desc.nms_method.  Soft-NMS is mmcv's batched_nms with nms=dict(type='soft_nms', method=...) (stated by
  * mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127), per image and class over the candidates the hard NMS would get: pick the highest current score
  * (equal scores: the candidate that comes first in (level, slot, class) order - with views, (view, level, slot, class)), emit it
