@@ -34,6 +34,7 @@ OP_QUANT_FP8, OP_QUANT_FP8_W, OP_FP8_COMB = 22, 23, 24
 OP_FP8_PREP, OP_QUANT_FP8_DELAYED = 27, 28
 OP_STEM_POOL = 25
 OP_BNECK = 26
+OP_GFL_QUALITY = 29
 PROF_CLASSES = 8
 MAX_MULTI = 16
 SLOT_TAIL, SLOT_PREFIX = 13, 14     # pipelined frozen prefix: 'previous backward's data-gradient chain done', 'prefix of this step done'
@@ -125,6 +126,8 @@ HEAD_INSIDE_BOX, HEAD_RAW_TARGETS, HEAD_EXP_DECODE, HEAD_IOU_LOSS = 1, 2, 4, 8
 HEAD_LOSS_EXT = 16      # dsl_fcos_desc only: box_kind .. w_ctr are set
 HEAD_ATSS = 32          # ATSSHead: anchor-delta decode, ATSS targets and normalisers; the descriptor's `atss` is set
 ATSS_MAX_TOPK = 16
+HEAD_GFL = 64           # GFLHead: the dsl_fcos_desc is a dsl_gfl_desc's first member, the dsl_det_desc a dsl_det_gfl_desc's
+GFL_MAX_REG = 16
 BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_DIOU, BOX_CIOU = range(5)      # DSL_BOX_*: dsl_fcos_desc.box_kind
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
@@ -145,8 +148,17 @@ class DetDesc(C.Structure):
                 ('nms_method', C.c_int32), ('soft_sigma', C.c_float), ('soft_min_score', C.c_float)]
 
 
+class GflDesc(C.Structure):      # dsl_gfl_desc: a GFL head's loss descriptor (HEAD_GFL | HEAD_ATSS | HEAD_LOSS_EXT in fcos.head_flags)
+    _fields_ = [('fcos', FcosDesc), ('reg_max', C.c_int32), ('qfl_beta', C.c_float), ('w_dfl', C.c_float),
+                ('score', C.c_void_p), ('weight', C.c_void_p)]
+
+
 class DetAtssDesc(C.Structure):      # dsl_det_atss_desc: the detection descriptor of an ATSS head (HEAD_ATSS in det.head_flags)
     _fields_ = [('det', DetDesc), ('atss', C.c_void_p)]
+
+
+class DetGflDesc(C.Structure):      # dsl_det_gfl_desc: the detection descriptor of a GFL head (HEAD_GFL in det.head_flags)
+    _fields_ = [('det', DetDesc), ('reg_max', C.c_int32)]
 
 
 class PackItem(C.Structure):
@@ -294,6 +306,7 @@ _SIGS = {
     'dsl_groupnorm_relu_fwd': [_vp, _vp], 'dsl_groupnorm_relu_bwd': [_vp, _vp], 'dsl_groupnorm_workspace_bytes': [_vp],
     'dsl_sum2x2': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], 'dsl_colsum': [_vp, _vp, _l, _i, _i, _vp],
     'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_atss_assign': [_vp, _vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
+    'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
     'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],

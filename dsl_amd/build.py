@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libdsl_hip.so')
-SOURCES = ['api.hip', 'conv.hip', 'wgrad.hip', 'misc.hip', 'fcos_loss.hip', 'optim.hip', 'detect.hip', 'rla.hip', 'datapath.hip', 'comm.hip', 'stem.hip', 'bneck.hip', 'evalmap.hip']
+SOURCES = ['api.hip', 'conv.hip', 'wgrad.hip', 'misc.hip', 'fcos_loss.hip', 'gfl_loss.hip', 'optim.hip', 'detect.hip', 'rla.hip', 'datapath.hip', 'comm.hip', 'stem.hip', 'bneck.hip', 'evalmap.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-unused-value']
 # conv.hip only: its kernels carry a scalar hot header in front of their by-value parameter struct, which this makes the
 # compiler preload into user SGPRs (.amdhsa_user_sgpr_kernarg_preload_length; DESIGN.md section 3.1, "front end")
@@ -32,7 +32,7 @@ def _stale(out, deps):
 
 def build_lib(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(HERE, '..', 'include', 'dsl_hip.h')]
+    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'box_loss.hpp'), os.path.join(HERE, '..', 'include', 'dsl_hip.h')]
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     objs = [os.path.join(LIBDIR, os.path.basename(s)[:-4] + '.o') for s in srcs]
     hipcc = _hipcc()

@@ -19,6 +19,11 @@
 // ATSSHead (DSL_HEAD_ATSS in head_flags, the descriptor then being a dsl_det_atss_desc; ATSSHead._get_bboxes,
 // mmdet/models/dense_heads/atss_head.py:420-495): det_decode decodes anchor deltas (delta2bbox,
 // core/bbox/coder/delta_xywh_bbox_coder.py:144-269, clipped to img_shape) instead of distances; every stage behind it is shared.
+//
+// GFLHead (DSL_HEAD_GFL, the descriptor then being a dsl_det_gfl_desc; GFLHead._get_bboxes, mmdet/models/dense_heads/gfl_head.py:
+// 372-443): det_decode takes the distances as Integral(scale x) * stride (gfl_head.py:15-48) from the anchor centre.  There is no
+// centerness factor: the kernels' centerness logit is then one constant whose sigmoid is exactly 1 (kNoCtr, row stride 0), so
+// key, pair score and pool rows are the class sigmoid alone and no kernel in front of or behind the decode branches on the head.
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -38,6 +43,7 @@ struct DetK {
   int exp_decode;                    // norm_on_bbox=False: exp(scale x), no stride multiply (fcos_head.py:162-167)
   int atss;                          // DSL_HEAD_ATSS: delta2bbox against the location's anchor (atss_head.py:420-495)
   float anchor_scale, stds[4];
+  int gfl_R;                         // DSL_HEAD_GFL: reg_max + 1 bins per side (0 = not a GFL head)
   const float* scales; const float* img_shapes; const float* scale_factors;
   float* dets; long long* det_labels; int* det_count;
   // workspace
@@ -61,6 +67,9 @@ struct AugK {
 };
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
+// the "centerness logit" of a head without centerness (DSL_HEAD_GFL): expf(-100) is 0, sigmoidf_ gives exactly 1
+__device__ __attribute__((used)) float kNoCtr = 100.f;      // (never written)
 
 // key[m] = max_c sigmoid(cls) * sigmoid(ctr)     (fcos_head.py:472-473).  Full groups of 4 classes, then the partial
 // last group (C % 4 != 0) with its lanes c >= C left out: the row's padding columns hold whatever the buffer held.
@@ -265,6 +274,29 @@ __device__ __forceinline__ void det_decode(const DetK& p, int img, int lvl, int 
   const float px = (float)x * (float)s + (float)(s / 2), py = (float)y * (float)s + (float)(s / 2);
   const float sc = p.scales[lvl];
   const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
+  if (p.gfl_R) {
+    // per side the softmax expectation over its R bins of scale x (Integral, gfl_head.py:15-48), times the stride; distance2bbox from
+    // the anchor centre (x s, y s), clipped to img_shape (gfl_head.py:416-426)
+    float d[4];
+    for (int e = 0; e < 4; ++e) {
+      const float* z = rc + e * p.gfl_R;
+      float mx = z[0] * sc;
+      for (int j = 1; j < p.gfl_R; ++j) mx = fmaxf(mx, z[j] * sc);
+      float S = 0.f, A = 0.f;
+      for (int j = 0; j < p.gfl_R; ++j) {
+        const float ex = expf(z[j] * sc - mx);
+        S += ex;
+        A += (float)j * ex;
+      }
+      d[e] = A / S * (float)s;
+    }
+    const float ax = (float)x * (float)s, ay = (float)y * (float)s;
+    b[0] = fminf(fmaxf(ax - d[0], 0.f), W);
+    b[1] = fminf(fmaxf(ay - d[1], 0.f), H);
+    b[2] = fminf(fmaxf(ax + d[2], 0.f), W);
+    b[3] = fminf(fmaxf(ay + d[3], 0.f), H);
+    return;
+  }
   if (p.atss) {
     // anchor centre (x s, y s), side a = anchor_scale * s; delta2bbox with max_shape = img_shape (delta_xywh_bbox_coder.py:209-269):
     // d = scale * x * stds, dw / dh clamped to +-|log(16 / 1000)|
@@ -888,6 +920,16 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
       DSL_CHECK(a->delta_stds[e] > 0.f && a->delta_stds[e] < 1e30f, "%s: delta_stds must be finite and > 0", who);
       k.stds[e] = a->delta_stds[e];
     }
+  }
+  if (d->head_flags & DSL_HEAD_GFL) {
+    const dsl_det_gfl_desc* g = reinterpret_cast<const dsl_det_gfl_desc*>(d);      // the flag says: d is a dsl_det_gfl_desc's first member
+    DSL_CHECK(g->reg_max >= 1 && g->reg_max <= DSL_GFL_MAX_REG, "%s: DSL_HEAD_GFL needs a dsl_det_gfl_desc with reg_max in 1..16", who);
+    DSL_CHECK(!k.exp_decode && !k.atss && !d->ctr, "%s: DSL_HEAD_GFL goes with no other decode flag and has no centerness", who);
+    DSL_CHECK(d->ld_rc >= 4 * (g->reg_max + 1), "%s: ld_rc must hold 4 (reg_max + 1) columns", who);
+    k.gfl_R = g->reg_max + 1;
+    void* one = nullptr;
+    DSL_CHECK(hipGetSymbolAddress(&one, HIP_SYMBOL(kNoCtr)) == hipSuccess && one, "%s: no address for the unit centerness", who);
+    k.ctr = (const float*)one; k.ld_ctr = 0;
   }
   k.scales = d->scales; k.img_shapes = d->img_shapes; k.scale_factors = d->scale_factors;
   k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;

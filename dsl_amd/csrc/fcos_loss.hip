@@ -31,6 +31,7 @@
 // compiled with floating-point contraction off and the comparisons are written exactly as there.
 #include "common.hpp"
 #pragma clang fp contract(off)
+#include "box_loss.hpp"      // (behind the pragma: its functions are compiled without contraction too)
 
 namespace {
 
@@ -432,10 +433,6 @@ __device__ __forceinline__ void focal_fb(float x, bool t, float& loss, float& gr
   }
 }
 
-// grad of max(a,b) w.r.t. a (ties split evenly, as torch.maximum) and of min(a,b) w.r.t. a
-__device__ __forceinline__ float dmax_a(float a, float b) { return a > b ? 1.f : (a == b ? 0.5f : 0.f); }
-__device__ __forceinline__ float dmin_a(float a, float b) { return a < b ? 1.f : (a == b ? 0.5f : 0.f); }
-
 // ---- loss family (kExt) -------------------------------------------------------------------------------------------------------
 // focal loss and dloss/dx with gamma >= 0, 0 <= alpha <= 1 (focal_loss.py:34-40).  gamma == 2 keeps focal_fb's q * q sequence
 // (launch-uniform branch).  Otherwise q = 1 - p is formed as sigmoid(-x), without cancellation, and the gradient as
@@ -471,74 +468,6 @@ __device__ __forceinline__ void focal_fb_ext(float x, bool t, float gamma, float
     loss = (1.f - alpha) * mod * sp;
     grad = (1.f - alpha) * mod * (gamma * q * sp + pp);
   }
-}
-
-// One positive location's box loss of kind DSL_BOX_IOU_LINEAR / DIOU / CIOU on the decoded boxes (prediction x, target X) and
-// dl[k] = dloss / d(x1, y1, x2, y2), written as the reference's torch lines so that the subgradients are autograd's (max / min ties
-// split 0.5, clamp(min=0) passes the gradient at 0).
-__device__ __forceinline__ float box_loss_ext(int kind, float eps, float x1, float y1, float x2, float y2, float X1, float Y1,
-                                              float X2, float Y2, float dl[4]) {
-  const float a1 = (x2 - x1) * (y2 - y1), a2 = (X2 - X1) * (Y2 - Y1);
-  const float ltx = fmaxf(x1, X1), lty = fmaxf(y1, Y1), rbx = fminf(x2, X2), rby = fminf(y2, Y2);
-  const float w0 = rbx - ltx, h0 = rby - lty;
-  const float iw = fmaxf(w0, 0.f), ih = fmaxf(h0, 0.f);
-  const float ov = iw * ih;
-  const float u0 = a1 + a2 - ov;
-  const float cw = w0 >= 0.f ? 1.f : 0.f, chh = h0 >= 0.f ? 1.f : 0.f;
-  const float dov[4] = {ih * (-dmax_a(x1, X1) * cw), iw * (-dmax_a(y1, Y1) * chh), ih * (dmin_a(x2, X2) * cw), iw * (dmin_a(y2, Y2) * chh)};
-  const float da1[4] = {-(y2 - y1), -(x2 - x1), (y2 - y1), (x2 - x1)};
-  if (kind == DSL_BOX_IOU_LINEAR) {
-    // iou_loss.py:31-33: 1 - bbox_overlaps(...).clamp(min=eps); union = max(., eps) (iou2d_calculator.py:242-247), both eps 1e-6
-    const float e6 = 1e-6f;
-    const float U = fmaxf(u0, e6);
-    const float ug = u0 > e6 ? 1.f : (u0 == e6 ? 0.5f : 0.f);
-    const float iou = ov / U;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float dU = (da1[k] - dov[k]) * ug;
-      dl[k] = iou >= e6 ? -(dov[k] / U - ov * dU / (U * U)) : 0.f;      // no gradient where the clamp is active
-    }
-    return 1.f - fmaxf(iou, e6);
-  }
-  // diou_loss / ciou_loss (iou_loss.py:121-156, :177-218): union = ap + ag - overlap + eps (an add), c2 = cw^2 + ch^2 + eps
-  const float U = u0 + eps;
-  const float iou = ov / U;
-  const float ew0 = fmaxf(x2, X2) - fminf(x1, X1), eh0 = fmaxf(y2, Y2) - fminf(y1, Y1);
-  const float ew = fmaxf(ew0, 0.f), eh = fmaxf(eh0, 0.f);
-  const float cew = ew0 >= 0.f ? 1.f : 0.f, ceh = eh0 >= 0.f ? 1.f : 0.f;
-  const float c2 = ew * ew + eh * eh + eps;
-  const float dc2[4] = {2.f * ew * (-dmin_a(x1, X1) * cew), 2.f * eh * (-dmin_a(y1, Y1) * ceh), 2.f * ew * (dmax_a(x2, X2) * cew),
-                        2.f * eh * (dmax_a(y2, Y2) * ceh)};
-  const float sx = (X1 + X2) - (x1 + x2), sy = (Y1 + Y2) - (y1 + y2);
-  const float rho2 = sx * sx / 4.f + sy * sy / 4.f;
-  const float drho[4] = {-sx / 2.f, -sy / 2.f, -sx / 2.f, -sy / 2.f};
-  float pen = 0.f, kv = 0.f, ki = 0.f;
-  float dv[4] = {0.f, 0.f, 0.f, 0.f};
-  if (kind == DSL_BOX_CIOU) {
-    const float w1 = x2 - x1, h1 = y2 - y1 + eps, w2 = X2 - X1, h2 = Y2 - Y1 + eps;
-    const float r = w1 / h1;
-    const float A = atanf(w2 / h2) - atanf(r);
-    const float f = 0.40528473456935109f;          // 4 / pi^2
-    const float v = f * (A * A);
-    // DEVIATION: the reference's v^2 / (1 - iou + v) is 0/0 = NaN in fp32 when prediction and target coincide (1 - iou + v rounds to
-    // 0); the penalty and its gradient are taken as 0 where v == 0, which is the fp64 value
-    if (v != 0.f) {
-      const float D = 1.f - iou + v;
-      pen = v * v / D;
-      ki = pen / D;                                 // d pen / d iou  = v^2 / D^2
-      kv = 2.f * v / D - ki;                        // d pen / d v
-      const float da = 2.f * f * A / (1.f + r * r); // -dv / d(w1 / h1)
-      const float dvw = -da / h1, dvh = da * (w1 / (h1 * h1));
-      dv[0] = -dvw; dv[1] = -dvh; dv[2] = dvw; dv[3] = dvh;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float dU = da1[k] - dov[k];
-    const float diou = dov[k] / U - ov * dU / (U * U);
-    dl[k] = -diou + (drho[k] / c2 - rho2 * dc2[k] / (c2 * c2)) + (kv * dv[k] + ki * diou);
-  }
-  return 1.f - (iou - (rho2 / c2 + pen));
 }
 
 // kTail: C % 4 != 0, the last group of 4 classes of a location is partial.  Its lanes c + e >= C add no loss and no
@@ -915,6 +844,7 @@ extern "C" int dsl_atss_assign(const dsl_fcos_desc* d, const dsl_atss_desc* a, v
 extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   FcK k;
   if (fill(d, k)) return -1;
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_GFL), "dsl_fcos_loss: a DSL_HEAD_GFL descriptor's loss is dsl_gfl_loss");
   DSL_CHECK(d->labels && d->bbox_targets && d->cls_weight && d->pos_weight && d->cls_logits && d->regctr &&
                 d->scales && d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses,
             "dsl_fcos_loss: null pointer");

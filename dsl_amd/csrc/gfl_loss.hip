@@ -1,0 +1,413 @@
+// GFLHead on the HIP step: the quality pass (IoU score and weight of every positive, the second normaliser) and the loss pass
+// (Quality Focal Loss, box loss and Distribution Focal Loss with their gradients, one launch) of a dsl_gfl_desc.
+// Restates mmdet/models/dense_heads/gfl_head.py:15-48 (Integral), :210-296 (loss_single), :348-370 (avg_factor),
+// mmdet/models/losses/gfocal_loss.py:11-78 (quality_focal_loss, distribution_focal_loss), mmdet/core/bbox/transforms.py:165-186
+// (bbox2distance) and bbox_overlaps(is_aligned=True) (iou2d_calculator.py:212-260); semantics: include/dsl_hip.h.
+//
+// Positives are a few hundred among tens of thousands of locations, and each costs 4 (reg_max + 1) loads and exponentials.  They
+// are neither compacted into a list (a second launch and an ordering to keep the sums reproducible) nor left to single lanes (a
+// wavefront would run the 68-wide row serially for one active lane): each wavefront takes 64 consecutive locations, ballots its
+// positives and processes them one after the other with all 64 lanes - 16 lanes per box side, two bins per lane, reductions inside
+// the 16-lane group - so every branch is wavefront-uniform.  The rows of the non-positives are zeroed by the same wavefront with
+// 16-byte stores, several rows per store.
+#include "common.hpp"
+#pragma clang fp contract(off)
+#include "box_loss.hpp"
+
+namespace {
+
+struct GfK {
+  int nlvl, n, C, R, M;
+  int h[DSL_MAX_SEG], w[DSL_MAX_SEG], stride[DSL_MAX_SEG];
+  int mstart[DSL_MAX_SEG + 1];
+  const long long* labels; const float* bbox_targets; const float* cls_weight;
+  const float* cls; int ld_cls;
+  const float* rc; int ld_rc;
+  const float* scales; const float* norm;
+  float inv_world, grad_scale;
+  uint16_t* g_cls; int ld_gcls; uint16_t* g_rc; int ld_grc;
+  float* score; float* weight;
+  float* part;            // block records (fixed-order second pass, no float atomics)
+  int box_kind;
+  float box_eps, beta, w_cls, w_bbox, w_dfl;
+  float tmax;             // reg_max - 0.1 (bbox2distance's clamp, transforms.py:183-184)
+};
+
+__device__ __forceinline__ void gfl_loc(const GfK& p, int m, int& lvl, int& y, int& x) {
+  lvl = 0;
+#pragma unroll
+  for (int s = 1; s < DSL_MAX_SEG; ++s)
+    if (s < p.nlvl && m >= p.mstart[s]) lvl = s;
+  const int q = m - p.mstart[lvl];
+  const int hw = p.h[lvl] * p.w[lvl];
+  const int r = q - (q / hw) * hw;
+  y = r / p.w[lvl];
+  x = r - y * p.w[lvl];
+}
+
+// reductions inside a 16-lane group (one box side)
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float group_max(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// One positive location, the whole wavefront: lane = 16 k + j holds bins j and j + 16 of side k (R <= 17).  raw = the predictor's
+// logits, z = scale * raw, p = softmax(z_k), lse = log sum exp z_k, d[0..3] = the four sides' expectations (gfl_head.py:15-48).
+struct GflRow {
+  bool has0, has1;
+  float raw0, raw1, z0, z1, p0, p1, lse, dk, d[4], sc;
+};
+__device__ __forceinline__ void gfl_row(const GfK& p, int m, int lvl, int lane, GflRow& o) {
+  const int k = lane >> 4, j = lane & 15;
+  o.has0 = j < p.R;
+  o.has1 = j + 16 < p.R;
+  const float* row = p.rc + (long long)m * p.ld_rc + k * p.R;
+  o.sc = p.scales[lvl];
+  o.raw0 = o.has0 ? row[j] : 0.f;
+  o.raw1 = o.has1 ? row[j + 16] : 0.f;
+  o.z0 = o.raw0 * o.sc;
+  o.z1 = o.raw1 * o.sc;
+  const float ninf = -__builtin_inff();
+  const float mx = group_max(fmaxf(o.has0 ? o.z0 : ninf, o.has1 ? o.z1 : ninf));      // (bins 0 and 1 always exist: finite)
+  const float e0 = o.has0 ? expf(o.z0 - mx) : 0.f, e1 = o.has1 ? expf(o.z1 - mx) : 0.f;
+  const float S = group_sum(e0 + e1);
+  o.p0 = e0 / S;
+  o.p1 = e1 / S;
+  o.lse = mx + logf(S);
+  o.dk = group_sum((float)j * o.p0 + (float)(j + 16) * o.p1);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) o.d[q] = __shfl(o.dk, 16 * q, 64);
+}
+
+__device__ __forceinline__ float gfl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ---- quality pass ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gfl_quality_kernel(const GfK p) {
+  __shared__ float sh[16];
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  const int base = m - lane;
+  const bool pos = m < p.M && (int)p.labels[m] < p.C;
+  float my_s = 0.f, my_w = 0.f;
+  unsigned long long mask = __ballot(pos);
+  while (mask) {
+    const int r = __ffsll((long long)mask) - 1;
+    mask &= mask - 1;
+    const int mm = base + r;
+    int lvl, y, x;
+    gfl_loc(p, mm, lvl, y, x);
+    GflRow o;
+    gfl_row(p, mm, lvl, lane, o);
+    const float s = (float)p.stride[lvl];
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p.bbox_targets + 4ll * mm);
+    const float X1 = t[0] / s, Y1 = t[1] / s, X2 = t[2] / s, Y2 = t[3] / s;
+    const float x1 = (float)x - o.d[0], y1 = (float)y - o.d[1], x2 = (float)x + o.d[2], y2 = (float)y + o.d[3];
+    // bbox_overlaps(is_aligned=True), mode 'iou', eps 1e-6
+    const float a1 = (x2 - x1) * (y2 - y1), a2 = (X2 - X1) * (Y2 - Y1);
+    const float iw = fmaxf(fminf(x2, X2) - fmaxf(x1, X1), 0.f), ih = fmaxf(fminf(y2, Y2) - fmaxf(y1, Y1), 0.f);
+    const float ov = iw * ih;
+    const float iou = ov / fmaxf(a1 + a2 - ov, 1e-6f);
+    // max_c sigmoid(cls): the sigmoid of the largest logit (sigmoid is monotonic)
+    float best = -__builtin_inff();
+    const float* c = p.cls + (long long)mm * p.ld_cls;
+    for (int i = lane; i < p.C; i += 64) best = fmaxf(best, c[i]);
+#pragma unroll
+    for (int q = 32; q > 0; q >>= 1) best = fmaxf(best, __shfl_xor(best, q, 64));
+    const float wv = gfl_sigmoid(best);
+    if (lane == r) {
+      my_s = iou;
+      my_w = wv;
+    }
+  }
+  if (m < p.M) {
+    p.score[m] = my_s;
+    p.weight[m] = my_w;
+  }
+  const float bs = block_sum(my_w, sh);
+  if (threadIdx.x == 0) p.part[blockIdx.x] = bs;
+}
+
+// out[0] = sum_b part[b], in a fixed order; one workgroup
+constexpr int GFL_FIN_T = 256;
+__global__ __launch_bounds__(GFL_FIN_T) void gfl_sum_kernel(const float* __restrict__ part, int nblocks, float* out) {
+  __shared__ float sh[GFL_FIN_T];
+  float a = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += GFL_FIN_T) a += part[b];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < GFL_FIN_T; ++k) t += sh[k];
+    out[0] = t;
+  }
+}
+
+// ---- Quality Focal Loss of one logit and dloss/dx (gfocal_loss.py:11-52) ---------------------------------------------------------
+// negative: BCE(x, 0) p^beta; the positive's label column: BCE(x, t) |t - p|^beta with t = the IoU score, a constant.
+// d/dx = p^beta (beta q sp + p), and sign(p - t) (a^(beta + 1) + beta BCE p q a^(beta - 1)) with a = |t - p|; a == 0: 0.
+__device__ __forceinline__ void qfl_fb(float x, bool pos, float t, float beta, bool beta2, float& loss, float& grad) {
+  const float e = __expf(-fabsf(x));
+  const float l1p = log1pf(e);
+  const float inv = 1.f / (1.f + e);
+  const float pp = x >= 0.f ? inv : e * inv;   // sigmoid(x)
+  const float q = x >= 0.f ? e * inv : inv;    // sigmoid(-x)
+  if (!pos) {
+    const float sp = fmaxf(x, 0.f) + l1p;      // -log(1 - p)
+    const float mod = beta2 ? pp * pp : powf(pp, beta);
+    loss = mod * sp;
+    grad = mod * (beta * q * sp + pp);
+    return;
+  }
+  const float bce = fmaxf(x, 0.f) - x * t + l1p;
+  const float a = fabsf(t - pp);
+  const float sg = pp > t ? 1.f : -1.f;
+  if (beta2) {
+    loss = bce * (a * a);
+    grad = sg * a * (a * a + 2.f * bce * pp * q);
+  } else if (a == 0.f) {
+    loss = bce * powf(0.f, beta);
+    grad = 0.f;
+  } else {
+    const float mod = powf(a, beta);
+    loss = bce * mod;
+    grad = sg * (mod * a + beta * bce * pp * q * (mod / a));
+  }
+}
+
+// ---- loss pass: block records [cls, 0, bbox, dfl, g_scale x 5, pad] ---------------------------------------------------------------
+template <bool kTail>
+__global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
+  __shared__ float sh[16];
+  const int M = p.M, C = p.C;
+  const int c4 = kTail ? (C + 3) / 4 : C / 4;
+  const float num = fmaxf(p.norm[0] * p.inv_world, 1.0f);
+  const float avg = fmaxf(p.norm[1] * p.inv_world, 1.0f);
+  const bool beta2 = p.beta == 2.f;
+
+  // ---------------- QFL: one thread per 4 consecutive classes of one location ----------
+  float lsum = 0.f;
+  const long long total = (long long)M * c4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int m = (int)(i / c4);
+    const int c = (int)(i - (long long)m * c4) * 4;
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(p.cls + (long long)m * p.ld_cls + c);
+    const int label = (int)p.labels[m];
+    const float wgt = p.cls_weight[m];
+    const float gs = wgt / num * p.grad_scale * p.w_cls;
+    const bool mine = label >= c && label < c + 4 && label < C;
+    const float sc = mine ? p.score[m] : 0.f;
+    float g[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float l, d;
+      qfl_fb(xv[e], mine && label == c + e, sc, p.beta, beta2, l, d);
+      if (kTail && c + e >= C) l = d = 0.f;
+      lsum += l * wgt;
+      g[e] = d * gs;
+    }
+    u32x2 o = {pack2bf(g[0], g[1]), pack2bf(g[2], g[3])};
+    *reinterpret_cast<u32x2*>(p.g_cls + (long long)m * p.ld_gcls + c) = o;
+  }
+  lsum = block_sum(lsum, sh);
+  float* rec = p.part + 16ll * blockIdx.x;
+  if (threadIdx.x == 0) {
+    rec[0] = lsum;
+    rec[1] = 0.f;
+  }
+
+  // ---------------- boxes + DFL: one wavefront per 64 consecutive locations ----------------------
+  float bsum = 0.f, dsum = 0.f;
+  float gsc[DSL_MAX_SEG] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int k = lane >> 4, j = lane & 15;
+  const int nchunk = (M + 63) / 64;
+  const int lpr = p.ld_grc / 8;          // 16-byte stores per row of g_rc (a power of two <= 64)
+  const int rps = 64 / lpr;              // rows per wavefront store
+  for (int ch = blockIdx.x * 4 + wave; ch < nchunk; ch += gridDim.x * 4) {
+    const int base = ch * 64;
+    const int m = base + lane;
+    const bool pos = m < M && (int)p.labels[m] < C;
+    unsigned long long mask = __ballot(pos);
+    for (int r0 = 0; r0 < 64; r0 += rps) {
+      const int r = r0 + lane / lpr;
+      if (base + r < M && !((mask >> r) & 1ull))
+        *reinterpret_cast<u32x4*>(p.g_rc + (long long)(base + r) * p.ld_grc + (lane % lpr) * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+    while (mask) {
+      const int r = __ffsll((long long)mask) - 1;
+      mask &= mask - 1;
+      const int mm = base + r;
+      int lvl, y, x;
+      gfl_loc(p, mm, lvl, y, x);
+      GflRow o;
+      gfl_row(p, mm, lvl, lane, o);
+      const float s = (float)p.stride[lvl];
+      const f32x4 t = *reinterpret_cast<const f32x4*>(p.bbox_targets + 4ll * mm);
+      const float X1 = t[0] / s, Y1 = t[1] / s, X2 = t[2] / s, Y2 = t[3] / s;
+      const float fx = (float)x, fy = (float)y;
+      const float x1 = fx - o.d[0], y1 = fy - o.d[1], x2 = fx + o.d[2], y2 = fy + o.d[3];
+      const float wv = p.weight[mm];
+      float dl[4];
+      const float bl = p.box_kind <= DSL_BOX_IOU_LOG ? box_loss_giou(p.box_kind == DSL_BOX_IOU_LOG, x1, y1, x2, y2, X1, Y1, X2, Y2, dl)
+                                                     : box_loss_ext(p.box_kind, p.box_eps, x1, y1, x2, y2, X1, Y1, X2, Y2, dl);
+      const float coef_b = wv / avg * p.grad_scale * p.w_bbox;
+      const float coef_d = wv / avg * p.grad_scale * p.w_dfl * 0.25f;
+      // x1 = x - d0, y1 = y - d1, x2 = x + d2, y2 = y + d3
+      const float ddk = coef_b != 0.f ? coef_b * (k == 0 ? -dl[0] : k == 1 ? -dl[1] : k == 2 ? dl[2] : dl[3]) : 0.f;
+      // DFL (gfocal_loss.py:55-78) against bbox2distance's clamped target of this side
+      const float td = k == 0 ? fx - X1 : k == 1 ? fy - Y1 : k == 2 ? X2 - fx : Y2 - fy;
+      const float tt = fminf(fmaxf(td, 0.f), p.tmax);
+      const float lf = floorf(tt);
+      const int li = (int)lf;
+      const float wl = (lf + 1.f) - tt, wr = tt - lf;
+      const float s0 = j == li ? wl : (j == li + 1 ? wr : 0.f);
+      const float s1 = j + 16 == li ? wl : (j + 16 == li + 1 ? wr : 0.f);
+      const float zt = group_sum((o.has0 ? s0 * o.z0 : 0.f) + (o.has1 ? s1 * o.z1 : 0.f));
+      const float dfl = o.lse * wl + o.lse * wr - zt;      // CE(z, l) wl + CE(z, l + 1) wr
+      const float g0 = o.has0 ? ddk * (o.p0 * ((float)j - o.dk)) + coef_d * (o.p0 * wl + o.p0 * wr - s0) : 0.f;
+      const float g1 = o.has1 ? ddk * (o.p1 * ((float)(j + 16) - o.dk)) + coef_d * (o.p1 * wl + o.p1 * wr - s1) : 0.f;
+      uint16_t* gr = p.g_rc + (long long)mm * p.ld_grc + k * p.R;
+      if (o.has0) gr[j] = f2bf(g0 * o.sc);
+      if (o.has1) gr[j + 16] = f2bf(g1 * o.sc);
+      // the row's padding columns 4R .. ld_grc: zero, so that every row of g_rc is rewritten whole by every launch
+      for (int i = 4 * p.R + lane; i < p.ld_grc; i += 64) p.g_rc[(long long)mm * p.ld_grc + i] = 0;
+      const float gs = g0 * o.raw0 + g1 * o.raw1;
+#pragma unroll
+      for (int l = 0; l < DSL_MAX_SEG; ++l) gsc[l] += l == lvl ? gs : 0.f;
+      if (lane == 0) bsum += wv * bl;
+      if (j == 0) dsum += wv * dfl;
+    }
+  }
+  bsum = block_sum(bsum, sh);
+  dsum = block_sum(dsum, sh);
+  if (threadIdx.x == 0) {
+    rec[2] = bsum;
+    rec[3] = dsum;
+  }
+#pragma unroll
+  for (int l = 0; l < DSL_MAX_SEG; ++l) {
+    const float v = block_sum(gsc[l], sh);
+    if (threadIdx.x == 0) rec[4 + l] = v;
+  }
+#pragma unroll
+  for (int l = 4 + DSL_MAX_SEG; l < 16; ++l)
+    if (threadIdx.x == 0) rec[l] = 0.f;
+}
+
+// fixed-order sum of the 16-float block records -> losses[4] (cls, bbox, dfl, 0), g_scales[5], logvec[4] (cls, bbox, dfl, their sum)
+__global__ __launch_bounds__(GFL_FIN_T) void gfl_finalize_kernel(const float* __restrict__ part, int nblocks, float* losses, float* g_scales,
+                                                                 const float* norm, float inv_world, float* logvec, float w_cls,
+                                                                 float w_bbox, float w_dfl) {
+  __shared__ float sh[GFL_FIN_T];
+  constexpr int V = 16, Q = GFL_FIN_T / V;
+  const int v = threadIdx.x % V, q = threadIdx.x / V;
+  float a = 0.f;
+#pragma unroll 8
+  for (int b = q; b < nblocks; b += Q) a += part[(long long)b * V + v];
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  float fv = 0.f;
+  if (threadIdx.x < V) {
+    float t = 0.f;
+    for (int i = 0; i < Q; ++i) t += sh[i * V + threadIdx.x];
+    const float num = fmaxf(norm[0] * inv_world, 1.0f), avg = fmaxf(norm[1] * inv_world, 1.0f);
+    if (threadIdx.x == 0) losses[0] = fv = t / num * w_cls;
+    else if (threadIdx.x == 1) losses[3] = 0.f;
+    else if (threadIdx.x == 2) losses[1] = fv = t / avg * w_bbox;
+    else if (threadIdx.x == 3) losses[2] = fv = t / avg * (w_dfl * 0.25f);
+    else if (threadIdx.x - 4 < DSL_MAX_SEG) g_scales[threadIdx.x - 4] = t;
+  }
+  if (logvec) {      // the log vector of _parse_losses (detectors/base.py:175-208): the loss terms and their sum
+    __syncthreads();
+    if (threadIdx.x < 4) sh[threadIdx.x] = fv;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const float cls = sh[0], bbox = sh[2], dfl = sh[3];
+      logvec[0] = cls; logvec[1] = bbox; logvec[2] = dfl; logvec[3] = (cls + bbox) + dfl;
+    }
+  }
+}
+
+int gfl_fill(const dsl_gfl_desc* g, GfK& k, const char* who) {
+  DSL_CHECK(g, "%s: null descriptor", who);
+  const dsl_fcos_desc* d = &g->fcos;
+  DSL_CHECK(d->nlvl >= 1 && d->nlvl <= DSL_MAX_SEG && d->n >= 1 && d->num_classes >= 1, "%s: bad descriptor", who);
+  DSL_CHECK((d->head_flags & DSL_HEAD_GFL) && (d->head_flags & DSL_HEAD_ATSS) && (d->head_flags & DSL_HEAD_LOSS_EXT),
+            "%s: a dsl_gfl_desc needs DSL_HEAD_GFL | DSL_HEAD_ATSS | DSL_HEAD_LOSS_EXT in fcos.head_flags", who);
+  DSL_CHECK((d->head_flags & (DSL_HEAD_INSIDE_BOX | DSL_HEAD_RAW_TARGETS | DSL_HEAD_EXP_DECODE)) == 0,
+            "%s: DSL_HEAD_GFL goes with no FCOS assignment / decode flag", who);      // (DSL_HEAD_IOU_LOSS: replaced by fcos.box_kind)
+  DSL_CHECK(!d->ctr && !d->g_ctr, "%s: a GFL head has no centerness", who);
+  DSL_CHECK(d->loss_weight == 1.0f && d->soft_weight == 0.f, "%s: no DSL stream weight / sisoft term", who);
+  DSL_CHECK(g->reg_max >= 1 && g->reg_max <= DSL_GFL_MAX_REG, "%s: reg_max must be in 1..%d, got %d", who, DSL_GFL_MAX_REG, g->reg_max);
+  memset(&k, 0, sizeof(k));
+  k.nlvl = d->nlvl; k.n = d->n; k.C = d->num_classes; k.R = g->reg_max + 1;
+  long long m = 0;
+  for (int l = 0; l < d->nlvl; ++l) {
+    DSL_CHECK(d->h[l] >= 1 && d->w[l] >= 1 && d->stride[l] >= 1, "%s: bad level %d", who, l);
+    k.h[l] = d->h[l]; k.w[l] = d->w[l]; k.stride[l] = d->stride[l];
+    k.mstart[l] = (int)m;
+    m += (long long)d->n * d->h[l] * d->w[l];
+  }
+  DSL_CHECK(m < (1ll << 31) - 256, "%s: too many locations", who);
+  k.mstart[d->nlvl] = (int)m;
+  k.M = (int)m;
+  DSL_CHECK(d->labels && d->bbox_targets && d->cls_weight && d->cls_logits && d->regctr && d->scales && d->stats && g->score && g->weight,
+            "%s: null pointer", who);
+  DSL_CHECK(d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= 4 * k.R, "%s: ld_cls / ld_rc do not hold C / 4 (reg_max + 1) columns", who);
+  DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d) && ((uintptr_t)d->workspace & 15) == 0,
+            "%s: workspace too small or not 16-byte aligned", who);
+  k.labels = (const long long*)d->labels; k.bbox_targets = d->bbox_targets; k.cls_weight = d->cls_weight;
+  k.cls = d->cls_logits; k.ld_cls = d->ld_cls; k.rc = d->regctr; k.ld_rc = d->ld_rc;
+  k.scales = d->scales; k.norm = d->norm; k.inv_world = d->inv_world; k.grad_scale = d->grad_scale;
+  k.g_cls = (uint16_t*)d->g_cls; k.ld_gcls = d->ld_gcls; k.g_rc = (uint16_t*)d->g_rc; k.ld_grc = d->ld_grc;
+  k.score = g->score; k.weight = g->weight; k.part = (float*)d->workspace;
+  k.tmax = (float)((double)g->reg_max - 0.1);
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int dsl_gfl_quality(const dsl_gfl_desc* g, void* stream) {
+  GfK k;
+  if (gfl_fill(g, k, "dsl_gfl_quality")) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = (k.M + 255) / 256;      // (<= the workspace's (M + 255) / 256 * 2 floats)
+  hipLaunchKernelGGL(gfl_quality_kernel, dim3(nb), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(gfl_sum_kernel, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, nb, g->fcos.stats + 1);
+  DSL_LAUNCH_CHECK("gfl_quality_kernel");
+  return 0;
+}
+
+extern "C" int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream) {
+  GfK k;
+  if (gfl_fill(g, k, "dsl_gfl_loss")) return -1;
+  const dsl_fcos_desc* d = &g->fcos;
+  DSL_CHECK(d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses, "dsl_gfl_loss: null pointer");
+  DSL_CHECK(d->ld_gcls % 4 == 0 && d->ld_gcls >= d->ld_cls, "dsl_gfl_loss: ld_gcls must be a multiple of 4 and >= ld_cls");
+  DSL_CHECK(d->ld_grc >= 8 && d->ld_grc <= 512 && (d->ld_grc & (d->ld_grc - 1)) == 0 && d->ld_grc >= 4 * k.R && ((uintptr_t)d->g_rc & 15) == 0,
+            "dsl_gfl_loss: ld_grc must be a power of two in 8..512 and >= 4 (reg_max + 1), g_rc 16-byte aligned");
+  DSL_CHECK(d->box_kind >= DSL_BOX_GIOU && d->box_kind <= DSL_BOX_CIOU, "dsl_gfl_loss: box_kind is not a DSL_BOX_* value");
+  DSL_CHECK(d->box_kind < DSL_BOX_DIOU || (d->box_eps > 0.f && d->box_eps < 1.f), "dsl_gfl_loss: DIoU / CIoU need 0 < box_eps < 1");
+  DSL_CHECK(d->w_cls >= 0.f && d->w_cls < 1e30f && d->w_bbox >= 0.f && d->w_bbox < 1e30f && g->w_dfl >= 0.f && g->w_dfl < 1e30f,
+            "dsl_gfl_loss: loss weights must be finite and >= 0");
+  DSL_CHECK(g->qfl_beta >= 0.f && g->qfl_beta < 1e30f, "dsl_gfl_loss: qfl_beta must be finite and >= 0");
+  k.box_kind = d->box_kind; k.box_eps = d->box_eps; k.beta = g->qfl_beta;
+  k.w_cls = d->w_cls; k.w_bbox = d->w_bbox; k.w_dfl = g->w_dfl;
+  hipStream_t st = (hipStream_t)stream;
+  int blocks = (int)(((long long)k.M * ((k.C + 3) / 4) + 255) / 256);
+  if (blocks > 2048) blocks = 2048;      // (the workspace holds 2048 records of 16 floats)
+  if (k.C % 4 != 0)
+    hipLaunchKernelGGL(gfl_loss_kernel<true>, dim3(blocks), dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL(gfl_loss_kernel<false>, dim3(blocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(gfl_finalize_kernel, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, blocks, d->losses, d->g_scales, d->norm,
+                     d->inv_world, d->logvec, k.w_cls, k.w_bbox, k.w_dfl);
+  DSL_LAUNCH_CHECK("gfl_loss_kernel");
+  return 0;
+}

@@ -237,6 +237,24 @@ class CrossEntropyLoss(_LossCfg):
         _expect(use_sigmoid and not use_mask and class_weight is None, 'sigmoid BCE centerness loss')
 
 
+@LOSSES.register_module()
+class QualityFocalLoss(_LossCfg):
+    """mmdet/models/losses/gfocal_loss.py:11-52,81-133: the classification loss of GFLHead, whose target is the IoU of the decoded
+    prediction with the assigned box (dsl_gfl_desc.qfl_beta, dsl_fcos_desc.w_cls)."""
+
+    def __init__(self, use_sigmoid=True, beta=2.0, **kw):
+        super().__init__(**kw)
+        _expect(use_sigmoid, 'QualityFocalLoss use_sigmoid=True (the reference builds only the sigmoid form)')
+        _expect(isinstance(beta, (int, float)) and 0.0 <= float(beta) < float('inf'), f'QualityFocalLoss beta >= 0 (got {beta!r})')
+        self.beta = float(beta)
+
+
+@LOSSES.register_module()
+class DistributionFocalLoss(_LossCfg):
+    """mmdet/models/losses/gfocal_loss.py:55-78,136-185: cross entropy against the two bins around the target distance
+    (dsl_gfl_desc.w_dfl)."""
+
+
 @HEADS.register_module()
 class FCOSHead(nn.Module):
     def __init__(self, num_classes, in_channels, regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8)),
@@ -293,6 +311,40 @@ def _cfg_get(cfg, key, default=None):
     return cfg.get(key, default) if hasattr(cfg, 'get') else getattr(cfg, key, default)
 
 
+def _square_anchor_scale(anchor_generator):
+    """octave_base_scale of the one square anchor per location that ATSSHead / GFLHead are built for (anchor_generator.py:99-143)."""
+    ag = dict(anchor_generator)
+    _expect(ag.pop('type', None) == 'AnchorGenerator', "anchor_generator type='AnchorGenerator'")
+    _expect(list(ag.pop('ratios', [])) == [1.0], 'anchor_generator ratios=[1.0] (one square anchor per location)')
+    _expect(ag.pop('scales_per_octave', None) == 1 and ag.get('scales') is None, 'anchor_generator scales_per_octave=1 (no scales list)')
+    obs = ag.pop('octave_base_scale', None)
+    _expect(isinstance(obs, (int, float)) and 0.0 < float(obs) < float('inf'), f'anchor_generator octave_base_scale > 0 (got {obs!r})')
+    _expect(list(ag.pop('strides', [])) == [8, 16, 32, 64, 128], 'anchor_generator strides 8..128')
+    _expect(float(ag.pop('center_offset', 0.0)) == 0.0, 'anchor_generator center_offset=0')
+    ag.pop('scales', None)
+    _expect(ag.pop('base_sizes', None) is None and ag.pop('centers', None) is None and ag.pop('scale_major', True),
+            'anchor_generator default base_sizes / centers / scale_major')
+    _expect(not ag, f'anchor_generator: unknown arguments {sorted(ag)}')
+    return float(obs)
+
+
+def _atss_topk(train_cfg):
+    """topk of train_cfg.assigner = ATSSAssigner (9 without a train_cfg), with the refusals of what dsl_atss_assign does not build."""
+    topk = 9
+    if train_cfg is not None:
+        asg = dict(_cfg_get(train_cfg, 'assigner') or {})
+        _expect(asg.pop('type', None) == 'ATSSAssigner', "train_cfg.assigner type='ATSSAssigner'")
+        topk = asg.pop('topk', None)
+        _expect(isinstance(topk, int) and 1 <= topk <= 16, f'train_cfg.assigner topk in 1..16 (got {topk!r})')
+        _expect(float(asg.pop('ignore_iof_thr', -1)) <= 0, 'train_cfg.assigner ignore_iof_thr <= 0 (gt_bboxes_ignore is not read)')
+        ic = asg.pop('iou_calculator', dict(type='BboxOverlaps2D'))
+        _expect(dict(ic) == dict(type='BboxOverlaps2D'), 'train_cfg.assigner iou_calculator BboxOverlaps2D')
+        _expect(not asg, f'train_cfg.assigner: unknown arguments {sorted(asg)}')
+        _expect(_cfg_get(train_cfg, 'allowed_border', -1) == -1, 'train_cfg.allowed_border=-1')
+        _expect(_cfg_get(train_cfg, 'pos_weight', -1) <= 0, 'train_cfg.pos_weight=-1')
+    return topk
+
+
 @HEADS.register_module()
 class ATSSHead(nn.Module):
     """mmdet/models/dense_heads/atss_head.py:14-684 on AnchorHead (anchor_head.py:36-100): the FCOS network (GN-32 towers without
@@ -318,18 +370,7 @@ class ATSSHead(nn.Module):
         _expect(conv_cfg is None, 'conv_cfg=None (no DCN)')
         _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers (norm_cfg)')
         _expect(not reg_decoded_bbox, 'reg_decoded_bbox=False')
-        ag = dict(anchor_generator)
-        _expect(ag.pop('type', None) == 'AnchorGenerator', "anchor_generator type='AnchorGenerator'")
-        _expect(list(ag.pop('ratios', [])) == [1.0], 'anchor_generator ratios=[1.0] (one square anchor per location)')
-        _expect(ag.pop('scales_per_octave', None) == 1 and ag.get('scales') is None, 'anchor_generator scales_per_octave=1 (no scales list)')
-        obs = ag.pop('octave_base_scale', None)
-        _expect(isinstance(obs, (int, float)) and 0.0 < float(obs) < float('inf'), f'anchor_generator octave_base_scale > 0 (got {obs!r})')
-        _expect(list(ag.pop('strides', [])) == [8, 16, 32, 64, 128], 'anchor_generator strides 8..128')
-        _expect(float(ag.pop('center_offset', 0.0)) == 0.0, 'anchor_generator center_offset=0')
-        ag.pop('scales', None)
-        _expect(ag.pop('base_sizes', None) is None and ag.pop('centers', None) is None and ag.pop('scale_major', True),
-                'anchor_generator default base_sizes / centers / scale_major')
-        _expect(not ag, f'anchor_generator: unknown arguments {sorted(ag)}')
+        obs = _square_anchor_scale(anchor_generator)
         bc = dict(bbox_coder)
         _expect(bc.pop('type', None) == 'DeltaXYWHBBoxCoder', "bbox_coder type='DeltaXYWHBBoxCoder'")
         _expect(all(float(v) == 0.0 for v in bc.pop('target_means', (0., 0., 0., 0.))), 'bbox_coder target_means all 0')
@@ -338,18 +379,7 @@ class ATSSHead(nn.Module):
         _expect(bc.pop('clip_border', True) and not bc.pop('add_ctr_clamp', False), 'bbox_coder clip_border=True, add_ctr_clamp=False')
         bc.pop('ctr_clamp', None)
         _expect(not bc, f'bbox_coder: unknown arguments {sorted(bc)}')
-        topk = 9
-        if train_cfg is not None:
-            asg = dict(_cfg_get(train_cfg, 'assigner') or {})
-            _expect(asg.pop('type', None) == 'ATSSAssigner', "train_cfg.assigner type='ATSSAssigner'")
-            topk = asg.pop('topk', None)
-            _expect(isinstance(topk, int) and 1 <= topk <= 16, f'train_cfg.assigner topk in 1..16 (got {topk!r})')
-            _expect(float(asg.pop('ignore_iof_thr', -1)) <= 0, 'train_cfg.assigner ignore_iof_thr <= 0 (gt_bboxes_ignore is not read)')
-            ic = asg.pop('iou_calculator', dict(type='BboxOverlaps2D'))
-            _expect(dict(ic) == dict(type='BboxOverlaps2D'), 'train_cfg.assigner iou_calculator BboxOverlaps2D')
-            _expect(not asg, f'train_cfg.assigner: unknown arguments {sorted(asg)}')
-            _expect(_cfg_get(train_cfg, 'allowed_border', -1) == -1, 'train_cfg.allowed_border=-1')
-            _expect(_cfg_get(train_cfg, 'pos_weight', -1) <= 0, 'train_cfg.pos_weight=-1')
+        topk = _atss_topk(train_cfg)
         self.num_classes, self.strides = num_classes, (8, 16, 32, 64, 128)
         self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
         self.loss_cls = build_loss(loss_cls)
@@ -370,6 +400,61 @@ class ATSSHead(nn.Module):
         self.options = HeadOptions(box_loss=lbm.box_loss, box_eps=lbm.eps, focal_gamma=self.loss_cls.gamma, focal_alpha=self.loss_cls.alpha,
                                    cls_weight=self.loss_cls.loss_weight, bbox_weight=wb, ctr_weight=self.loss_centerness.loss_weight,
                                    assigner='atss', atss_topk=topk, anchor_scale=float(obs), delta_stds=stds)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    def effective_soft_weight(self, batch_size):
+        return 0.0
+
+
+@HEADS.register_module()
+class GFLHead(nn.Module):
+    """mmdet/models/dense_heads/gfl_head.py:50-647 on AnchorHead: ATSSHead's network and targets (dsl_atss_assign, one square anchor
+    per location) without centerness, a box predictor of 4 (reg_max + 1) distribution logits decoded by the Integral layer, Quality
+    Focal Loss, a box loss and Distribution Focal Loss weighted by the location's best class score (dsl_gfl_quality, dsl_gfl_loss,
+    DSL_HEAD_GFL).  The signature is the reference's; what the kernels do not build is refused, naming the option."""
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_dfl=dict(type='DistributionFocalLoss', loss_weight=0.25), reg_max=16, init_cfg=None, feat_channels=256,
+                 anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0], strides=[4, 8, 16, 32, 64]),
+                 bbox_coder=None, reg_decoded_bbox=False, loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None, **kw):
+        super().__init__()
+        class_layout(num_classes)
+        for k in ('soft_weight', 'soft_warm_up', 'loss_weight'):
+            _expect(k not in kw, f'GFLHead: no DSL key {k} (the scale-invariant soft term and the per-stream loss_weight are FCOSHead options)')
+        _expect(not kw, f'GFLHead: unknown arguments {sorted(kw)}')
+        _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
+        _expect(stacked_convs == 4, 'stacked_convs=4')
+        _expect(conv_cfg is None, 'conv_cfg=None (no DCN)')
+        _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers (norm_cfg)')
+        _expect(not reg_decoded_bbox, 'reg_decoded_bbox=False')
+        _expect(isinstance(reg_max, int) and not isinstance(reg_max, bool) and 1 <= reg_max <= 16,
+                f'reg_max in 1..16 (got {reg_max!r}; DSL_GFL_MAX_REG)')
+        obs = _square_anchor_scale(anchor_generator)
+        # (the reference's GFLHead never calls its bbox_coder: boxes are distances from the anchor centre)
+        _expect(bbox_coder is None or dict(bbox_coder).get('type') == 'DeltaXYWHBBoxCoder', "bbox_coder: AnchorHead's DeltaXYWHBBoxCoder or none")
+        topk = _atss_topk(train_cfg)
+        self.num_classes, self.strides, self.reg_max = num_classes, (8, 16, 32, 64, 128), reg_max
+        self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
+        self.loss_cls = build_loss(loss_cls)
+        self.loss_dfl = build_loss(loss_dfl)
+        # (as ATSSHead: GIoULoss / IoULoss refuse a loss_weight in their own constructors; configs/gfl's GIoULoss(loss_weight=2.0) is
+        # taken off the dict and goes to the kernel as dsl_fcos_desc.w_bbox)
+        lb = dict(loss_bbox)
+        wb = 1.0
+        if lb.get('type') in ('GIoULoss', 'IoULoss'):
+            wb = _loss_weight(lb['type'], lb.pop('loss_weight', 1.0), lb.get('reduction', 'mean'))
+        self.loss_bbox = build_loss(lb)
+        _expect(isinstance(self.loss_cls, QualityFocalLoss), 'loss_cls: QualityFocalLoss(use_sigmoid=True, beta, loss_weight)')
+        _expect(isinstance(self.loss_dfl, DistributionFocalLoss), 'loss_dfl: DistributionFocalLoss(loss_weight)')
+        _expect(isinstance(self.loss_bbox, (GIoULoss, IoULoss, DIoULoss)), 'loss_bbox: GIoULoss, IoULoss, DIoULoss or CIoULoss')
+        lbm = self.loss_bbox
+        wb = wb if isinstance(lbm, (GIoULoss, IoULoss)) else lbm.loss_weight
+        self.bbox_weight = wb
+        self.options = HeadOptions(box_loss=lbm.box_loss, box_eps=lbm.eps, cls_weight=self.loss_cls.loss_weight, bbox_weight=wb,
+                                   assigner='atss', atss_topk=topk, anchor_scale=obs, head_kind='gfl', reg_max=reg_max,
+                                   qfl_beta=self.loss_cls.beta, dfl_weight=self.loss_dfl.loss_weight)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
 
     def effective_soft_weight(self, batch_size):
@@ -714,7 +799,16 @@ class FCOS(nn.Module):
         work = None
         # an ATSS head's valid anchors come from each image's pad_shape (atss_head.py:615-617); absent: the batch tensor's size
         pad = [tuple(m.get('pad_shape', (H, W)))[:2] for m in img_metas] if lp.atss is not None else None
-        if ws > 1:
+        if lp.gfl is not None:
+            # a GFL head's second normaliser, the sum of the positives' best class scores, exists only behind the predictors: the
+            # quality pass, then the 2-float all-reduce of (num_total, that sum), then the loss (gfl_head.py:348-366)
+            fwd.run()
+            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
+            plan.assign_ops.run()
+            plan.quality_ops.run()
+            if ws > 1 and not self.comm_off:
+                self._all_reduce_async(lp.stats[:2], after_current=True).wait()
+        elif ws > 1:
             # target assignment first: the reduce_mean of (num_pos, sum centerness targets) - one 2-float all-reduce
             # (fcos_head.py:264-274) - then runs under the forward pass
             lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
@@ -740,7 +834,7 @@ class FCOS(nn.Module):
                 eager_now = True
         self._eager_now = eager_now
         out = _TrainStepFn.apply(self._anchor, self, plan)
-        losses = _LossDict(loss_cls=out[0], loss_bbox=out[1], loss_centerness=out[2])
+        losses = _LossDict(loss_cls=out[0], loss_bbox=out[1], **{'loss_dfl' if lp.gfl is not None else 'loss_centerness': out[2]})
         if sw != 0.0:
             losses['loss_sisoft'] = out[3]
         losses.vec = out[:len(losses)]      # the same scalars as ONE tensor: lets _parse_losses avoid per-key device ops
@@ -996,4 +1090,14 @@ class ATSS(FCOS):
 
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
         _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'ATSSHead', "ATSS with bbox_head type='ATSSHead'")
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
+
+
+@DETECTORS.register_module()
+class GFL(FCOS):
+    """mmdet/models/detectors/gfl.py:5-18: SingleStageDetector with a GFLHead, on the FCOS detector's machinery (the same network
+    up to the box predictor's width; assignment, box decode, losses and their normalisers are the head's)."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
+        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'GFLHead', "GFL with bbox_head type='GFLHead'")
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)

@@ -148,8 +148,12 @@ class OpList:
         """atss: the head's dsl_atss_desc (dsl_atss_assign), None = dsl_fcos_assign."""
         self._add(L.OP_ASSIGN, d, p=(C.addressof(atss),) if atss is not None else ())
 
-    def loss(self, d):
-        self._add(L.OP_LOSS, d)
+    def loss(self, d, gfl=None):
+        """gfl: the head's dsl_gfl_desc (dsl_gfl_loss; `d` is its first member), None = dsl_fcos_loss."""
+        self._add(L.OP_LOSS, d, p=(C.addressof(gfl),) if gfl is not None else ())
+
+    def gfl_quality(self, gfl):
+        self._add(L.OP_GFL_QUALITY, gfl)
 
     def maxpool(self, x, y, n, h, w, c):
         self._add(L.OP_MAXPOOL, i=(n, h, w, c), p=(x, y))
@@ -223,7 +227,13 @@ class Plan:
             if self._fside:             # the regression tower's side stream: joined here, not at the end of the forward list,
                 self.loss_ops.join(self._fside)       # so that target upload + assignment run while it finishes
             self.loss_ops.prof(4, 1)
-            self.loss_ops.loss(self.lossplan.desc)
+            # a GFL head: the quality pass (score, weight, stats[1]) sits between the predictors and the exchange of stats[0:2]
+            # between ranks, which the detector runs between these two lists (gfl_head.py:348-366)
+            self.quality_ops = None
+            if self.lossplan.gfl is not None:
+                self.quality_ops, self.loss_ops = self.loss_ops, OpList()
+                self.quality_ops.gfl_quality(self.lossplan.gfl)
+            self.loss_ops.loss(self.lossplan.desc, self.lossplan.gfl)
             self._build_backward()
 
     # ---------------------------------------------------------------------------------------------
@@ -339,9 +349,9 @@ class Plan:
         # (centerness_on_reg=False: the classification predictor has conv_centerness as one more computed row / output column and
         # the regression predictor four, ParamStore.ctr_on_cls - the same two launches either way)
         ncls, cls_pad, cls_ld = st.cls_rows, st.cls_pad, st.logit_ld
-        nreg = 4 if st.ctr_on_cls else 5
-        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + 5) * 2304)
-        self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + 8) * 4.0
+        nreg = st.reg_rows
+        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + (nreg if st.gfl else 5)) * 2304)
+        self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + st.reg_ld) * 4.0
         f.prof(4, 0, self._head_flops, self._head_bytes)
         # fp8 forward of the tower convolutions (FCOS(fp8=dict(...)), BASELINE.json configs[4], off by default), DELAYED scaling
         # (round 6): every fp8 tensor is written by its producer's own pass - GroupNorm's apply pass writes the e4m3 copy of its output
@@ -417,12 +427,13 @@ class Plan:
                 xin, xin8 = act, act8
             self.tower[tower] = lays
         cls_logits = self.buf('cls_logits', self.M, cls_ld, dtype=torch.float32, zero=st.ctr_on_cls)      # (zero: the three floats behind the centerness column)
-        regctr = self.buf('regctr', self.M, 8, dtype=torch.float32, zero=True)
+        # (a GFL head: 4 (reg_max + 1) distribution logits per row, the launch shapes of a one- or two-tile classification predictor)
+        regctr = self.buf('regctr', self.M, st.reg_ld, dtype=torch.float32, zero=True)
         f.conv(ops.conv_desc(self.tower['cls_convs'][3]['act'], st.t16_ptr('head.cls_w'), cls_logits, n=N, grid=ls,
                              src_hw=ls, dst_hw=ls, cs=256, cd=ncls, cd_pad=cls_pad, ldd=cls_ld, kh=3, kw=3, stride=1, pad=1,
                              flags=L.CONV_OUT_F32, bias=st.t32_ptr('head.cls_b'), workspace=self.conv_ws))
         f.conv(ops.conv_desc(self.tower['reg_convs'][3]['act'], st.t16_ptr('head.regctr_w'), regctr, n=N, grid=ls,
-                             src_hw=ls, dst_hw=ls, cs=256, cd=nreg, cd_pad=64, ldd=8, kh=3, kw=3, stride=1, pad=1,
+                             src_hw=ls, dst_hw=ls, cs=256, cd=nreg, cd_pad=st.reg_pad, ldd=st.reg_ld, kh=3, kw=3, stride=1, pad=1,
                              flags=L.CONV_OUT_F32, bias=st.t32_ptr('head.regctr_b'), workspace=self.conv_ws_side),
                side=FSIDE)
         self._fside = FSIDE
@@ -702,7 +713,7 @@ class Plan:
         # the predictors' weight gradients need nothing from this pass but the loss gradients: first thing on the side stream
         self._wgrad(ol, None, lp.g_cls, self.tower['cls_convs'][3]['act'], N, ls, ls, cy=st.cls_pad, cd=st.cls_rows, wregion='head.cls_w',
                     bregion='head.cls_b', side=SIDE)
-        self._wgrad(ol, None, lp.g_rc, self.tower['reg_convs'][3]['act'], N, ls, ls, cy=64, cd=4 if st.ctr_on_cls else 5, wregion='head.regctr_w',
+        self._wgrad(ol, None, lp.g_rc, self.tower['reg_convs'][3]['act'], N, ls, ls, cy=st.reg_pad, cd=st.reg_rows, wregion='head.regctr_w',
                     bregion='head.regctr_b', side=SIDE)
         # (measured, tools/experiments_r2.txt (exp_r2t) / exp_r2u.sh: weight gradients that start while the head's large data-gradient launches
         # still run cost more than the idle side stream saves - predictors first: 5.97 vs 5.94 ms, tower halves: 6.10 vs 6.05)
@@ -732,7 +743,7 @@ class Plan:
                                                          cs_real=st.cls_rows)),
                                    tower, 3, sd), side=sd)
             else:
-                ol.conv(gn_records(wsf(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=64, cd=256, k=3, stride=1, pad=1, cs_real=4 if st.ctr_on_cls else 5)),
+                ol.conv(gn_records(wsf(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=st.reg_pad, cd=256, k=3, stride=1, pad=1, cs_real=st.reg_rows)),
                                    tower, 3, sd), side=sd)
         # layer by layer, both towers: their weight gradients go out in two groups of four (layers 3, 2 and layers 1, 0 of
         # both towers) as soon as the GroupNorm backward passes that produce their dY are queued - the side stream works from

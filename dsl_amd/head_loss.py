@@ -27,9 +27,17 @@ class FcosLossPlan:
         round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls.  The head's loss
         settings (box_loss, focal gamma / alpha, the loss weights) go into the descriptor: losses, logvec and the gradients are the
         weighted ones.  An ATSS head (head.assigner == 'atss'): the assignment is dsl_atss_assign, fed the images' pad_shape
-        (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554)."""
+        (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554).
+        A GFL head (head.head_kind == 'gfl'): the descriptor is a dsl_gfl_desc (`gfl`, whose first member is `desc`), the box
+        predictor's rows are 4 (reg_max + 1) floats / round_up(that, 64) gradient columns wide, quality() runs between the predictors
+        and the exchange of stats[0:2] and writes stats[1], loss() is dsl_gfl_loss; losses = (cls, bbox, dfl, 0)."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head
+        self.gfl = None
+        if head is not None and head.head_kind == 'gfl':
+            self.gfl = L.GflDesc()
+            self.LD_RC = 4 * (head.reg_max + 1)
+            self.LD_GRC = (self.LD_RC + 63) // 64 * 64
         self.ctr_col = None
         if head is not None and not head.centerness_on_reg:
             self.ctr_col = self.LD_CLS
@@ -66,7 +74,7 @@ class FcosLossPlan:
                             pad=torch.zeros(n, 2, dtype=torch.int32, pin_memory=pin), ev=None) for _ in range(4)]
         self._slot_i = 0
         self.desc = ops.fcos_desc(n=n, sizes=self.sizes, strides=strides, ranges=ranges, radius=radius,
-                                  num_classes=num_classes)
+                                  num_classes=num_classes, into=self.gfl.fcos if self.gfl is not None else None)
         ops.set_ptrs(self.desc, gt_boxes=self.gt_boxes, gt_labels=self.gt_labels, gt_off=self.gt_off,
                      labels=self.labels, bbox_targets=self.bbox_targets, assign_idx=self.assign_idx,
                      cls_weight=self.cls_weight, pos_weight=self.pos_weight, stats=self.stats,
@@ -76,7 +84,9 @@ class FcosLossPlan:
         self.desc.ld_gcls, self.desc.ld_grc = self.LD_GCLS, self.LD_GRC
         if head is not None:
             self.desc.head_flags = head.flags()
-            if not head.loss_is_default():      # box kind, focal gamma / alpha, the three loss weights (HEAD_LOSS_EXT is in the flags)
+            # box kind, focal gamma / alpha, the three loss weights, wherever HEAD_LOSS_EXT is in the flags: a head off the default
+            # loss family, and every GFL head (dsl_gfl_loss reads w_cls / w_bbox / box_kind with no default to fall back to)
+            if not head.loss_is_default() or self.gfl is not None:
                 head.fill_loss_desc(self.desc)
         if self.ctr_col is not None:
             self.desc.g_ctr, self.desc.ld_gctr = self.g_cls.data_ptr() + 2 * self.ctr_col, self.LD_GCLS
@@ -86,6 +96,13 @@ class FcosLossPlan:
             self.npos = torch.zeros(n, dtype=torch.int32, device=dev)
             self.atss.max_gt, self.atss.pad_shapes, self.atss.npos = max_gt, L.ptr(self.pad_shapes), L.ptr(self.npos)
             self.desc.atss = C.addressof(self.atss)
+        if self.gfl is not None:
+            self.score = torch.zeros(M, dtype=torch.float32, device=dev)
+            self.weight = torch.zeros(M, dtype=torch.float32, device=dev)
+            g = self.gfl
+            g.reg_max, g.qfl_beta, g.w_dfl = head.reg_max, head.qfl_beta, head.dfl_weight
+            g.score, g.weight = L.ptr(self.score), L.ptr(self.weight)
+            self.logvec = self.logvec[:4]      # cls, bbox, dfl, their sum
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         self.desc.workspace, self.desc.workspace_bytes = L.ptr(self.ws), need
@@ -163,5 +180,12 @@ class FcosLossPlan:
             return
         L.check(L.lib.dsl_fcos_assign(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_assign')
 
+    def quality(self):
+        """GFL only: score / weight of the positives and stats[1] = sum of the weights (dsl_gfl_quality)."""
+        L.check(L.lib.dsl_gfl_quality(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_quality')
+
     def loss(self):
+        if self.gfl is not None:
+            L.check(L.lib.dsl_gfl_loss(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_loss')
+            return
         L.check(L.lib.dsl_fcos_loss(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_loss')

@@ -279,8 +279,9 @@ def gn_desc(x, y, gamma, beta, stats, workspace=None, *, n, hw, c=256, groups=32
     return d
 
 
-def fcos_desc(*, n, sizes, strides, ranges, radius=1.5, num_classes=80):
-    d = L.FcosDesc()
+def fcos_desc(*, n, sizes, strides, ranges, radius=1.5, num_classes=80, into=None):
+    """into: an FcosDesc to fill instead of a new one (the first member of a GflDesc: writes go to the wrapping descriptor)."""
+    d = L.FcosDesc() if into is None else into
     d.nlvl, d.n = len(sizes), n
     d.h, d.w = _segs(sizes)
     d.stride = L.seg5(strides)

@@ -137,15 +137,45 @@ class HeadOptions:
     does not read - and the reference's predictor names (atss_cls, atss_reg, atss_centerness):
       atss_topk          ATSSAssigner(topk), 1..16
       anchor_scale       AnchorGenerator(octave_base_scale): the one square anchor of a location has side anchor_scale * stride
-      delta_stds         DeltaXYWHBBoxCoder(target_stds); the means are 0"""
+      delta_stds         DeltaXYWHBBoxCoder(target_stds); the means are 0
+    The head kind ('fcos'; 'gfl' = GFLHead, mmdet/models/dense_heads/gfl_head.py, dsl_gfl_desc of include/dsl_hip.h): a GFL head is an
+    ATSS head (assigner='atss' is forced, and with it conv_bias=False; anchor_scale and atss_topk count, delta_stds is not read; the FCOS
+    options center_sampling / norm_on_bbox / centerness_on_reg / iou_loss and focal_gamma / focal_alpha / ctr_weight are refused off their defaults) without centerness, whose box
+    predictor emits 4 (reg_max + 1) distribution logits - round_up(4 (reg_max + 1), 64) stored rows, fp32 rows 4 (reg_max + 1) wide - with
+    the predictor names gfl_cls / gfl_reg.  focal_gamma, focal_alpha and ctr_weight are not read:
+      reg_max            bins 0..reg_max per box side, 1..16 (the reference's configs use 16)
+      qfl_beta           QualityFocalLoss(beta) >= 0 (losses/gfocal_loss.py:11-52)
+      dfl_weight         DistributionFocalLoss(loss_weight) (losses/gfocal_loss.py:55-78)"""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
     BOX_KINDS = dict(giou=L.BOX_GIOU, iou=L.BOX_IOU_LOG, iou_linear=L.BOX_IOU_LINEAR, diou=L.BOX_DIOU, ciou=L.BOX_CIOU)
     ATSS_FIELDS = ('assigner', 'atss_topk', 'anchor_scale', 'delta_stds')
+    GFL_FIELDS = ('head_kind', 'reg_max', 'qfl_beta', 'dfl_weight')
 
     def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
                  box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0,
-                 assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2)):
+                 assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2),
+                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25):
+        if head_kind not in ('fcos', 'gfl'):
+            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos' or 'gfl', got {head_kind!r}")
+        self.head_kind = head_kind
+        self.reg_max, self.qfl_beta, self.dfl_weight = reg_max, float(qfl_beta), float(dfl_weight)
+        if head_kind == 'gfl':
+            if not (isinstance(reg_max, int) and 1 <= reg_max <= L.GFL_MAX_REG):
+                raise NotImplementedError(f'dsl_amd hot path: reg_max must be an integer in 1..{L.GFL_MAX_REG}, got {reg_max!r}')
+            if not (0.0 <= self.qfl_beta < float('inf')):
+                raise NotImplementedError(f'dsl_amd hot path: qfl_beta must be a finite number >= 0, got {qfl_beta!r}')
+            if not (0.0 <= self.dfl_weight < float('inf')):
+                raise NotImplementedError(f'dsl_amd hot path: dfl_weight must be a finite number >= 0, got {dfl_weight!r}')
+            # what a GFL head does not read, or fixes itself, is refused off its default instead of being dropped
+            for name, val, want in (('center_sampling', center_sampling, True), ('norm_on_bbox', norm_on_bbox, True),
+                                    ('centerness_on_reg', centerness_on_reg, True), ('iou_loss', iou_loss, False),
+                                    ('focal_gamma', focal_gamma, 2.0), ('focal_alpha', focal_alpha, 0.25), ('ctr_weight', ctr_weight, 1.0)):
+                if val != want:
+                    raise NotImplementedError(f"dsl_amd hot path: head_kind='gfl' does not read {name} (got {val!r}; leave it at {want!r})")
+            if assigner not in ('fcos', 'atss'):
+                raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
+            assigner = 'atss'      # (the default 'fcos' stands for "not given": a GFL head's targets are ATSS's)
         if assigner not in ('fcos', 'atss'):
             raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
         self.assigner = assigner
@@ -180,7 +210,8 @@ class HeadOptions:
         """The five FIELDS for every head that existed before the loss family; the loss settings follow only where one is set."""
         k = tuple(getattr(self, f) for f in self.FIELDS)
         k = k if self.loss_is_default() else k + self.loss_key()
-        return k + tuple(getattr(self, f) for f in self.ATSS_FIELDS) if self.assigner == 'atss' else k
+        k = k + tuple(getattr(self, f) for f in self.ATSS_FIELDS) if self.assigner == 'atss' else k
+        return k + tuple(getattr(self, f) for f in self.GFL_FIELDS) if self.head_kind == 'gfl' else k
 
     def is_default(self):
         return self.key() == HeadOptions().key()
@@ -189,7 +220,8 @@ class HeadOptions:
         """dsl_fcos_desc.head_flags / dsl_det_desc.head_flags."""
         return ((0 if self.center_sampling else L.HEAD_INSIDE_BOX) | (0 if self.norm_on_bbox else L.HEAD_RAW_TARGETS | L.HEAD_EXP_DECODE)
                 | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT)
-                | (L.HEAD_ATSS if self.assigner == 'atss' else 0))
+                | (L.HEAD_ATSS if self.assigner == 'atss' else 0)
+                | (L.HEAD_GFL | L.HEAD_LOSS_EXT if self.head_kind == 'gfl' else 0))      # (a dsl_gfl_desc always carries its loss settings)
 
     def atss_desc(self):
         """A dsl_atss_desc with the head's settings (None for an FCOS head); the caller fills max_gt, pad_shapes and npos."""
@@ -210,6 +242,7 @@ class HeadOptions:
     def __repr__(self):
         fields = self.FIELDS if self.loss_is_default() else self.FIELDS + self.LOSS_FIELDS
         fields += self.ATSS_FIELDS if self.assigner == 'atss' else ()
+        fields += self.GFL_FIELDS if self.head_kind == 'gfl' else ()
         return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in fields) + ')'
 
 
@@ -239,6 +272,13 @@ class ParamStore:
                 raise NotImplementedError(f'dsl_amd hot path: centerness_on_reg=False needs num_classes <= {MAX_CLASSES - 4} (its logit is a '
                                           f'column of the classification predictor, at most {MAX_CLASSES} columns), got {num_classes}')
             self.cls_pad = _round_up(self.cls_rows, 64)
+        # the box predictor: conv_reg (4) + conv_centerness (1, unless it sits on the classification predictor) in 64 stored rows whose
+        # fp32 output rows are 8 wide; a GFL head's 4 (reg_max + 1) distribution logits in one or two 64-row tiles (the launch shapes
+        # of a 128-row classification predictor), fp32 rows exactly that wide, no centerness
+        self.gfl = self.head.head_kind == 'gfl'
+        self.reg_rows = 4 * (self.head.reg_max + 1) if self.gfl else (4 if self.ctr_on_cls else 5)
+        self.reg_pad = _round_up(self.reg_rows, 64)
+        self.reg_ld = self.reg_rows if self.gfl else 8
         self.defer_head = False       # deferred head update (FlatSGD._sync_defer decides; engine.Plan.defer reads it)
         self._pending_ev = None
         bspecs = backbone_specs() if backbone == 'resnet' else rla_backbone_specs()
@@ -298,8 +338,8 @@ class ParamStore:
         # of conv_cls stay zero: their output columns' gradients are zero, so SGD / weight decay / EMA keep them at 0
         toff = add(self.train_regions, toff, 'head.cls_w', (self.cls_pad, 3, 3, 256))
         toff = add(self.train_regions, toff, 'head.cls_b', (self.cls_pad,))
-        toff = add(self.train_regions, toff, 'head.regctr_w', (64, 3, 3, 256))
-        toff = add(self.train_regions, toff, 'head.regctr_b', (64,))
+        toff = add(self.train_regions, toff, 'head.regctr_w', (self.reg_pad, 3, 3, 256))
+        toff = add(self.train_regions, toff, 'head.regctr_b', (self.reg_pad,))
         toff = add(self.train_regions, toff, 'head.scales', (8,))
         self.n_train, self.n_frozen = toff, foff
         self.device = torch.device(device)
@@ -388,9 +428,12 @@ class ParamStore:
         pc, pr, pt = [f'bbox_head.{n}' for n in self.predictor_names()]
         out[pc + '.weight'] = cw[:self.num_classes].permute(0, 3, 1, 2)
         out[pc + '.bias'] = cb[:self.num_classes]
-        out[pr + '.weight'] = rw[:4].permute(0, 3, 1, 2)
-        out[pr + '.bias'] = rb[:4]
-        if self.ctr_on_cls:       # (row 4 of the regression predictor is then zero and stays zero)
+        nbox = self.reg_rows if self.gfl else 4
+        out[pr + '.weight'] = rw[:nbox].permute(0, 3, 1, 2)
+        out[pr + '.bias'] = rb[:nbox]
+        if self.gfl:              # (gfl_head.py:128-133: no centerness predictor)
+            pass
+        elif self.ctr_on_cls:       # (row 4 of the regression predictor is then zero and stays zero)
             out[pt + '.weight'] = cw[self.cls_ld:self.cls_ld + 1].permute(0, 3, 1, 2)
             out[pt + '.bias'] = cb[self.cls_ld:self.cls_ld + 1]
         else:
@@ -402,7 +445,9 @@ class ParamStore:
         return out
 
     def predictor_names(self):
-        """Module names of the class, box and centerness predictors under bbox_head."""
+        """Module names of the class, box and centerness predictors under bbox_head (a GFL head has no centerness predictor)."""
+        if self.gfl:
+            return 'gfl_cls', 'gfl_reg', None
         if self.head.assigner == 'atss':
             return 'atss_cls', 'atss_reg', 'atss_centerness'
         return 'conv_cls', 'conv_reg', 'conv_centerness'
@@ -474,8 +519,8 @@ class ParamStore:
                             off += _round_up(lay[f'{s.name}#s2{py}{px}'][1], 8)
             lay['head.cls'] = (off, 256 * 9 * self.cls_pad)
             off += 256 * 9 * self.cls_pad
-            lay['head.regctr'] = (off, 256 * 9 * 64)
-            off += 256 * 9 * 64
+            lay['head.regctr'] = (off, 256 * 9 * self.reg_pad)
+            off += 256 * 9 * self.reg_pad
             self._wT, self._wT_total = lay, off
         return self._wT, self._wT_total
 
@@ -562,7 +607,7 @@ class ParamStore:
                 if name == 'head.cls':
                     w, co, cop, taps, cin, sc = self.tview('head.cls_w'), self.cls_rows, self.cls_pad, 9, 256, None
                 elif name == 'head.regctr':
-                    w, co, cop, taps, cin, sc = self.tview('head.regctr_w'), (4 if self.ctr_on_cls else 5), 64, 9, 256, None
+                    w, co, cop, taps, cin, sc = self.tview('head.regctr_w'), self.reg_rows, self.reg_pad, 9, 256, None
                 else:
                     s = self.convs[name.split('#')[0]]
                     w, co, cop, taps, cin = self.tview(s.name + '.weight'), s.cout, s.cout_pad, s.k * s.k, s.cin_store
@@ -672,7 +717,7 @@ class ParamStore:
                     t = torch.zeros(shape)          # zero_init_last_bn (resnet_rla.py:251-256)
             else:
                 t = torch.zeros(shape)
-                if k == f'bbox_head.{self.predictor_names()[0]}.bias':      # (atss_head.py:30-42: the same prior on atss_cls)
+                if k == f'bbox_head.{self.predictor_names()[0]}.bias':      # (atss_head.py:30-42, gfl_head.py:135-142: the same prior on atss_cls / gfl_cls)
                     t = torch.full(shape, -math.log((1 - 0.01) / 0.01))
             sd[k] = t
         self.load_named(sd)

@@ -20,11 +20,16 @@ from . import _lib as L
 
 class DetectPlan:
     def __init__(self, n, sizes, strides, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05,
-                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, atss=None):
-        """atss: the dsl_atss_desc of an ATSS head (params.HeadOptions.atss_desc), with HEAD_ATSS in head_flags."""
+                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, atss=None, reg_max=None):
+        """atss: the dsl_atss_desc of an ATSS head (params.HeadOptions.atss_desc), with HEAD_ATSS in head_flags.
+        reg_max: of a GFL head, with HEAD_GFL alone in head_flags and ld_rc >= 4 (reg_max + 1)."""
         d = L.DetDesc()
         self.atss = atss
-        if atss is not None:      # dsl_det_atss_desc: `d` is its first member (and keeps it alive)
+        if reg_max is not None:      # dsl_det_gfl_desc: `d` is its first member (and keeps it alive)
+            self._ext = L.DetGflDesc()
+            self._ext.reg_max = reg_max
+            d = self._ext.det
+        elif atss is not None:      # dsl_det_atss_desc: `d` is its first member (and keeps it alive)
             self._ext = L.DetAtssDesc()
             self._ext.atss = C.addressof(atss)
             d = self._ext.det
@@ -141,7 +146,9 @@ def _detplan(det, plan, store, N):
     dp = getattr(plan, 'detplan', None)
     if dp is None:
         dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
-                        ld_cls=store.logit_ld, head_flags=store.head.flags() & (L.HEAD_EXP_DECODE | L.HEAD_ATSS), atss=store.head.atss_desc(),
+                        ld_cls=store.logit_ld, ld_rc=store.reg_ld, reg_max=store.head.reg_max if store.gfl else None,
+                        head_flags=L.HEAD_GFL if store.gfl else store.head.flags() & (L.HEAD_EXP_DECODE | L.HEAD_ATSS),
+                        atss=None if store.gfl else store.head.atss_desc(),
                         ctr_col=store.cls_ld if store.ctr_on_cls else None, **_test_cfg(det))
         dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
         plan.detplan = dp

@@ -615,6 +615,55 @@ int dsl_fcos_assign(const dsl_fcos_desc* d, void* stream);
 int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * GFL: GFLHead's Quality Focal Loss, Distribution Focal Loss and integral box decode (mmdet/models/dense_heads/gfl_head.py:15-48
+ * Integral, :210-296 loss_single, :348-370 the avg_factor exchange, :416-443 detection; mmdet/models/losses/gfocal_loss.py:11-78;
+ * mmdet/core/bbox/transforms.py:165-186 bbox2distance), fp32, contraction off.
+ *
+ * A dsl_gfl_desc wraps a dsl_fcos_desc with DSL_HEAD_ATSS | DSL_HEAD_GFL | DSL_HEAD_LOSS_EXT in head_flags: targets come from
+ * dsl_atss_assign (bbox_targets = the assigned ground-truth box in pixels).  R = reg_max + 1.  fcos.regctr holds the box predictor's
+ * fp32 output [M][ld_rc], ld_rc >= 4R, side k's R logits at columns k R .. k R + R - 1; there is no centerness (ctr, g_ctr NULL, w_ctr,
+ * focal_gamma, focal_alpha not read).  A location's point is its anchor's centre (x s, y s).
+ *
+ * Per positive (label < num_classes), in units of the stride s: z = scale_l * logits, d_k = sum_j j softmax(z_k)_j (Integral),
+ * prediction (x - d0, y - d1, x + d2, y + d3), target = bbox_targets / s.
+ *
+ * dsl_gfl_quality (behind the predictors, in front of the exchange of stats[0:2] between ranks): score[m] = IoU(prediction, target),
+ * bbox_overlaps aligned with max(union, 1e-6); weight[m] = max_c sigmoid(cls[m][c]); 0 for every other location.
+ * fcos.stats[1] = sum_m weight[m], block records added in block order (bit-identical from run to run); stats[0] stays
+ * dsl_atss_assign's sum_i max(npos_i, 1).
+ *
+ * dsl_gfl_loss (forward and backward in one launch + the fixed-order sum of its block records), with
+ * num = max(norm[0] * inv_world, 1), avg = max(norm[1] * inv_world, 1):
+ *   losses[0] = w_cls / num * sum_m cls_weight[m] sum_c qfl(m, c), qfl = BCE(x, 0) sigmoid(x)^beta, at a positive's label column
+ *               BCE(x, score[m]) |score[m] - sigmoid(x)|^beta (score is a constant for the gradient; beta == 2 multiplies, other
+ *               beta >= 0 use powf; at |score - sigmoid| == 0 the gradient is taken as 0, also for beta < 1 where it diverges)
+ *   losses[1] = w_bbox / avg * sum_pos weight[m] box_loss(prediction, target), box_kind any DSL_BOX_*
+ *   losses[2] = w_dfl / (4 avg) * sum_pos weight[m] sum_k [CE(z_k, l) (l + 1 - t) + CE(z_k, l + 1) (t - l)],
+ *               t = clamp(target side distance in stride units, 0, reg_max - 0.1), l = floor(t)
+ *   losses[3] = 0; logvec = [cls, bbox, dfl, their sum].
+ * g_cls as dsl_fcos_loss.  g_rc[m][0 .. 4R) = scale_l * dL/dz (bf16) for a positive - the box loss chained through the softmax
+ * expectation's Jacobian p_j (j - d_k), plus DFL's p_j - [j == l] (l + 1 - t) - [j == l + 1] (t - l) - and the whole row of ld_grc
+ * elements zero for every other location; columns 4R .. ld_grc of a positive's row are written zero too: every launch rewrites
+ * the whole buffer.  g_scales[l] = sum over the level's positives of dL/dz * logit.  weight is a constant for the gradient.
+ * ld_grc: a power of two in 8..512, >= 4R.  Workspace: dsl_fcos_workspace_bytes(&g->fcos).
+ *
+ * Each wavefront walks 64 locations: the rows of its non-positives are zeroed with 16-byte stores by the whole wavefront, and each
+ * positive is processed by the whole wavefront (16 lanes per side, two bins per lane), so no lane runs the 4R-wide row alone.
+ * ---------------------------------------------------------------------------------------- */
+#define DSL_HEAD_GFL 64         /* GFLHead: dsl_fcos_desc inside a dsl_gfl_desc; dsl_det_desc inside a dsl_det_gfl_desc */
+#define DSL_GFL_MAX_REG 16
+typedef struct dsl_gfl_desc {
+  dsl_fcos_desc fcos;
+  int32_t reg_max;                     /* 1..16 */
+  float qfl_beta;                      /* QualityFocalLoss beta >= 0 (2) */
+  float w_dfl;                         /* DistributionFocalLoss loss_weight >= 0 (0.25) */
+  float* score;                        /* [M] out of dsl_gfl_quality, in of dsl_gfl_loss */
+  float* weight;                       /* [M] likewise */
+} dsl_gfl_desc;
+int dsl_gfl_quality(const dsl_gfl_desc* g, void* stream);
+int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer / EMA over flat fp32 buffers (mmcv OptimizerHook + torch SGD, wired at
  * apis/train.py:111,157-166; EMA at runner/hooks/semi_epoch_based_runner.py:368-409)
  * ---------------------------------------------------------------------------------------- */
@@ -691,6 +740,14 @@ typedef struct dsl_det_atss_desc {
   dsl_det_desc det;
   const struct dsl_atss_desc* atss;
 } dsl_det_atss_desc;
+/* A GFL head's detection descriptor (DSL_HEAD_GFL in det.head_flags, no other decode flag; gfl_head.py:416-443): regctr holds
+ * [M][ld_rc >= 4 (reg_max + 1)] distribution logits, distances = Integral(scale_l * logits) * stride from the anchor centre (x s, y s),
+ * boxes clipped to img_shapes; the candidate score is the class sigmoid alone (no centerness factor: ctr is not read), nms_pre ranks
+ * by the location's maximum class score.  Everything behind candidate collection is shared. */
+typedef struct dsl_det_gfl_desc {
+  dsl_det_desc det;
+  int32_t reg_max;                           /* 1..16 */
+} dsl_det_gfl_desc;
 /* dsl_det_desc.nms_method.  Soft-NMS is mmcv's batched_nms with nms=dict(type='soft_nms', method=...) (stated by
  * mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127), per image and class over the candidates the hard NMS would get: pick the highest current score
  * (equal scores: the candidate that comes first in (level, slot, class) order - with views, (view, level, slot, class)), emit it
@@ -832,6 +889,7 @@ int dsl_allreduce_bucket_bf16(void* comm, void* buf_bf16, size_t count, void* st
 enum { DSL_OP_CONV = 1, DSL_OP_WGRAD = 2, DSL_OP_GN_FWD = 3, DSL_OP_GN_BWD = 4, DSL_OP_MAXPOOL = 5,
        DSL_OP_SUM2X2 = 6, DSL_OP_COLSUM = 7, DSL_OP_MEMSET = 8, DSL_OP_PACK_IMAGE = 9,
        DSL_OP_ASSIGN = 10, DSL_OP_LOSS = 11,   /* MAXPOOL: i[4] = output row stride (0 = c) */
+       DSL_OP_GFL_QUALITY = 29,  /* desc = dsl_gfl_desc -> dsl_gfl_quality; DSL_OP_LOSS with p[0] = a dsl_gfl_desc -> dsl_gfl_loss(p[0]) */
        DSL_OP_FORK = 12,   /* side stream i[0] (default 1) waits for everything queued so far on stream i[1] (default 0 = caller's) */
        DSL_OP_JOIN = 13,   /* stream i[1] (default 0 = caller's) waits for everything queued so far on side stream i[0] (default 1) */
        DSL_OP_WGRAD_GROUP = 14,  /* desc = dsl_wgrad_desc[i[0]] -> dsl_conv2d_wgrad_group */
