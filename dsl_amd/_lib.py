@@ -128,6 +128,7 @@ HEAD_ATSS = 32          # ATSSHead: anchor-delta decode, ATSS targets and normal
 ATSS_MAX_TOPK = 16
 HEAD_GFL = 64           # GFLHead: the dsl_fcos_desc is a dsl_gfl_desc's first member, the dsl_det_desc a dsl_det_gfl_desc's
 GFL_MAX_REG = 16
+HEAD_LD = 128           # LDHead: the dsl_gfl_desc is a dsl_ld_desc's first member (dsl_ld_loss)
 BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_DIOU, BOX_CIOU = range(5)      # DSL_BOX_*: dsl_fcos_desc.box_kind
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
@@ -151,6 +152,11 @@ class DetDesc(C.Structure):
 class GflDesc(C.Structure):      # dsl_gfl_desc: a GFL head's loss descriptor (HEAD_GFL | HEAD_ATSS | HEAD_LOSS_EXT in fcos.head_flags)
     _fields_ = [('fcos', FcosDesc), ('reg_max', C.c_int32), ('qfl_beta', C.c_float), ('w_dfl', C.c_float),
                 ('score', C.c_void_p), ('weight', C.c_void_p)]
+
+
+class LdDesc(C.Structure):      # dsl_ld_desc: an LD head's loss descriptor (HEAD_LD beside the GFL flags in gfl.fcos.head_flags)
+    _fields_ = [('gfl', GflDesc), ('soft', C.c_void_p), ('ld_soft', C.c_int32), ('soft_scales', C.c_void_p),
+                ('T', C.c_float), ('w_ld', C.c_float)]
 
 
 class DetAtssDesc(C.Structure):      # dsl_det_atss_desc: the detection descriptor of an ATSS head (HEAD_ATSS in det.head_flags)
@@ -306,7 +312,7 @@ _SIGS = {
     'dsl_groupnorm_relu_fwd': [_vp, _vp], 'dsl_groupnorm_relu_bwd': [_vp, _vp], 'dsl_groupnorm_workspace_bytes': [_vp],
     'dsl_sum2x2': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], 'dsl_colsum': [_vp, _vp, _l, _i, _i, _vp],
     'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_atss_assign': [_vp, _vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
-    'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp],
+    'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp], 'dsl_ld_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
     'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],

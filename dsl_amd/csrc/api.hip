@@ -247,8 +247,13 @@ extern "C" int dsl_run_ops(const dsl_op* ops, int n_ops, void* stream) {
         rc = o.p[0] ? dsl_atss_assign((const dsl_fcos_desc*)o.desc, (const dsl_atss_desc*)o.p[0], stream)
                     : dsl_fcos_assign((const dsl_fcos_desc*)o.desc, stream);
         break;
-      case DSL_OP_LOSS:        // p[0]: the dsl_gfl_desc of a GFL head (dsl_gfl_loss), else null
-        rc = o.p[0] ? dsl_gfl_loss((const dsl_gfl_desc*)o.p[0], stream) : dsl_fcos_loss((const dsl_fcos_desc*)o.desc, stream);
+      case DSL_OP_LOSS:        // p[0]: the dsl_gfl_desc of a GFL head (dsl_gfl_loss; with DSL_HEAD_LD a dsl_ld_desc, dsl_ld_loss), else null
+        if (!o.p[0])
+          rc = dsl_fcos_loss((const dsl_fcos_desc*)o.desc, stream);
+        else if (((const dsl_gfl_desc*)o.p[0])->fcos.head_flags & DSL_HEAD_LD)
+          rc = dsl_ld_loss((const dsl_ld_desc*)o.p[0], stream);
+        else
+          rc = dsl_gfl_loss((const dsl_gfl_desc*)o.p[0], stream);
         break;
       case DSL_OP_GFL_QUALITY: rc = dsl_gfl_quality((const dsl_gfl_desc*)o.desc, stream); break;
       case DSL_OP_QUANT_FP8: {

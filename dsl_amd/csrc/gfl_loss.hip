@@ -3,6 +3,8 @@
 // Restates mmdet/models/dense_heads/gfl_head.py:15-48 (Integral), :210-296 (loss_single), :348-370 (avg_factor),
 // mmdet/models/losses/gfocal_loss.py:11-78 (quality_focal_loss, distribution_focal_loss), mmdet/core/bbox/transforms.py:165-186
 // (bbox2distance) and bbox_overlaps(is_aligned=True) (iou2d_calculator.py:212-260); semantics: include/dsl_hip.h.
+// LDHead's loss pass (dsl_ld_loss on a dsl_ld_desc: ld_head.py:99-126,253-261, losses/kd_loss.py:27-35) is the same kernel with the
+// Localization Distillation term behind a template argument.
 //
 // Positives are a few hundred among tens of thousands of locations, and each costs 4 (reg_max + 1) loads and exponentials.  They
 // are neither compacted into a list (a second launch and an ordering to keep the sums reproducible) nor left to single lanes (a
@@ -31,6 +33,9 @@ struct GfK {
   int box_kind;
   float box_eps, beta, w_cls, w_bbox, w_dfl;
   float tmax;             // reg_max - 0.1 (bbox2distance's clamp, transforms.py:183-184)
+  // dsl_ld_loss only (gfl_loss_kernel<., true>; all zero otherwise)
+  const float* soft; int ld_soft; const float* soft_scales;
+  float T, w_ld;
 };
 
 __device__ __forceinline__ void gfl_loc(const GfK& p, int m, int& lvl, int& y, int& x) {
@@ -83,6 +88,21 @@ __device__ __forceinline__ void gfl_row(const GfK& p, int m, int lvl, int lane, 
   o.dk = group_sum((float)j * o.p0 + (float)(j + 16) * o.p1);
 #pragma unroll
   for (int q = 0; q < 4; ++q) o.d[q] = __shfl(o.dk, 16 * q, 64);
+}
+
+// softmax(v / T) and its logarithm over one side's bins (kd_loss.py:27-35: F.softmax(soft_label / T), F.log_softmax(pred / T)); the
+// student's and the teacher's rows go through this one function, so equal rows give equal bits
+__device__ __forceinline__ void ld_softmax(float v0, float v1, bool has0, bool has1, float T, float& p0, float& p1, float& l0, float& l1) {
+  const float a0 = v0 / T, a1 = v1 / T;
+  const float ninf = -__builtin_inff();
+  const float mx = group_max(fmaxf(has0 ? a0 : ninf, has1 ? a1 : ninf));
+  const float e0 = has0 ? expf(a0 - mx) : 0.f, e1 = has1 ? expf(a1 - mx) : 0.f;
+  const float S = group_sum(e0 + e1);
+  const float lS = logf(S);
+  p0 = e0 / S;
+  p1 = e1 / S;
+  l0 = (a0 - mx) - lS;
+  l1 = (a1 - mx) - lS;
 }
 
 __device__ __forceinline__ float gfl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
@@ -180,8 +200,11 @@ __device__ __forceinline__ void qfl_fb(float x, bool pos, float t, float beta, b
   }
 }
 
-// ---- loss pass: block records [cls, 0, bbox, dfl, g_scale x 5, pad] ---------------------------------------------------------------
-template <bool kTail>
+// ---- loss pass: block records [cls, ld (0 without kLd), bbox, dfl, g_scale x 5, pad] ----------------------------------------------
+// kLd (dsl_ld_loss, ld_head.py:99-126, kd_loss.py:27-35): per positive and side, T^2 / R KL(softmax(s / T) || softmax(z / T)) against the
+// teacher's row s, weighted like the box terms; its gradient joins the row's in front of the bf16 rounding.  Compiled out of the GFL
+// instantiations.
+template <bool kTail, bool kLd>
 __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
   __shared__ float sh[16];
   const int M = p.M, C = p.C;
@@ -218,11 +241,12 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
   float* rec = p.part + 16ll * blockIdx.x;
   if (threadIdx.x == 0) {
     rec[0] = lsum;
-    rec[1] = 0.f;
+    if constexpr (!kLd) rec[1] = 0.f;
   }
 
   // ---------------- boxes + DFL: one wavefront per 64 consecutive locations ----------------------
   float bsum = 0.f, dsum = 0.f;
+  [[maybe_unused]] float ksum = 0.f;
   float gsc[DSL_MAX_SEG] = {0.f, 0.f, 0.f, 0.f, 0.f};
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int k = lane >> 4, j = lane & 15;
@@ -270,8 +294,25 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
       const float s1 = j + 16 == li ? wl : (j + 16 == li + 1 ? wr : 0.f);
       const float zt = group_sum((o.has0 ? s0 * o.z0 : 0.f) + (o.has1 ? s1 * o.z1 : 0.f));
       const float dfl = o.lse * wl + o.lse * wr - zt;      // CE(z, l) wl + CE(z, l + 1) wr
-      const float g0 = o.has0 ? ddk * (o.p0 * ((float)j - o.dk)) + coef_d * (o.p0 * wl + o.p0 * wr - s0) : 0.f;
-      const float g1 = o.has1 ? ddk * (o.p1 * ((float)(j + 16) - o.dk)) + coef_d * (o.p1 * wl + o.p1 * wr - s1) : 0.f;
+      float g0 = o.has0 ? ddk * (o.p0 * ((float)j - o.dk)) + coef_d * (o.p0 * wl + o.p0 * wr - s0) : 0.f;
+      float g1 = o.has1 ? ddk * (o.p1 * ((float)(j + 16) - o.dk)) + coef_d * (o.p1 * wl + o.p1 * wr - s1) : 0.f;
+      if constexpr (kLd) {
+        const float* srow = p.soft + (long long)mm * p.ld_soft + k * p.R;
+        const float ssc = p.soft_scales[lvl];
+        const float s0r = o.has0 ? srow[j] : 0.f, s1r = o.has1 ? srow[j + 16] : 0.f;
+        float q0, q1, lq0, lq1, t0, t1, lt0, lt1;
+        ld_softmax(o.z0, o.z1, o.has0, o.has1, p.T, q0, q1, lq0, lq1);
+        ld_softmax(s0r * ssc, s1r * ssc, o.has0, o.has1, p.T, t0, t1, lt0, lt1);
+        // F.kl_div: target (log target - input), 0 where the target is 0; .mean(1) * T^2
+        const float kl = group_sum((t0 > 0.f ? t0 * (lt0 - lq0) : 0.f) + (t1 > 0.f ? t1 * (lt1 - lq1) : 0.f));
+        const float kd = kl * (p.T * p.T) / (float)p.R;
+        // d kd / d z_j = T / R (p_j - t_j); not divided by avg (ld_head.py:253-261 leaves loss_ld as weighted_loss returned it)
+        const float coef_l = wv * p.grad_scale * p.w_ld * 0.25f * (p.T / (float)p.R);
+        const float a0 = coef_l * (q0 - t0), a1 = coef_l * (q1 - t1);
+        if (o.has0 && a0 != 0.f) g0 += a0;      // (a zero term leaves the row's bits alone, the sign of a zero included)
+        if (o.has1 && a1 != 0.f) g1 += a1;
+        if (j == 0) ksum += wv * kd;
+      }
       uint16_t* gr = p.g_rc + (long long)mm * p.ld_grc + k * p.R;
       if (o.has0) gr[j] = f2bf(g0 * o.sc);
       if (o.has1) gr[j + 16] = f2bf(g1 * o.sc);
@@ -290,6 +331,10 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
     rec[2] = bsum;
     rec[3] = dsum;
   }
+  if constexpr (kLd) {
+    ksum = block_sum(ksum, sh);
+    if (threadIdx.x == 0) rec[1] = ksum;
+  }
 #pragma unroll
   for (int l = 0; l < DSL_MAX_SEG; ++l) {
     const float v = block_sum(gsc[l], sh);
@@ -300,10 +345,12 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
     if (threadIdx.x == 0) rec[l] = 0.f;
 }
 
-// fixed-order sum of the 16-float block records -> losses[4] (cls, bbox, dfl, 0), g_scales[5], logvec[4] (cls, bbox, dfl, their sum)
+// fixed-order sum of the 16-float block records -> losses[4] (cls, bbox, dfl, 0), g_scales[5], logvec[4] (cls, bbox, dfl, their sum);
+// kLd: losses[3] = w_ld / 4 * the records' LD sums (no normaliser), logvec[5] (cls, bbox, dfl, ld, their sum)
+template <bool kLd>
 __global__ __launch_bounds__(GFL_FIN_T) void gfl_finalize_kernel(const float* __restrict__ part, int nblocks, float* losses, float* g_scales,
                                                                  const float* norm, float inv_world, float* logvec, float w_cls,
-                                                                 float w_bbox, float w_dfl) {
+                                                                 float w_bbox, float w_dfl, float w_ld) {
   __shared__ float sh[GFL_FIN_T];
   constexpr int V = 16, Q = GFL_FIN_T / V;
   const int v = threadIdx.x % V, q = threadIdx.x / V;
@@ -318,7 +365,7 @@ __global__ __launch_bounds__(GFL_FIN_T) void gfl_finalize_kernel(const float* __
     for (int i = 0; i < Q; ++i) t += sh[i * V + threadIdx.x];
     const float num = fmaxf(norm[0] * inv_world, 1.0f), avg = fmaxf(norm[1] * inv_world, 1.0f);
     if (threadIdx.x == 0) losses[0] = fv = t / num * w_cls;
-    else if (threadIdx.x == 1) losses[3] = 0.f;
+    else if (threadIdx.x == 1) losses[3] = fv = kLd ? t * (w_ld * 0.25f) : 0.f;
     else if (threadIdx.x == 2) losses[1] = fv = t / avg * w_bbox;
     else if (threadIdx.x == 3) losses[2] = fv = t / avg * (w_dfl * 0.25f);
     else if (threadIdx.x - 4 < DSL_MAX_SEG) g_scales[threadIdx.x - 4] = t;
@@ -329,7 +376,13 @@ __global__ __launch_bounds__(GFL_FIN_T) void gfl_finalize_kernel(const float* __
     __syncthreads();
     if (threadIdx.x == 0) {
       const float cls = sh[0], bbox = sh[2], dfl = sh[3];
-      logvec[0] = cls; logvec[1] = bbox; logvec[2] = dfl; logvec[3] = (cls + bbox) + dfl;
+      logvec[0] = cls; logvec[1] = bbox; logvec[2] = dfl;
+      if constexpr (kLd) {
+        logvec[3] = sh[1];
+        logvec[4] = ((cls + bbox) + dfl) + sh[1];
+      } else {
+        logvec[3] = (cls + bbox) + dfl;
+      }
     }
   }
 }
@@ -384,30 +437,63 @@ extern "C" int dsl_gfl_quality(const dsl_gfl_desc* g, void* stream) {
   return 0;
 }
 
-extern "C" int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream) {
-  GfK k;
-  if (gfl_fill(g, k, "dsl_gfl_loss")) return -1;
+// what dsl_gfl_loss checks and fills beyond gfl_fill; `blocks` = the launch's grid
+static int gfl_loss_fill(const dsl_gfl_desc* g, GfK& k, int& blocks, const char* who) {
+  if (gfl_fill(g, k, who)) return -1;
   const dsl_fcos_desc* d = &g->fcos;
-  DSL_CHECK(d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses, "dsl_gfl_loss: null pointer");
-  DSL_CHECK(d->ld_gcls % 4 == 0 && d->ld_gcls >= d->ld_cls, "dsl_gfl_loss: ld_gcls must be a multiple of 4 and >= ld_cls");
+  DSL_CHECK(d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses, "%s: null pointer", who);
+  DSL_CHECK(d->ld_gcls % 4 == 0 && d->ld_gcls >= d->ld_cls, "%s: ld_gcls must be a multiple of 4 and >= ld_cls", who);
   DSL_CHECK(d->ld_grc >= 8 && d->ld_grc <= 512 && (d->ld_grc & (d->ld_grc - 1)) == 0 && d->ld_grc >= 4 * k.R && ((uintptr_t)d->g_rc & 15) == 0,
-            "dsl_gfl_loss: ld_grc must be a power of two in 8..512 and >= 4 (reg_max + 1), g_rc 16-byte aligned");
-  DSL_CHECK(d->box_kind >= DSL_BOX_GIOU && d->box_kind <= DSL_BOX_CIOU, "dsl_gfl_loss: box_kind is not a DSL_BOX_* value");
-  DSL_CHECK(d->box_kind < DSL_BOX_DIOU || (d->box_eps > 0.f && d->box_eps < 1.f), "dsl_gfl_loss: DIoU / CIoU need 0 < box_eps < 1");
+            "%s: ld_grc must be a power of two in 8..512 and >= 4 (reg_max + 1), g_rc 16-byte aligned", who);
+  DSL_CHECK(d->box_kind >= DSL_BOX_GIOU && d->box_kind <= DSL_BOX_CIOU, "%s: box_kind is not a DSL_BOX_* value", who);
+  DSL_CHECK(d->box_kind < DSL_BOX_DIOU || (d->box_eps > 0.f && d->box_eps < 1.f), "%s: DIoU / CIoU need 0 < box_eps < 1", who);
   DSL_CHECK(d->w_cls >= 0.f && d->w_cls < 1e30f && d->w_bbox >= 0.f && d->w_bbox < 1e30f && g->w_dfl >= 0.f && g->w_dfl < 1e30f,
-            "dsl_gfl_loss: loss weights must be finite and >= 0");
-  DSL_CHECK(g->qfl_beta >= 0.f && g->qfl_beta < 1e30f, "dsl_gfl_loss: qfl_beta must be finite and >= 0");
+            "%s: loss weights must be finite and >= 0", who);
+  DSL_CHECK(g->qfl_beta >= 0.f && g->qfl_beta < 1e30f, "%s: qfl_beta must be finite and >= 0", who);
   k.box_kind = d->box_kind; k.box_eps = d->box_eps; k.beta = g->qfl_beta;
   k.w_cls = d->w_cls; k.w_bbox = d->w_bbox; k.w_dfl = g->w_dfl;
-  hipStream_t st = (hipStream_t)stream;
-  int blocks = (int)(((long long)k.M * ((k.C + 3) / 4) + 255) / 256);
+  blocks = (int)(((long long)k.M * ((k.C + 3) / 4) + 255) / 256);
   if (blocks > 2048) blocks = 2048;      // (the workspace holds 2048 records of 16 floats)
+  return 0;
+}
+
+extern "C" int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream) {
+  GfK k;
+  int blocks;
+  if (gfl_loss_fill(g, k, blocks, "dsl_gfl_loss")) return -1;
+  const dsl_fcos_desc* d = &g->fcos;
+  hipStream_t st = (hipStream_t)stream;
   if (k.C % 4 != 0)
-    hipLaunchKernelGGL(gfl_loss_kernel<true>, dim3(blocks), dim3(256), 0, st, k);
+    hipLaunchKernelGGL((gfl_loss_kernel<true, false>), dim3(blocks), dim3(256), 0, st, k);
   else
-    hipLaunchKernelGGL(gfl_loss_kernel<false>, dim3(blocks), dim3(256), 0, st, k);
-  hipLaunchKernelGGL(gfl_finalize_kernel, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, blocks, d->losses, d->g_scales, d->norm,
-                     d->inv_world, d->logvec, k.w_cls, k.w_bbox, k.w_dfl);
+    hipLaunchKernelGGL((gfl_loss_kernel<false, false>), dim3(blocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(gfl_finalize_kernel<false>, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, blocks, d->losses, d->g_scales, d->norm,
+                     d->inv_world, d->logvec, k.w_cls, k.w_bbox, k.w_dfl, 0.f);
+  DSL_LAUNCH_CHECK("gfl_loss_kernel");
+  return 0;
+}
+
+extern "C" int dsl_ld_loss(const dsl_ld_desc* l, void* stream) {
+  DSL_CHECK(l, "dsl_ld_loss: null descriptor");
+  const dsl_gfl_desc* g = &l->gfl;
+  const dsl_fcos_desc* d = &g->fcos;
+  DSL_CHECK((d->head_flags & DSL_HEAD_LD) && (d->head_flags & DSL_HEAD_GFL),
+            "dsl_ld_loss: a dsl_ld_desc needs DSL_HEAD_LD | DSL_HEAD_GFL in gfl.fcos.head_flags");
+  GfK k;
+  int blocks;
+  if (gfl_loss_fill(g, k, blocks, "dsl_ld_loss")) return -1;
+  DSL_CHECK(l->soft && l->soft_scales, "dsl_ld_loss: soft / soft_scales null");
+  DSL_CHECK(l->ld_soft >= 4 * k.R, "dsl_ld_loss: ld_soft does not hold 4 (reg_max + 1) columns (got %d)", l->ld_soft);
+  DSL_CHECK(l->T >= 1.f && l->T < 1e30f, "dsl_ld_loss: T must be finite and >= 1");
+  DSL_CHECK(l->w_ld >= 0.f && l->w_ld < 1e30f, "dsl_ld_loss: w_ld must be finite and >= 0");
+  k.soft = l->soft; k.ld_soft = l->ld_soft; k.soft_scales = l->soft_scales; k.T = l->T; k.w_ld = l->w_ld;
+  hipStream_t st = (hipStream_t)stream;
+  if (k.C % 4 != 0)
+    hipLaunchKernelGGL((gfl_loss_kernel<true, true>), dim3(blocks), dim3(256), 0, st, k);
+  else
+    hipLaunchKernelGGL((gfl_loss_kernel<false, true>), dim3(blocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(gfl_finalize_kernel<true>, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, blocks, d->losses, d->g_scales, d->norm,
+                     d->inv_world, d->logvec, k.w_cls, k.w_bbox, k.w_dfl, k.w_ld);
   DSL_LAUNCH_CHECK("gfl_loss_kernel");
   return 0;
 }

@@ -255,6 +255,18 @@ class DistributionFocalLoss(_LossCfg):
     (dsl_gfl_desc.w_dfl)."""
 
 
+@LOSSES.register_module()
+class KnowledgeDistillationKLDivLoss(_LossCfg):
+    """mmdet/models/losses/kd_loss.py:9-87: T^2 times the KL divergence between softmax(teacher / T) and softmax(student / T),
+    the loss_ld of LDHead (dsl_ld_desc.T, dsl_ld_desc.w_ld)."""
+
+    def __init__(self, reduction='mean', loss_weight=1.0, T=10):
+        super().__init__(loss_weight=loss_weight, reduction=reduction)
+        _expect(isinstance(T, (int, float)) and not isinstance(T, bool) and 1.0 <= float(T) < float('inf'),
+                f'KnowledgeDistillationKLDivLoss T: a finite number >= 1 (got {T!r}; kd_loss.py:50)')
+        self.T = float(T)
+
+
 @HEADS.register_module()
 class FCOSHead(nn.Module):
     def __init__(self, num_classes, in_channels, regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8)),
@@ -452,13 +464,27 @@ class GFLHead(nn.Module):
         lbm = self.loss_bbox
         wb = wb if isinstance(lbm, (GIoULoss, IoULoss)) else lbm.loss_weight
         self.bbox_weight = wb
-        self.options = HeadOptions(box_loss=lbm.box_loss, box_eps=lbm.eps, cls_weight=self.loss_cls.loss_weight, bbox_weight=wb,
-                                   assigner='atss', atss_topk=topk, anchor_scale=obs, head_kind='gfl', reg_max=reg_max,
-                                   qfl_beta=self.loss_cls.beta, dfl_weight=self.loss_dfl.loss_weight)
+        self._option_kw = dict(box_loss=lbm.box_loss, box_eps=lbm.eps, cls_weight=self.loss_cls.loss_weight, bbox_weight=wb,
+                               assigner='atss', atss_topk=topk, anchor_scale=obs, head_kind='gfl', reg_max=reg_max,
+                               qfl_beta=self.loss_cls.beta, dfl_weight=self.loss_dfl.loss_weight)
+        self.options = HeadOptions(**self._option_kw)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
 
     def effective_soft_weight(self, batch_size):
         return 0.0
+
+
+@HEADS.register_module()
+class LDHead(GFLHead):
+    """mmdet/models/dense_heads/ld_head.py:10-261: GFLHead with one more loss term, loss_ld = KnowledgeDistillationKLDivLoss between the
+    box distributions of a frozen teacher and the student's over the positives (dsl_ld_loss, DSL_HEAD_LD).  No new parameter; whatever
+    GFLHead refuses stays refused.  (The reference's own default names a loss type it does not register; its configs give this one.)"""
+
+    def __init__(self, num_classes, in_channels, loss_ld=dict(type='KnowledgeDistillationKLDivLoss', loss_weight=0.25, T=10), **kwargs):
+        super().__init__(num_classes, in_channels, **kwargs)
+        self.loss_ld = build_loss(loss_ld)
+        _expect(isinstance(self.loss_ld, KnowledgeDistillationKLDivLoss), 'loss_ld: KnowledgeDistillationKLDivLoss(loss_weight, T)')
+        self.options = HeadOptions(**self._option_kw, ld_weight=self.loss_ld.loss_weight, ld_T=self.loss_ld.T)
 
 
 # One stream per ROLE and device for the whole process, not per model instance (round 4).  Streams are dealt onto four hardware
@@ -545,7 +571,7 @@ class _TrainStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, det, plan):
         ctx.det, ctx.plan, ctx.eager = det, plan, bool(getattr(det, '_eager_now', False))      # were the backward lists queued already?
-        ctx.n_losses = 4 if plan.lossplan.desc.soft_weight != 0.0 else 3
+        ctx.n_losses = 4 if (plan.lossplan.desc.soft_weight != 0.0 or plan.lossplan.ld is not None) else 3      # (sisoft / loss_ld)
         # the loss terms in log order and, last, their sum - written by the loss kernel's finalize pass (dsl_fcos_desc.logvec)
         return plan.lossplan.logvec[:ctx.n_losses + 1].clone()
 
@@ -837,6 +863,8 @@ class FCOS(nn.Module):
         losses = _LossDict(loss_cls=out[0], loss_bbox=out[1], **{'loss_dfl' if lp.gfl is not None else 'loss_centerness': out[2]})
         if sw != 0.0:
             losses['loss_sisoft'] = out[3]
+        elif lp.ld is not None:
+            losses['loss_ld'] = out[3]
         losses.vec = out[:len(losses)]      # the same scalars as ONE tensor: lets _parse_losses avoid per-key device ops
         losses.vec_total = out              # ... and with their sum (the loss kernel's) as the last element: no device op at all
         return losses
@@ -1097,7 +1125,86 @@ class ATSS(FCOS):
 class GFL(FCOS):
     """mmdet/models/detectors/gfl.py:5-18: SingleStageDetector with a GFLHead, on the FCOS detector's machinery (the same network
     up to the box predictor's width; assignment, box decode, losses and their normalisers are the head's)."""
+    HEAD_TYPE = 'GFLHead'
 
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
-        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'GFLHead', "GFL with bbox_head type='GFLHead'")
+        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == self.HEAD_TYPE,
+                f"{type(self).__name__} with bbox_head type='{self.HEAD_TYPE}'")
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
+
+
+@DETECTORS.register_module()
+class KnowledgeDistillationSingleStageDetector(GFL):
+    """mmdet/models/detectors/kd_one_stage.py:10-100 with an LDHead: a GFL student whose loss has one more term against the box
+    distributions of a frozen teacher detector.  The teacher is a detector of this project with a GFL-family head on the student's
+    grid (reg_max, strides and level sizes equal); it is held as a plain attribute, so that it shows up in no parameters(),
+    state_dict(), flat store, EMA hook, optimizer or gradient bucket of the student, and it runs inference plans only.
+    simple_test / aug_test are the student's."""
+    HEAD_TYPE = 'LDHead'
+
+    def __init__(self, backbone, neck, bbox_head, teacher_config, teacher_ckpt=None, eval_teacher=True, train_cfg=None, test_cfg=None,
+                 pretrained=None, init_cfg=None, fp8=None):
+        """teacher_config: a config file's path (Config.fromfile, `_base_` followed) or a dict - a whole config with a `model` key, or
+        the model's dict itself.  teacher_ckpt: a whole-detector checkpoint (resolve_checkpoint; a path that cannot be found raises,
+        None loads nothing).  eval_teacher: accepted with either value - every teacher this project builds (GroupNorm towers, frozen
+        BatchNorm with norm_eval) computes the same thing in both modes.  init_cfg / fp8: FCOS's (fp8 towers are refused, as for GFL)."""
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
+        from .registry import Config, build_detector
+        self.eval_teacher = bool(eval_teacher)
+        if isinstance(teacher_config, (str, os.PathLike)):
+            teacher_config = Config.fromfile(os.fspath(teacher_config))
+        _expect(hasattr(teacher_config, '__getitem__'), f'teacher_config: a config path or a dict (got {type(teacher_config).__name__})')
+        tm = teacher_config['model'] if 'model' in teacher_config else teacher_config
+        teacher = build_detector(dict(tm))
+        th = getattr(getattr(teacher, 'store', None), 'head', None)
+        _expect(isinstance(teacher, FCOS) and th is not None and th.head_kind == 'gfl',
+                f'teacher_config: a detector with a GFL-family head (GFLHead / LDHead), got {type(teacher).__name__} with '
+                f'{type(getattr(teacher, "bbox_head", None)).__name__}')
+        sh = self.store.head
+        _expect(th.reg_max == sh.reg_max, f'teacher reg_max {th.reg_max} != student reg_max {sh.reg_max} (the distributions are compared bin by bin)')
+        _expect(tuple(teacher.bbox_head.strides) == tuple(self.bbox_head.strides),
+                f'teacher strides {tuple(teacher.bbox_head.strides)} != student strides {tuple(self.bbox_head.strides)}')
+        if teacher_ckpt is not None:
+            path = resolve_checkpoint(teacher_ckpt)
+            if path is None:
+                raise FileNotFoundError(f'teacher_ckpt {teacher_ckpt!r} not found (looked in $DSL_PRETRAINED_DIR and the torch hub cache): '
+                                        'a randomly initialised teacher is never what a distillation config means')
+            ck = torch.load(path, map_location='cpu')
+            sd = ck.get('state_dict', ck) if isinstance(ck, dict) else ck
+            # (mmcv's load_checkpoint: strict=False, 'module.' stripped; a file none of whose keys is the teacher's is refused)
+            sd = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in sd.items())
+            missing, _ = teacher.load_state_dict(sd, strict=False)
+            if len(missing) == len(teacher.state_dict()):
+                raise KeyError(f'{path}: no key of this checkpoint matches the teacher (first keys: {list(sd)[:5]})')
+        self.teacher_model = teacher
+
+    def __setattr__(self, name, value):
+        """kd_one_stage.py:89-100: the teacher is a plain attribute, not a registered submodule."""
+        if name == 'teacher_model':
+            object.__setattr__(self, name, value)
+        else:
+            super().__setattr__(name, value)
+
+    def _apply(self, fn, recurse=True):
+        self.teacher_model._apply(fn)          # kd_one_stage.py:75-79 (.cuda() / .to() move the teacher too)
+        return super()._apply(fn, recurse)
+
+    def train(self, mode=True):
+        self.teacher_model.train(False if self.eval_teacher else mode)
+        return super().train(mode)
+
+    def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
+        """kd_one_stage.py:43-73.  The teacher's forward is an inference plan (no loss plan, no gradient or momentum buffer) on the
+        caller's stream, in front of the student's forward; its box predictor's fp32 output and its Scale values go to the student's
+        loss descriptor (bind_soft), the rest is the GFL step.  loss_ld has no normaliser: data parallel adds no collective."""
+        eng = self._get_engine()
+        ts = self.teacher_model.store
+        N, _, H, W = img.shape
+        tplan = eng.plan(ts, N, H, W, training=False)
+        plan = eng.plan(self.store, N, H, W, training=True)
+        if [tuple(s) for s in tplan.level_sizes] != [tuple(s) for s in plan.level_sizes]:
+            raise NotImplementedError(f'dsl_amd hot path: teacher level sizes {tplan.level_sizes} != student level sizes {plan.level_sizes}')
+        tplan.bind_image(img)
+        tplan.fwd.run()
+        plan.lossplan.bind_soft(tplan.bufs['regctr'], ts.reg_ld, ts.t32_ptr('head.scales'))
+        return super().forward_train(img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore)

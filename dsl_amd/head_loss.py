@@ -30,12 +30,17 @@ class FcosLossPlan:
         (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554).
         A GFL head (head.head_kind == 'gfl'): the descriptor is a dsl_gfl_desc (`gfl`, whose first member is `desc`), the box
         predictor's rows are 4 (reg_max + 1) floats / round_up(that, 64) gradient columns wide, quality() runs between the predictors
-        and the exchange of stats[0:2] and writes stats[1], loss() is dsl_gfl_loss; losses = (cls, bbox, dfl, 0)."""
+        and the exchange of stats[0:2] and writes stats[1], loss() is dsl_gfl_loss; losses = (cls, bbox, dfl, 0).
+        An LD head (a GFL head with head.ld_weight set): the dsl_gfl_desc is the first member of a dsl_ld_desc (`ld`), bind_soft() names
+        the teacher's box predictor output, loss() is dsl_ld_loss; losses = (cls, bbox, dfl, ld), logvec has five elements."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head
-        self.gfl = None
+        self.gfl = self.ld = None
         if head is not None and head.head_kind == 'gfl':
-            self.gfl = L.GflDesc()
+            if head.ld_weight is not None:
+                self.ld = L.LdDesc()
+                self.ld.T, self.ld.w_ld = head.ld_T, head.ld_weight
+            self.gfl = self.ld.gfl if self.ld is not None else L.GflDesc()
             self.LD_RC = 4 * (head.reg_max + 1)
             self.LD_GRC = (self.LD_RC + 63) // 64 * 64
         self.ctr_col = None
@@ -102,7 +107,8 @@ class FcosLossPlan:
             g = self.gfl
             g.reg_max, g.qfl_beta, g.w_dfl = head.reg_max, head.qfl_beta, head.dfl_weight
             g.score, g.weight = L.ptr(self.score), L.ptr(self.weight)
-            self.logvec = self.logvec[:4]      # cls, bbox, dfl, their sum
+            if self.ld is None:
+                self.logvec = self.logvec[:4]      # cls, bbox, dfl, their sum (an LD head: cls, bbox, dfl, ld, their sum)
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         self.desc.workspace, self.desc.workspace_bytes = L.ptr(self.ws), need
@@ -174,6 +180,11 @@ class FcosLossPlan:
         if self.ctr_col is not None:
             self.desc.ctr, self.desc.ld_ctr = self.desc.cls_logits + 4 * self.ctr_col, self.LD_CLS
 
+    def bind_soft(self, regctr, ld, scales):
+        """LD only: the teacher's box predictor output (fp32 [M][ld], the layout of bind_outputs' regctr) and its five Scale values."""
+        self.ld.soft, self.ld.ld_soft, self.ld.soft_scales = L.ptr(regctr), ld, L.ptr(scales)
+        self._soft_keep = (regctr, scales)
+
     def assign(self):
         if self.atss is not None:
             L.check(L.lib.dsl_atss_assign(C.byref(self.desc), C.byref(self.atss), L.stream_ptr()), 'dsl_atss_assign')
@@ -185,6 +196,9 @@ class FcosLossPlan:
         L.check(L.lib.dsl_gfl_quality(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_quality')
 
     def loss(self):
+        if self.ld is not None:
+            L.check(L.lib.dsl_ld_loss(C.byref(self.ld), L.stream_ptr()), 'dsl_ld_loss')
+            return
         if self.gfl is not None:
             L.check(L.lib.dsl_gfl_loss(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_loss')
             return

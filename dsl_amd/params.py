@@ -145,21 +145,35 @@ class HeadOptions:
     the predictor names gfl_cls / gfl_reg.  focal_gamma, focal_alpha and ctr_weight are not read:
       reg_max            bins 0..reg_max per box side, 1..16 (the reference's configs use 16)
       qfl_beta           QualityFocalLoss(beta) >= 0 (losses/gfocal_loss.py:11-52)
-      dfl_weight         DistributionFocalLoss(loss_weight) (losses/gfocal_loss.py:55-78)"""
+      dfl_weight         DistributionFocalLoss(loss_weight) (losses/gfocal_loss.py:55-78)
+    Localization Distillation (LDHead, mmdet/models/dense_heads/ld_head.py, dsl_ld_desc) is a GFL head with one more loss term against
+    a frozen teacher's box distributions; the network and the parameter layout are GFL's:
+      ld_weight          KnowledgeDistillationKLDivLoss(loss_weight) >= 0; None (default): no LD term, a plain GFL head
+      ld_T               its temperature, finite and >= 1 (losses/kd_loss.py:50)"""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
     BOX_KINDS = dict(giou=L.BOX_GIOU, iou=L.BOX_IOU_LOG, iou_linear=L.BOX_IOU_LINEAR, diou=L.BOX_DIOU, ciou=L.BOX_CIOU)
     ATSS_FIELDS = ('assigner', 'atss_topk', 'anchor_scale', 'delta_stds')
     GFL_FIELDS = ('head_kind', 'reg_max', 'qfl_beta', 'dfl_weight')
+    LD_FIELDS = ('ld_weight', 'ld_T')
 
     def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
                  box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0,
                  assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2),
-                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25):
+                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0):
         if head_kind not in ('fcos', 'gfl'):
             raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos' or 'gfl', got {head_kind!r}")
         self.head_kind = head_kind
         self.reg_max, self.qfl_beta, self.dfl_weight = reg_max, float(qfl_beta), float(dfl_weight)
+        self.ld_weight, self.ld_T = None, 10.0
+        if ld_weight is not None:
+            if head_kind != 'gfl':
+                raise NotImplementedError(f"dsl_amd hot path: ld_weight is an option of head_kind='gfl' (LDHead), got head_kind={head_kind!r}")
+            if not (isinstance(ld_weight, (int, float)) and 0.0 <= float(ld_weight) < float('inf')):
+                raise NotImplementedError(f'dsl_amd hot path: ld_weight must be a finite number >= 0, got {ld_weight!r}')
+            if not (isinstance(ld_T, (int, float)) and 1.0 <= float(ld_T) < float('inf')):
+                raise NotImplementedError(f'dsl_amd hot path: ld_T must be a finite number >= 1, got {ld_T!r}')
+            self.ld_weight, self.ld_T = float(ld_weight), float(ld_T)
         if head_kind == 'gfl':
             if not (isinstance(reg_max, int) and 1 <= reg_max <= L.GFL_MAX_REG):
                 raise NotImplementedError(f'dsl_amd hot path: reg_max must be an integer in 1..{L.GFL_MAX_REG}, got {reg_max!r}')
@@ -211,7 +225,8 @@ class HeadOptions:
         k = tuple(getattr(self, f) for f in self.FIELDS)
         k = k if self.loss_is_default() else k + self.loss_key()
         k = k + tuple(getattr(self, f) for f in self.ATSS_FIELDS) if self.assigner == 'atss' else k
-        return k + tuple(getattr(self, f) for f in self.GFL_FIELDS) if self.head_kind == 'gfl' else k
+        k = k + tuple(getattr(self, f) for f in self.GFL_FIELDS) if self.head_kind == 'gfl' else k
+        return k + tuple(getattr(self, f) for f in self.LD_FIELDS) if self.ld_weight is not None else k
 
     def is_default(self):
         return self.key() == HeadOptions().key()
@@ -221,7 +236,8 @@ class HeadOptions:
         return ((0 if self.center_sampling else L.HEAD_INSIDE_BOX) | (0 if self.norm_on_bbox else L.HEAD_RAW_TARGETS | L.HEAD_EXP_DECODE)
                 | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT)
                 | (L.HEAD_ATSS if self.assigner == 'atss' else 0)
-                | (L.HEAD_GFL | L.HEAD_LOSS_EXT if self.head_kind == 'gfl' else 0))      # (a dsl_gfl_desc always carries its loss settings)
+                | (L.HEAD_GFL | L.HEAD_LOSS_EXT if self.head_kind == 'gfl' else 0)       # (a dsl_gfl_desc always carries its loss settings)
+                | (L.HEAD_LD if self.ld_weight is not None else 0))
 
     def atss_desc(self):
         """A dsl_atss_desc with the head's settings (None for an FCOS head); the caller fills max_gt, pad_shapes and npos."""
@@ -243,6 +259,7 @@ class HeadOptions:
         fields = self.FIELDS if self.loss_is_default() else self.FIELDS + self.LOSS_FIELDS
         fields += self.ATSS_FIELDS if self.assigner == 'atss' else ()
         fields += self.GFL_FIELDS if self.head_kind == 'gfl' else ()
+        fields += self.LD_FIELDS if self.ld_weight is not None else ()
         return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in fields) + ')'
 
 

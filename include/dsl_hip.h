@@ -664,6 +664,41 @@ int dsl_gfl_quality(const dsl_gfl_desc* g, void* stream);
 int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LD: LDHead's Localization Distillation term on top of GFL (mmdet/models/dense_heads/ld_head.py:99-126 loss_single, :253-261 the
+ * reduction of the level lists; mmdet/models/losses/kd_loss.py:27-35 knowledge_distillation_kl_div_loss), fp32, contraction off.
+ *
+ * A dsl_ld_desc wraps a dsl_gfl_desc whose fcos.head_flags carry DSL_HEAD_LD beside DSL_HEAD_GFL | DSL_HEAD_ATSS | DSL_HEAD_LOSS_EXT;
+ * dsl_gfl_desc keeps its size and offsets, and dsl_gfl_quality(&l->gfl) is the quality pass.  soft holds a frozen teacher's box
+ * predictor output for the same locations, laid out as fcos.regctr with row stride ld_soft; soft_scales its five Scale values.
+ *
+ * dsl_ld_loss = everything dsl_gfl_loss does (the same kernel, the LD code behind a template argument), plus for each positive m
+ * and side k, with R = reg_max + 1, z = scales[l] * student logits, s = soft_scales[l] * teacher logits, p = softmax(z / T),
+ * t = softmax(s / T):
+ *   kd(m, k)  = T^2 / R * sum_j t_j (log t_j - log p_j), a term with t_j == 0 counting as 0 (F.kl_div)
+ *   losses[3] = w_ld / 4 * sum_pos weight[m] sum_k kd(m, k)
+ * losses[3] is NOT divided by avg: the reference divides only loss_bbox and loss_dfl by the exchanged weight sum and leaves loss_ld
+ * as weighted_loss(avg_factor=4.0) returned it.  It therefore needs no value from other ranks.  weight[m] is the quality pass's
+ * value, a constant for the gradient; the teacher receives no gradient.
+ * Gradient: dL/dz_j += w_ld * weight[m] / 4 * T / R * (p_j - t_j) * grad_scale, added to the row's box and DFL gradient in front of
+ * the one bf16 rounding of g_rc and chained into g_scales[l] like them (a term that is exactly zero leaves the row's bits as
+ * dsl_gfl_loss writes them).  logvec = [cls, bbox, dfl, ld, their sum].
+ * Refused: DSL_HEAD_LD without DSL_HEAD_GFL (or a descriptor without DSL_HEAD_LD), soft or soft_scales NULL, ld_soft < 4R,
+ * T not finite or < 1, w_ld < 0 or not finite, and whatever dsl_gfl_loss refuses.
+ * One soft row load per positive and two more max / sum reductions per side inside the 16-lane groups; no LDS, launch or pass
+ * over non-positive rows beyond dsl_gfl_loss's.
+ * ---------------------------------------------------------------------------------------- */
+#define DSL_HEAD_LD 128         /* LDHead: dsl_gfl_desc inside a dsl_ld_desc */
+typedef struct dsl_ld_desc {
+  dsl_gfl_desc gfl;
+  const float* soft;                   /* teacher's box predictor output, fp32 [M][ld_soft], laid out as fcos.regctr */
+  int32_t ld_soft;                     /* >= 4R */
+  const float* soft_scales;            /* teacher's 5 Scale values (device) */
+  float T;                             /* temperature, finite, >= 1 (kd_loss.py:50) */
+  float w_ld;                          /* loss_ld.loss_weight >= 0 */
+} dsl_ld_desc;
+int dsl_ld_loss(const dsl_ld_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer / EMA over flat fp32 buffers (mmcv OptimizerHook + torch SGD, wired at
  * apis/train.py:111,157-166; EMA at runner/hooks/semi_epoch_based_runner.py:368-409)
  * ---------------------------------------------------------------------------------------- */
