@@ -312,7 +312,7 @@ _SIGS = {
     'dsl_groupnorm_relu_fwd': [_vp, _vp], 'dsl_groupnorm_relu_bwd': [_vp, _vp], 'dsl_groupnorm_workspace_bytes': [_vp],
     'dsl_sum2x2': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], 'dsl_colsum': [_vp, _vp, _l, _i, _i, _vp],
     'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_atss_assign': [_vp, _vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
-    'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp], 'dsl_ld_loss': [_vp, _vp],
+    'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp], 'dsl_ld_loss': [_vp, _vp], 'dsl_head_assign': [_vp, _vp], 'dsl_head_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
     'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],

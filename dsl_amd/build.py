@@ -32,7 +32,7 @@ def _stale(out, deps):
 
 def build_lib(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
-    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'box_loss.hpp'), os.path.join(HERE, '..', 'include', 'dsl_hip.h')]
+    hdrs = [os.path.join(CSRC, 'common.hpp'), os.path.join(CSRC, 'box_loss.hpp'), os.path.join(CSRC, 'head_common.hpp'), os.path.join(HERE, '..', 'include', 'dsl_hip.h')]
     srcs = [os.path.join(CSRC, s) for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     objs = [os.path.join(LIBDIR, os.path.basename(s)[:-4] + '.o') for s in srcs]
     hipcc = _hipcc()

@@ -243,18 +243,8 @@ extern "C" int dsl_run_ops(const dsl_op* ops, int n_ops, void* stream) {
         rc = dsl_stem_pool_half((const float*)o.p[0], o.p[1], (const float*)(intptr_t)o.l[0], (const float*)(intptr_t)o.l[1], o.p[2], o.i[0],
                                 o.i[1], o.i[2], o.i[3], o.i[4], stream);
         break;
-      case DSL_OP_ASSIGN:      // p[0]: the dsl_atss_desc of an ATSS head (dsl_atss_assign), else null
-        rc = o.p[0] ? dsl_atss_assign((const dsl_fcos_desc*)o.desc, (const dsl_atss_desc*)o.p[0], stream)
-                    : dsl_fcos_assign((const dsl_fcos_desc*)o.desc, stream);
-        break;
-      case DSL_OP_LOSS:        // p[0]: the dsl_gfl_desc of a GFL head (dsl_gfl_loss; with DSL_HEAD_LD a dsl_ld_desc, dsl_ld_loss), else null
-        if (!o.p[0])
-          rc = dsl_fcos_loss((const dsl_fcos_desc*)o.desc, stream);
-        else if (((const dsl_gfl_desc*)o.p[0])->fcos.head_flags & DSL_HEAD_LD)
-          rc = dsl_ld_loss((const dsl_ld_desc*)o.p[0], stream);
-        else
-          rc = dsl_gfl_loss((const dsl_gfl_desc*)o.p[0], stream);
-        break;
+      case DSL_OP_ASSIGN: rc = dsl_head_assign((const dsl_fcos_desc*)o.desc, stream); break;
+      case DSL_OP_LOSS: rc = dsl_head_loss((const dsl_fcos_desc*)o.desc, stream); break;
       case DSL_OP_GFL_QUALITY: rc = dsl_gfl_quality((const dsl_gfl_desc*)o.desc, stream); break;
       case DSL_OP_QUANT_FP8: {
         float sc;

@@ -32,32 +32,25 @@
 #include "common.hpp"
 #pragma clang fp contract(off)
 #include "box_loss.hpp"      // (behind the pragma: its functions are compiled without contraction too)
+#include "head_common.hpp"
 
 namespace {
 
 constexpr float kINF = 1e8f;   // fcos_head.py:11
 
-struct FcK {
-  int nlvl, n, num_classes, n_labeled;
-  int h[DSL_MAX_SEG], w[DSL_MAX_SEG], stride[DSL_MAX_SEG];
-  int mstart[DSL_MAX_SEG + 1];
+struct FcK : HeadK {
+  int n_labeled;
   float lo[DSL_MAX_SEG], hi[DSL_MAX_SEG];
-  float radius, loss_weight, soft_weight, grad_scale, inv_world;
+  float radius, loss_weight, soft_weight;
   const float* gt_boxes; const long long* gt_labels; const int* gt_off;
   const float* ig_boxes; const int* ig_off;
-  long long* labels; float* bbox_targets; int* assign_idx; float* cls_weight; float* pos_weight;
+  int* assign_idx; float* pos_weight;
   float* stats;
-  const float* cls_logits; const float* regctr; int ld_cls, ld_rc;
-  const float* scales; const float* norm;
-  uint16_t* g_cls; int ld_gcls; uint16_t* g_rc; int ld_grc;
-  float* g_scales; float* losses;
   int flags;              // DSL_HEAD_*
   const float* ctr; int ld_ctr;      // centerness logit of location m: ctr[m * ld_ctr]
   uint16_t* g_ctr; int ld_gctr;      // its gradient, when it does not live in column 4 of g_rc (else null)
-  float* part;            // block records of the loss / assignment sums (fixed-order second pass, no float atomics)
-  // loss family (loss_kernel<., true> only): DSL_BOX_*, eps of DIoU / CIoU, focal gamma / alpha, the three loss weights
-  int box_kind;
-  float box_eps, gamma, alpha, w_cls, w_bbox, w_ctr;
+  // loss family (loss_kernel<., true> only; box kind and eps, w_cls, w_bbox: HeadK): focal gamma / alpha, loss_centerness's weight
+  float gamma, alpha, w_ctr;
   // ATSS (DSL_HEAD_ATSS: the atss_* kernels and loss_kernel<., true, true> only)
   float anchor_scale, stds[4];
   int topk;
@@ -65,19 +58,6 @@ struct FcK {
   unsigned long long* akeys;        // [M] (IoU bits << 32 | ~gt index) of the winning box, 0 = none (workspace)
   int* npos;                        // [n] positives per image
 };
-
-__device__ __forceinline__ void decode_loc(const FcK& p, int m, int& lvl, int& img, int& y, int& x) {
-  lvl = 0;
-#pragma unroll
-  for (int s = 1; s < DSL_MAX_SEG; ++s)
-    if (s < p.nlvl && m >= p.mstart[s]) lvl = s;
-  const int q = m - p.mstart[lvl];
-  const int hw = p.h[lvl] * p.w[lvl];
-  img = q / hw;
-  const int r = q - img * hw;
-  y = r / p.w[lvl];
-  x = r - y * p.w[lvl];
-}
 
 // one image, one location against a list of boxes: area-argmin with centre sampling + range test
 // (fcos_head.py:632-700).  Returns min_area; idx = first argmin; ltrb of that box in t[4].
@@ -114,12 +94,12 @@ __device__ __forceinline__ float assign_one(float px, float py, float rs, float 
 
 __global__ __launch_bounds__(256) void assign_kernel(const FcK p) {
   __shared__ float sh[16];
-  const int M = p.mstart[p.nlvl];
+  const int M = p.M;
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   float is_pos = 0.f, ctr = 0.f;
   if (m < M) {
     int lvl, img, y, x;
-    decode_loc(p, m, lvl, img, y, x);
+    head_loc(p, m, lvl, img, y, x);
     const int s = p.stride[lvl];
     const float px = (float)x * (float)s + (float)(s / 2);
     const float py = (float)y * (float)s + (float)(s / 2);
@@ -204,7 +184,7 @@ __device__ __forceinline__ float atss_iou(const float a[4], float x1, float y1, 
 }
 
 __global__ __launch_bounds__(ATSS_T) void atss_zero_kernel(const FcK p) {
-  const int M = p.mstart[p.nlvl];
+  const int M = p.M;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < M) p.akeys[i] = 0ull;
   if (i < p.n) p.npos[i] = 0;
@@ -289,12 +269,12 @@ __global__ __launch_bounds__(ATSS_T) void atss_cand_kernel(const FcK p) {
 // one thread per anchor: the outputs of dsl_fcos_assign from the winning claim; block records [positives, centerness targets]
 __global__ __launch_bounds__(ATSS_T) void atss_write_kernel(const FcK p) {
   __shared__ float sh[16];
-  const int M = p.mstart[p.nlvl];
+  const int M = p.M;
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   float is_pos = 0.f, ctr = 0.f;
   if (m < M) {
     int lvl, img, y, x, vh, vw;
-    decode_loc(p, m, lvl, img, y, x);
+    head_loc(p, m, lvl, img, y, x);
     atss_valid(p, lvl, img, vh, vw);
     const bool valid = y < vh && x < vw;
     const unsigned long long key = p.akeys[m];
@@ -330,80 +310,59 @@ __global__ __launch_bounds__(ATSS_T) void atss_write_kernel(const FcK p) {
   }
 }
 
-// stats[0] = sum_i max(npos_i, 1) (atss_head.py:554), stats[1] = the block records' centerness sums in block order, stats[2..7] = 0
-__global__ __launch_bounds__(ATSS_T) void atss_finalize_kernel(const FcK p, int nblocks) {
-  __shared__ float sh[ATSS_T];
-  float a = 0.f;
-  for (int b = threadIdx.x; b < nblocks; b += ATSS_T) a += p.part[2 * b + 1];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < ATSS_T; ++k) t += sh[k];
-    int tot = 0;
-    for (int i = 0; i < p.n; ++i) tot += max(p.npos[i], 1);
-    p.stats[0] = (float)tot;
-    p.stats[1] = t;
-  } else if (threadIdx.x < 8 && threadIdx.x >= 2) {
-    p.stats[threadIdx.x] = 0.f;
+// The assignment's block records [positives, centerness targets], added in block order -> stats[0] = num_pos, stats[1] = the sum of
+// the centerness targets (this rank); stats[2..7] are reserved, kept zero.  kAtss: stats[0] = sum_i max(npos_i, 1) (atss_head.py:554)
+template <bool kAtss>
+__global__ __launch_bounds__(REC_T) void assign_finalize_kernel(const FcK p, int nblocks) {
+  __shared__ float sh[REC_T];
+  if constexpr (kAtss) {
+    const float t = record_sum(p.part, nblocks, 2, 1, 1, sh);
+    if (threadIdx.x == 0) {
+      int tot = 0;
+      for (int i = 0; i < p.n; ++i) tot += max(p.npos[i], 1);
+      p.stats[0] = (float)tot;
+      p.stats[1] = t;
+    }
+  } else {
+    const float t = record_sum(p.part, nblocks, 2, 0, 2, sh);
+    if (threadIdx.x < 2) p.stats[threadIdx.x] = t;
   }
+  if (threadIdx.x >= 2 && threadIdx.x < 8) p.stats[threadIdx.x] = 0.f;
 }
 
-// fixed-order sum of per-block records: out[v] = sum_b part[b * V + v] * scale(v); one workgroup
-constexpr int FIN_T = 256;
+// The loss records [cls, sisoft, bbox, centerness, g_scale x 5, pad], added in block order -> losses[4], g_scales[5] and logvec.
 // kAtss: loss_bbox's normaliser is clamped at 1 (atss_head.py:286), not at 1e-6
-template <bool kAtss = false>
-__global__ __launch_bounds__(FIN_T) void fcos_finalize_kernel(const float* __restrict__ part, int nblocks, int V, float* out0,
-                                                              int n0, float* out1, const float* norm, float inv_world,
-                                                              float soft_weight, int mode, float* logvec = nullptr,
-                                                              float w_cls = 1.f, float w_bbox = 1.f, float w_ctr = 1.f) {
-  __shared__ float sh[FIN_T];
-  // thread (q, v): blocks q, q + Q, ... ; then thread v adds the Q partial sums in order
-  const int Q = FIN_T / V;
-  const int v = threadIdx.x % V, q = threadIdx.x / V;
-  float a = 0.f;
-  if (q < Q) {
-#pragma unroll 8                    // (the loads of eight records in flight; the additions stay in record order)
-    for (int b = q; b < nblocks; b += Q) a += part[(long long)b * V + v];
+template <bool kAtss>
+__global__ __launch_bounds__(REC_T) void fcos_finalize_kernel(const FcK p, int nblocks) {
+  __shared__ float sh[REC_T];
+  const float t = record_sum(p.part, nblocks, 16, 0, 16, sh);
+  if (threadIdx.x < 16) {
+    const float num_pos = fmaxf(p.norm[0] * p.inv_world, 1.0f), denorm = fmaxf(p.norm[1] * p.inv_world, kAtss ? 1.0f : 1e-6f);
+    float fv = t;
+    // (loss_weight * the mean, as the loss modules do; a weight of 1 leaves the bits as they are)
+    if (threadIdx.x == 0) p.losses[0] = fv = t / num_pos * p.w_cls;
+    else if (threadIdx.x == 1) p.losses[3] = fv = t * p.soft_weight;
+    else if (threadIdx.x == 2) p.losses[1] = fv = t / denorm * p.w_bbox;
+    else if (threadIdx.x == 3) p.losses[2] = fv = t / num_pos * p.w_ctr;
+    else if (threadIdx.x - 4 < DSL_MAX_SEG) p.g_scales[threadIdx.x - 4] = t;
+    if (threadIdx.x < 4) sh[threadIdx.x] = fv;
   }
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  if (threadIdx.x < V) {
-    float t = 0.f;
-    for (int k = 0; k < Q; ++k) t += sh[k * V + threadIdx.x];
-    if (mode == 1) {           // loss records: [cls, sisoft, bbox, centerness, g_scale x 5] -> losses[4] + g_scales[5]
-      const float num_pos = fmaxf(norm[0] * inv_world, 1.0f), denorm = fmaxf(norm[1] * inv_world, kAtss ? 1.0f : 1e-6f);
-      float fv = t;
-      // (loss_weight * the mean, as the loss modules do; a weight of 1 leaves the bits as they are)
-      if (threadIdx.x == 0) out0[0] = fv = t / num_pos * w_cls;
-      else if (threadIdx.x == 1) out0[3] = fv = t * soft_weight;
-      else if (threadIdx.x == 2) out0[1] = fv = t / denorm * w_bbox;
-      else if (threadIdx.x == 3) out0[2] = fv = t / num_pos * w_ctr;
-      else if (threadIdx.x - 4 < n0) out1[threadIdx.x - 4] = t;
-      if (threadIdx.x < 4) sh[threadIdx.x] = fv;          // (slot x of sh is read by thread x only, above)
-    } else if (threadIdx.x < n0) {
-      out0[threadIdx.x] = t;
-    }
-  }
-  if (mode == 1 && logvec) {       // the log vector of _parse_losses (detectors/base.py:175-208): the loss terms and their sum
+  if (p.logvec) {       // the log vector of _parse_losses (detectors/base.py:175-208): the loss terms and their sum
     __syncthreads();
     if (threadIdx.x == 0) {
       const float cls = sh[0], soft = sh[1], bbox = sh[2], ctr = sh[3];
       float tot = (cls + bbox) + ctr;
       int n = 3;
-      logvec[0] = cls; logvec[1] = bbox; logvec[2] = ctr;
-      if (soft_weight != 0.f) { logvec[n++] = soft; tot += soft; }
-      logvec[n] = tot;
+      p.logvec[0] = cls; p.logvec[1] = bbox; p.logvec[2] = ctr;
+      if (p.soft_weight != 0.f) { p.logvec[n++] = soft; tot += soft; }
+      p.logvec[n] = tot;
     }
   }
-  if (mode == 0 && (int)threadIdx.x >= V && threadIdx.x < 8) out0[threadIdx.x] = 0.f;      // stats[2..7] are reserved, kept zero
 }
 
 __global__ void points_kernel(const FcK p, float* __restrict__ pts) {
-  int P = 0;
-  for (int l = 0; l < p.nlvl; ++l) P += p.h[l] * p.w[l];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
+  if (i >= p.M / p.n) return;
   int l = 0, q = i;
   while (q >= p.h[l] * p.w[l]) {
     q -= p.h[l] * p.w[l];
@@ -479,7 +438,7 @@ __device__ __forceinline__ void focal_fb_ext(float x, bool t, float gamma, float
 template <bool kTail, bool kExt, bool kAtss = false>
 __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
   __shared__ float sh[16];
-  const int M = p.mstart[p.nlvl];
+  const int M = p.M;
   const int C = p.num_classes;
   const int c4 = kTail ? (C + 3) / 4 : C / 4;
   const float num_pos = fmaxf(p.norm[0] * p.inv_world, 1.0f);
@@ -512,7 +471,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
     }
     if (sisoft) {
       int lvl, img, y, x;
-      decode_loc(p, m, lvl, img, y, x);
+      head_loc(p, m, lvl, img, y, x);
       if (img == p.n - 2 && lvl >= 1) {
         // this is cls_scores[lvl][B-2]; partner cls_scores[lvl-1][B-1][:, :h, :w]  (fcos_head.py:315-319)
         const int pl = lvl - 1;
@@ -556,7 +515,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
     const int label = (int)p.labels[m];
     if (label < C) {
       int lvl, img, y, x;
-      decode_loc(p, m, lvl, img, y, x);
+      head_loc(p, m, lvl, img, y, x);
       const int s = p.stride[lvl];
       const float px = (float)x * (float)s + (float)(s / 2), py = (float)y * (float)s + (float)(s / 2);
       const float sc = p.scales[lvl];
@@ -601,6 +560,8 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) dbox[k] = coef != 0.f ? coef * dl[k] : 0.f;
       } else {
+        // (kept inline, not box_loss_giou: that forms the IoU log loss's gradient as c * (dg / iouc), this block as (c / iouc) * dg -
+        // other bits in the plain FCOS head's gradients)
         const float eps = 1e-6f;
         const float a1 = (x2 - x1) * (y2 - y1), a2 = (X2 - X1) * (Y2 - Y1);
         const float ltx = fmaxf(x1, X1), lty = fmaxf(y1, Y1), rbx = fminf(x2, X2), rby = fminf(y2, Y2);
@@ -708,29 +669,16 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
 }
 
 int fill(const dsl_fcos_desc* d, FcK& k) {
-  DSL_CHECK(d && d->nlvl >= 1 && d->nlvl <= DSL_MAX_SEG && d->n >= 1, "fcos: bad descriptor");
-  memset(&k, 0, sizeof(k));
-  k.nlvl = d->nlvl; k.n = d->n; k.num_classes = d->num_classes;
+  k = FcK{};
+  if (head_fill(d, k, "fcos")) return -1;
   k.n_labeled = d->n / 2;      // fcos_head.py:225-231: first floor(B/2) images are the labeled stream
-  int m = 0;
   for (int l = 0; l < d->nlvl; ++l) {
-    k.h[l] = d->h[l]; k.w[l] = d->w[l]; k.stride[l] = d->stride[l];
     k.lo[l] = d->range_lo[l]; k.hi[l] = d->range_hi[l];
-    k.mstart[l] = m;
-    m += d->n * d->h[l] * d->w[l];
   }
-  k.mstart[d->nlvl] = m;
-  k.part = (float*)d->workspace;
   k.radius = d->radius; k.loss_weight = d->loss_weight; k.soft_weight = d->soft_weight;
-  k.grad_scale = d->grad_scale; k.inv_world = d->inv_world;
   k.gt_boxes = d->gt_boxes; k.gt_labels = (const long long*)d->gt_labels; k.gt_off = d->gt_off;
   k.ig_boxes = d->ig_boxes; k.ig_off = d->ig_off;
-  k.labels = (long long*)d->labels; k.bbox_targets = d->bbox_targets; k.assign_idx = d->assign_idx;
-  k.cls_weight = d->cls_weight; k.pos_weight = d->pos_weight; k.stats = d->stats;
-  k.cls_logits = d->cls_logits; k.regctr = d->regctr; k.ld_cls = d->ld_cls; k.ld_rc = d->ld_rc;
-  k.scales = d->scales; k.norm = d->norm;
-  k.g_cls = (uint16_t*)d->g_cls; k.ld_gcls = d->ld_gcls; k.g_rc = (uint16_t*)d->g_rc; k.ld_grc = d->ld_grc;
-  k.g_scales = d->g_scales; k.losses = d->losses;
+  k.assign_idx = d->assign_idx; k.pos_weight = d->pos_weight; k.stats = d->stats;
   k.flags = d->head_flags;
   // centerness_on_reg=False: the logit and its gradient live with the classification predictor (caller-given addresses)
   k.ctr = d->ctr ? d->ctr : (d->regctr ? d->regctr + 4 : nullptr);
@@ -740,14 +688,10 @@ int fill(const dsl_fcos_desc* d, FcK& k) {
   k.box_kind = (k.flags & DSL_HEAD_IOU_LOSS) ? DSL_BOX_IOU_LOG : DSL_BOX_GIOU;
   k.box_eps = 1e-6f; k.gamma = 2.f; k.alpha = 0.25f; k.w_cls = k.w_bbox = k.w_ctr = 1.f;
   if (k.flags & DSL_HEAD_LOSS_EXT) {
-    DSL_CHECK(d->box_kind >= DSL_BOX_GIOU && d->box_kind <= DSL_BOX_CIOU, "fcos: box_kind is not a DSL_BOX_* value");
+    if (head_loss_settings(d, d->w_ctr, k, "fcos")) return -1;
     DSL_CHECK(d->focal_gamma >= 0.f && d->focal_gamma < 1e30f && d->focal_alpha >= 0.f && d->focal_alpha <= 1.f,
               "fcos: focal gamma must be >= 0 and alpha in [0, 1]");
-    DSL_CHECK(d->w_cls >= 0.f && d->w_cls < 1e30f && d->w_bbox >= 0.f && d->w_bbox < 1e30f && d->w_ctr >= 0.f && d->w_ctr < 1e30f,
-              "fcos: loss weights must be finite and >= 0");
-    DSL_CHECK(d->box_kind < DSL_BOX_DIOU || (d->box_eps > 0.f && d->box_eps < 1.f), "fcos: DIoU / CIoU need 0 < box_eps < 1");
-    k.box_kind = d->box_kind; k.box_eps = d->box_eps; k.gamma = d->focal_gamma; k.alpha = d->focal_alpha;
-    k.w_cls = d->w_cls; k.w_bbox = d->w_bbox; k.w_ctr = d->w_ctr;
+    k.gamma = d->focal_gamma; k.alpha = d->focal_alpha; k.w_ctr = d->w_ctr;
     k.flags = (k.flags & ~DSL_HEAD_IOU_LOSS) | (k.box_kind == DSL_BOX_IOU_LOG ? DSL_HEAD_IOU_LOSS : 0);
   }
   if (k.flags & DSL_HEAD_ATSS) {
@@ -774,15 +718,19 @@ bool loss_is_default(const FcK& k) {
   return k.box_kind <= DSL_BOX_IOU_LOG && k.gamma == 2.f && k.alpha == 0.25f && k.w_cls == 1.f && k.w_bbox == 1.f && k.w_ctr == 1.f;
 }
 
+// loss_kernel's instantiations, [C % 4 != 0][0 the default head, 1 the loss family, 2 ATSS (always the loss family's kernel: with
+// the default settings it computes the default terms)]
+void (*const kLossKernel[2][3])(const FcK) = {{loss_kernel<false, false>, loss_kernel<false, true>, loss_kernel<false, true, true>},
+                                              {loss_kernel<true, false>, loss_kernel<true, true>, loss_kernel<true, true, true>}};
+
 }  // namespace
 
 extern "C" size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d) {
-  if (!d) return 0;
-  long long M = 0;
-  for (int l = 0; l < d->nlvl; ++l) M += (long long)d->n * d->h[l] * d->w[l];
-  const size_t assign_rec = (size_t)((M + 255) / 256) * 2, loss_rec = 2048 * 16;
+  HeadGeom g;
+  if (head_geom(d, g, "dsl_fcos_workspace_bytes")) return 0;
+  const size_t assign_rec = (size_t)((g.M + 255) / 256) * 2, loss_rec = 2048 * 16;
   const size_t need = (assign_rec > loss_rec ? assign_rec : loss_rec) * sizeof(float);
-  if (d->head_flags & DSL_HEAD_ATSS) return need > atss_assign_bytes(M) ? need : atss_assign_bytes(M);
+  if (d->head_flags & DSL_HEAD_ATSS) return need > atss_assign_bytes(g.M) ? need : atss_assign_bytes(g.M);
   return need;
 }
 
@@ -790,9 +738,7 @@ extern "C" int dsl_fcos_points(const dsl_fcos_desc* d, float* points, void* stre
   FcK k;
   if (fill(d, k)) return -1;
   DSL_CHECK(points, "dsl_fcos_points: null output");
-  int P = 0;
-  for (int l = 0; l < d->nlvl; ++l) P += d->h[l] * d->w[l];
-  hipLaunchKernelGGL(points_kernel, dim3((P + 255) / 256), dim3(256), 0, (hipStream_t)stream, k, points);
+  hipLaunchKernelGGL(points_kernel, dim3((k.M / k.n + 255) / 256), dim3(256), 0, (hipStream_t)stream, k, points);
   DSL_LAUNCH_CHECK("points_kernel");
   return 0;
 }
@@ -805,13 +751,10 @@ extern "C" int dsl_fcos_assign(const dsl_fcos_desc* d, void* stream) {
             "dsl_fcos_assign: null pointer");
   DSL_CHECK(!(d->head_flags & DSL_HEAD_ATSS), "dsl_fcos_assign: a DSL_HEAD_ATSS descriptor is assigned by dsl_atss_assign");
   hipStream_t st = (hipStream_t)stream;
-  const int M = k.mstart[k.nlvl];
-  const int nb = (M + 255) / 256;
+  const int nb = (k.M + 255) / 256;
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d), "dsl_fcos_assign: workspace too small");
   hipLaunchKernelGGL(assign_kernel, dim3(nb), dim3(256), 0, st, k);
-  // stats[0] = num_pos, stats[1] = sum of centerness targets (this rank), stats[2..7] = 0: block records added in block order
-  hipLaunchKernelGGL(fcos_finalize_kernel<false>, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, nb, 2, d->stats, 2, (float*)nullptr,
-                     (const float*)nullptr, 1.f, 0.f, 0);
+  hipLaunchKernelGGL(assign_finalize_kernel<false>, dim3(1), dim3(REC_T), 0, st, k, nb);
   DSL_LAUNCH_CHECK("assign_kernel");
   return 0;
 }
@@ -828,7 +771,7 @@ extern "C" int dsl_atss_assign(const dsl_fcos_desc* d, const dsl_atss_desc* a, v
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d) && ((uintptr_t)d->workspace & 15) == 0,
             "dsl_atss_assign: workspace too small or not 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  const int M = k.mstart[k.nlvl];
+  const int M = k.M;
   const int nb = (M + ATSS_T - 1) / ATSS_T;
   k.topk = a->topk; k.pad_shapes = a->pad_shapes; k.npos = a->npos;
   k.akeys = (unsigned long long*)((char*)d->workspace + (atss_assign_bytes(M) - (size_t)M * 8));
@@ -836,7 +779,7 @@ extern "C" int dsl_atss_assign(const dsl_fcos_desc* d, const dsl_atss_desc* a, v
   hipLaunchKernelGGL(atss_zero_kernel, dim3((nz + ATSS_T - 1) / ATSS_T), dim3(ATSS_T), 0, st, k);
   hipLaunchKernelGGL(atss_cand_kernel, dim3(a->max_gt), dim3(ATSS_T), 0, st, k);
   hipLaunchKernelGGL(atss_write_kernel, dim3(nb), dim3(ATSS_T), 0, st, k);
-  hipLaunchKernelGGL(atss_finalize_kernel, dim3(1), dim3(ATSS_T), 0, st, k, nb);
+  hipLaunchKernelGGL(assign_finalize_kernel<true>, dim3(1), dim3(REC_T), 0, st, k, nb);
   DSL_LAUNCH_CHECK("atss_assign");
   return 0;
 }
@@ -845,42 +788,31 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   FcK k;
   if (fill(d, k)) return -1;
   DSL_CHECK(!(d->head_flags & DSL_HEAD_GFL), "dsl_fcos_loss: a DSL_HEAD_GFL descriptor's loss is dsl_gfl_loss");
-  DSL_CHECK(d->labels && d->bbox_targets && d->cls_weight && d->pos_weight && d->cls_logits && d->regctr &&
-                d->scales && d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses,
-            "dsl_fcos_loss: null pointer");
+  if (head_loss_ptrs(d, "dsl_fcos_loss")) return -1;
+  DSL_CHECK(d->pos_weight, "dsl_fcos_loss: null pointer");
   DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_gcls % 4 == 0 &&
                 d->ld_gcls >= d->ld_cls && d->ld_grc % 8 == 0 && d->ld_rc >= (d->ctr ? 4 : 5),
             "dsl_fcos_loss: unsupported strides / class count");
   DSL_CHECK((d->ctr != nullptr) == (d->g_ctr != nullptr), "dsl_fcos_loss: ctr and g_ctr go together");
   hipStream_t st = (hipStream_t)stream;
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d), "dsl_fcos_loss: workspace too small");
-  const int M = k.mstart[k.nlvl];
-  const bool tail = d->num_classes % 4 != 0;
-  int blocks = (int)(((long long)M * ((d->num_classes + 3) / 4) + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
-  if (k.flags & DSL_HEAD_ATSS) {      // (always the loss family's kernel: with the default settings it computes the default terms)
-    if (tail)
-      hipLaunchKernelGGL((loss_kernel<true, true, true>), dim3(blocks), dim3(256), 0, st, k);
-    else
-      hipLaunchKernelGGL((loss_kernel<false, true, true>), dim3(blocks), dim3(256), 0, st, k);
-    hipLaunchKernelGGL(fcos_finalize_kernel<true>, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
-                       DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec, k.w_cls, k.w_bbox, k.w_ctr);
-    DSL_LAUNCH_CHECK("loss_kernel");
-    return 0;
-  }
-  if (loss_is_default(k)) {
-    if (tail)
-      hipLaunchKernelGGL((loss_kernel<true, false>), dim3(blocks), dim3(256), 0, st, k);
-    else
-      hipLaunchKernelGGL((loss_kernel<false, false>), dim3(blocks), dim3(256), 0, st, k);
-  } else {
-    if (tail)
-      hipLaunchKernelGGL((loss_kernel<true, true>), dim3(blocks), dim3(256), 0, st, k);
-    else
-      hipLaunchKernelGGL((loss_kernel<false, true>), dim3(blocks), dim3(256), 0, st, k);
-  }
-  hipLaunchKernelGGL(fcos_finalize_kernel<false>, dim3(1), dim3(FIN_T), 0, st, (const float*)k.part, blocks, 16, d->losses,
-                     DSL_MAX_SEG, d->g_scales, d->norm, d->inv_world, d->soft_weight, 1, d->logvec, k.w_cls, k.w_bbox, k.w_ctr);
+  const bool atss = (k.flags & DSL_HEAD_ATSS) != 0;
+  const int blocks = head_loss_blocks(k);
+  hipLaunchKernelGGL(kLossKernel[d->num_classes % 4 != 0][atss ? 2 : !loss_is_default(k)], dim3(blocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(atss ? fcos_finalize_kernel<true> : fcos_finalize_kernel<false>, dim3(1), dim3(REC_T), 0, st, k, blocks);
   DSL_LAUNCH_CHECK("loss_kernel");
   return 0;
+}
+
+/* one dispatch for every head: the entry point a descriptor's head_flags name (include/dsl_hip.h) */
+extern "C" int dsl_head_assign(const dsl_fcos_desc* d, void* stream) {
+  DSL_CHECK(d, "dsl_head_assign: null descriptor");
+  return (d->head_flags & DSL_HEAD_ATSS) ? dsl_atss_assign(d, d->atss, stream) : dsl_fcos_assign(d, stream);
+}
+
+extern "C" int dsl_head_loss(const dsl_fcos_desc* d, void* stream) {
+  DSL_CHECK(d, "dsl_head_loss: null descriptor");
+  if (d->head_flags & DSL_HEAD_LD) return dsl_ld_loss((const dsl_ld_desc*)d, stream);
+  if (d->head_flags & DSL_HEAD_GFL) return dsl_gfl_loss((const dsl_gfl_desc*)d, stream);
+  return dsl_fcos_loss(d, stream);
 }

@@ -15,40 +15,19 @@
 #include "common.hpp"
 #pragma clang fp contract(off)
 #include "box_loss.hpp"
+#include "head_common.hpp"
 
 namespace {
 
-struct GfK {
-  int nlvl, n, C, R, M;
-  int h[DSL_MAX_SEG], w[DSL_MAX_SEG], stride[DSL_MAX_SEG];
-  int mstart[DSL_MAX_SEG + 1];
-  const long long* labels; const float* bbox_targets; const float* cls_weight;
-  const float* cls; int ld_cls;
-  const float* rc; int ld_rc;
-  const float* scales; const float* norm;
-  float inv_world, grad_scale;
-  uint16_t* g_cls; int ld_gcls; uint16_t* g_rc; int ld_grc;
+struct GfK : HeadK {
+  int R;                  // reg_max + 1
   float* score; float* weight;
-  float* part;            // block records (fixed-order second pass, no float atomics)
-  int box_kind;
-  float box_eps, beta, w_cls, w_bbox, w_dfl;
+  float beta, w_dfl;
   float tmax;             // reg_max - 0.1 (bbox2distance's clamp, transforms.py:183-184)
   // dsl_ld_loss only (gfl_loss_kernel<., true>; all zero otherwise)
   const float* soft; int ld_soft; const float* soft_scales;
   float T, w_ld;
 };
-
-__device__ __forceinline__ void gfl_loc(const GfK& p, int m, int& lvl, int& y, int& x) {
-  lvl = 0;
-#pragma unroll
-  for (int s = 1; s < DSL_MAX_SEG; ++s)
-    if (s < p.nlvl && m >= p.mstart[s]) lvl = s;
-  const int q = m - p.mstart[lvl];
-  const int hw = p.h[lvl] * p.w[lvl];
-  const int r = q - (q / hw) * hw;
-  y = r / p.w[lvl];
-  x = r - y * p.w[lvl];
-}
 
 // reductions inside a 16-lane group (one box side)
 __device__ __forceinline__ float group_sum(float v) {
@@ -72,7 +51,7 @@ __device__ __forceinline__ void gfl_row(const GfK& p, int m, int lvl, int lane, 
   const int k = lane >> 4, j = lane & 15;
   o.has0 = j < p.R;
   o.has1 = j + 16 < p.R;
-  const float* row = p.rc + (long long)m * p.ld_rc + k * p.R;
+  const float* row = p.regctr + (long long)m * p.ld_rc + k * p.R;
   o.sc = p.scales[lvl];
   o.raw0 = o.has0 ? row[j] : 0.f;
   o.raw1 = o.has1 ? row[j + 16] : 0.f;
@@ -113,15 +92,15 @@ __global__ __launch_bounds__(256) void gfl_quality_kernel(const GfK p) {
   const int lane = threadIdx.x & 63;
   const int m = blockIdx.x * 256 + threadIdx.x;
   const int base = m - lane;
-  const bool pos = m < p.M && (int)p.labels[m] < p.C;
+  const bool pos = m < p.M && (int)p.labels[m] < p.num_classes;
   float my_s = 0.f, my_w = 0.f;
   unsigned long long mask = __ballot(pos);
   while (mask) {
     const int r = __ffsll((long long)mask) - 1;
     mask &= mask - 1;
     const int mm = base + r;
-    int lvl, y, x;
-    gfl_loc(p, mm, lvl, y, x);
+    int lvl, img, y, x;
+    head_loc(p, mm, lvl, img, y, x);
     GflRow o;
     gfl_row(p, mm, lvl, lane, o);
     const float s = (float)p.stride[lvl];
@@ -135,8 +114,8 @@ __global__ __launch_bounds__(256) void gfl_quality_kernel(const GfK p) {
     const float iou = ov / fmaxf(a1 + a2 - ov, 1e-6f);
     // max_c sigmoid(cls): the sigmoid of the largest logit (sigmoid is monotonic)
     float best = -__builtin_inff();
-    const float* c = p.cls + (long long)mm * p.ld_cls;
-    for (int i = lane; i < p.C; i += 64) best = fmaxf(best, c[i]);
+    const float* c = p.cls_logits + (long long)mm * p.ld_cls;
+    for (int i = lane; i < p.num_classes; i += 64) best = fmaxf(best, c[i]);
 #pragma unroll
     for (int q = 32; q > 0; q >>= 1) best = fmaxf(best, __shfl_xor(best, q, 64));
     const float wv = gfl_sigmoid(best);
@@ -153,19 +132,11 @@ __global__ __launch_bounds__(256) void gfl_quality_kernel(const GfK p) {
   if (threadIdx.x == 0) p.part[blockIdx.x] = bs;
 }
 
-// out[0] = sum_b part[b], in a fixed order; one workgroup
-constexpr int GFL_FIN_T = 256;
-__global__ __launch_bounds__(GFL_FIN_T) void gfl_sum_kernel(const float* __restrict__ part, int nblocks, float* out) {
-  __shared__ float sh[GFL_FIN_T];
-  float a = 0.f;
-  for (int b = threadIdx.x; b < nblocks; b += GFL_FIN_T) a += part[b];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float t = 0.f;
-    for (int k = 0; k < GFL_FIN_T; ++k) t += sh[k];
-    out[0] = t;
-  }
+// stats[1] = the sum of the block records (the weights), in block order
+__global__ __launch_bounds__(REC_T) void gfl_quality_finalize_kernel(const GfK p, int nblocks, float* out) {
+  __shared__ float sh[REC_T];
+  const float t = record_sum(p.part, nblocks, 1, 0, 1, sh);
+  if (threadIdx.x == 0) out[0] = t;
 }
 
 // ---- Quality Focal Loss of one logit and dloss/dx (gfocal_loss.py:11-52) ---------------------------------------------------------
@@ -207,7 +178,7 @@ __device__ __forceinline__ void qfl_fb(float x, bool pos, float t, float beta, b
 template <bool kTail, bool kLd>
 __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
   __shared__ float sh[16];
-  const int M = p.M, C = p.C;
+  const int M = p.M, C = p.num_classes;
   const int c4 = kTail ? (C + 3) / 4 : C / 4;
   const float num = fmaxf(p.norm[0] * p.inv_world, 1.0f);
   const float avg = fmaxf(p.norm[1] * p.inv_world, 1.0f);
@@ -219,7 +190,7 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const int m = (int)(i / c4);
     const int c = (int)(i - (long long)m * c4) * 4;
-    const f32x4 xv = *reinterpret_cast<const f32x4*>(p.cls + (long long)m * p.ld_cls + c);
+    const f32x4 xv = *reinterpret_cast<const f32x4*>(p.cls_logits + (long long)m * p.ld_cls + c);
     const int label = (int)p.labels[m];
     const float wgt = p.cls_weight[m];
     const float gs = wgt / num * p.grad_scale * p.w_cls;
@@ -267,8 +238,8 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
       const int r = __ffsll((long long)mask) - 1;
       mask &= mask - 1;
       const int mm = base + r;
-      int lvl, y, x;
-      gfl_loc(p, mm, lvl, y, x);
+      int lvl, img, y, x;
+      head_loc(p, mm, lvl, img, y, x);
       GflRow o;
       gfl_row(p, mm, lvl, lane, o);
       const float s = (float)p.stride[lvl];
@@ -348,40 +319,29 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(const GfK p) {
 // fixed-order sum of the 16-float block records -> losses[4] (cls, bbox, dfl, 0), g_scales[5], logvec[4] (cls, bbox, dfl, their sum);
 // kLd: losses[3] = w_ld / 4 * the records' LD sums (no normaliser), logvec[5] (cls, bbox, dfl, ld, their sum)
 template <bool kLd>
-__global__ __launch_bounds__(GFL_FIN_T) void gfl_finalize_kernel(const float* __restrict__ part, int nblocks, float* losses, float* g_scales,
-                                                                 const float* norm, float inv_world, float* logvec, float w_cls,
-                                                                 float w_bbox, float w_dfl, float w_ld) {
-  __shared__ float sh[GFL_FIN_T];
-  constexpr int V = 16, Q = GFL_FIN_T / V;
-  const int v = threadIdx.x % V, q = threadIdx.x / V;
-  float a = 0.f;
-#pragma unroll 8
-  for (int b = q; b < nblocks; b += Q) a += part[(long long)b * V + v];
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  float fv = 0.f;
-  if (threadIdx.x < V) {
-    float t = 0.f;
-    for (int i = 0; i < Q; ++i) t += sh[i * V + threadIdx.x];
-    const float num = fmaxf(norm[0] * inv_world, 1.0f), avg = fmaxf(norm[1] * inv_world, 1.0f);
-    if (threadIdx.x == 0) losses[0] = fv = t / num * w_cls;
-    else if (threadIdx.x == 1) losses[3] = fv = kLd ? t * (w_ld * 0.25f) : 0.f;
-    else if (threadIdx.x == 2) losses[1] = fv = t / avg * w_bbox;
-    else if (threadIdx.x == 3) losses[2] = fv = t / avg * (w_dfl * 0.25f);
-    else if (threadIdx.x - 4 < DSL_MAX_SEG) g_scales[threadIdx.x - 4] = t;
-  }
-  if (logvec) {      // the log vector of _parse_losses (detectors/base.py:175-208): the loss terms and their sum
-    __syncthreads();
+__global__ __launch_bounds__(REC_T) void gfl_finalize_kernel(const GfK p, int nblocks) {
+  __shared__ float sh[REC_T];
+  const float t = record_sum(p.part, nblocks, 16, 0, 16, sh);
+  if (threadIdx.x < 16) {
+    const float num = fmaxf(p.norm[0] * p.inv_world, 1.0f), avg = fmaxf(p.norm[1] * p.inv_world, 1.0f);
+    float fv = 0.f;
+    if (threadIdx.x == 0) p.losses[0] = fv = t / num * p.w_cls;
+    else if (threadIdx.x == 1) p.losses[3] = fv = kLd ? t * (p.w_ld * 0.25f) : 0.f;
+    else if (threadIdx.x == 2) p.losses[1] = fv = t / avg * p.w_bbox;
+    else if (threadIdx.x == 3) p.losses[2] = fv = t / avg * (p.w_dfl * 0.25f);
+    else if (threadIdx.x - 4 < DSL_MAX_SEG) p.g_scales[threadIdx.x - 4] = t;
     if (threadIdx.x < 4) sh[threadIdx.x] = fv;
+  }
+  if (p.logvec) {      // the log vector of _parse_losses (detectors/base.py:175-208): the loss terms and their sum
     __syncthreads();
     if (threadIdx.x == 0) {
       const float cls = sh[0], bbox = sh[2], dfl = sh[3];
-      logvec[0] = cls; logvec[1] = bbox; logvec[2] = dfl;
+      p.logvec[0] = cls; p.logvec[1] = bbox; p.logvec[2] = dfl;
       if constexpr (kLd) {
-        logvec[3] = sh[1];
-        logvec[4] = ((cls + bbox) + dfl) + sh[1];
+        p.logvec[3] = sh[1];
+        p.logvec[4] = ((cls + bbox) + dfl) + sh[1];
       } else {
-        logvec[3] = (cls + bbox) + dfl;
+        p.logvec[3] = (cls + bbox) + dfl;
       }
     }
   }
@@ -398,30 +358,40 @@ int gfl_fill(const dsl_gfl_desc* g, GfK& k, const char* who) {
   DSL_CHECK(!d->ctr && !d->g_ctr, "%s: a GFL head has no centerness", who);
   DSL_CHECK(d->loss_weight == 1.0f && d->soft_weight == 0.f, "%s: no DSL stream weight / sisoft term", who);
   DSL_CHECK(g->reg_max >= 1 && g->reg_max <= DSL_GFL_MAX_REG, "%s: reg_max must be in 1..%d, got %d", who, DSL_GFL_MAX_REG, g->reg_max);
-  memset(&k, 0, sizeof(k));
-  k.nlvl = d->nlvl; k.n = d->n; k.C = d->num_classes; k.R = g->reg_max + 1;
-  long long m = 0;
-  for (int l = 0; l < d->nlvl; ++l) {
-    DSL_CHECK(d->h[l] >= 1 && d->w[l] >= 1 && d->stride[l] >= 1, "%s: bad level %d", who, l);
-    k.h[l] = d->h[l]; k.w[l] = d->w[l]; k.stride[l] = d->stride[l];
-    k.mstart[l] = (int)m;
-    m += (long long)d->n * d->h[l] * d->w[l];
-  }
-  DSL_CHECK(m < (1ll << 31) - 256, "%s: too many locations", who);
-  k.mstart[d->nlvl] = (int)m;
-  k.M = (int)m;
+  k = GfK{};
+  if (head_fill(d, k, who)) return -1;
+  k.R = g->reg_max + 1;
   DSL_CHECK(d->labels && d->bbox_targets && d->cls_weight && d->cls_logits && d->regctr && d->scales && d->stats && g->score && g->weight,
             "%s: null pointer", who);
   DSL_CHECK(d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= 4 * k.R, "%s: ld_cls / ld_rc do not hold C / 4 (reg_max + 1) columns", who);
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d) && ((uintptr_t)d->workspace & 15) == 0,
             "%s: workspace too small or not 16-byte aligned", who);
-  k.labels = (const long long*)d->labels; k.bbox_targets = d->bbox_targets; k.cls_weight = d->cls_weight;
-  k.cls = d->cls_logits; k.ld_cls = d->ld_cls; k.rc = d->regctr; k.ld_rc = d->ld_rc;
-  k.scales = d->scales; k.norm = d->norm; k.inv_world = d->inv_world; k.grad_scale = d->grad_scale;
-  k.g_cls = (uint16_t*)d->g_cls; k.ld_gcls = d->ld_gcls; k.g_rc = (uint16_t*)d->g_rc; k.ld_grc = d->ld_grc;
-  k.score = g->score; k.weight = g->weight; k.part = (float*)d->workspace;
+  k.score = g->score; k.weight = g->weight;
   k.tmax = (float)((double)g->reg_max - 0.1);
   return 0;
+}
+
+// what the loss passes check and fill beyond gfl_fill
+int gfl_loss_fill(const dsl_gfl_desc* g, GfK& k, const char* who) {
+  if (gfl_fill(g, k, who)) return -1;
+  const dsl_fcos_desc* d = &g->fcos;
+  if (head_loss_ptrs(d, who)) return -1;
+  DSL_CHECK(d->ld_gcls % 4 == 0 && d->ld_gcls >= d->ld_cls, "%s: ld_gcls must be a multiple of 4 and >= ld_cls", who);
+  DSL_CHECK(d->ld_grc >= 8 && d->ld_grc <= 512 && (d->ld_grc & (d->ld_grc - 1)) == 0 && d->ld_grc >= 4 * k.R && ((uintptr_t)d->g_rc & 15) == 0,
+            "%s: ld_grc must be a power of two in 8..512 and >= 4 (reg_max + 1), g_rc 16-byte aligned", who);
+  if (head_loss_settings(d, g->w_dfl, k, who)) return -1;
+  DSL_CHECK(g->qfl_beta >= 0.f && g->qfl_beta < 1e30f, "%s: qfl_beta must be finite and >= 0", who);
+  k.beta = g->qfl_beta; k.w_dfl = g->w_dfl;
+  return 0;
+}
+
+// the loss kernel [C % 4 != 0][LD] and the sum of its records
+void gfl_loss_launch(const GfK& k, bool ld, hipStream_t st) {
+  static void (*const kernel[2][2])(const GfK) = {{gfl_loss_kernel<false, false>, gfl_loss_kernel<false, true>},
+                                                  {gfl_loss_kernel<true, false>, gfl_loss_kernel<true, true>}};
+  const int blocks = head_loss_blocks(k);
+  hipLaunchKernelGGL(kernel[k.num_classes % 4 != 0][ld], dim3(blocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(ld ? gfl_finalize_kernel<true> : gfl_finalize_kernel<false>, dim3(1), dim3(REC_T), 0, st, k, blocks);
 }
 
 }  // namespace
@@ -432,43 +402,15 @@ extern "C" int dsl_gfl_quality(const dsl_gfl_desc* g, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int nb = (k.M + 255) / 256;      // (<= the workspace's (M + 255) / 256 * 2 floats)
   hipLaunchKernelGGL(gfl_quality_kernel, dim3(nb), dim3(256), 0, st, k);
-  hipLaunchKernelGGL(gfl_sum_kernel, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, nb, g->fcos.stats + 1);
+  hipLaunchKernelGGL(gfl_quality_finalize_kernel, dim3(1), dim3(REC_T), 0, st, k, nb, g->fcos.stats + 1);
   DSL_LAUNCH_CHECK("gfl_quality_kernel");
-  return 0;
-}
-
-// what dsl_gfl_loss checks and fills beyond gfl_fill; `blocks` = the launch's grid
-static int gfl_loss_fill(const dsl_gfl_desc* g, GfK& k, int& blocks, const char* who) {
-  if (gfl_fill(g, k, who)) return -1;
-  const dsl_fcos_desc* d = &g->fcos;
-  DSL_CHECK(d->norm && d->g_cls && d->g_rc && d->g_scales && d->losses, "%s: null pointer", who);
-  DSL_CHECK(d->ld_gcls % 4 == 0 && d->ld_gcls >= d->ld_cls, "%s: ld_gcls must be a multiple of 4 and >= ld_cls", who);
-  DSL_CHECK(d->ld_grc >= 8 && d->ld_grc <= 512 && (d->ld_grc & (d->ld_grc - 1)) == 0 && d->ld_grc >= 4 * k.R && ((uintptr_t)d->g_rc & 15) == 0,
-            "%s: ld_grc must be a power of two in 8..512 and >= 4 (reg_max + 1), g_rc 16-byte aligned", who);
-  DSL_CHECK(d->box_kind >= DSL_BOX_GIOU && d->box_kind <= DSL_BOX_CIOU, "%s: box_kind is not a DSL_BOX_* value", who);
-  DSL_CHECK(d->box_kind < DSL_BOX_DIOU || (d->box_eps > 0.f && d->box_eps < 1.f), "%s: DIoU / CIoU need 0 < box_eps < 1", who);
-  DSL_CHECK(d->w_cls >= 0.f && d->w_cls < 1e30f && d->w_bbox >= 0.f && d->w_bbox < 1e30f && g->w_dfl >= 0.f && g->w_dfl < 1e30f,
-            "%s: loss weights must be finite and >= 0", who);
-  DSL_CHECK(g->qfl_beta >= 0.f && g->qfl_beta < 1e30f, "%s: qfl_beta must be finite and >= 0", who);
-  k.box_kind = d->box_kind; k.box_eps = d->box_eps; k.beta = g->qfl_beta;
-  k.w_cls = d->w_cls; k.w_bbox = d->w_bbox; k.w_dfl = g->w_dfl;
-  blocks = (int)(((long long)k.M * ((k.C + 3) / 4) + 255) / 256);
-  if (blocks > 2048) blocks = 2048;      // (the workspace holds 2048 records of 16 floats)
   return 0;
 }
 
 extern "C" int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream) {
   GfK k;
-  int blocks;
-  if (gfl_loss_fill(g, k, blocks, "dsl_gfl_loss")) return -1;
-  const dsl_fcos_desc* d = &g->fcos;
-  hipStream_t st = (hipStream_t)stream;
-  if (k.C % 4 != 0)
-    hipLaunchKernelGGL((gfl_loss_kernel<true, false>), dim3(blocks), dim3(256), 0, st, k);
-  else
-    hipLaunchKernelGGL((gfl_loss_kernel<false, false>), dim3(blocks), dim3(256), 0, st, k);
-  hipLaunchKernelGGL(gfl_finalize_kernel<false>, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, blocks, d->losses, d->g_scales, d->norm,
-                     d->inv_world, d->logvec, k.w_cls, k.w_bbox, k.w_dfl, 0.f);
+  if (gfl_loss_fill(g, k, "dsl_gfl_loss")) return -1;
+  gfl_loss_launch(k, false, (hipStream_t)stream);
   DSL_LAUNCH_CHECK("gfl_loss_kernel");
   return 0;
 }
@@ -476,24 +418,16 @@ extern "C" int dsl_gfl_loss(const dsl_gfl_desc* g, void* stream) {
 extern "C" int dsl_ld_loss(const dsl_ld_desc* l, void* stream) {
   DSL_CHECK(l, "dsl_ld_loss: null descriptor");
   const dsl_gfl_desc* g = &l->gfl;
-  const dsl_fcos_desc* d = &g->fcos;
-  DSL_CHECK((d->head_flags & DSL_HEAD_LD) && (d->head_flags & DSL_HEAD_GFL),
+  DSL_CHECK((g->fcos.head_flags & DSL_HEAD_LD) && (g->fcos.head_flags & DSL_HEAD_GFL),
             "dsl_ld_loss: a dsl_ld_desc needs DSL_HEAD_LD | DSL_HEAD_GFL in gfl.fcos.head_flags");
   GfK k;
-  int blocks;
-  if (gfl_loss_fill(g, k, blocks, "dsl_ld_loss")) return -1;
+  if (gfl_loss_fill(g, k, "dsl_ld_loss")) return -1;
   DSL_CHECK(l->soft && l->soft_scales, "dsl_ld_loss: soft / soft_scales null");
   DSL_CHECK(l->ld_soft >= 4 * k.R, "dsl_ld_loss: ld_soft does not hold 4 (reg_max + 1) columns (got %d)", l->ld_soft);
   DSL_CHECK(l->T >= 1.f && l->T < 1e30f, "dsl_ld_loss: T must be finite and >= 1");
   DSL_CHECK(l->w_ld >= 0.f && l->w_ld < 1e30f, "dsl_ld_loss: w_ld must be finite and >= 0");
   k.soft = l->soft; k.ld_soft = l->ld_soft; k.soft_scales = l->soft_scales; k.T = l->T; k.w_ld = l->w_ld;
-  hipStream_t st = (hipStream_t)stream;
-  if (k.C % 4 != 0)
-    hipLaunchKernelGGL((gfl_loss_kernel<true, true>), dim3(blocks), dim3(256), 0, st, k);
-  else
-    hipLaunchKernelGGL((gfl_loss_kernel<false, true>), dim3(blocks), dim3(256), 0, st, k);
-  hipLaunchKernelGGL(gfl_finalize_kernel<true>, dim3(1), dim3(GFL_FIN_T), 0, st, (const float*)k.part, blocks, d->losses, d->g_scales, d->norm,
-                     d->inv_world, d->logvec, k.w_cls, k.w_bbox, k.w_dfl, k.w_ld);
+  gfl_loss_launch(k, true, (hipStream_t)stream);
   DSL_LAUNCH_CHECK("gfl_loss_kernel");
   return 0;
 }

@@ -267,6 +267,43 @@ class KnowledgeDistillationKLDivLoss(_LossCfg):
         self.T = float(T)
 
 
+def _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, no_dcn, anchor_head=True):
+    """The network every head here is built on: four 256-channel GN-32 tower convolutions, no DCN.  anchor_head: the refusals name
+    AnchorHead's arguments (conv_cfg, norm_cfg), else FCOSHead's."""
+    _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
+    _expect(stacked_convs == 4, 'stacked_convs=4')
+    _expect(no_dcn, 'conv_cfg=None (no DCN)' if anchor_head else 'dcn_on_last_conv=False (no DCN)')
+    _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32,
+            'GN-32 towers (norm_cfg)' if anchor_head else 'GN-32 towers')
+
+
+def _expect_no_dsl_keys(name, kw):
+    for k in ('soft_weight', 'soft_warm_up', 'loss_weight'):
+        _expect(k not in kw, f'{name}: no DSL key {k} (the scale-invariant soft term and the per-stream loss_weight are FCOSHead options)')
+    _expect(not kw, f'{name}: unknown arguments {sorted(kw)}')
+
+
+def _build_loss_bbox(loss_bbox, refusal, lift_weight=True):
+    """(module, loss_weight) of a head's loss_bbox; `refusal` names what the head accepts.  lift_weight (ATSSHead, GFLHead): GIoULoss /
+    IoULoss keep refusing a loss_weight in their own constructors (FCOSHead's configuration surface), so the weight of configs/atss and
+    configs/gfl (GIoULoss(loss_weight=2.0)) is taken off the dict here; it goes to the kernel as dsl_fcos_desc.w_bbox."""
+    lb, wb = dict(loss_bbox), None
+    if lift_weight and lb.get('type') in ('GIoULoss', 'IoULoss'):
+        wb = _loss_weight(lb['type'], lb.pop('loss_weight', 1.0), lb.get('reduction', 'mean'))
+    module = build_loss(lb)
+    _expect(isinstance(module, (GIoULoss, IoULoss, DIoULoss)), refusal)
+    return module, module.loss_weight if wb is None else wb
+
+
+def _atss_option_kw(head):
+    """What the ATSS-assigned heads (ATSSHead, GFLHead) pass to HeadOptions alike."""
+    return dict(box_loss=head.loss_bbox.box_loss, box_eps=head.loss_bbox.eps, cls_weight=head.loss_cls.loss_weight,
+                bbox_weight=head.bbox_weight, assigner='atss')
+
+
+_FCOS_LOSSES = 'FocalLoss + GIoULoss, IoULoss, DIoULoss or CIoULoss + CrossEntropyLoss'
+
+
 @HEADS.register_module()
 class FCOSHead(nn.Module):
     def __init__(self, num_classes, in_channels, regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8)),
@@ -280,11 +317,8 @@ class FCOSHead(nn.Module):
                  init_cfg=None, **kw):
         super().__init__()
         class_layout(num_classes)            # 1..MAX_CLASSES, else NotImplementedError naming the range
-        _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
-        _expect(stacked_convs == 4, 'stacked_convs=4')
+        _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, not dcn_on_last_conv, anchor_head=False)
         _expect(list(strides) == [8, 16, 32, 64, 128], 'strides 8..128')
-        _expect(not dcn_on_last_conv, 'dcn_on_last_conv=False (no DCN)')
-        _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers')
         # mmcv ConvModule: bias='auto' = no bias in front of a norm layer - with the GroupNorm towers, False
         _expect(conv_bias is True or conv_bias is False or conv_bias == 'auto', "conv_bias True, False or 'auto'")
         self.center_sampling, self.norm_on_bbox, self.centerness_on_reg = bool(center_sampling), bool(norm_on_bbox), bool(centerness_on_reg)
@@ -294,17 +328,16 @@ class FCOSHead(nn.Module):
         self.center_sample_radius = center_sample_radius
         self.loss_weight, self.soft_weight, self.soft_warm_up = loss_weight, soft_weight, soft_warm_up
         self.cur_iter = 0                               # fcos_head.py:103
-        self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)
+        self.loss_cls = build_loss(loss_cls)
+        self.loss_bbox, wb = _build_loss_bbox(loss_bbox, _FCOS_LOSSES, lift_weight=False)
         self.loss_centerness = build_loss(loss_centerness)
-        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, (GIoULoss, IoULoss, DIoULoss))
-                and isinstance(self.loss_centerness, CrossEntropyLoss),
-                'FocalLoss + GIoULoss, IoULoss, DIoULoss or CIoULoss + CrossEntropyLoss')
+        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_centerness, CrossEntropyLoss), _FCOS_LOSSES)
         # what the kernels and the parameter layout are built for (fixed per model: ParamStore.head)
         lb = self.loss_bbox
         self.options = HeadOptions(self.center_sampling, self.norm_on_bbox, self.centerness_on_reg,
                                    isinstance(lb, IoULoss), self.conv_bias, box_loss=lb.box_loss, box_eps=lb.eps,
                                    focal_gamma=self.loss_cls.gamma, focal_alpha=self.loss_cls.alpha, cls_weight=self.loss_cls.loss_weight,
-                                   bbox_weight=lb.loss_weight, ctr_weight=self.loss_centerness.loss_weight)
+                                   bbox_weight=wb, ctr_weight=self.loss_centerness.loss_weight)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
 
     def effective_soft_weight(self, batch_size):
@@ -374,13 +407,8 @@ class ATSSHead(nn.Module):
                  loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None, **kw):
         super().__init__()
         class_layout(num_classes)
-        for k in ('soft_weight', 'soft_warm_up', 'loss_weight'):
-            _expect(k not in kw, f'ATSSHead: no DSL key {k} (the scale-invariant soft term and the per-stream loss_weight are FCOSHead options)')
-        _expect(not kw, f'ATSSHead: unknown arguments {sorted(kw)}')
-        _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
-        _expect(stacked_convs == 4, 'stacked_convs=4')
-        _expect(conv_cfg is None, 'conv_cfg=None (no DCN)')
-        _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers (norm_cfg)')
+        _expect_no_dsl_keys('ATSSHead', kw)
+        _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, conv_cfg is None)
         _expect(not reg_decoded_bbox, 'reg_decoded_bbox=False')
         obs = _square_anchor_scale(anchor_generator)
         bc = dict(bbox_coder)
@@ -395,23 +423,11 @@ class ATSSHead(nn.Module):
         self.num_classes, self.strides = num_classes, (8, 16, 32, 64, 128)
         self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
         self.loss_cls = build_loss(loss_cls)
-        # GIoULoss / IoULoss keep refusing a loss_weight in their own constructors (FCOSHead's configuration surface); here the weight
-        # of configs/atss (GIoULoss(loss_weight=2.0)) is taken off the dict and goes to the kernel as dsl_fcos_desc.w_bbox
-        lb = dict(loss_bbox)
-        wb = 1.0
-        if lb.get('type') in ('GIoULoss', 'IoULoss'):
-            wb = _loss_weight(lb['type'], lb.pop('loss_weight', 1.0), lb.get('reduction', 'mean'))
-        self.loss_bbox = build_loss(lb)
+        self.loss_bbox, self.bbox_weight = _build_loss_bbox(loss_bbox, _FCOS_LOSSES)
         self.loss_centerness = build_loss(loss_centerness)
-        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_bbox, (GIoULoss, IoULoss, DIoULoss))
-                and isinstance(self.loss_centerness, CrossEntropyLoss),
-                'FocalLoss + GIoULoss, IoULoss, DIoULoss or CIoULoss + CrossEntropyLoss')
-        lbm = self.loss_bbox
-        wb = wb if isinstance(lbm, (GIoULoss, IoULoss)) else lbm.loss_weight
-        self.bbox_weight = wb
-        self.options = HeadOptions(box_loss=lbm.box_loss, box_eps=lbm.eps, focal_gamma=self.loss_cls.gamma, focal_alpha=self.loss_cls.alpha,
-                                   cls_weight=self.loss_cls.loss_weight, bbox_weight=wb, ctr_weight=self.loss_centerness.loss_weight,
-                                   assigner='atss', atss_topk=topk, anchor_scale=float(obs), delta_stds=stds)
+        _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_centerness, CrossEntropyLoss), _FCOS_LOSSES)
+        self.options = HeadOptions(**_atss_option_kw(self), atss_topk=topk, anchor_scale=obs, focal_gamma=self.loss_cls.gamma,
+                                   focal_alpha=self.loss_cls.alpha, ctr_weight=self.loss_centerness.loss_weight, delta_stds=stds)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
 
     def effective_soft_weight(self, batch_size):
@@ -433,13 +449,8 @@ class GFLHead(nn.Module):
                  loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None, **kw):
         super().__init__()
         class_layout(num_classes)
-        for k in ('soft_weight', 'soft_warm_up', 'loss_weight'):
-            _expect(k not in kw, f'GFLHead: no DSL key {k} (the scale-invariant soft term and the per-stream loss_weight are FCOSHead options)')
-        _expect(not kw, f'GFLHead: unknown arguments {sorted(kw)}')
-        _expect(in_channels == 256 and feat_channels == 256, 'in_channels=256, feat_channels=256')
-        _expect(stacked_convs == 4, 'stacked_convs=4')
-        _expect(conv_cfg is None, 'conv_cfg=None (no DCN)')
-        _expect(norm_cfg is not None and norm_cfg.get('type') == 'GN' and norm_cfg.get('num_groups') == 32, 'GN-32 towers (norm_cfg)')
+        _expect_no_dsl_keys('GFLHead', kw)
+        _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, conv_cfg is None)
         _expect(not reg_decoded_bbox, 'reg_decoded_bbox=False')
         _expect(isinstance(reg_max, int) and not isinstance(reg_max, bool) and 1 <= reg_max <= 16,
                 f'reg_max in 1..16 (got {reg_max!r}; DSL_GFL_MAX_REG)')
@@ -449,23 +460,11 @@ class GFLHead(nn.Module):
         topk = _atss_topk(train_cfg)
         self.num_classes, self.strides, self.reg_max = num_classes, (8, 16, 32, 64, 128), reg_max
         self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
-        self.loss_cls = build_loss(loss_cls)
-        self.loss_dfl = build_loss(loss_dfl)
-        # (as ATSSHead: GIoULoss / IoULoss refuse a loss_weight in their own constructors; configs/gfl's GIoULoss(loss_weight=2.0) is
-        # taken off the dict and goes to the kernel as dsl_fcos_desc.w_bbox)
-        lb = dict(loss_bbox)
-        wb = 1.0
-        if lb.get('type') in ('GIoULoss', 'IoULoss'):
-            wb = _loss_weight(lb['type'], lb.pop('loss_weight', 1.0), lb.get('reduction', 'mean'))
-        self.loss_bbox = build_loss(lb)
+        self.loss_cls, self.loss_dfl = build_loss(loss_cls), build_loss(loss_dfl)
         _expect(isinstance(self.loss_cls, QualityFocalLoss), 'loss_cls: QualityFocalLoss(use_sigmoid=True, beta, loss_weight)')
         _expect(isinstance(self.loss_dfl, DistributionFocalLoss), 'loss_dfl: DistributionFocalLoss(loss_weight)')
-        _expect(isinstance(self.loss_bbox, (GIoULoss, IoULoss, DIoULoss)), 'loss_bbox: GIoULoss, IoULoss, DIoULoss or CIoULoss')
-        lbm = self.loss_bbox
-        wb = wb if isinstance(lbm, (GIoULoss, IoULoss)) else lbm.loss_weight
-        self.bbox_weight = wb
-        self._option_kw = dict(box_loss=lbm.box_loss, box_eps=lbm.eps, cls_weight=self.loss_cls.loss_weight, bbox_weight=wb,
-                               assigner='atss', atss_topk=topk, anchor_scale=obs, head_kind='gfl', reg_max=reg_max,
+        self.loss_bbox, self.bbox_weight = _build_loss_bbox(loss_bbox, 'loss_bbox: GIoULoss, IoULoss, DIoULoss or CIoULoss')
+        self._option_kw = dict(_atss_option_kw(self), atss_topk=topk, anchor_scale=obs, head_kind='gfl', reg_max=reg_max,
                                qfl_beta=self.loss_cls.beta, dfl_weight=self.loss_dfl.loss_weight)
         self.options = HeadOptions(**self._option_kw)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg

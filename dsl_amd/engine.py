@@ -144,13 +144,13 @@ class OpList:
     def gn_bwd(self, d, side=False):
         self._add(L.OP_GN_BWD, d, i=(0, 0, 0, 0, 0, 0, int(side)))
 
-    def assign(self, d, atss=None):
-        """atss: the head's dsl_atss_desc (dsl_atss_assign), None = dsl_fcos_assign."""
-        self._add(L.OP_ASSIGN, d, p=(C.addressof(atss),) if atss is not None else ())
+    def assign(self, d):
+        """d: a head's dsl_fcos_desc; its head_flags name the entry point (dsl_head_assign)."""
+        self._add(L.OP_ASSIGN, d)
 
-    def loss(self, d, gfl=None):
-        """gfl: the head's dsl_gfl_desc (dsl_gfl_loss; `d` is its first member), None = dsl_fcos_loss."""
-        self._add(L.OP_LOSS, d, p=(C.addressof(gfl),) if gfl is not None else ())
+    def loss(self, d):
+        """d: a head's dsl_fcos_desc, for a GFL / LD head the first member of its dsl_gfl_desc / dsl_ld_desc (dsl_head_loss)."""
+        self._add(L.OP_LOSS, d)
 
     def gfl_quality(self, gfl):
         self._add(L.OP_GFL_QUALITY, gfl)
@@ -223,7 +223,7 @@ class Plan:
             self.lossplan.bind_outputs(self.bufs['cls_logits'], self.bufs['regctr'], store.t32_ptr('head.scales'))
             # scale gradients go straight into the flat gradient buffer
             self.lossplan.desc.g_scales = store.t32_ptr('head.scales', store.grad)
-            self.assign_ops.assign(self.lossplan.desc, self.lossplan.atss)
+            self.assign_ops.assign(self.lossplan.desc)
             if self._fside:             # the regression tower's side stream: joined here, not at the end of the forward list,
                 self.loss_ops.join(self._fside)       # so that target upload + assignment run while it finishes
             self.loss_ops.prof(4, 1)
@@ -233,7 +233,7 @@ class Plan:
             if self.lossplan.gfl is not None:
                 self.quality_ops, self.loss_ops = self.loss_ops, OpList()
                 self.quality_ops.gfl_quality(self.lossplan.gfl)
-            self.loss_ops.loss(self.lossplan.desc, self.lossplan.gfl)
+            self.loss_ops.loss(self.lossplan.desc)
             self._build_backward()
 
     # ---------------------------------------------------------------------------------------------

@@ -186,20 +186,14 @@ class FcosLossPlan:
         self._soft_keep = (regctr, scales)
 
     def assign(self):
-        if self.atss is not None:
-            L.check(L.lib.dsl_atss_assign(C.byref(self.desc), C.byref(self.atss), L.stream_ptr()), 'dsl_atss_assign')
-            return
-        L.check(L.lib.dsl_fcos_assign(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_assign')
+        L.check(L.lib.dsl_head_assign(C.byref(self.desc), L.stream_ptr()), 'dsl_head_assign')
 
     def quality(self):
         """GFL only: score / weight of the positives and stats[1] = sum of the weights (dsl_gfl_quality)."""
         L.check(L.lib.dsl_gfl_quality(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_quality')
 
     def loss(self):
-        if self.ld is not None:
-            L.check(L.lib.dsl_ld_loss(C.byref(self.ld), L.stream_ptr()), 'dsl_ld_loss')
-            return
-        if self.gfl is not None:
-            L.check(L.lib.dsl_gfl_loss(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_loss')
-            return
-        L.check(L.lib.dsl_fcos_loss(C.byref(self.desc), L.stream_ptr()), 'dsl_fcos_loss')
+        """The entry point of the descriptor this plan built, not dsl_head_loss's choice by head_flags: a dsl_ld_desc whose flags lost
+        DSL_HEAD_LD is then refused by dsl_ld_loss instead of running as a GFL head."""
+        name = 'dsl_ld_loss' if self.ld is not None else 'dsl_gfl_loss' if self.gfl is not None else 'dsl_fcos_loss'
+        L.check(getattr(L.lib, name)(C.byref(self.desc), L.stream_ptr()), name)

@@ -698,6 +698,14 @@ typedef struct dsl_ld_desc {
 } dsl_ld_desc;
 int dsl_ld_loss(const dsl_ld_desc* d, void* stream);
 
+/* One dispatch for every head, on head_flags.  The contract the flags state: with DSL_HEAD_GFL `d` is the first member of a
+ * dsl_gfl_desc, with DSL_HEAD_LD of a dsl_ld_desc (whose first member is that dsl_gfl_desc), so the three share one address.
+ * dsl_head_assign: DSL_HEAD_ATSS -> dsl_atss_assign(d, d->atss), else dsl_fcos_assign.
+ * dsl_head_loss: DSL_HEAD_LD -> dsl_ld_loss (which refuses the flag without DSL_HEAD_GFL), else DSL_HEAD_GFL -> dsl_gfl_loss, else
+ * dsl_fcos_loss.  DSL_OP_ASSIGN / DSL_OP_LOSS of an op list are these two calls on the op's desc. */
+int dsl_head_assign(const dsl_fcos_desc* d, void* stream);
+int dsl_head_loss(const dsl_fcos_desc* d, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Optimizer / EMA over flat fp32 buffers (mmcv OptimizerHook + torch SGD, wired at
  * apis/train.py:111,157-166; EMA at runner/hooks/semi_epoch_based_runner.py:368-409)
@@ -923,8 +931,8 @@ int dsl_allreduce_bucket_bf16(void* comm, void* buf_bf16, size_t count, void* st
  * ---------------------------------------------------------------------------------------- */
 enum { DSL_OP_CONV = 1, DSL_OP_WGRAD = 2, DSL_OP_GN_FWD = 3, DSL_OP_GN_BWD = 4, DSL_OP_MAXPOOL = 5,
        DSL_OP_SUM2X2 = 6, DSL_OP_COLSUM = 7, DSL_OP_MEMSET = 8, DSL_OP_PACK_IMAGE = 9,
-       DSL_OP_ASSIGN = 10, DSL_OP_LOSS = 11,   /* MAXPOOL: i[4] = output row stride (0 = c) */
-       DSL_OP_GFL_QUALITY = 29,  /* desc = dsl_gfl_desc -> dsl_gfl_quality; DSL_OP_LOSS with p[0] = a dsl_gfl_desc -> dsl_gfl_loss(p[0]) */
+       DSL_OP_ASSIGN = 10, DSL_OP_LOSS = 11,   /* desc = dsl_fcos_desc -> dsl_head_assign, dsl_head_loss.  MAXPOOL: i[4] = output row stride (0 = c) */
+       DSL_OP_GFL_QUALITY = 29,  /* desc = dsl_gfl_desc -> dsl_gfl_quality */
        DSL_OP_FORK = 12,   /* side stream i[0] (default 1) waits for everything queued so far on stream i[1] (default 0 = caller's) */
        DSL_OP_JOIN = 13,   /* stream i[1] (default 0 = caller's) waits for everything queued so far on side stream i[0] (default 1) */
        DSL_OP_WGRAD_GROUP = 14,  /* desc = dsl_wgrad_desc[i[0]] -> dsl_conv2d_wgrad_group */

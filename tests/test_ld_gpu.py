@@ -279,7 +279,7 @@ def test_wrong_descriptors_are_refused_and_launch_nothing(golden):
     # the op list dispatches on DSL_HEAD_LD: without DSL_HEAD_GFL it reaches dsl_ld_loss, which refuses
     plan.desc.head_flags = flags & ~L.HEAD_GFL
     ol = OpList()
-    ol.loss(plan.desc, plan.gfl)
+    ol.loss(plan.desc)
     with pytest.raises(RuntimeError, match='DSL_HEAD_LD'):
         ol.run()
     plan.desc.head_flags = flags
