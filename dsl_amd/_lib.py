@@ -35,6 +35,7 @@ OP_FP8_PREP, OP_QUANT_FP8_DELAYED = 27, 28
 OP_STEM_POOL = 25
 OP_BNECK = 26
 OP_GFL_QUALITY = 29
+OP_PAA_REFINE = 30      # dsl_paa_pos_loss, then dsl_paa_reassign
 PROF_CLASSES = 8
 MAX_MULTI = 16
 SLOT_TAIL, SLOT_PREFIX = 13, 14     # pipelined frozen prefix: 'previous backward's data-gradient chain done', 'prefix of this step done'
@@ -129,6 +130,7 @@ ATSS_MAX_TOPK = 16
 HEAD_GFL = 64           # GFLHead: the dsl_fcos_desc is a dsl_gfl_desc's first member, the dsl_det_desc a dsl_det_gfl_desc's
 GFL_MAX_REG = 16
 HEAD_LD = 128           # LDHead: the dsl_gfl_desc is a dsl_ld_desc's first member (dsl_ld_loss)
+HEAD_PAA = 256          # PAAHead: the dsl_fcos_desc is a dsl_paa_desc's first member, the dsl_det_desc a dsl_det_paa_desc's
 BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_DIOU, BOX_CIOU = range(5)      # DSL_BOX_*: dsl_fcos_desc.box_kind
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
@@ -159,8 +161,17 @@ class LdDesc(C.Structure):      # dsl_ld_desc: an LD head's loss descriptor (HEA
                 ('T', C.c_float), ('w_ld', C.c_float)]
 
 
+class PaaDesc(C.Structure):      # dsl_paa_desc: a PAA head's loss descriptor (HEAD_ATSS | HEAD_PAA | HEAD_LOSS_EXT in fcos.head_flags)
+    _fields_ = [('fcos', FcosDesc), ('pos_iou_thr', C.c_float), ('pos_loss', C.c_void_p), ('iou_target', C.c_void_p),
+                ('cand_gt', C.c_void_p), ('gmm_iters', C.c_void_p), ('gmm_flags', C.c_void_p)]
+
+
 class DetAtssDesc(C.Structure):      # dsl_det_atss_desc: the detection descriptor of an ATSS head (HEAD_ATSS in det.head_flags)
     _fields_ = [('det', DetDesc), ('atss', C.c_void_p)]
+
+
+class DetPaaDesc(C.Structure):      # dsl_det_paa_desc: the detection descriptor of a PAA head (HEAD_ATSS | HEAD_PAA in det.head_flags)
+    _fields_ = [('atss', DetAtssDesc), ('score_voting', C.c_int32)]
 
 
 class DetGflDesc(C.Structure):      # dsl_det_gfl_desc: the detection descriptor of a GFL head (HEAD_GFL in det.head_flags)
@@ -313,6 +324,7 @@ _SIGS = {
     'dsl_sum2x2': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], 'dsl_colsum': [_vp, _vp, _l, _i, _i, _vp],
     'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_atss_assign': [_vp, _vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
     'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp], 'dsl_ld_loss': [_vp, _vp], 'dsl_head_assign': [_vp, _vp], 'dsl_head_loss': [_vp, _vp],
+    'dsl_paa_assign': [_vp, _vp], 'dsl_paa_pos_loss': [_vp, _vp], 'dsl_paa_reassign': [_vp, _vp], 'dsl_paa_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
     'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],

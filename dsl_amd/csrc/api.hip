@@ -246,6 +246,10 @@ extern "C" int dsl_run_ops(const dsl_op* ops, int n_ops, void* stream) {
       case DSL_OP_ASSIGN: rc = dsl_head_assign((const dsl_fcos_desc*)o.desc, stream); break;
       case DSL_OP_LOSS: rc = dsl_head_loss((const dsl_fcos_desc*)o.desc, stream); break;
       case DSL_OP_GFL_QUALITY: rc = dsl_gfl_quality((const dsl_gfl_desc*)o.desc, stream); break;
+      case DSL_OP_PAA_REFINE:
+        rc = dsl_paa_pos_loss((const dsl_paa_desc*)o.desc, stream);
+        if (rc == 0) rc = dsl_paa_reassign((const dsl_paa_desc*)o.desc, stream);
+        break;
       case DSL_OP_QUANT_FP8: {
         float sc;
         const int32_t bits = (int32_t)o.l[1];

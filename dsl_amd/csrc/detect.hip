@@ -24,6 +24,10 @@
 // 372-443): det_decode takes the distances as Integral(scale x) * stride (gfl_head.py:15-48) from the anchor centre.  There is no
 // centerness factor: the kernels' centerness logit is then one constant whose sigmoid is exactly 1 (kNoCtr, row stride 0), so
 // key, pair score and pool rows are the class sigmoid alone and no kernel in front of or behind the decode branches on the head.
+//
+// PAAHead (DSL_HEAD_PAA beside DSL_HEAD_ATSS, the descriptor then being a dsl_det_paa_desc; PAAHead._get_bboxes and score_voting,
+// mmdet/models/dense_heads/paa_head.py:519-673): ATSS's decode; the key and the pair score are sqrt(sigmoid(cls) * sigmoid(iou)),
+// which score_thr tests and which is the final score (no centerness factor); with score_voting det_vote_kernel runs behind the NMS.
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -44,6 +48,7 @@ struct DetK {
   int atss;                          // DSL_HEAD_ATSS: delta2bbox against the location's anchor (atss_head.py:420-495)
   float anchor_scale, stds[4];
   int gfl_R;                         // DSL_HEAD_GFL: reg_max + 1 bins per side (0 = not a GFL head)
+  int paa;                           // DSL_HEAD_PAA: the pair score is sqrt(sigmoid(cls) * sigmoid(iou)), threshold and final score alike
   const float* scales; const float* img_shapes; const float* scale_factors;
   float* dets; long long* det_labels; int* det_count;
   // workspace
@@ -84,13 +89,13 @@ __global__ void det_key_kernel(const DetK p) {
   for (int k = 0; k < full; k += 4) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(c + k);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) best = fmaxf(best, sigmoidf_(v[e]) * ctr);
+    for (int e = 0; e < 4; ++e) best = fmaxf(best, p.paa ? sqrtf(sigmoidf_(v[e]) * ctr) : sigmoidf_(v[e]) * ctr);
   }
   if (full < p.num_classes) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(c + full);
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      if (full + e < p.num_classes) best = fmaxf(best, sigmoidf_(v[e]) * ctr);
+      if (full + e < p.num_classes) best = fmaxf(best, p.paa ? sqrtf(sigmoidf_(v[e]) * ctr) : sigmoidf_(v[e]) * ctr);
   }
   p.keys[m] = best;
 }
@@ -261,7 +266,10 @@ __global__ void det_pairscore_kernel(const DetK p) {
     const int loc = p.sel[((long long)img * p.nlvl + lvl) * p.nms_pre + slot];
     const int m = p.mstart[lvl] + img * P + loc;
     const float score = sigmoidf_(p.cls[(long long)m * p.ld_cls + c]);
-    if (score > p.score_thr) out = score * sigmoidf_(p.ctr[(long long)m * p.ld_ctr]);
+    if (p.paa) {      // paa_head.py:587-599: the NMS score itself is thresholded, score_factors=None
+      const float ns = sqrtf(score * sigmoidf_(p.ctr[(long long)m * p.ld_ctr]));
+      if (ns > p.score_thr) out = ns;
+    } else if (score > p.score_thr) out = score * sigmoidf_(p.ctr[(long long)m * p.ld_ctr]);
   }
   p.pairscore[((long long)img * p.nlvl + lvl) * p.nms_pre * p.num_classes + t] = out;
 }
@@ -819,6 +827,63 @@ __global__ __launch_bounds__(FUSE_T) void pseudo_fuse_kernel(const FuseK p) {
   if (threadIdx.x == 0) p.out_count[img] = nk;
 }
 
+// ---- PAA score voting (paa_head.py:608-673) ---------------------------------------------------------------------------------------
+// One workgroup per image, one wavefront per kept detection at a time: over the image's candidates of the detection's class (the pairs
+// dsl_fcos_detect keeps, every one above score_thr) with IoU > 0.01 against the kept box - bbox_overlaps, union clamped at 1e-6 -
+// p = exp(-(1 - iou)^2 / 0.025) * score; the box becomes sum p * box / sum p (accumulated in fp64, butterfly sums of fixed order), the
+// score stays.  Then the detections are rewritten class ascending, within a class in the NMS's order (the reference's loop order).
+__global__ __launch_bounds__(NMS_THREADS) void det_vote_kernel(const DetK p) {
+  __shared__ float s_box[NMS_THREADS * 5];
+  __shared__ int s_lab[NMS_THREADS];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nk = p.det_count[img];
+  int n = p.ccount[img];
+  if (n > CAND_CAP) n = CAND_CAP;
+  const float* cbox = p.cbox + (long long)img * CAND_CAP * 4;
+  const float* cscore = p.cscore + (long long)img * CAND_CAP;
+  const int* clabel = p.clabel + (long long)img * CAND_CAP;
+  float* dets = p.dets + (long long)img * p.max_per_img * 5;
+  long long* labels = p.det_labels + (long long)img * p.max_per_img;
+  for (int k = wave; k < nk; k += NMS_THREADS / 64) {
+    const float d0 = dets[5 * k], d1 = dets[5 * k + 1], d2 = dets[5 * k + 2], d3 = dets[5 * k + 3];
+    const int lab = (int)labels[k];
+    const float ad = (d2 - d0) * (d3 - d1);
+    double acc[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = lane; i < n; i += 64) {
+      if (clabel[i] != lab) continue;
+      const f32x4 b = *reinterpret_cast<const f32x4*>(cbox + 4 * i);
+      const float iw = fmaxf(fminf(d2, b[2]) - fmaxf(d0, b[0]), 0.f), ih = fmaxf(fminf(d3, b[3]) - fmaxf(d1, b[1]), 0.f);
+      const float ov = iw * ih;
+      const float iou = ov / fmaxf(ad + (b[2] - b[0]) * (b[3] - b[1]) - ov, 1e-6f);
+      if (!(iou > 0.01f)) continue;
+      const float w = expf(-((1.f - iou) * (1.f - iou)) / 0.025f) * cscore[i];
+      acc[0] += (double)w * b[0]; acc[1] += (double)w * b[1]; acc[2] += (double)w * b[2]; acc[3] += (double)w * b[3];
+      acc[4] += (double)w;
+    }
+#pragma unroll
+    for (int e = 0; e < 5; ++e)
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) acc[e] += __shfl_xor(acc[e], o, 64);
+    if (lane == 0) {
+      // (the kept box is one of its own candidates at IoU 1, so the sum is positive; a pool cut at CAND_CAP could drop it: keep the box)
+      const bool ok = acc[4] > 0.0;
+      s_box[5 * k] = ok ? (float)(acc[0] / acc[4]) : d0; s_box[5 * k + 1] = ok ? (float)(acc[1] / acc[4]) : d1;
+      s_box[5 * k + 2] = ok ? (float)(acc[2] / acc[4]) : d2; s_box[5 * k + 3] = ok ? (float)(acc[3] / acc[4]) : d3;
+      s_box[5 * k + 4] = dets[5 * k + 4];
+      s_lab[k] = lab;
+    }
+  }
+  __syncthreads();
+  if (tid < nk) {
+    const int lab = s_lab[tid];
+    int rank = 0;
+    for (int j = 0; j < nk; ++j) rank += (s_lab[j] < lab || (s_lab[j] == lab && j < tid)) ? 1 : 0;
+#pragma unroll
+    for (int e = 0; e < 5; ++e) dets[5 * rank + e] = s_box[5 * tid + e];
+    labels[rank] = lab;
+  }
+}
+
 size_t ws_layout(const dsl_det_desc* d, size_t off[9]) {
   long long M = 0;
   for (int l = 0; l < d->nlvl; ++l) M += (long long)d->n * d->h[l] * d->w[l];
@@ -931,6 +996,10 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
     DSL_CHECK(hipGetSymbolAddress(&one, HIP_SYMBOL(kNoCtr)) == hipSuccess && one, "%s: no address for the unit centerness", who);
     k.ctr = (const float*)one; k.ld_ctr = 0;
   }
+  if (d->head_flags & DSL_HEAD_PAA) {
+    DSL_CHECK(k.atss, "%s: DSL_HEAD_PAA goes with DSL_HEAD_ATSS (the descriptor is a dsl_det_paa_desc around a dsl_det_atss_desc)", who);
+    k.paa = 1;
+  }
   k.scales = d->scales; k.img_shapes = d->img_shapes; k.scale_factors = d->scale_factors;
   k.dets = d->dets; k.det_labels = (long long*)d->det_labels; k.det_count = d->det_count;
   unsigned char* ws = (unsigned char*)d->workspace;
@@ -963,6 +1032,8 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   DetK k;
   int m = 0;
   if (view_detk(d, k, m, "dsl_fcos_detect")) return -1;
+  const bool vote = k.paa && reinterpret_cast<const dsl_det_paa_desc*>(d)->score_voting != 0;
+  DSL_CHECK(!vote || d->nms_method == DSL_NMS_HARD, "dsl_fcos_detect: score_voting is built behind the hard NMS only (nms_method)");
   hipStream_t st = (hipStream_t)stream;
   hipMemsetAsync(k.ccount, 0, sizeof(int) * d->n, st);
   hipMemsetAsync(d->dets, 0, sizeof(float) * 5 * d->n * d->max_per_img, st);
@@ -974,6 +1045,7 @@ extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   hipLaunchKernelGGL(det_scatter_kernel, dim3(DET_CB, d->n), dim3(1024), 0, st, k);
   hipLaunchKernelGGL(det_compact_kernel, dim3(d->n), dim3(1024), 0, st, k);
   launch_nms(k, d->n, st);
+  if (vote) hipLaunchKernelGGL(det_vote_kernel, dim3(d->n), dim3(NMS_THREADS), 0, st, k);
   DSL_LAUNCH_CHECK("dsl_fcos_detect");
   return 0;
 }
@@ -987,6 +1059,7 @@ extern "C" size_t dsl_detect_aug_workspace_bytes(const dsl_det_desc* d, int nvie
 extern "C" int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc* pool_desc, int view, int nviews, int flip, void* pool,
                                        size_t pool_bytes, void* stream) {
   if (aug_check(d, nviews, "dsl_fcos_detect_collect")) return -1;
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_PAA), "dsl_fcos_detect_collect: DSL_HEAD_PAA has no test-time augmentation (paa_head.py:536-538)");
   DSL_CHECK(pool_desc, "dsl_fcos_detect_collect: null pool descriptor");
   if (soft_check(pool_desc, "dsl_fcos_detect_collect")) return -1;          // its nms_method sizes the pool's scratch (aug_layout)
   // the pool is laid out by ITS nlvl / nms_pre / num_classes: a view that differs would write into other views' rows

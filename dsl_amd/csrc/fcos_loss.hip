@@ -57,6 +57,13 @@ struct FcK : HeadK {
   const int* pad_shapes;            // [n][2] (pad_h, pad_w)
   unsigned long long* akeys;        // [M] (IoU bits << 32 | ~gt index) of the winning box, 0 = none (workspace)
   int* npos;                        // [n] positives per image
+  // PAA (DSL_HEAD_PAA: the paa_* kernels and loss_kernel<., true, true, true> only)
+  float pos_iou_thr;
+  float* pos_loss; float* iou_target;     // [M]
+  int* cand_gt;                     // [M] the first assignment's box index within the image, -1 = none
+  int* gmm_iters; int* gmm_flags;   // [max_gt]
+  float* gtmax;                     // [max_gt] every box's maximum IoU over its image's valid anchors (workspace)
+  int max_gt;
 };
 
 // one image, one location against a list of boxes: area-argmin with centre sampling + range test
@@ -332,18 +339,23 @@ __global__ __launch_bounds__(REC_T) void assign_finalize_kernel(const FcK p, int
 
 // The loss records [cls, sisoft, bbox, centerness, g_scale x 5, pad], added in block order -> losses[4], g_scales[5] and logvec.
 // kAtss: loss_bbox's normaliser is clamped at 1 (atss_head.py:286), not at 1e-6
-template <bool kAtss>
+// kHead: 0 FCOS, 1 ATSS, 2 PAA (loss_cls over max(num_pos, images), loss_bbox over the sum of the IoU targets: loss_kernel)
+template <int kHead>
 __global__ __launch_bounds__(REC_T) void fcos_finalize_kernel(const FcK p, int nblocks) {
   __shared__ float sh[REC_T];
+  constexpr bool kAtss = kHead == 1, kPaa = kHead == 2;
   const float t = record_sum(p.part, nblocks, 16, 0, 16, sh);
   if (threadIdx.x < 16) {
-    const float num_pos = fmaxf(p.norm[0] * p.inv_world, 1.0f), denorm = fmaxf(p.norm[1] * p.inv_world, kAtss ? 1.0f : 1e-6f);
+    const float num_ctr = fmaxf(p.norm[0] * p.inv_world, 1.0f);
+    const float num_pos = kPaa ? fmaxf(p.norm[0] * p.inv_world, (float)p.n) : num_ctr;
+    const float denorm = kPaa ? (p.norm[1] * p.inv_world > 0.f ? p.norm[1] * p.inv_world : 1.0f)
+                              : fmaxf(p.norm[1] * p.inv_world, kAtss ? 1.0f : 1e-6f);
     float fv = t;
     // (loss_weight * the mean, as the loss modules do; a weight of 1 leaves the bits as they are)
     if (threadIdx.x == 0) p.losses[0] = fv = t / num_pos * p.w_cls;
     else if (threadIdx.x == 1) p.losses[3] = fv = t * p.soft_weight;
     else if (threadIdx.x == 2) p.losses[1] = fv = t / denorm * p.w_bbox;
-    else if (threadIdx.x == 3) p.losses[2] = fv = t / num_pos * p.w_ctr;
+    else if (threadIdx.x == 3) p.losses[2] = fv = t / num_ctr * p.w_ctr;
     else if (threadIdx.x - 4 < DSL_MAX_SEG) p.g_scales[threadIdx.x - 4] = t;
     if (threadIdx.x < 4) sh[threadIdx.x] = fv;
   }
@@ -435,14 +447,21 @@ __device__ __forceinline__ void focal_fb_ext(float x, bool t, float gamma, float
 // of those fields.
 // kAtss (with kExt): DSL_HEAD_ATSS - delta2bbox decode against the location's anchor, the stored ground-truth box as target, the
 // normaliser of loss_bbox clamped at 1 (atss_head.py:142-215,268-287); the kAtss = false instantiations are the FCOS kernels, unchanged.
-template <bool kTail, bool kExt, bool kAtss = false>
+// kPaa (with kAtss): DSL_HEAD_PAA - loss_cls over max(num_pos, images), the IoU branch's BCE against iou_target over num_pos, loss_bbox
+// weighted by max(iou_target, 1e-12) over the sum of the IoU targets (paa_head.py:169-199); kPaa = false leaves the other
+// instantiations as they were.
+template <bool kTail, bool kExt, bool kAtss = false, bool kPaa = false>
 __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
   __shared__ float sh[16];
   const int M = p.M;
   const int C = p.num_classes;
   const int c4 = kTail ? (C + 3) / 4 : C / 4;
-  const float num_pos = fmaxf(p.norm[0] * p.inv_world, 1.0f);
-  const float denorm = fmaxf(p.norm[1] * p.inv_world, kAtss ? 1.0f : 1e-6f);
+  const float num_pos = fmaxf(p.norm[0] * p.inv_world, kPaa ? (float)p.n : 1.0f);
+  const float num_iou = fmaxf(p.norm[0] * p.inv_world, 1.0f);      // kPaa: avg_factor of loss_iou (no positive: nothing is divided)
+  // kPaa: the sum of the IoU targets.  The reference divides by it as it is (0 / 0 when every positive's IoU is 0); here a sum that
+  // is not positive counts as 1
+  const float denorm = kPaa ? (p.norm[1] * p.inv_world > 0.f ? p.norm[1] * p.inv_world : 1.0f)
+                            : fmaxf(p.norm[1] * p.inv_world, kAtss ? 1.0f : 1e-6f);
   const bool sisoft = (p.soft_weight != 0.f) && (p.n % 2 != 0) && p.n >= 3;
 
   // ---------------- classification: one thread per 4 consecutive classes of one location ----------
@@ -551,7 +570,8 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
         x1 = px - d[0]; y1 = py - d[1]; x2 = px + d[2]; y2 = py + d[3];
         X1 = px - t[0]; Y1 = py - t[1]; X2 = px + t[2]; Y2 = py + t[3];
       }
-      const float wb = ct * pw;
+      if constexpr (kPaa) ct = p.iou_target[m];      // the target of the IoU branch, a constant for the gradient (paa_head.py:183-184)
+      const float wb = (kPaa ? fmaxf(ct, 1e-12f) : ct) * pw;
       float dbox[4];
       if (kExt && p.box_kind >= DSL_BOX_IOU_LINEAR) {
         float dl[4];
@@ -640,7 +660,7 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
       const float e = __expf(-fabsf(cl));
       const float sig = cl >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
       csum += (fmaxf(cl, 0.f) - cl * ct + log1pf(e)) * pw;
-      gc = (sig - ct) * pw / num_pos * p.grad_scale;
+      gc = (sig - ct) * pw / (kPaa ? num_iou : num_pos) * p.grad_scale;
       if constexpr (kExt) gc *= p.w_ctr;
     }
     if (p.g_ctr) {      // the centerness gradient belongs to the classification predictor's columns
@@ -666,6 +686,314 @@ __global__ __launch_bounds__(256) void loss_kernel(const FcK p) {
 #pragma unroll
   for (int l = 4 + DSL_MAX_SEG; l < 16; ++l)
     if (threadIdx.x == 0) rec[l] = 0.f;
+}
+
+// ---- PAA (paa_head.py:86-399, max_iou_assigner.py:127-212; semantics, tie rules and deviations: include/dsl_hip.h) ---------------
+constexpr int PAA_MAXS = DSL_MAX_SEG * DSL_ATSS_MAX_TOPK;      // samples of one mixture fit
+
+// gtmax[g] = the box's maximum IoU over the valid anchors of its image (gt_max_overlaps); -1 for an unused slot
+__global__ __launch_bounds__(ATSS_T) void paa_gtmax_kernel(const FcK p) {
+  __shared__ float red[ATSS_T];
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (g >= p.gt_off[p.n]) {
+    if (tid == 0) p.gtmax[g] = -1.f;
+    return;
+  }
+  int img = 0;
+  for (int i = 1; i < p.n; ++i)
+    if (g >= p.gt_off[i]) img = i;
+  const float x1 = p.gt_boxes[4 * g], y1 = p.gt_boxes[4 * g + 1], x2 = p.gt_boxes[4 * g + 2], y2 = p.gt_boxes[4 * g + 3];
+  float best = -1.f;
+  for (int lvl = 0; lvl < p.nlvl; ++lvl) {
+    int vh, vw;
+    atss_valid(p, lvl, img, vh, vw);
+    const int nvalid = vh * vw;
+    for (int i = tid; i < nvalid; i += ATSS_T) {
+      const int y = i / vw, x = i - y * vw;
+      float a[4];
+      atss_anchor(p, lvl, x, y, a);
+      best = fmaxf(best, atss_iou(a, x1, y1, x2, y2));
+    }
+  }
+  red[tid] = best;
+  __syncthreads();
+  for (int o = ATSS_T / 2; o > 0; o >>= 1) {
+    if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
+    __syncthreads();
+  }
+  if (tid == 0) p.gtmax[g] = red[0];
+}
+
+// one thread per anchor: assign_wrt_overlaps.  The argmax box if its IoU >= pos_iou_thr (equal maxima: the lower box), then the
+// low-quality pass in box order - the LAST box whose maximum over anchors this anchor's IoU equals takes it (the same atss_iou bits
+// on both sides of the comparison)
+__global__ __launch_bounds__(ATSS_T) void paa_write_kernel(const FcK p) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m == 0) {
+    for (int i = 0; i < 8; ++i) p.stats[i] = 0.f;
+    for (int i = 0; i < p.n; ++i) p.npos[i] = 0;
+  }
+  if (m >= p.M) return;
+  int lvl, img, y, x, vh, vw;
+  head_loc(p, m, lvl, img, y, x);
+  atss_valid(p, lvl, img, vh, vw);
+  const bool valid = y < vh && x < vw;
+  const int g0 = p.gt_off[img], g1 = p.gt_off[img + 1];
+  int cand = -1;
+  if (valid && g1 > g0) {
+    float a[4];
+    atss_anchor(p, lvl, x, y, a);
+    float best = -1.f;
+    int arg = 0, low = -1;
+    for (int g = g0; g < g1; ++g) {
+      const float iou = atss_iou(a, p.gt_boxes[4 * g], p.gt_boxes[4 * g + 1], p.gt_boxes[4 * g + 2], p.gt_boxes[4 * g + 3]);
+      if (iou > best) { best = iou; arg = g - g0; }
+      if (iou == p.gtmax[g]) low = g - g0;
+    }
+    cand = low >= 0 ? low : (best >= p.pos_iou_thr ? arg : -1);
+  }
+  long long label = p.num_classes;
+  f32x4 t = {0.f, 0.f, 0.f, 0.f};
+  if (cand >= 0) {
+    label = p.gt_labels[g0 + cand];
+    t = *reinterpret_cast<const f32x4*>(p.gt_boxes + 4ll * (g0 + cand));
+  }
+  p.cand_gt[m] = cand;
+  p.assign_idx[m] = cand;
+  p.labels[m] = label;
+  *reinterpret_cast<f32x4*>(p.bbox_targets + 4ll * m) = t;
+  p.cls_weight[m] = valid ? 1.f : 0.f;
+  p.pos_weight[m] = 1.f;
+}
+
+// one thread per anchor: a candidate's loss w_cls * sum_c focal + w_bbox * box_loss(decode, target), reduction 'none'
+// (paa_head.py:201-255), and the aligned IoU of the same two boxes, which dsl_paa_reassign keeps as iou_target for the positives
+__global__ __launch_bounds__(256) void paa_pos_loss_kernel(const FcK p) {
+  const int m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= p.M) return;
+  float pl = 0.f, it = 0.f;
+  if (p.cand_gt[m] >= 0) {
+    const int C = p.num_classes, label = (int)p.labels[m];
+    const float* row = p.cls_logits + (long long)m * p.ld_cls;
+    const bool gamma2 = p.gamma == 2.f;
+    float acc = 0.f;
+    for (int c = 0; c < C; c += 4) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(row + c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (c + e < C) {
+          float l, d;
+          focal_fb_ext(xv[e], label == c + e, p.gamma, p.alpha, gamma2, l, d);
+          acc += l;
+        }
+      }
+    }
+    int lvl, img, y, x;
+    head_loc(p, m, lvl, img, y, x);
+    const float s = (float)p.stride[lvl], sc = p.scales[lvl];
+    const float* rc = p.regctr + (long long)m * p.ld_rc;
+    float d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) d[k] = rc[k] * sc * p.stds[k];
+    // delta2bbox against the anchor (centre (x s, y s), side anchor_scale * s): loss_kernel<., true, true>'s lines
+    const float acx = (float)x * s, acy = (float)y * s, aw = p.anchor_scale * s;
+    const float gw = aw * expf(fminf(fmaxf(d[2], -kMaxRatio), kMaxRatio)), gh = aw * expf(fminf(fmaxf(d[3], -kMaxRatio), kMaxRatio));
+    const float gx = acx + aw * d[0], gy = acy + aw * d[1];
+    const float x1 = gx - gw * 0.5f, y1 = gy - gh * 0.5f, x2 = gx + gw * 0.5f, y2 = gy + gh * 0.5f;
+    const f32x4 t = *reinterpret_cast<const f32x4*>(p.bbox_targets + 4ll * m);
+    float dl[4];
+    const float bl = p.box_kind >= DSL_BOX_IOU_LINEAR ? box_loss_ext(p.box_kind, p.box_eps, x1, y1, x2, y2, t[0], t[1], t[2], t[3], dl)
+                                                      : box_loss_giou(p.box_kind == DSL_BOX_IOU_LOG, x1, y1, x2, y2, t[0], t[1], t[2], t[3], dl);
+    pl = p.w_cls * acc + p.w_bbox * bl;
+    const float a1 = (x2 - x1) * (y2 - y1), a2 = (t[2] - t[0]) * (t[3] - t[1]);
+    const float iw = fmaxf(fminf(x2, t[2]) - fmaxf(x1, t[0]), 0.f), ih = fmaxf(fminf(y2, t[3]) - fmaxf(y1, t[1]), 0.f);
+    const float ov = iw * ih;
+    it = ov / fmaxf(a1 + a2 - ov, 1e-6f);      // bbox_overlaps, is_aligned (paa_head.py:183-184)
+  }
+  p.pos_loss[m] = pl;
+  p.iou_target[m] = it;
+}
+
+// fixed-order butterfly sum over the wavefront: every lane ends with the same bits
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ double lse2(double a, double b) {
+  const double m = fmax(a, b);
+  return m + log(exp(a - m) + exp(b - m));
+}
+
+// weighted log probabilities of a lane's two samples under both components, as sklearn's _estimate_log_gaussian_prob ('diag') +
+// log(weights) forms them: -0.5 (log(2 pi) + mu^2 P - 2 x (mu P) + x^2 P) + log(prec_chol) + log(w), log(2 pi) rounded to float32
+__device__ __forceinline__ void paa_wlp(const double mu[2], const double mu2[2], const double pc[2], const double lw[2], double x0, double xx0,
+                                        double x1, double xx1, double& a00, double& a01, double& a10, double& a11) {
+  const double c2pi = (double)1.8378770664093453f;      // np.log(2 * np.pi).astype(float32)
+  double b[2][2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const double prec = pc[k] * pc[k], mp = mu[k] * prec, ld = log(pc[k]);
+    const double l0 = mu2[k] * prec - 2.0 * (x0 * mp) + xx0 * prec, l1 = mu2[k] * prec - 2.0 * (x1 * mp) + xx1 * prec;
+    b[0][k] = -0.5 * (c2pi + l0) + ld + lw[k];
+    b[1][k] = -0.5 * (c2pi + l1) + ld + lw[k];
+  }
+  a00 = b[0][0]; a01 = b[0][1]; a10 = b[1][0]; a11 = b[1][1];
+}
+
+// One workgroup per ground-truth box: its candidates' per-level top-k by loss, the sorted sample list, the mixture fit by the first
+// wavefront (two samples per lane, float64 on the float32 losses, sklearn's GaussianMixture(2, 'diag') as paa_head.py:326-345 sets
+// it up), the separation scheme (:392-399) and the demotion of every candidate that is not kept.  Block record [positives, sum of
+// their IoU targets].  iou_target is paa_pos_loss_kernel's: kept where an anchor stays positive, cleared where not - the two launches
+// are an ordered pair (include/dsl_hip.h).
+__global__ __launch_bounds__(ATSS_T) void paa_reassign_kernel(const FcK p) {
+  __shared__ unsigned long long red[ATSS_T];
+  __shared__ unsigned long long c_key[PAA_MAXS], s_key[PAA_MAXS];      // (loss bits << 32 | location): a loss is >= 0, so the bits order it
+  __shared__ int s_keep[PAA_MAXS];
+  __shared__ int s_iters, s_flag;
+  const int g = blockIdx.x, tid = threadIdx.x;
+  if (g >= p.gt_off[p.n]) {
+    if (tid == 0) {
+      p.part[2 * g] = 0.f; p.part[2 * g + 1] = 0.f;
+      p.gmm_iters[g] = 0; p.gmm_flags[g] = 0;
+    }
+    return;
+  }
+  int img = 0;
+  for (int i = 1; i < p.n; ++i)
+    if (g >= p.gt_off[i]) img = i;
+  const int gl = g - p.gt_off[img];
+  int ncand = 0;
+  for (int lvl = 0; lvl < p.nlvl; ++lvl) {      // TIE RULE: equal losses go to the lower location index
+    const int hw = p.h[lvl] * p.w[lvl], base = p.mstart[lvl] + img * hw;
+    unsigned long long last = 0ull;
+    int found = 0;
+    for (int r = 0; r < p.topk; ++r) {
+      unsigned long long best = ~0ull;
+      for (int i = tid; i < hw; i += ATSS_T) {
+        const int m = base + i;
+        if (p.cand_gt[m] != gl) continue;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(p.pos_loss[m]) << 32) | (unsigned)m;
+        if ((r == 0 || key > last) && key < best) best = key;
+      }
+      red[tid] = best;
+      __syncthreads();
+      for (int o = ATSS_T / 2; o > 0; o >>= 1) {
+        if (tid < o && red[tid + o] < red[tid]) red[tid] = red[tid + o];
+        __syncthreads();
+      }
+      last = red[0];
+      __syncthreads();
+      if (last == ~0ull) break;      // (uniform: fewer than topk candidates on this level)
+      if (tid == 0) c_key[ncand + found] = last;
+      ++found;
+    }
+    ncand += found;
+  }
+  __syncthreads();
+  if (tid < ncand) {      // rank sort: the keys are distinct (the location is part of them)
+    const unsigned long long key = c_key[tid];
+    int rank = 0;
+    for (int j = 0; j < ncand; ++j) rank += c_key[j] < key ? 1 : 0;
+    s_key[rank] = key;
+    s_keep[tid] = 0;
+  }
+  if (tid == 0) { s_iters = 0; s_flag = ncand < 2 ? 1 : 0; }      // fewer than two samples: the box keeps none (paa_head.py:320-321)
+  __syncthreads();
+  if (tid < 64 && ncand >= 2) {
+    const int n = ncand, i0 = tid, i1 = tid + 64;
+    const bool v0 = i0 < n, v1 = i1 < n;
+    const float f0 = v0 ? __uint_as_float((unsigned)(s_key[i0] >> 32)) : 0.f, f1 = v1 ? __uint_as_float((unsigned)(s_key[i1] >> 32)) : 0.f;
+    // sklearn keeps float32 samples: X * X, X**2 and the initial means**2 are float32 products, widened afterwards
+    const double x0 = f0, x1 = f1, xx0 = (double)(f0 * f0), xx1 = (double)(f1 * f1);
+    const float fmin_ = __uint_as_float((unsigned)(s_key[0] >> 32)), fmax_ = __uint_as_float((unsigned)(s_key[n - 1] >> 32));
+    double mu[2] = {(double)fmin_, (double)fmax_}, mu2[2] = {(double)(fmin_ * fmin_), (double)(fmax_ * fmax_)};
+    double pc[2] = {1.0, 1.0}, lw[2] = {log(0.5), log(0.5)};
+    double lower = -INFINITY;
+    int it = 0, flag = 0;
+    double a00 = 0, a01 = 0, a10 = 0, a11 = 0;
+    for (it = 1; it <= 100; ++it) {
+      const double prev = lower;
+      paa_wlp(mu, mu2, pc, lw, x0, xx0, x1, xx1, a00, a01, a10, a11);
+      const double n0 = lse2(a00, a01), n1 = lse2(a10, a11);
+      const double r00 = v0 ? exp(a00 - n0) : 0.0, r01 = v0 ? exp(a01 - n0) : 0.0;
+      const double r10 = v1 ? exp(a10 - n1) : 0.0, r11 = v1 ? exp(a11 - n1) : 0.0;
+      const double nk0 = wave_sum_f64(r00 + r10) + 10.0 * 2.220446049250313e-16, nk1 = wave_sum_f64(r01 + r11) + 10.0 * 2.220446049250313e-16;
+      const double sx0 = wave_sum_f64(r00 * x0 + r10 * x1), sx1 = wave_sum_f64(r01 * x0 + r11 * x1);
+      const double sq0 = wave_sum_f64(r00 * xx0 + r10 * xx1), sq1 = wave_sum_f64(r01 * xx0 + r11 * xx1);
+      const double sn = wave_sum_f64((v0 ? n0 : 0.0) + (v1 ? n1 : 0.0));
+      mu[0] = sx0 / nk0; mu[1] = sx1 / nk1;
+      mu2[0] = mu[0] * mu[0]; mu2[1] = mu[1] * mu[1];
+      const double var0 = sq0 / nk0 - mu2[0] + 1e-6, var1 = sq1 / nk1 - mu2[1] + 1e-6;
+      const double wsum = nk0 + nk1;
+      lw[0] = log(nk0 / wsum); lw[1] = log(nk1 / wsum);
+      if (!(var0 > 0.0) || !(var1 > 0.0)) {      // sklearn raises here ("ill-defined empirical covariance"): the box keeps no positive
+        flag = 2;
+        break;
+      }
+      pc[0] = 1.0 / sqrt(var0); pc[1] = 1.0 / sqrt(var1);
+      lower = sn / (double)n;
+      if (fabs(lower - prev) < 1e-3) break;
+    }
+    if (it > 100) it = 100;
+    if (flag == 0) {
+      paa_wlp(mu, mu2, pc, lw, x0, xx0, x1, xx1, a00, a01, a10, a11);      // predict / score_samples with the parameters of the last M-step
+      const bool fg0 = v0 && !(a01 > a00), fg1 = v1 && !(a11 > a10);      // argmax: ties go to component 0
+      const double sc0 = lse2(a00, a01), sc1 = lse2(a10, a11);
+      // the foreground sample with the highest score (equal scores: the first in sorted order)
+      double bs = fg0 ? sc0 : -INFINITY;
+      int bi = fg0 ? i0 : 0x7fffffff;
+      if (fg1 && (sc1 > bs || bi == 0x7fffffff)) { bs = sc1; bi = i1; }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const double os = __shfl_xor(bs, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (oi != 0x7fffffff && (bi == 0x7fffffff || os > bs || (os == bs && oi < bi))) { bs = os; bi = oi; }
+      }
+      if (fg0 && i0 <= bi) s_keep[i0] = 1;      // the first j + 1 foreground samples (paa_head.py:396-397)
+      if (fg1 && i1 <= bi) s_keep[i1] = 1;
+    }
+    if (tid == 0) { s_iters = it; s_flag = flag; }
+  }
+  __syncthreads();
+  // every candidate of the box that is not kept: background, no box weight (cls_weight stays 1: nothing is ignored)
+  for (int lvl = 0; lvl < p.nlvl; ++lvl) {
+    const int hw = p.h[lvl] * p.w[lvl], base = p.mstart[lvl] + img * hw;
+    for (int i = tid; i < hw; i += ATSS_T) {
+      const int m = base + i;
+      if (p.cand_gt[m] != gl) continue;
+      bool keep = false;
+      for (int j = 0; j < ncand; ++j) keep = keep || ((int)(unsigned)s_key[j] == m && s_keep[j]);
+      if (!keep) {
+        p.labels[m] = p.num_classes;
+        p.assign_idx[m] = -1;
+        p.pos_weight[m] = 0.f;
+        p.iou_target[m] = 0.f;
+      }
+    }
+  }
+  if (tid == 0) {
+    int np = 0;
+    float isum = 0.f;
+    for (int j = 0; j < ncand; ++j)      // in sorted order
+      if (s_keep[j]) { ++np; isum += p.iou_target[(int)(unsigned)s_key[j]]; }
+    p.part[2 * g] = (float)np; p.part[2 * g + 1] = isum;
+    p.gmm_iters[g] = s_iters; p.gmm_flags[g] = s_flag;
+  }
+}
+
+// npos per image, stats[0] = their sum (not clamped per image), stats[1] = the sum of the IoU targets: the boxes' records in box order
+__global__ __launch_bounds__(REC_T) void paa_finalize_kernel(const FcK p, int nrec) {
+  __shared__ float sh[REC_T];
+  const float t = record_sum(p.part, nrec, 2, 0, 2, sh);
+  if (threadIdx.x < 2) p.stats[threadIdx.x] = t;
+  if (threadIdx.x >= 2 && threadIdx.x < 8) p.stats[threadIdx.x] = 0.f;
+  for (int i = threadIdx.x; i < p.n; i += REC_T) {
+    int c = 0;
+    for (int g = p.gt_off[i]; g < p.gt_off[i + 1]; ++g) c += (int)p.part[2 * g];
+    p.npos[i] = c;
+  }
 }
 
 int fill(const dsl_fcos_desc* d, FcK& k) {
@@ -720,8 +1048,49 @@ bool loss_is_default(const FcK& k) {
 
 // loss_kernel's instantiations, [C % 4 != 0][0 the default head, 1 the loss family, 2 ATSS (always the loss family's kernel: with
 // the default settings it computes the default terms)]
-void (*const kLossKernel[2][3])(const FcK) = {{loss_kernel<false, false>, loss_kernel<false, true>, loss_kernel<false, true, true>},
-                                              {loss_kernel<true, false>, loss_kernel<true, true>, loss_kernel<true, true, true>}};
+void (*const kLossKernel[2][4])(const FcK) = {
+    {loss_kernel<false, false>, loss_kernel<false, true>, loss_kernel<false, true, true>, loss_kernel<false, true, true, true>},
+    {loss_kernel<true, false>, loss_kernel<true, true>, loss_kernel<true, true, true>, loss_kernel<true, true, true, true>}};
+
+// PAA workspace: the boxes' records [positives, IoU sum] of paa_reassign_kernel, then gtmax
+size_t paa_bytes(int max_gt) { return (size_t)max_gt * 3 * sizeof(float); }
+
+// a dsl_paa_desc the kernels build, or -1 with dsl_last_error naming the field
+int paa_fill(const dsl_paa_desc* q, FcK& k, const char* who) {
+  DSL_CHECK(q, "%s: null descriptor", who);
+  const dsl_fcos_desc* d = &q->fcos;
+  const int want = DSL_HEAD_ATSS | DSL_HEAD_PAA | DSL_HEAD_LOSS_EXT;
+  DSL_CHECK((d->head_flags & want) == want && !(d->head_flags & (DSL_HEAD_GFL | DSL_HEAD_LD)),
+            "%s: head_flags must be DSL_HEAD_ATSS | DSL_HEAD_PAA | DSL_HEAD_LOSS_EXT", who);
+  if (fill(d, k)) return -1;
+  const dsl_atss_desc* a = d->atss;
+  DSL_CHECK(a->topk >= 1 && a->topk <= DSL_ATSS_MAX_TOPK, "%s: atss.topk must be in 1..16", who);
+  DSL_CHECK(a->max_gt >= 1 && a->max_gt <= 65535, "%s: atss.max_gt must be in 1..65535", who);
+  DSL_CHECK(a->pad_shapes, "%s: atss.pad_shapes is null", who);
+  DSL_CHECK(a->npos, "%s: atss.npos is null", who);
+  DSL_CHECK(q->pos_iou_thr > 0.f && q->pos_iou_thr < 1.f, "%s: pos_iou_thr must be in (0, 1)", who);
+  DSL_CHECK(q->pos_loss, "%s: pos_loss is null", who);
+  DSL_CHECK(q->iou_target, "%s: iou_target is null", who);
+  DSL_CHECK(q->cand_gt, "%s: cand_gt is null", who);
+  DSL_CHECK(q->gmm_iters, "%s: gmm_iters is null", who);
+  DSL_CHECK(q->gmm_flags, "%s: gmm_flags is null", who);
+  DSL_CHECK(d->gt_boxes && d->gt_labels && d->gt_off && d->labels && d->bbox_targets && d->assign_idx && d->cls_weight && d->pos_weight &&
+                d->stats, "%s: null pointer in fcos (ground truth, targets or stats)", who);
+  DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d) && ((uintptr_t)d->workspace & 15) == 0,
+            "%s: fcos.workspace too small or not 16-byte aligned", who);
+  k.topk = a->topk; k.pad_shapes = a->pad_shapes; k.npos = a->npos; k.max_gt = a->max_gt;
+  k.pos_iou_thr = q->pos_iou_thr; k.pos_loss = q->pos_loss; k.iou_target = q->iou_target; k.cand_gt = q->cand_gt;
+  k.gmm_iters = q->gmm_iters; k.gmm_flags = q->gmm_flags;
+  k.gtmax = (float*)d->workspace + 2 * (size_t)a->max_gt;
+  return 0;
+}
+
+int paa_head_outputs(const dsl_fcos_desc* d, const char* who) {
+  DSL_CHECK(d->cls_logits && d->regctr && d->scales, "%s: null head output (fcos.cls_logits, regctr, scales)", who);
+  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= 5,
+            "%s: unsupported fcos.ld_cls / ld_rc / num_classes", who);
+  return 0;
+}
 
 }  // namespace
 
@@ -730,6 +1099,10 @@ extern "C" size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d) {
   if (head_geom(d, g, "dsl_fcos_workspace_bytes")) return 0;
   const size_t assign_rec = (size_t)((g.M + 255) / 256) * 2, loss_rec = 2048 * 16;
   const size_t need = (assign_rec > loss_rec ? assign_rec : loss_rec) * sizeof(float);
+  if (d->head_flags & DSL_HEAD_PAA) {      // the boxes' records and maxima (d->atss->max_gt of them)
+    const size_t paa = d->atss ? paa_bytes(d->atss->max_gt > 0 ? d->atss->max_gt : 0) : 0;
+    return need > paa ? need : paa;
+  }
   if (d->head_flags & DSL_HEAD_ATSS) return need > atss_assign_bytes(g.M) ? need : atss_assign_bytes(g.M);
   return need;
 }
@@ -762,6 +1135,7 @@ extern "C" int dsl_fcos_assign(const dsl_fcos_desc* d, void* stream) {
 extern "C" int dsl_atss_assign(const dsl_fcos_desc* d, const dsl_atss_desc* a, void* stream) {
   FcK k;
   DSL_CHECK(d && a && d->atss == a && (d->head_flags & DSL_HEAD_ATSS), "dsl_atss_assign: DSL_HEAD_ATSS and d->atss == a are required");
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_PAA), "dsl_atss_assign: a DSL_HEAD_PAA descriptor is assigned by dsl_paa_assign");
   if (fill(d, k)) return -1;
   DSL_CHECK(d->gt_boxes && d->gt_labels && d->gt_off && d->labels && d->bbox_targets && d->assign_idx && d->cls_weight &&
                 d->pos_weight && d->stats && a->pad_shapes && a->npos,
@@ -788,6 +1162,7 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   FcK k;
   if (fill(d, k)) return -1;
   DSL_CHECK(!(d->head_flags & DSL_HEAD_GFL), "dsl_fcos_loss: a DSL_HEAD_GFL descriptor's loss is dsl_gfl_loss");
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_PAA), "dsl_fcos_loss: a DSL_HEAD_PAA descriptor's loss is dsl_paa_loss");
   if (head_loss_ptrs(d, "dsl_fcos_loss")) return -1;
   DSL_CHECK(d->pos_weight, "dsl_fcos_loss: null pointer");
   DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_gcls % 4 == 0 &&
@@ -799,19 +1174,63 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   const bool atss = (k.flags & DSL_HEAD_ATSS) != 0;
   const int blocks = head_loss_blocks(k);
   hipLaunchKernelGGL(kLossKernel[d->num_classes % 4 != 0][atss ? 2 : !loss_is_default(k)], dim3(blocks), dim3(256), 0, st, k);
-  hipLaunchKernelGGL(atss ? fcos_finalize_kernel<true> : fcos_finalize_kernel<false>, dim3(1), dim3(REC_T), 0, st, k, blocks);
+  hipLaunchKernelGGL(atss ? fcos_finalize_kernel<1> : fcos_finalize_kernel<0>, dim3(1), dim3(REC_T), 0, st, k, blocks);
   DSL_LAUNCH_CHECK("loss_kernel");
+  return 0;
+}
+
+extern "C" int dsl_paa_assign(const dsl_paa_desc* q, void* stream) {
+  FcK k;
+  if (paa_fill(q, k, "dsl_paa_assign")) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(paa_gtmax_kernel, dim3(k.max_gt), dim3(ATSS_T), 0, st, k);
+  hipLaunchKernelGGL(paa_write_kernel, dim3((k.M + ATSS_T - 1) / ATSS_T), dim3(ATSS_T), 0, st, k);
+  DSL_LAUNCH_CHECK("paa_assign");
+  return 0;
+}
+
+extern "C" int dsl_paa_pos_loss(const dsl_paa_desc* q, void* stream) {
+  FcK k;
+  if (paa_fill(q, k, "dsl_paa_pos_loss") || paa_head_outputs(&q->fcos, "dsl_paa_pos_loss")) return -1;
+  hipLaunchKernelGGL(paa_pos_loss_kernel, dim3((k.M + 255) / 256), dim3(256), 0, (hipStream_t)stream, k);
+  DSL_LAUNCH_CHECK("paa_pos_loss");
+  return 0;
+}
+
+extern "C" int dsl_paa_reassign(const dsl_paa_desc* q, void* stream) {
+  FcK k;
+  if (paa_fill(q, k, "dsl_paa_reassign")) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(paa_reassign_kernel, dim3(k.max_gt), dim3(ATSS_T), 0, st, k);
+  hipLaunchKernelGGL(paa_finalize_kernel, dim3(1), dim3(REC_T), 0, st, k, k.max_gt);
+  DSL_LAUNCH_CHECK("paa_reassign");
+  return 0;
+}
+
+extern "C" int dsl_paa_loss(const dsl_paa_desc* q, void* stream) {
+  FcK k;
+  if (paa_fill(q, k, "dsl_paa_loss") || paa_head_outputs(&q->fcos, "dsl_paa_loss")) return -1;
+  const dsl_fcos_desc* d = &q->fcos;
+  if (head_loss_ptrs(d, "dsl_paa_loss")) return -1;
+  DSL_CHECK(d->ld_gcls % 4 == 0 && d->ld_gcls >= d->ld_cls && d->ld_grc % 8 == 0, "dsl_paa_loss: unsupported fcos.ld_gcls / ld_grc");
+  hipStream_t st = (hipStream_t)stream;
+  const int blocks = head_loss_blocks(k);
+  hipLaunchKernelGGL(kLossKernel[d->num_classes % 4 != 0][3], dim3(blocks), dim3(256), 0, st, k);
+  hipLaunchKernelGGL(fcos_finalize_kernel<2>, dim3(1), dim3(REC_T), 0, st, k, blocks);
+  DSL_LAUNCH_CHECK("paa_loss");
   return 0;
 }
 
 /* one dispatch for every head: the entry point a descriptor's head_flags name (include/dsl_hip.h) */
 extern "C" int dsl_head_assign(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(d, "dsl_head_assign: null descriptor");
+  if (d->head_flags & DSL_HEAD_PAA) return dsl_paa_assign((const dsl_paa_desc*)d, stream);
   return (d->head_flags & DSL_HEAD_ATSS) ? dsl_atss_assign(d, d->atss, stream) : dsl_fcos_assign(d, stream);
 }
 
 extern "C" int dsl_head_loss(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(d, "dsl_head_loss: null descriptor");
+  if (d->head_flags & DSL_HEAD_PAA) return dsl_paa_loss((const dsl_paa_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_LD) return dsl_ld_loss((const dsl_ld_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_GFL) return dsl_gfl_loss((const dsl_gfl_desc*)d, stream);
   return dsl_fcos_loss(d, stream);

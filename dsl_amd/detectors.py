@@ -5,6 +5,8 @@ configs/fcos_semi/*.py build unmodified:
   ResNet                        mmdet/models/backbones/resnet.py:304-656   (depth 50, caffe, frozen BN)
   FPN                           mmdet/models/necks/fpn.py:9-202
   FCOSHead                      mmdet/models/dense_heads/fcos_head.py:14-726
+  PAA / PAAHead                 mmdet/models/detectors/paa.py, mmdet/models/dense_heads/paa_head.py:44-673 with
+                                core/bbox/assigners/max_iou_assigner.py; sklearn's GaussianMixture restated in the kernel
   ATSS / ATSSHead               mmdet/models/detectors/atss.py, mmdet/models/dense_heads/atss_head.py:14-684 with
                                 core/bbox/assigners/atss_assigner.py, core/anchor/anchor_generator.py, core/bbox/coder/delta_xywh_bbox_coder.py
   FocalLoss / GIoULoss / IoULoss / DIoULoss / CIoULoss / CrossEntropyLoss   mmdet/models/losses/*.py
@@ -407,9 +409,9 @@ class ATSSHead(nn.Module):
                  loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None, **kw):
         super().__init__()
         class_layout(num_classes)
-        _expect_no_dsl_keys('ATSSHead', kw)
+        _expect_no_dsl_keys(type(self).__name__, kw)
         _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, conv_cfg is None)
-        _expect(not reg_decoded_bbox, 'reg_decoded_bbox=False')
+        _expect(bool(reg_decoded_bbox) == self.REG_DECODED_BBOX, f'reg_decoded_bbox={self.REG_DECODED_BBOX}')
         obs = _square_anchor_scale(anchor_generator)
         bc = dict(bbox_coder)
         _expect(bc.pop('type', None) == 'DeltaXYWHBBoxCoder', "bbox_coder type='DeltaXYWHBBoxCoder'")
@@ -419,19 +421,70 @@ class ATSSHead(nn.Module):
         _expect(bc.pop('clip_border', True) and not bc.pop('add_ctr_clamp', False), 'bbox_coder clip_border=True, add_ctr_clamp=False')
         bc.pop('ctr_clamp', None)
         _expect(not bc, f'bbox_coder: unknown arguments {sorted(bc)}')
-        topk = _atss_topk(train_cfg)
+        assigner_kw = self._assigner_options(train_cfg)
         self.num_classes, self.strides = num_classes, (8, 16, 32, 64, 128)
         self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
         self.loss_cls = build_loss(loss_cls)
         self.loss_bbox, self.bbox_weight = _build_loss_bbox(loss_bbox, _FCOS_LOSSES)
         self.loss_centerness = build_loss(loss_centerness)
         _expect(isinstance(self.loss_cls, FocalLoss) and isinstance(self.loss_centerness, CrossEntropyLoss), _FCOS_LOSSES)
-        self.options = HeadOptions(**_atss_option_kw(self), atss_topk=topk, anchor_scale=obs, focal_gamma=self.loss_cls.gamma,
-                                   focal_alpha=self.loss_cls.alpha, ctr_weight=self.loss_centerness.loss_weight, delta_stds=stds)
+        self.options = HeadOptions(**_atss_option_kw(self), anchor_scale=obs, focal_gamma=self.loss_cls.gamma,
+                                   focal_alpha=self.loss_cls.alpha, ctr_weight=self.loss_centerness.loss_weight, delta_stds=stds,
+                                   **assigner_kw)
         self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    REG_DECODED_BBOX = False      # (PAAHead: True - its loss works on decoded boxes)
+
+    def _assigner_options(self, train_cfg):
+        """The HeadOptions keywords that train_cfg and the subclass's own arguments decide."""
+        return dict(atss_topk=_atss_topk(train_cfg))
 
     def effective_soft_weight(self, batch_size):
         return 0.0
+
+
+def _paa_pos_iou_thr(train_cfg):
+    """pos_iou_thr of train_cfg.assigner = MaxIoUAssigner as configs/paa sets it (0.1 without a train_cfg), with the refusals of what
+    dsl_paa_assign does not build (max_iou_assigner.py:43-62: every other argument at its default)."""
+    thr = 0.1
+    if train_cfg is not None:
+        asg = dict(_cfg_get(train_cfg, 'assigner') or {})
+        _expect(asg.pop('type', None) == 'MaxIoUAssigner', "train_cfg.assigner type='MaxIoUAssigner'")
+        thr, neg = asg.pop('pos_iou_thr', None), asg.pop('neg_iou_thr', None)
+        _expect(isinstance(thr, (int, float)) and not isinstance(thr, bool) and 0.0 < float(thr) < 1.0,
+                f'train_cfg.assigner pos_iou_thr in (0, 1) (got {thr!r})')
+        _expect(isinstance(neg, (int, float)) and float(neg) == float(thr), f'train_cfg.assigner neg_iou_thr == pos_iou_thr (got {neg!r})')
+        _expect(float(asg.pop('min_pos_iou', 0.0)) == 0.0, 'train_cfg.assigner min_pos_iou=0')
+        _expect(float(asg.pop('ignore_iof_thr', -1)) == -1.0, 'train_cfg.assigner ignore_iof_thr=-1 (gt_bboxes_ignore is not read)')
+        _expect(asg.pop('gt_max_assign_all', True) is True, 'train_cfg.assigner gt_max_assign_all=True')
+        _expect(asg.pop('ignore_wrt_candidates', True) is True, 'train_cfg.assigner ignore_wrt_candidates=True')
+        _expect(asg.pop('match_low_quality', True) is True, 'train_cfg.assigner match_low_quality=True')
+        _expect(float(asg.pop('gpu_assign_thr', -1)) <= 0, 'train_cfg.assigner gpu_assign_thr=-1')
+        ic = asg.pop('iou_calculator', dict(type='BboxOverlaps2D'))
+        _expect(dict(ic) == dict(type='BboxOverlaps2D'), 'train_cfg.assigner iou_calculator BboxOverlaps2D')
+        _expect(not asg, f'train_cfg.assigner: unknown arguments {sorted(asg)}')
+        _expect(_cfg_get(train_cfg, 'allowed_border', -1) == -1, 'train_cfg.allowed_border=-1')
+        _expect(_cfg_get(train_cfg, 'pos_weight', -1) <= 0, 'train_cfg.pos_weight=-1')
+    return float(thr)
+
+
+@HEADS.register_module()
+class PAAHead(ATSSHead):
+    """mmdet/models/dense_heads/paa_head.py:44-673: ATSSHead's network, parameters, anchors and box decode - the centerness predictor
+    is the IoU-prediction branch - with MaxIoUAssigner's candidates, their reassignment by a two-component Gaussian mixture of the
+    candidates' losses per ground-truth box, an IoU-weighted box loss (dsl_paa_assign / _pos_loss / _reassign / _loss, DSL_HEAD_PAA),
+    and at test time the sqrt(cls * iou) score with score voting.  The signature is the reference's; what the kernels do not build
+    is refused, naming the option."""
+    REG_DECODED_BBOX = True
+
+    def __init__(self, *args, topk=9, score_voting=True, covariance_type='diag', **kwargs):
+        _expect(isinstance(topk, int) and not isinstance(topk, bool) and 1 <= topk <= 16, f'topk in 1..16 (got {topk!r})')
+        _expect(covariance_type == 'diag', f"covariance_type='diag' (got {covariance_type!r})")
+        self.topk, self.with_score_voting, self.covariance_type = topk, bool(score_voting), covariance_type
+        super().__init__(*args, **kwargs)
+
+    def _assigner_options(self, train_cfg):
+        return dict(head_kind='paa', atss_topk=self.topk, pos_iou_thr=_paa_pos_iou_thr(train_cfg), score_voting=self.with_score_voting)
 
 
 @HEADS.register_module()
@@ -775,7 +828,9 @@ class FCOS(nn.Module):
         lp = plan.lossplan
         sw = head.effective_soft_weight(N)
         ws = self.world_size
-        lp.configure(loss_weight=head.loss_weight, soft_weight=sw, grad_scale=self.loss_scale / ws, inv_world=1.0 / ws)
+        # (a PAA head normalises by this rank's own stats: the reference does not reduce_mean there, paa_head.py:173-193)
+        lp.configure(loss_weight=head.loss_weight, soft_weight=sw, grad_scale=self.loss_scale / ws,
+                     inv_world=1.0 if lp.paa is not None else 1.0 / ws)
         pipe = self.pipeline_prefix and plan.prefix is not None
         if pipe:
             # frozen prefix of THIS step on its own stream: it waits for the previous backward's data-gradient chain only (named
@@ -833,6 +888,13 @@ class FCOS(nn.Module):
             plan.quality_ops.run()
             if ws > 1 and not self.comm_off:
                 self._all_reduce_async(lp.stats[:2], after_current=True).wait()
+        elif lp.paa is not None:
+            # a PAA head takes the GFL branch's order - forward, targets, first assignment, then the candidates' losses and the
+            # reassignment behind the predictors (paa_head.py:141-157) - and exchanges no normaliser
+            fwd.run()
+            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
+            plan.assign_ops.run()
+            plan.quality_ops.run()
         elif ws > 1:
             # target assignment first: the reduce_mean of (num_pos, sum centerness targets) - one 2-float all-reduce
             # (fcos_head.py:264-274) - then runs under the forward pass
@@ -859,7 +921,8 @@ class FCOS(nn.Module):
                 eager_now = True
         self._eager_now = eager_now
         out = _TrainStepFn.apply(self._anchor, self, plan)
-        losses = _LossDict(loss_cls=out[0], loss_bbox=out[1], **{'loss_dfl' if lp.gfl is not None else 'loss_centerness': out[2]})
+        third = 'loss_dfl' if lp.gfl is not None else 'loss_iou' if lp.paa is not None else 'loss_centerness'
+        losses = _LossDict(loss_cls=out[0], loss_bbox=out[1], **{third: out[2]})
         if sw != 0.0:
             losses['loss_sisoft'] = out[3]
         elif lp.ld is not None:
@@ -1043,6 +1106,9 @@ class FCOS(nn.Module):
 
     def aug_test(self, imgs, img_metas, rescale=False):
         """detectors/single_stage.py:109-135: `imgs` / `img_metas` hold one entry per view, each with ONE image."""
+        if getattr(self.bbox_head.options, 'head_kind', 'fcos') == 'paa':
+            raise NotImplementedError('PAAHead does not support test-time augmentation (aug_test): PAA only supports with_nms=True '
+                                      '(paa_head.py:536-538)')
         from .sweep import aug_test
         self.store.wait_pending()
         return aug_test(self, imgs, img_metas, rescale)
@@ -1129,6 +1195,16 @@ class GFL(FCOS):
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
         _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == self.HEAD_TYPE,
                 f"{type(self).__name__} with bbox_head type='{self.HEAD_TYPE}'")
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
+
+
+@DETECTORS.register_module()
+class PAA(FCOS):
+    """mmdet/models/detectors/paa.py:5-18: SingleStageDetector with a PAAHead, on the FCOS detector's machinery (ATSS's network and
+    parameters; assignment, losses, normalisers and the detection score are the head's)."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
+        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'PAAHead', "PAA with bbox_head type='PAAHead'")
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
 
 

@@ -155,6 +155,9 @@ class OpList:
     def gfl_quality(self, gfl):
         self._add(L.OP_GFL_QUALITY, gfl)
 
+    def paa_refine(self, paa):
+        self._add(L.OP_PAA_REFINE, paa)
+
     def maxpool(self, x, y, n, h, w, c):
         self._add(L.OP_MAXPOOL, i=(n, h, w, c), p=(x, y))
 
@@ -233,6 +236,11 @@ class Plan:
             if self.lossplan.gfl is not None:
                 self.quality_ops, self.loss_ops = self.loss_ops, OpList()
                 self.quality_ops.gfl_quality(self.lossplan.gfl)
+            elif self.lossplan.paa is not None:
+                # a PAA head: the candidates' losses and the reassignment sit where GFL's quality pass does, behind the predictors
+                # and the first assignment (paa_head.py:141-157); nothing crosses ranks between the two lists
+                self.quality_ops, self.loss_ops = self.loss_ops, OpList()
+                self.quality_ops.paa_refine(self.lossplan.paa)
             self.loss_ops.loss(self.lossplan.desc)
             self._build_backward()
 

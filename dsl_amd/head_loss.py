@@ -32,7 +32,10 @@ class FcosLossPlan:
         predictor's rows are 4 (reg_max + 1) floats / round_up(that, 64) gradient columns wide, quality() runs between the predictors
         and the exchange of stats[0:2] and writes stats[1], loss() is dsl_gfl_loss; losses = (cls, bbox, dfl, 0).
         An LD head (a GFL head with head.ld_weight set): the dsl_gfl_desc is the first member of a dsl_ld_desc (`ld`), bind_soft() names
-        the teacher's box predictor output, loss() is dsl_ld_loss; losses = (cls, bbox, dfl, ld), logvec has five elements."""
+        the teacher's box predictor output, loss() is dsl_ld_loss; losses = (cls, bbox, dfl, ld), logvec has five elements.
+        A PAA head (head.head_kind == 'paa'): the descriptor is a dsl_paa_desc (`paa`, whose first member is `desc`) on an ATSS head's
+        buffers; assign() is dsl_paa_assign, refine() = dsl_paa_pos_loss + dsl_paa_reassign runs between the predictors and the loss,
+        loss() is dsl_paa_loss; losses = (cls, bbox, iou, 0); `cand_gt`, `pos_loss`, `iou_target`, `gmm_iters`, `gmm_flags` are its."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head
         self.gfl = self.ld = None
@@ -43,6 +46,7 @@ class FcosLossPlan:
             self.gfl = self.ld.gfl if self.ld is not None else L.GflDesc()
             self.LD_RC = 4 * (head.reg_max + 1)
             self.LD_GRC = (self.LD_RC + 63) // 64 * 64
+        self.paa = L.PaaDesc() if head is not None and head.head_kind == 'paa' else None
         self.ctr_col = None
         if head is not None and not head.centerness_on_reg:
             self.ctr_col = self.LD_CLS
@@ -79,7 +83,7 @@ class FcosLossPlan:
                             pad=torch.zeros(n, 2, dtype=torch.int32, pin_memory=pin), ev=None) for _ in range(4)]
         self._slot_i = 0
         self.desc = ops.fcos_desc(n=n, sizes=self.sizes, strides=strides, ranges=ranges, radius=radius,
-                                  num_classes=num_classes, into=self.gfl.fcos if self.gfl is not None else None)
+                                  num_classes=num_classes, into=self.gfl.fcos if self.gfl is not None else self.paa.fcos if self.paa is not None else None)
         ops.set_ptrs(self.desc, gt_boxes=self.gt_boxes, gt_labels=self.gt_labels, gt_off=self.gt_off,
                      labels=self.labels, bbox_targets=self.bbox_targets, assign_idx=self.assign_idx,
                      cls_weight=self.cls_weight, pos_weight=self.pos_weight, stats=self.stats,
@@ -91,7 +95,7 @@ class FcosLossPlan:
             self.desc.head_flags = head.flags()
             # box kind, focal gamma / alpha, the three loss weights, wherever HEAD_LOSS_EXT is in the flags: a head off the default
             # loss family, and every GFL head (dsl_gfl_loss reads w_cls / w_bbox / box_kind with no default to fall back to)
-            if not head.loss_is_default() or self.gfl is not None:
+            if not head.loss_is_default() or self.gfl is not None or self.paa is not None:
                 head.fill_loss_desc(self.desc)
         if self.ctr_col is not None:
             self.desc.g_ctr, self.desc.ld_gctr = self.g_cls.data_ptr() + 2 * self.ctr_col, self.LD_GCLS
@@ -109,6 +113,17 @@ class FcosLossPlan:
             g.score, g.weight = L.ptr(self.score), L.ptr(self.weight)
             if self.ld is None:
                 self.logvec = self.logvec[:4]      # cls, bbox, dfl, their sum (an LD head: cls, bbox, dfl, ld, their sum)
+        if self.paa is not None:
+            self.pos_loss = torch.zeros(M, dtype=torch.float32, device=dev)
+            self.iou_target = torch.zeros(M, dtype=torch.float32, device=dev)
+            self.cand_gt = torch.full((M,), -1, dtype=torch.int32, device=dev)
+            self.gmm_iters = torch.zeros(max_gt, dtype=torch.int32, device=dev)
+            self.gmm_flags = torch.zeros(max_gt, dtype=torch.int32, device=dev)
+            q = self.paa
+            q.pos_iou_thr = head.pos_iou_thr
+            q.pos_loss, q.iou_target, q.cand_gt = L.ptr(self.pos_loss), L.ptr(self.iou_target), L.ptr(self.cand_gt)
+            q.gmm_iters, q.gmm_flags = L.ptr(self.gmm_iters), L.ptr(self.gmm_flags)
+            self.logvec = self.logvec[:4]      # cls, bbox, iou, their sum
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         self.desc.workspace, self.desc.workspace_bytes = L.ptr(self.ws), need
@@ -192,8 +207,14 @@ class FcosLossPlan:
         """GFL only: score / weight of the positives and stats[1] = sum of the weights (dsl_gfl_quality)."""
         L.check(L.lib.dsl_gfl_quality(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_quality')
 
+    def refine(self):
+        """PAA only: the candidates' losses, then the mixture fit and the reassignment (what DSL_OP_PAA_REFINE runs)."""
+        L.check(L.lib.dsl_paa_pos_loss(C.byref(self.paa), L.stream_ptr()), 'dsl_paa_pos_loss')
+        L.check(L.lib.dsl_paa_reassign(C.byref(self.paa), L.stream_ptr()), 'dsl_paa_reassign')
+
     def loss(self):
         """The entry point of the descriptor this plan built, not dsl_head_loss's choice by head_flags: a dsl_ld_desc whose flags lost
         DSL_HEAD_LD is then refused by dsl_ld_loss instead of running as a GFL head."""
-        name = 'dsl_ld_loss' if self.ld is not None else 'dsl_gfl_loss' if self.gfl is not None else 'dsl_fcos_loss'
+        name = ('dsl_ld_loss' if self.ld is not None else 'dsl_gfl_loss' if self.gfl is not None else
+                'dsl_paa_loss' if self.paa is not None else 'dsl_fcos_loss')
         L.check(getattr(L.lib, name)(C.byref(self.desc), L.stream_ptr()), name)

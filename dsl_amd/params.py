@@ -149,20 +149,26 @@ class HeadOptions:
     Localization Distillation (LDHead, mmdet/models/dense_heads/ld_head.py, dsl_ld_desc) is a GFL head with one more loss term against
     a frozen teacher's box distributions; the network and the parameter layout are GFL's:
       ld_weight          KnowledgeDistillationKLDivLoss(loss_weight) >= 0; None (default): no LD term, a plain GFL head
-      ld_T               its temperature, finite and >= 1 (losses/kd_loss.py:50)"""
+      ld_T               its temperature, finite and >= 1 (losses/kd_loss.py:50)
+    Probabilistic anchor assignment (head_kind 'paa' = PAAHead, mmdet/models/dense_heads/paa_head.py, dsl_paa_desc): an ATSS head in
+    network, parameter layout, decode and predictor names (assigner='atss' is forced; its centerness predictor is the IoU-prediction
+    branch) whose targets come from MaxIoUAssigner and the Gaussian-mixture reassignment; atss_topk is PAAHead's per-level topk:
+      pos_iou_thr        MaxIoUAssigner pos_iou_thr == neg_iou_thr, in (0, 1)
+      score_voting       detection: score voting behind the NMS (paa_head.py:608-673)"""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
     BOX_KINDS = dict(giou=L.BOX_GIOU, iou=L.BOX_IOU_LOG, iou_linear=L.BOX_IOU_LINEAR, diou=L.BOX_DIOU, ciou=L.BOX_CIOU)
     ATSS_FIELDS = ('assigner', 'atss_topk', 'anchor_scale', 'delta_stds')
     GFL_FIELDS = ('head_kind', 'reg_max', 'qfl_beta', 'dfl_weight')
     LD_FIELDS = ('ld_weight', 'ld_T')
+    PAA_FIELDS = ('head_kind', 'pos_iou_thr', 'score_voting')
 
     def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
                  box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0,
                  assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2),
-                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0):
-        if head_kind not in ('fcos', 'gfl'):
-            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos' or 'gfl', got {head_kind!r}")
+                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0, pos_iou_thr=0.1, score_voting=True):
+        if head_kind not in ('fcos', 'gfl', 'paa'):
+            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos', 'gfl' or 'paa', got {head_kind!r}")
         self.head_kind = head_kind
         self.reg_max, self.qfl_beta, self.dfl_weight = reg_max, float(qfl_beta), float(dfl_weight)
         self.ld_weight, self.ld_T = None, 10.0
@@ -190,6 +196,13 @@ class HeadOptions:
             if assigner not in ('fcos', 'atss'):
                 raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
             assigner = 'atss'      # (the default 'fcos' stands for "not given": a GFL head's targets are ATSS's)
+        self.pos_iou_thr, self.score_voting = float(pos_iou_thr), bool(score_voting)
+        if head_kind == 'paa':
+            if not (isinstance(pos_iou_thr, (int, float)) and 0.0 < self.pos_iou_thr < 1.0):
+                raise NotImplementedError(f'dsl_amd hot path: pos_iou_thr must be a number in (0, 1), got {pos_iou_thr!r}')
+            if assigner not in ('fcos', 'atss'):
+                raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
+            assigner = 'atss'      # (the anchors, valid flags, decode and parameter layout of an ATSS head)
         if assigner not in ('fcos', 'atss'):
             raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
         self.assigner = assigner
@@ -226,6 +239,7 @@ class HeadOptions:
         k = k if self.loss_is_default() else k + self.loss_key()
         k = k + tuple(getattr(self, f) for f in self.ATSS_FIELDS) if self.assigner == 'atss' else k
         k = k + tuple(getattr(self, f) for f in self.GFL_FIELDS) if self.head_kind == 'gfl' else k
+        k = k + tuple(getattr(self, f) for f in self.PAA_FIELDS) if self.head_kind == 'paa' else k
         return k + tuple(getattr(self, f) for f in self.LD_FIELDS) if self.ld_weight is not None else k
 
     def is_default(self):
@@ -237,6 +251,7 @@ class HeadOptions:
                 | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT)
                 | (L.HEAD_ATSS if self.assigner == 'atss' else 0)
                 | (L.HEAD_GFL | L.HEAD_LOSS_EXT if self.head_kind == 'gfl' else 0)       # (a dsl_gfl_desc always carries its loss settings)
+                | (L.HEAD_PAA | L.HEAD_LOSS_EXT if self.head_kind == 'paa' else 0)       # (so does a dsl_paa_desc)
                 | (L.HEAD_LD if self.ld_weight is not None else 0))
 
     def atss_desc(self):
@@ -260,6 +275,7 @@ class HeadOptions:
         fields += self.ATSS_FIELDS if self.assigner == 'atss' else ()
         fields += self.GFL_FIELDS if self.head_kind == 'gfl' else ()
         fields += self.LD_FIELDS if self.ld_weight is not None else ()
+        fields += self.PAA_FIELDS if self.head_kind == 'paa' else ()
         return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in fields) + ')'
 
 

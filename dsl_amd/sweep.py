@@ -20,8 +20,9 @@ from . import _lib as L
 
 class DetectPlan:
     def __init__(self, n, sizes, strides, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05,
-                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, atss=None, reg_max=None):
+                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, atss=None, reg_max=None, score_voting=None):
         """atss: the dsl_atss_desc of an ATSS head (params.HeadOptions.atss_desc), with HEAD_ATSS in head_flags.
+        score_voting: of a PAA head (True / False; None = not a PAA head), with HEAD_ATSS | HEAD_PAA in head_flags and `atss` set.
         reg_max: of a GFL head, with HEAD_GFL alone in head_flags and ld_rc >= 4 (reg_max + 1)."""
         d = L.DetDesc()
         self.atss = atss
@@ -29,6 +30,10 @@ class DetectPlan:
             self._ext = L.DetGflDesc()
             self._ext.reg_max = reg_max
             d = self._ext.det
+        elif atss is not None and score_voting is not None:      # dsl_det_paa_desc around a dsl_det_atss_desc: `d` is the innermost first member
+            self._ext = L.DetPaaDesc()
+            self._ext.atss.atss, self._ext.score_voting = C.addressof(atss), int(bool(score_voting))
+            d = self._ext.atss.det
         elif atss is not None:      # dsl_det_atss_desc: `d` is its first member (and keeps it alive)
             self._ext = L.DetAtssDesc()
             self._ext.atss = C.addressof(atss)
@@ -147,8 +152,9 @@ def _detplan(det, plan, store, N):
     if dp is None:
         dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
                         ld_cls=store.logit_ld, ld_rc=store.reg_ld, reg_max=store.head.reg_max if store.gfl else None,
-                        head_flags=L.HEAD_GFL if store.gfl else store.head.flags() & (L.HEAD_EXP_DECODE | L.HEAD_ATSS),
+                        head_flags=L.HEAD_GFL if store.gfl else store.head.flags() & (L.HEAD_EXP_DECODE | L.HEAD_ATSS | L.HEAD_PAA),
                         atss=None if store.gfl else store.head.atss_desc(),
+                        score_voting=store.head.score_voting if store.head.head_kind == 'paa' else None,
                         ctr_col=store.cls_ld if store.ctr_on_cls else None, **_test_cfg(det))
         dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
         plan.detplan = dp

@@ -565,7 +565,8 @@ typedef struct dsl_fcos_desc {
 #define DSL_BOX_IOU_LINEAR 2
 #define DSL_BOX_DIOU 3
 #define DSL_BOX_CIOU 4
-size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d);   /* with DSL_HEAD_ATSS: also what dsl_atss_assign needs */
+size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d);   /* with DSL_HEAD_ATSS: also what dsl_atss_assign needs; with DSL_HEAD_PAA: what
+                                                            * the dsl_paa_* passes need (reads d->atss->max_gt) */
 
 /* ------------------------------------------------------------------------------------------
  * ATSS: adaptive training sample selection (mmdet/core/bbox/assigners/atss_assigner.py:66-178,
@@ -698,11 +699,87 @@ typedef struct dsl_ld_desc {
 } dsl_ld_desc;
 int dsl_ld_loss(const dsl_ld_desc* d, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PAA: probabilistic anchor assignment (mmdet/models/dense_heads/paa_head.py:86-399 loss, get_pos_loss, paa_reassign,
+ * gmm_separation_scheme; mmdet/core/bbox/assigners/max_iou_assigner.py:127-212 assign_wrt_overlaps; sklearn.mixture.GaussianMixture
+ * as paa_head.py:326-347 sets it up), fp32 with contraction off, the mixture fit in fp64.
+ *
+ * A dsl_paa_desc wraps a dsl_fcos_desc with DSL_HEAD_ATSS | DSL_HEAD_PAA | DSL_HEAD_LOSS_EXT in head_flags.  PAAHead is an ATSSHead: the
+ * anchors, the valid flags, the delta2bbox decode and the gradient layout are DSL_HEAD_ATSS's; fcos.atss supplies anchor_scale,
+ * delta_stds, pad_shapes, npos, max_gt and topk - here PAA's per-level top-k, 1..16.  The centerness column of regctr / g_rc carries the
+ * IoU-prediction logit and its gradient.  Order of a step: dsl_paa_assign (reads no prediction), the predictors, dsl_paa_pos_loss,
+ * dsl_paa_reassign, dsl_paa_loss; DSL_OP_PAA_REFINE is the middle pair.  No call synchronises with the host or allocates.
+ *
+ * dsl_paa_assign = MaxIoUAssigner(pos_iou_thr = neg_iou_thr, min_pos_iou = 0, ignore_iof_thr = -1, gt_max_assign_all) on the valid
+ * anchors, IoU as BboxOverlaps2D (union clamped at 1e-6): an anchor is a candidate of its argmax box if that IoU >= pos_iou_thr, equal
+ * maxima go to the lower box index.  Then the low-quality pass: for every box i in ascending order, every valid anchor whose IoU with
+ * i equals i's maximum over the image's valid anchors is given to i - even at IoU 0, even if a better box had it; a later box
+ * overwrites an earlier one (max_iou_assigner.py:190-198).  Both sides of that comparison are the same fp32 expression, so equal IoUs
+ * are equal bits.  Outputs: cand_gt (= assign_idx), labels (the box's label, or num_classes), bbox_targets (the box in pixels, zeros
+ * elsewhere), cls_weight (1 valid, 0 invalid anchor), pos_weight 1; stats and npos are cleared.  ig_boxes are not read.  No atomics:
+ * a second run is bit-identical.
+ *
+ * dsl_paa_pos_loss (behind the predictors): for every candidate pos_loss[m] = w_cls * sum_c focal(m, c) + w_bbox * box_loss(decode(m),
+ * target) with the head's focal gamma / alpha and box_kind - the reference's reduction_override='none', where avg_factor is not
+ * applied (paa_head.py:201-255) - and 0 elsewhere.  It also leaves the aligned IoU of the same two boxes (union clamped at 1e-6) in
+ * iou_target[m] for every candidate, 0 elsewhere.
+ * dsl_paa_pos_loss and dsl_paa_reassign are an ORDERED PAIR: dsl_paa_reassign keeps iou_target where an anchor stays positive and
+ * clears it where it does not, and neither it nor dsl_paa_assign restores a cleared value.  So dsl_paa_reassign is right only
+ * directly behind a dsl_paa_pos_loss of the same assignment and head outputs (pos_loss itself may be rewritten in between);
+ * DSL_OP_PAA_REFINE is that pair.  Run again without dsl_paa_pos_loss on unchanged inputs it repeats its result bit for bit.
+ *
+ * dsl_paa_reassign, one workgroup per ground-truth box (max_gt launched): per level the min(topk, count) candidates of the box with
+ * the smallest pos_loss, concatenated in level order and sorted ascending.  TIE RULE in both places: equal losses go to the lower
+ * location index (torch.topk / sort leave it unspecified).  Fewer than two samples: the box keeps none (gmm_flags 1).  Else
+ * GaussianMixture(2, covariance_type='diag', weights (0.5, 0.5), means (min, max), precisions (1, 1), tol 1e-3, reg_covar 1e-6,
+ * max_iter 100) is fitted by the workgroup's first wavefront (at most 80 samples, two per lane, fixed-order butterfly sums): the lower
+ * bound is the mean of the E-step's log-normaliser, starting from -inf, the loop stops when |change| < tol, the parameters are those
+ * of the last M-step: nk = sum resp + 10 eps(fp64), mean = resp . x / nk, variance = resp . (x * x) / nk - mean^2 + reg_covar, weights
+ * nk / sum nk.  The arithmetic is fp64 on the fp32 losses.  What sklearn 1.7.2 does with float32 input was read from its source and
+ * confirmed on the fixtures (scores within 3e-10 of sklearn's on every fitted box): the samples stay float32, so x * x (M-step),
+ * x**2 (E-step) and the initial means**2 are float32 products widened afterwards, log(2 pi) is rounded to float32, everything else is
+ * float64.  predict = argmax of the weighted log-probabilities (component 0 = the low-loss one, ties to 0), score_samples = their
+ * logsumexp.  With fgs = the samples of component 0, the positives are the first j + 1 of them in sorted order, j the position within
+ * fgs of the highest score (equal scores: the first; paa_head.py:392-399).  Nothing is ignored.
+ * DEVIATION: where a variance comes out <= 0 sklearn raises ("ill-defined empirical covariance") and the reference's training step
+ * dies; here the box keeps no positive, gmm_flags = 2, and the step goes on.
+ * Every candidate that is not kept gets label = num_classes, assign_idx = -1, pos_weight = 0, iou_target = 0; cls_weight stays 1.  The
+ * kept ones keep dsl_paa_pos_loss's iou_target, a constant for the gradient.  gmm_iters[g] = EM iterations (sklearn's n_iter_; 0 = not
+ * fitted), gmm_flags[g] = 0 fitted | 1 fewer than two candidates | 2 ill-defined covariance.  npos[i] = positives of image i,
+ * stats[0] = sum_i npos_i (not clamped per image), stats[1] = sum_m iou_target[m], from the boxes' records added in box order.
+ *
+ * dsl_paa_loss = the DSL_HEAD_ATSS loss kernel behind the flag (forward and backward in one launch, paa_head.py:169-199):
+ *   losses[0] = w_cls / max(norm[0], n) * sum focal          losses[2] = w_ctr / norm[0] * sum_pos BCE(iou logit, iou_target)
+ *   losses[1] = w_bbox / norm[1] * sum_pos max(iou_target, 1e-12) * box_loss
+ * both box terms and their gradients are 0 without a positive.  norm is this rank's own stats: the reference does not reduce_mean
+ * here, so the host passes inv_world = 1 and exchanges nothing.  norm[1] == 0 with positives present (every IoU exactly 0) is the
+ * reference's own division by zero; the kernel divides by 1 instead.  logvec = [cls, bbox, iou, sum]; the gradient buffers use the
+ * ATSS layout, the IoU logit's gradient where the centerness gradient goes.
+ * Refused, with dsl_last_error naming the field: head_flags other than the three above (or with DSL_HEAD_GFL / DSL_HEAD_LD),
+ * atss.topk, atss.max_gt, atss.pad_shapes, atss.npos, pos_iou_thr outside (0, 1), a null pos_loss / iou_target / cand_gt / gmm_iters /
+ * gmm_flags, a workspace below dsl_fcos_workspace_bytes(&q->fcos), and what DSL_HEAD_ATSS refuses.
+ * ---------------------------------------------------------------------------------------- */
+#define DSL_HEAD_PAA 256        /* PAAHead: dsl_fcos_desc inside a dsl_paa_desc; dsl_det_desc inside a dsl_det_paa_desc */
+typedef struct dsl_paa_desc {
+  dsl_fcos_desc fcos;
+  float pos_iou_thr;                   /* MaxIoUAssigner pos_iou_thr == neg_iou_thr, in (0, 1) (0.1) */
+  float* pos_loss;                     /* [M] out of dsl_paa_pos_loss, in of dsl_paa_reassign */
+  float* iou_target;                   /* [M] out of dsl_paa_pos_loss / dsl_paa_reassign, in of dsl_paa_loss */
+  int32_t* cand_gt;                    /* [M] the first assignment's box index within the image, -1 if none */
+  int32_t* gmm_iters;                  /* [max_gt] EM iterations per box, 0 if not fitted */
+  int32_t* gmm_flags;                  /* [max_gt] 0 fitted, 1 fewer than two candidates, 2 ill-defined covariance */
+} dsl_paa_desc;
+int dsl_paa_assign(const dsl_paa_desc* q, void* stream);
+int dsl_paa_pos_loss(const dsl_paa_desc* q, void* stream);
+int dsl_paa_reassign(const dsl_paa_desc* q, void* stream);
+int dsl_paa_loss(const dsl_paa_desc* q, void* stream);
+
 /* One dispatch for every head, on head_flags.  The contract the flags state: with DSL_HEAD_GFL `d` is the first member of a
  * dsl_gfl_desc, with DSL_HEAD_LD of a dsl_ld_desc (whose first member is that dsl_gfl_desc), so the three share one address.
- * dsl_head_assign: DSL_HEAD_ATSS -> dsl_atss_assign(d, d->atss), else dsl_fcos_assign.
- * dsl_head_loss: DSL_HEAD_LD -> dsl_ld_loss (which refuses the flag without DSL_HEAD_GFL), else DSL_HEAD_GFL -> dsl_gfl_loss, else
- * dsl_fcos_loss.  DSL_OP_ASSIGN / DSL_OP_LOSS of an op list are these two calls on the op's desc. */
+ * With DSL_HEAD_PAA `d` is the first member of a dsl_paa_desc.
+ * dsl_head_assign: DSL_HEAD_PAA -> dsl_paa_assign, else DSL_HEAD_ATSS -> dsl_atss_assign(d, d->atss), else dsl_fcos_assign.
+ * dsl_head_loss: DSL_HEAD_PAA -> dsl_paa_loss, else DSL_HEAD_LD -> dsl_ld_loss (which refuses the flag without DSL_HEAD_GFL), else
+ * DSL_HEAD_GFL -> dsl_gfl_loss, else dsl_fcos_loss.  DSL_OP_ASSIGN / DSL_OP_LOSS of an op list are these two calls on the op's desc. */
 int dsl_head_assign(const dsl_fcos_desc* d, void* stream);
 int dsl_head_loss(const dsl_fcos_desc* d, void* stream);
 
@@ -791,6 +868,21 @@ typedef struct dsl_det_gfl_desc {
   dsl_det_desc det;
   int32_t reg_max;                           /* 1..16 */
 } dsl_det_gfl_desc;
+/* A PAA head's detection descriptor (DSL_HEAD_ATSS | DSL_HEAD_PAA in det.head_flags; PAAHead._get_bboxes and score_voting,
+ * mmdet/models/dense_heads/paa_head.py:519-673): ATSS's decode.  The pair score is sqrt(sigmoid(cls) * sigmoid(iou)), the IoU logit
+ * where ATSS has its centerness logit: nms_pre ranks by its per-location maximum, score_thr applies to it, and it is the final score -
+ * there is no centerness factor.  With score_voting one more launch runs behind the (hard) NMS, one wavefront per kept detection:
+ * over the image's pre-NMS pairs of the same class with score > score_thr and IoU > 0.01 with the kept box (bbox_overlaps, union
+ * clamped at 1e-6), p = exp(-(1 - iou)^2 / 0.025) * score; the box becomes sum p * box / sum p (fp64 sums of a fixed order), the score
+ * stays; the output is ordered class ascending, then by the NMS's order (det_count is the NMS's).  Boxes are in the frame the
+ * reference votes in: divided by scale_factors when those are given (rescale).  The voting pool is the set of pairs dsl_fcos_detect
+ * keeps for the NMS - its best 16 384 per image: the existing deviation of this library, carried over.  Test-time augmentation is
+ * refused for this head, as in the reference (paa_head.py:536-538: with_nms=False is not supported): dsl_fcos_detect_collect refuses
+ * the flag.  score_voting with a Soft-NMS method is refused. */
+typedef struct dsl_det_paa_desc {
+  dsl_det_atss_desc atss;
+  int32_t score_voting;                      /* 0 = the NMS output as it is */
+} dsl_det_paa_desc;
 /* dsl_det_desc.nms_method.  Soft-NMS is mmcv's batched_nms with nms=dict(type='soft_nms', method=...) (stated by
  * mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127), per image and class over the candidates the hard NMS would get: pick the highest current score
  * (equal scores: the candidate that comes first in (level, slot, class) order - with views, (view, level, slot, class)), emit it
@@ -933,6 +1025,7 @@ enum { DSL_OP_CONV = 1, DSL_OP_WGRAD = 2, DSL_OP_GN_FWD = 3, DSL_OP_GN_BWD = 4, 
        DSL_OP_SUM2X2 = 6, DSL_OP_COLSUM = 7, DSL_OP_MEMSET = 8, DSL_OP_PACK_IMAGE = 9,
        DSL_OP_ASSIGN = 10, DSL_OP_LOSS = 11,   /* desc = dsl_fcos_desc -> dsl_head_assign, dsl_head_loss.  MAXPOOL: i[4] = output row stride (0 = c) */
        DSL_OP_GFL_QUALITY = 29,  /* desc = dsl_gfl_desc -> dsl_gfl_quality */
+       DSL_OP_PAA_REFINE = 30,   /* desc = dsl_paa_desc -> dsl_paa_pos_loss, then dsl_paa_reassign */
        DSL_OP_FORK = 12,   /* side stream i[0] (default 1) waits for everything queued so far on stream i[1] (default 0 = caller's) */
        DSL_OP_JOIN = 13,   /* stream i[1] (default 0 = caller's) waits for everything queued so far on side stream i[0] (default 1) */
        DSL_OP_WGRAD_GROUP = 14,  /* desc = dsl_wgrad_desc[i[0]] -> dsl_conv2d_wgrad_group */
