@@ -98,7 +98,8 @@ def _logsumexp2(a, b):
 def gmm_fit(x32):
     """GaussianMixture(2, 'diag', weights (0.5, 0.5), means (min, max), precisions (1, 1)).fit on the float32 column x32, restated in
     float64: the samples stay float32 (x * x and the first iteration's mean^2 are float32 products), log(2 pi) is rounded to float32.
-    Returns dict(flag 0 fitted | 2 non-positive variance, n_iter, pred, scores, stop / pred / gap margins)."""
+    Returns dict(flag 0 fitted | 2 non-positive variance, n_iter, pred, scores, stop / pred / gap margins, var_margin = the smallest
+    |variance| of any iteration: how far every variance stayed from the sign test)."""
     x32 = np.asarray(x32, np.float32)
     x, xx = x32.astype(np.float64), (x32 * x32).astype(np.float64)
     n = len(x)
@@ -112,7 +113,7 @@ def gmm_fit(x32):
         lp = mu2[None] * prec[None] - 2.0 * (x[:, None] * (mu * prec)[None]) + xx[:, None] * prec[None]
         return -0.5 * (LOG_2PI_F32 + lp) + np.log(pc)[None] + np.log(w)[None]
 
-    lower, stop_margin, it = -np.inf, np.inf, 0
+    lower, stop_margin, var_margin, it = -np.inf, np.inf, np.inf, 0
     for it in range(1, MAX_ITER + 1):
         prev = lower
         a = wlp(mu, mu2, pc, w)
@@ -123,8 +124,9 @@ def gmm_fit(x32):
         mu2 = mu ** 2
         var = (resp * xx[:, None]).sum(0) / nk - mu2 + REG_COVAR
         w = nk / nk.sum()
+        var_margin = min(var_margin, float(np.abs(var).min()))
         if np.any(var <= 0.0):
-            return dict(flag=2, n_iter=it)
+            return dict(flag=2, n_iter=it, stop_margin=float(stop_margin), var_margin=var_margin)
         pc = 1.0 / np.sqrt(var)
         lower = norm.mean()
         change = lower - prev
@@ -136,7 +138,7 @@ def gmm_fit(x32):
     scores = _logsumexp2(a[:, 0], a[:, 1])
     fg = scores[pred == 0]
     srt = np.sort(fg)[::-1]
-    return dict(flag=0, n_iter=it, pred=pred, scores=scores, stop_margin=float(stop_margin),
+    return dict(flag=0, n_iter=it, pred=pred, scores=scores, stop_margin=float(stop_margin), var_margin=var_margin,
                 pred_margin=float(np.abs(a[:, 0] - a[:, 1]).min()), gap=float(srt[0] - srt[1]) if len(srt) > 1 else np.inf)
 
 

@@ -23,9 +23,9 @@ def options(c, **kw):
                        bbox_weight=c['bbox_weight'], **kw)
 
 
-def assigned_plan(c):
+def assigned_plan(c, max_gt=64):
     from dsl_amd.head_loss import FcosLossPlan
-    plan = FcosLossPlan(c['B'], c['sizes'], 'cuda', num_classes=c['C'], head=options(c), max_gt=64)
+    plan = FcosLossPlan(c['B'], c['sizes'], 'cuda', num_classes=c['C'], head=options(c), max_gt=max_gt)
     plan.set_targets(c['gts'], c['gls'], None, c['pads'])
     plan.assign()
     return plan
@@ -86,6 +86,7 @@ def check_loss(c, cls, raw, ctr, scales):
     C = c['C']
     mine_c, mine_r = plan.g_cls.float().cpu(), plan.g_rc.float().cpu()
     for mine, ref in ((mine_c[:, :C], x.grad.float()), (mine_r[:, :4], r.grad.float()), (mine_r[:, 4], t.grad.float())):
+        print('max |grad err|', float((mine - ref).abs().max()), 'of', float(ref.abs().max()))
         assert torch.allclose(mine, ref, rtol=tol, atol=tol * float(ref.abs().max()) * 0.05 + 1e-9)
     assert float(mine_c[:, C:].abs().max()) == 0.0 and float(mine_r[:, 5:].abs().max()) == 0.0          # padding columns
     sgrad = s.grad.float() if s.grad is not None else torch.zeros(5)          # (no positive: the scales are not in the graph)
