@@ -8,8 +8,8 @@ What the lists compute is the reference's
       -> FCOSHead.forward (dense_heads/fcos_head.py:118-168) -> FCOSHead.loss (:170-338)
 and its autograd backward, written out by hand (no autograd graph exists here).
 """
+import collections
 import ctypes as C
-import os
 
 import torch
 
@@ -20,8 +20,18 @@ from .params import STAGE_BLOCKS, STAGE_PLANES
 from .tuning import skip_items, tune, tune_int
 
 DEFER_SLOTS = 144      # workgroup budget of the towers' weight-gradient group when the head update is deferred (FlatSGD(defer_head_update=True))
+# tuning knobs (both measured: on is better): group the last segment's weight gradients too, although nothing
+# is left on the caller's stream to overlap their tail with ...
+GROUP_LAST = True
+GROUP = True       # same-geometry weight gradients (tower layers, the blocks of a stage) as one launch
+# where in the backward pass the next step's frozen prefix (FCOS.pipeline_prefix) may start: 0 = with the pass, 3 / 2 / 1 = behind
+# layer4's / layer3's / layer2's data gradients (1 = the whole chain, the round-2 setting)
+PREFIX_LI = 2       # measured (tools/exp_env.sh): 1: 355.5, 3: 360, 2 / 0: +0.2 % over 3
 
 BF = torch.bfloat16
+
+# one ResNet bottleneck of the forward list, as its backward reads it (Plan.stage_blocks[stage])
+Block = collections.namedtuple('Block', 'prefix xin a1 a2 out in_hw out_hw stride b planes')
 
 
 class OpList:
@@ -216,8 +226,18 @@ class Plan:
         # split-K scratch shared by all convs of the plan (they run back to back on one stream); the library
         # lowers its split factor if a conv would need more than this
         self.conv_ws = torch.empty(128 << 20, dtype=torch.uint8, device=dev)
+        # ... and of the convs that run beside them on side stream 3 / side stream 2 (_on_stream_ws)
+        self.conv_ws_br = torch.empty(32 << 20, dtype=torch.uint8, device=dev)
+        self.conv_ws_side = torch.empty(32 << 20, dtype=torch.uint8, device=dev)
         self._gn_ws = {}          # GroupNorm block-record workspaces, one per stream that runs GroupNorm launches
-        self._build_forward()
+        self._l1_tracked = []     # (descriptor, field, byte offset): see _tracks_l1
+        side = tune('side') != '0' and not single_stream
+        # independent branches of the forward graph (a stage's downsample conv next to conv1 -> conv2; P5 -> P6 -> P7 next to
+        # the P4 / P3 path) run on side stream 3: their kernels are too small to fill the chip alone
+        self.BR = 3 if side else 0
+        self._fside = 2 if side else 0      # the regression tower's stream: side stream 1 carries the weight gradients (and may be CU-masked)
+        self._fwd_backbone()
+        self._fwd_head(self._fwd_fpn())
         self.prefix = None
         if training and store.backbone != 'rla' and tune('pipe_prefix') != '0' and tune('side') != '0':
             self._split_prefix()
@@ -242,7 +262,22 @@ class Plan:
                 self.quality_ops, self.loss_ops = self.loss_ops, OpList()
                 self.quality_ops.paa_refine(self.lossplan.paa)
             self.loss_ops.loss(self.lossplan.desc)
-            self._build_backward()
+            # Backward op lists.  The data-gradient chain runs on the caller's stream; every weight gradient is
+            # forked onto the library's side stream (its inputs - the forward activation and a gradient buffer that is
+            # written exactly once per step - are complete at the fork point), so the many small, under-filled
+            # backbone launches of the chain overlap with weight-gradient work.  Each segment ends with a JOIN.
+            self._side = tune('side') != '0'
+            # all weight gradients of a segment that share a tile configuration go out as one multi launch (_flush_wgrads)
+            self._multi_on = self._side
+            buckets = store.grad_buckets()
+            self._bwd_fpn(*self._bwd_head(), buckets)
+            if store.backbone == 'rla':
+                from . import engine_rla
+                # (the recurrent path's BatchNorm post-pass runs on the weight-gradient stream behind the stage's flush)
+                engine_rla.build_backward(self, buckets, self._side)
+            else:
+                for li in (3, 2, 1):        # ================= backbone: layer4, layer3, layer2 =================
+                    self._bwd_stage(li, buckets)
 
     # ---------------------------------------------------------------------------------------------
     def buf(self, name, *shape, dtype=BF, zero=False):
@@ -269,9 +304,34 @@ class Plan:
                              flags=f, scale=scale, bias=bias, addend=addend, lda=lda or spec.cout, add_hw=add_hw,
                              workspace=None if small_c else self.conv_ws, lds=lds)
 
-    def _build_forward(self):
+    def _on_stream_ws(self, desc, stream):
+        """A conv that runs on side stream 3 / 2 beside the caller's convs: that stream's own split-K scratch (stream 0, also
+        a side stream that is switched off: the descriptor as it is)."""
+        ws = {3: self.conv_ws_br, 2: self.conv_ws_side}.get(stream)
+        if ws is not None:
+            desc.workspace, desc.workspace_bytes = L.ptr(ws), ws.numel()
+        return desc
+
+    def _conv_on(self, ol, stream, desc):
+        """Queues conv `desc` on `stream` of list ol, with that stream's scratch."""
+        ol.conv(self._on_stream_ws(desc, stream), side=stream)
+        return desc
+
+    def _groups(self, split, side):
+        """Image groups (first image, end, stream) of a stage's chains: images [0, ceil(N/2)) on the caller's stream and the rest
+        on `side`, or the whole batch as one chain."""
+        half = (self.N + 1) // 2
+        return [(0, half, 0), (half, self.N, side)] if split else [(0, self.N, 0)]
+
+    def _tracks_l1(self, desc, field):
+        """desc.field points into layer1's output.  With the pipelined prefix that tensor has two buffers, alternating per step
+        (_split_prefix): set_parity re-points every descriptor registered here, a reader it does not know keeps the other step's
+        buffer - a race with that step's weight gradients, not a crash."""
+        self._l1_tracked.append((desc, field, getattr(desc, field) - self._l1_buf.data_ptr()))
+
+    def _fwd_backbone(self):
+        """Stem + backbone: fills stage_out / stage_ld."""
         st, N, H, W, f = self.store, self.N, self.H, self.W, self.fwd
-        cv = st.convs
         h1, w1 = conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3)
         h, w = conv_out(h1, 3, 2, 1), conv_out(w1, 3, 2, 1)
         # The frozen stem: image layout + conv1 + BN + ReLU + max pool as ONE kernel (dsl_stem_pool, csrc/stem.hip)
@@ -279,14 +339,10 @@ class Plan:
 
         def emit_pool(out, ld):
             """The pooled stem output into rows of `ld` elements."""
-            sc, bi = st.bn_ptrs(cv['backbone.conv1'].bn)
+            sc, bi = st.bn_ptrs(st.convs['backbone.conv1'].bn)
             self._img_op = len(f.items)         # bind_image() points this op at the caller's tensor
             f.stem_pool(self.img, st.stem_groups16, sc, bi, out, ld, N, H, W)
         self.stage_out, self.stage_ld = [], []      # per stage: (tensor / pointer of the output's first channel, (h, w)), row stride
-        # independent branches of the forward graph (a stage's downsample conv next to conv1 -> conv2; P5 -> P6 -> P7 next to
-        # the P4 / P3 path) run on side stream 3: their kernels are too small to fill the chip alone
-        self.BR = 3 if (tune('side') != '0' and not self.single_stream) else 0
-        self.conv_ws_br = torch.empty(32 << 20, dtype=torch.uint8, device=self.dev)
         if st.backbone == 'rla':
             from . import engine_rla
             engine_rla.build_forward(self, emit_pool, h1, w1)
@@ -294,7 +350,105 @@ class Plan:
             x = self.buf('pool', N, h, w, 64)
             emit_pool(x, 64)
             self._fwd_resnet(x, h, w)
-        # ---- FPN (start_level=1) ----
+
+    def _fwd_resnet(self, x, h, w):
+        N, f = self.N, self.fwd
+        self.stage_blocks = []        # per stage: its Blocks
+        # Image-split stages (tuning key img_split; measured in round 3's first half: none 372.6, 3: 384.0, 34: 383.4, 4: 372.1, 23: -0.5 % vs 3; re-measured on
+        # the final kernels, two boxes, both orders (profiles/r03_step_boundary.txt): 3: 416.8 / 432.1, 34: 420.3 / 435.1, 23: 420.0, 24: 420.9 (second
+        # box), 234: 420.9 / 436.2 img/s -> default layer2 + layer3 + layer4, + 1 %;
+        # profiles/r03b_* are the profiles of this setting, r03_* those of the layer3 split, DESIGN 3.2e / 5): their launches are 66-132 workgroups of 15-40 us - mostly
+        # fill, epilogue and kernel boundary on half a chip.  The images of a batch are independent through the backbone, so the
+        # batch goes through these stages as TWO chains (images [0, ceil(N/2)) on the caller's stream, the rest on stream 3) of
+        # half-size launches: one chain's fixed per-launch costs hide under the other chain's kernels.
+        SPLIT = tune('img_split') if (self.BR and N >= 2 and self.training) else ''
+        split_open = False
+        for li, (planes, nb) in enumerate(zip(STAGE_PLANES, STAGE_BLOCKS)):
+            # Fused stages (tuning key bneck_fwd, default layer2; '23' adds layer3): every bottleneck's forward pass is ONE launch over the whole
+            # batch (dsl_bottleneck_fwd, csrc/bneck.hip) - the image-split chains of three launches per block and half are its predecessor
+            fuse = str(li + 1) in tune('bneck_fwd') and planes in (128, 256)
+            split = str(li + 1) in SPLIT and not fuse
+            f.tag = f'fwd.l{li + 1}'
+            if li >= 1 and self.training:
+                # late exchange: this stage's gradient bucket (layer2: 3, layer3: 2, layer4: 1) of the last optimizer step may still be
+                # exchanged / updated beside the stages in front of it; both image chains wait (no-ops until the slot is recorded)
+                f.wait(L.SLOT_UPD + 4 - li, stream=0)
+                if split_open:
+                    f.wait(L.SLOT_UPD + 4 - li, stream=self.BR)
+            if split and not split_open:
+                f.fork(self.BR)
+                split_open = True
+            elif split_open and not split:
+                f.join(self.BR)
+                split_open = False
+            self.stage_blocks.append([])
+            groups = self._groups(split, self.BR)
+            for b in range(nb):
+                blk = self._fwd_block(li, b, x, h, w, planes, groups, fuse)
+                self.stage_blocks[li].append(blk)
+                x, (h, w) = blk.out, blk.out_hw
+            self.stage_out.append((x, (h, w)))
+            self.stage_ld.append(planes * 4)
+            if li == 0:
+                self._prefix_end = len(f.items)        # pack + stem + pool + layer1: frozen weights, a function of the image alone
+        if split_open:
+            f.join(self.BR)
+
+    def _fwd_block(self, li, b, x, h, w, planes, groups, fuse):
+        """One bottleneck of the forward list, chain by chain over `groups`: conv1 -> conv2 -> conv3 (+ identity) as three launches,
+        or - fuse, the whole batch, where the kernel takes the shape - as ONE launch (dsl_bottleneck_fwd).  A stage's first block
+        has the downsample conv as its identity: in front of conv1 in the chain's order, but for the three launches over the
+        whole batch on side stream 3 beside conv1 -> conv2 (it only meets the main branch at conv3's residual add)."""
+        st, f = self.store, self.fwd
+        cv = st.convs
+        p = f'backbone.layer{li + 1}.{b}'
+        c1, c2, c3 = cv[p + '.conv1'], cv[p + '.conv2'], cv[p + '.conv3']
+        s = c1.stride
+        oh, ow = conv_out(h, 1, s, 0), conv_out(w, 1, s, 0)
+        a1 = self.buf(p + '.a1', self.N, oh, ow, planes)
+        a2 = self.buf(p + '.a2', self.N, oh, ow, planes)
+        l1_out = li == 0 and b == STAGE_BLOCKS[0] - 1        # writes / reads layer1's output
+        l1_in = li == 1 and b == 0
+        out = self.buf(p + '.out', self.N, oh, ow, planes * 4)
+        if l1_out:
+            self._l1_buf = out
+        idt = self.buf(p + '.idt', self.N, oh, ow, planes * 4) if b == 0 else x
+        bd = None
+        if fuse:
+            bd = ops.bneck_desc(x, st.w16_ptr(c1), st.w16_ptr(c2), st.w16_ptr(c3), idt, st.bn_ptrs(c1.bn), st.bn_ptrs(c2.bn),
+                                st.bn_ptrs(c3.bn), a1, a2, out, n=self.N, hin=h, win=w, h=oh, w=ow, planes=planes, cin=c1.cin_store,
+                                ldx=int(x.shape[-1]), stride=s)
+            if not L.lib.dsl_bottleneck_fwd_supported(C.byref(bd)):
+                bd = None
+        ds_br = self.BR if (b == 0 and bd is None and len(groups) == 1) else 0
+        for g0, g1, sd in groups:
+            n_ = g1 - g0
+            if b == 0:          # (fused: the downsample branch beside nothing - it IS the block's identity, in front of the launch)
+                if ds_br:
+                    f.fork(ds_br)
+                dd = self._conv_on(f, ds_br or sd, self._conv(cv[p + '.downsample.0'], x[g0:g1], idt[g0:g1], n_, [(h, w)], [(oh, ow)]))
+                if l1_in:
+                    self._tracks_l1(dd, 'src')
+            if bd is not None:
+                f.bneck(bd)
+                if l1_in:
+                    self._tracks_l1(bd, 'x')
+                continue
+            d1 = self._conv_on(f, sd, self._conv(c1, x[g0:g1], a1[g0:g1], n_, [(h, w)], [(oh, ow)], relu=True))
+            if l1_in:
+                self._tracks_l1(d1, 'src')
+            self._conv_on(f, sd, self._conv(c2, a1[g0:g1], a2[g0:g1], n_, [(oh, ow)], [(oh, ow)], relu=True))
+            if ds_br:
+                f.join(ds_br)
+            d3 = self._conv_on(f, sd, self._conv(c3, a2[g0:g1], out[g0:g1], n_, [(oh, ow)], [(oh, ow)], relu=True, addend=idt[g0:g1]))
+            if l1_out:
+                self._tracks_l1(d3, 'dst')
+        return Block(p, x, a1, a2, out, (h, w), (oh, ow), s, b, planes)
+
+    def _fwd_fpn(self):
+        """FPN (start_level=1) on stage_out[1:]: fills level_sizes / seg_off / feat_seg, returns the five levels' rows."""
+        st, N, f = self.store, self.N, self.fwd
+        cv = st.convs
         f.tag = 'fwd.fpn'
         (c3, hw3), (c4, hw4), (c5, hw5) = self.stage_out[1], self.stage_out[2], self.stage_out[3]
         hw6 = (conv_out(hw5[0], 3, 2, 1), conv_out(hw5[1], 3, 2, 1))
@@ -308,12 +462,7 @@ class Plan:
         lat = [self.buf(f'lat{i}', N, hw[0], hw[1], 256) for i, hw in enumerate((hw3, hw4, hw5))]
         lc = [cv[f'neck.lateral_convs.{i}.conv'] for i in range(3)]
         ld3, ld4, ld5 = self.stage_ld[1:4]       # RLA keeps a stage output as the x part of the next [C + 128]-wide block input
-        BR = self.BR if st.backbone != 'rla' else 0
-
-        def br(cd_):        # a conv of the side branch: its own split-K scratch
-            if BR:
-                cd_.workspace, cd_.workspace_bytes = L.ptr(self.conv_ws_br), self.conv_ws_br.numel()
-            return cd_
+        BR = self.BR if st.backbone != 'rla' else 0       # the side branch: its convs take that stream's split-K scratch
         feats = self.buf('feats', self.M, 256)
         self.feat_seg = [feats.data_ptr() + self.seg_off[i] * 256 * 2 for i in range(5)]
         # late exchange (data parallel): bucket 0 (head + FPN) of the last optimizer step may still be on its way - its
@@ -333,26 +482,65 @@ class Plan:
         if BR:
             f.fork(BR)
         # P5 -> P6 -> P7: five tiny launches, beside the P4 / P3 path
-        f.conv(br(self._conv(fc[2], lat[2], self.feat_seg[2], N, [hw5], [hw5])), side=BR)
-        f.conv(br(self._conv(fc[3], self.feat_seg[2], self.feat_seg[3], N, [hw5], [hw6])), side=BR)      # P6 (no relu)
+        self._conv_on(f, BR, self._conv(fc[2], lat[2], self.feat_seg[2], N, [hw5], [hw5]))
+        self._conv_on(f, BR, self._conv(fc[3], self.feat_seg[2], self.feat_seg[3], N, [hw5], [hw6]))      # P6 (no relu)
         if self.p6_relu:
-            f.conv(br(self._conv(fc[3], self.feat_seg[2], p6r, N, [hw5], [hw6], relu=True)), side=BR)    # relu(P6)
-        f.conv(br(self._conv(fc[4], p6r, self.feat_seg[4], N, [hw6], [hw7])), side=BR)                   # P7
+            self._conv_on(f, BR, self._conv(fc[3], self.feat_seg[2], p6r, N, [hw5], [hw6], relu=True))    # relu(P6)
+        self._conv_on(f, BR, self._conv(fc[4], p6r, self.feat_seg[4], N, [hw6], [hw7]))                   # P7
         f.conv(self._conv(lc[1], c4, lat[1], N, [hw4], [hw4], addend=lat[2], add_hw=[hw5], lds=ld4))
         if BR:
             f.fork(BR)          # P4's output conv joins the side chain once its lateral exists: the caller's stream keeps C3 -> P3
-        f.conv(br(self._conv(fc[1], lat[1], self.feat_seg[1], N, [hw4], [hw4])), side=BR)
+        self._conv_on(f, BR, self._conv(fc[1], lat[1], self.feat_seg[1], N, [hw4], [hw4]))
         f.conv(self._conv(lc[0], c3, lat[0], N, [hw3], [hw3], addend=lat[1], add_hw=[hw4], lds=ld3))
         f.conv(self._conv(fc[0], lat[0], self.feat_seg[0], N, [hw3], [hw3]))
         if BR:
             f.join(BR)
-        # ---- head: shared weights, all 5 levels per launch ----
+        return feats
+
+    def _fp8_towers(self, feats, margin):
+        """fp8 forward of the tower convolutions (FCOS(fp8=dict(...)), BASELINE.json configs[4], off by default), DELAYED scaling
+        (round 6): every fp8 tensor is written by its producer's own pass - GroupNorm's apply pass writes the e4m3 copy of its output
+        next to the bf16 one, with the scale of the PREVIOUS step's maximum, and leaves this step's block maxima; one dsl_fp8_prep
+        launch per step quantises the eight weight tensors (per-output-channel scales, from the fp32 master weights) and turns the
+        recorded maxima into this step's input scales and epilogue scales.  The bf16 tensors stay what the backward pass reads
+        (straight-through).  A plan's first forward pass runs twice more in front (Plan.fp8_warm): nothing is recorded yet.
+        margin: headroom over the previous step's maximum (e4m3 saturates at 448).  Returns the e4m3 copy of `feats` and the
+        per-layer tensors {(tower, i): dict(w8, comb, am_out, scale_in)}."""
+        st, N, f, ls = self.store, self.N, self.fwd, self.level_sizes
+        nblk = (max(h_ * w_ for h_, w_ in ls) + 127) // 128
+        feats8 = self.buf('feats.f8', self.M, 256, dtype=torch.uint8)
+        am_feats = self.buf('feats.f8.amax', 512, dtype=torch.float32, zero=True)
+        scales = self.buf('fp8.scales', 8, dtype=torch.float32, zero=True)
+        items = (L.Fp8PrepItem * 8)()
+        f8lay = {}
+        for t_, tower in enumerate(('cls_convs', 'reg_convs')):
+            for i in range(4):
+                spec = st.convs[f'bbox_head.{tower}.{i}.conv']
+                assert spec.cout_pad == 256 and spec.cin == 256 and spec.k == 3, 'the fp8 slice is the 3x3 256 -> 256 tower layers'
+                w8 = self.buf(f'{tower}.{i}.w8', spec.cout_pad, 9 * 256, dtype=torch.uint8)
+                comb = self.buf(f'{tower}.{i}.comb', spec.cout_pad, dtype=torch.float32)
+                am_out = self.buf(f'{tower}.{i}.act8.amax', 5 * N * nblk, dtype=torch.float32, zero=True) if i < 3 else None
+                am_in = am_feats if i == 0 else f8lay[tower, i - 1]['am_out']
+                it = items[t_ * 4 + i]
+                it.w, it.w8, it.comb = st.t32_ptr(spec.name + '.weight'), w8.data_ptr(), comb.data_ptr()
+                it.amax, it.n_amax, it.cout = am_in.data_ptr(), am_in.numel(), spec.cout
+                it.scale = scales.data_ptr() + 4 * (t_ * 4 + i)
+                f8lay[tower, i] = dict(w8=w8, comb=comb, am_out=am_out, scale_in=it.scale)
+        items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.dev)
+        self.bufs['fp8.items'] = items_dev
+        f.fp8_prep(items_dev, 8, 256, 9 * 256, margin)
+        # the FPN outputs feed both towers: one pass writes their e4m3 copy (both first layers' scales are the same number)
+        f.quant_fp8_delayed(feats, feats8, self.M, 256, 256, f8lay['cls_convs', 0]['scale_in'], am_feats)
+        return feats8, f8lay
+
+    def _fwd_head(self, feats):
+        """Head: shared weights, all 5 levels per launch."""
+        st, N, f, ls = self.store, self.N, self.fwd, self.level_sizes
+        cv = st.convs
         f.tag = 'fwd.head'
-        ls = self.level_sizes
         self.tower = {}
         # the two towers are independent chains: the regression tower (+ its predictor) runs on the side stream
-        self.conv_ws_side = torch.empty(32 << 20, dtype=torch.uint8, device=self.dev)
-        FSIDE = 2 if (tune('side') != '0' and not self.single_stream) else 0      # side stream 1 carries the weight gradients (and may be CU-masked)
+        FSIDE = self._fside
         # phase marks for bench.py: 8 tower convs + 2 predictors over all M locations, 8 GroupNorm+ReLU passes
         # (centerness_on_reg=False: the classification predictor has conv_centerness as one more computed row / output column and
         # the regression predictor four, ParamStore.ctr_on_cls - the same two launches either way)
@@ -361,44 +549,12 @@ class Plan:
         self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + (nreg if st.gfl else 5)) * 2304)
         self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + st.reg_ld) * 4.0
         f.prof(4, 0, self._head_flops, self._head_bytes)
-        # fp8 forward of the tower convolutions (FCOS(fp8=dict(...)), BASELINE.json configs[4], off by default), DELAYED scaling
-        # (round 6): every fp8 tensor is written by its producer's own pass - GroupNorm's apply pass writes the e4m3 copy of its output
-        # next to the bf16 one, with the scale of the PREVIOUS step's maximum, and leaves this step's block maxima; one dsl_fp8_prep
-        # launch per step quantises the eight weight tensors (per-output-channel scales, from the fp32 master weights) and turns the
-        # recorded maxima into this step's input scales and epilogue scales.  The bf16 tensors stay what the backward pass reads
-        # (straight-through).  A plan's first forward pass runs twice more in front (Plan.fp8_warm): nothing is recorded yet.
         fp8 = getattr(st, 'fp8', None)
         f8 = bool(fp8) and 'towers' in str(fp8.get('layers', 'towers'))
         if f8 and not st.head.is_default():
             raise NotImplementedError(f'dsl_amd hot path: fp8 towers are built for the default head options only, got {st.head}')
         self.fp8_cold = f8
-        feats8 = None
-        if f8:
-            margin = float(fp8.get('margin', 1.25))         # headroom over the previous step's maximum (e4m3 saturates at 448)
-            nblk = (max(h_ * w_ for h_, w_ in ls) + 127) // 128
-            feats8 = self.buf('feats.f8', self.M, 256, dtype=torch.uint8)
-            am_feats = self.buf('feats.f8.amax', 512, dtype=torch.float32, zero=True)
-            scales = self.buf('fp8.scales', 8, dtype=torch.float32, zero=True)
-            items = (L.Fp8PrepItem * 8)()
-            f8lay = {}
-            for t_, tower in enumerate(('cls_convs', 'reg_convs')):
-                for i in range(4):
-                    spec = cv[f'bbox_head.{tower}.{i}.conv']
-                    assert spec.cout_pad == 256 and spec.cin == 256 and spec.k == 3, 'the fp8 slice is the 3x3 256 -> 256 tower layers'
-                    w8 = self.buf(f'{tower}.{i}.w8', spec.cout_pad, 9 * 256, dtype=torch.uint8)
-                    comb = self.buf(f'{tower}.{i}.comb', spec.cout_pad, dtype=torch.float32)
-                    am_out = self.buf(f'{tower}.{i}.act8.amax', 5 * N * nblk, dtype=torch.float32, zero=True) if i < 3 else None
-                    am_in = am_feats if i == 0 else f8lay[tower, i - 1]['am_out']
-                    it = items[t_ * 4 + i]
-                    it.w, it.w8, it.comb = st.t32_ptr(spec.name + '.weight'), w8.data_ptr(), comb.data_ptr()
-                    it.amax, it.n_amax, it.cout = am_in.data_ptr(), am_in.numel(), spec.cout
-                    it.scale = scales.data_ptr() + 4 * (t_ * 4 + i)
-                    f8lay[tower, i] = dict(w8=w8, comb=comb, am_out=am_out, scale_in=it.scale)
-            items_dev = torch.frombuffer(bytearray(bytes(items)), dtype=torch.uint8).to(self.dev)
-            self.bufs['fp8.items'] = items_dev
-            f.fp8_prep(items_dev, 8, 256, 9 * 256, margin)
-            # the FPN outputs feed both towers: one pass writes their e4m3 copy (both first layers' scales are the same number)
-            f.quant_fp8_delayed(feats, feats8, self.M, 256, 256, f8lay['cls_convs', 0]['scale_in'], am_feats)
+        feats8, f8lay = self._fp8_towers(feats, float(fp8.get('margin', 1.25))) if f8 else (None, None)
         if FSIDE:        # (starting the regression tower one convolution late, so that each tower's GroupNorm runs beside the other's
             f.fork(FSIDE)    # convolution instead of beside its GroupNorm: measured, 407.6 vs 408.9 img/s - no effect)
         for tower in ('cls_convs', 'reg_convs'):
@@ -416,8 +572,7 @@ class Plan:
                                         scale=f8lay[tower, i]['comb'], bias=st.t32_ptr(spec.name + '.bias'))
                 else:
                     cd_ = self._conv(spec, xin, pre, N, ls, ls)
-                if side:
-                    cd_.workspace, cd_.workspace_bytes = L.ptr(self.conv_ws_side), self.conv_ws_side.numel()
+                self._on_stream_ws(cd_, side)
                 base = f'bbox_head.{tower}.{i}.gn'
                 act8 = self.buf(f'{tower}.{i}.act8', self.M, 256, dtype=torch.uint8) if f8 and i < 3 else None
                 gd = ops.gn_desc(pre, act, st.t32_ptr(base + '.weight'), st.t32_ptr(base + '.bias'), stats,
@@ -444,128 +599,10 @@ class Plan:
                              src_hw=ls, dst_hw=ls, cs=256, cd=nreg, cd_pad=st.reg_pad, ldd=st.reg_ld, kh=3, kw=3, stride=1, pad=1,
                              flags=L.CONV_OUT_F32, bias=st.t32_ptr('head.regctr_b'), workspace=self.conv_ws_side),
                side=FSIDE)
-        self._fside = FSIDE
         if FSIDE and not self.training:
             f.join(FSIDE)               # (training plans: the loss op list starts with this join, see __init__)
         if not self.training:
             f.prof(4, 1)
-
-    def _fwd_resnet(self, x, h, w):
-        st, N, f = self.store, self.N, self.fwd
-        cv = st.convs
-        self.blocks = []        # per block: dict(xin, a1, a2, out, idt, in_hw, out_hw, prefix, stride)
-        self._pp = {}           # descriptors that touch layer1's output (pipelined prefix: two buffers, patched per step)
-        # Image-split stages (tuning key img_split; measured in round 3's first half: none 372.6, 3: 384.0, 34: 383.4, 4: 372.1, 23: -0.5 % vs 3; re-measured on
-        # the final kernels, two boxes, both orders (profiles/r03_step_boundary.txt): 3: 416.8 / 432.1, 34: 420.3 / 435.1, 23: 420.0, 24: 420.9 (second
-        # box), 234: 420.9 / 436.2 img/s -> default layer2 + layer3 + layer4, + 1 %;
-        # profiles/r03b_* are the profiles of this setting, r03_* those of the layer3 split, DESIGN 3.2e / 5): their launches are 66-132 workgroups of 15-40 us - mostly
-        # fill, epilogue and kernel boundary on half a chip.  The images of a batch are independent through the backbone, so the
-        # batch goes through these stages as TWO chains (images [0, ceil(N/2)) on the caller's stream, the rest on stream 3) of
-        # half-size launches: one chain's fixed per-launch costs hide under the other chain's kernels.
-        SPLIT = tune('img_split') if (self.BR and N >= 2 and self.training) else ''
-        split_open = False
-
-        def br_ws(d_):
-            d_.workspace, d_.workspace_bytes = L.ptr(self.conv_ws_br), self.conv_ws_br.numel()
-            return d_
-        for li, (planes, nb) in enumerate(zip(STAGE_PLANES, STAGE_BLOCKS)):
-            # Fused stages (tuning key bneck_fwd, default layer2; '23' adds layer3): every bottleneck's forward pass is ONE launch over the whole
-            # batch (dsl_bottleneck_fwd, csrc/bneck.hip) - the image-split chains of three launches per block and half are its predecessor
-            fuse = str(li + 1) in tune('bneck_fwd') and planes in (128, 256)
-            split = str(li + 1) in SPLIT and not fuse
-            f.tag = f'fwd.l{li + 1}'
-            if li >= 1 and self.training:
-                # late exchange: this stage's gradient bucket (layer2: 3, layer3: 2, layer4: 1) of the last optimizer step may still be
-                # exchanged / updated beside the stages in front of it; both image chains wait (no-ops until the slot is recorded)
-                f.wait(L.SLOT_UPD + 4 - li, stream=0)
-                if split_open:
-                    f.wait(L.SLOT_UPD + 4 - li, stream=self.BR)
-            if split and not split_open:
-                f.fork(self.BR)
-                split_open = True
-            elif split_open and not split:
-                f.join(self.BR)
-                split_open = False
-            groups = [(0, (N + 1) // 2, 0), ((N + 1) // 2, N, self.BR)] if split else [(0, N, 0)]
-            for b in range(nb):
-                p = f'backbone.layer{li + 1}.{b}'
-                c1, c2, c3 = cv[p + '.conv1'], cv[p + '.conv2'], cv[p + '.conv3']
-                s = c1.stride
-                oh, ow = conv_out(h, 1, s, 0), conv_out(w, 1, s, 0)
-                a1 = self.buf(p + '.a1', N, oh, ow, planes)
-                a2 = self.buf(p + '.a2', N, oh, ow, planes)
-                out = self.buf(p + '.out', N, oh, ow, planes * 4)
-                idt = x
-                if b == 0:      # the downsample conv only meets the main branch at conv3's residual add
-                    idt = self.buf(p + '.idt', N, oh, ow, planes * 4)
-                if split:
-                    for g0, g1, sd in groups:
-                        wsf = br_ws if sd else (lambda d_: d_)
-                        n_ = g1 - g0
-                        off = g0 * h * w * x.shape[-1] * 2          # this group's byte offset into the stage input
-                        if b == 0:
-                            dd = wsf(self._conv(cv[p + '.downsample.0'], x[g0:g1], idt[g0:g1], n_, [(h, w)], [(oh, ow)]))
-                            f.conv(dd, side=sd)
-                            if li == 1:
-                                self._pp.setdefault('ds', []).append((dd, off))
-                        d1 = wsf(self._conv(c1, x[g0:g1], a1[g0:g1], n_, [(h, w)], [(oh, ow)], relu=True))
-                        f.conv(d1, side=sd)
-                        if li == 1 and b == 0:
-                            self._pp.setdefault('c1', []).append((d1, off))
-                        f.conv(wsf(self._conv(c2, a1[g0:g1], a2[g0:g1], n_, [(oh, ow)], [(oh, ow)], relu=True)), side=sd)
-                        f.conv(wsf(self._conv(c3, a2[g0:g1], out[g0:g1], n_, [(oh, ow)], [(oh, ow)], relu=True, addend=idt[g0:g1])), side=sd)
-                    self.blocks.append(dict(prefix=p, xin=x, a1=a1, a2=a2, out=out, in_hw=(h, w), out_hw=(oh, ow), stride=s,
-                                            stage=li, b=b, planes=planes))
-                    x, h, w = out, oh, ow
-                    continue
-                use_br = self.BR
-                bd = None
-                if fuse:
-                    bd = ops.bneck_desc(x, st.w16_ptr(c1), st.w16_ptr(c2), st.w16_ptr(c3), idt, st.bn_ptrs(c1.bn), st.bn_ptrs(c2.bn),
-                                        st.bn_ptrs(c3.bn), a1, a2, out, n=N, hin=h, win=w, h=oh, w=ow, planes=planes, cin=c1.cin_store,
-                                        ldx=int(x.shape[-1]), stride=s)
-                    if not L.lib.dsl_bottleneck_fwd_supported(C.byref(bd)):
-                        bd = None
-                if bd is not None:
-                    if b == 0:          # the downsample branch beside nothing: it IS the block's identity, joined in front of the launch
-                        dd = self._conv(cv[p + '.downsample.0'], x, idt, N, [(h, w)], [(oh, ow)])
-                        f.conv(dd)
-                        if li == 1:
-                            self._pp['ds'] = [(dd, 0)]
-                            self._pp['c1'] = [(bd, 0)]
-                    f.bneck(bd)
-                    self.blocks.append(dict(prefix=p, xin=x, a1=a1, a2=a2, out=out, in_hw=(h, w), out_hw=(oh, ow), stride=s,
-                                            stage=li, b=b, planes=planes))
-                    x, h, w = out, oh, ow
-                    continue
-                if b == 0:
-                    dd = self._conv(cv[p + '.downsample.0'], x, idt, N, [(h, w)], [(oh, ow)])
-                    if use_br:
-                        dd.workspace, dd.workspace_bytes = L.ptr(self.conv_ws_br), self.conv_ws_br.numel()
-                        f.fork(self.BR)
-                    f.conv(dd, side=use_br)
-                if li == 1 and b == 0:
-                    self._pp['ds'] = [(dd, 0)]
-                d1 = self._conv(c1, x, a1, N, [(h, w)], [(oh, ow)], relu=True)
-                if li == 1 and b == 0:
-                    self._pp['c1'] = [(d1, 0)]
-                f.conv(d1)
-                f.conv(self._conv(c2, a1, a2, N, [(oh, ow)], [(oh, ow)], relu=True))
-                if b == 0 and use_br:
-                    f.join(self.BR)
-                d3 = self._conv(c3, a2, out, N, [(oh, ow)], [(oh, ow)], relu=True, addend=idt)
-                if li == 0 and b == nb - 1:
-                    self._pp['c3'], self._pp['out'] = d3, out
-                f.conv(d3)
-                self.blocks.append(dict(prefix=p, xin=x, a1=a1, a2=a2, out=out, in_hw=(h, w), out_hw=(oh, ow), stride=s,
-                                        stage=li, b=b, planes=planes))
-                x, h, w = out, oh, ow
-            self.stage_out.append((x, (h, w)))
-            self.stage_ld.append(planes * 4)
-            if li == 0:
-                self._prefix_end = len(f.items)        # pack + stem + pool + layer1: frozen weights, a function of the image alone
-        if split_open:
-            f.join(self.BR)
 
     def _gn_workspace(self, key):
         """The block-record scratch of one chain of (record-writing launch, GroupNorm pass) pairs that run one after the other."""
@@ -677,29 +714,11 @@ class Plan:
                              flags=f, addend=addend, lda=lda or cd, mask=mask, ldm=ldm or cd, workspace=self.conv_ws,
                              cs_real=cs_real)
 
-    def _build_backward(self):
-        """Backward op lists.  The data-gradient chain runs on the caller's stream; every weight gradient is
-        forked onto the library's side stream (its inputs - the forward activation and a gradient buffer that is
-        written exactly once per step - are complete at the fork point), so the many small, under-filled
-        backbone launches of the chain overlap with weight-gradient work.  Each segment ends with a JOIN."""
-        st, N, ls = self.store, self.N, self.level_sizes
-        lp = self.lossplan
-        reg = st.train_regions
-        M = self.M
-        SIDE = tune('side') != '0'
-        # tuning knobs (both measured: on is better): group the last segment's weight gradients too, although nothing
-        # is left on the caller's stream to overlap their tail with ...
-        GROUP_LAST = True
-        TAIL_SLOTS = tune_int('tail_slots')      # (round 3, tools/exp_env.sh: 160 / 192 / 224 / 256 = 421.3 / 421.9 / 419.8 / 418.2 img/s)
-        GROUP = True       # same-geometry weight gradients (tower layers, the blocks of a stage) as one launch
-        # ... and all weight gradients of a segment that share a tile configuration as one multi launch
-        self._multi_on = SIDE
-        self._wg_pending = []
+    def _bwd_head(self):
+        """Segment 0, first part: the head.  Returns the segment's list (the FPN's backward goes on) and the gradient w.r.t. the
+        five levels' rows."""
+        st, N, ls, lp, M, SIDE = self.store, self.N, self.level_sizes, self.lossplan, self.M, self._side
         g_feats = self.buf('g_feats', M, 256)
-        # ================= segment 0: head + FPN =================
-        # where in this pass the next step's frozen prefix (FCOS.pipeline_prefix) may start: 0 = with the pass, 3 / 2 / 1 = behind
-        # layer4's / layer3's / layer2's data gradients (1 = the whole chain, the round-2 setting)
-        PREFIX_LI = 2       # measured (tools/exp_env.sh): 1: 355.5, 3: 360, 2 / 0: +0.2 % over 3
         ol = OpList()
         ol.tag = 'bwd.head'
         ol.wait(L.SLOT_PACKS, stream=0)      # the data-gradient weight packs of the last optimizer step (ParamStore.repack_dgrad)
@@ -713,10 +732,6 @@ class Plan:
         BT = 2 if SIDE else 0
         if BT:
             ol.fork(BT)
-
-        def side_ws(cd_):
-            cd_.workspace, cd_.workspace_bytes = L.ptr(self.conv_ws_side), self.conv_ws_side.numel()
-            return cd_
         towers = (('reg_convs', BT), ('cls_convs', 0)) if BT else (('cls_convs', 0), ('reg_convs', 0))
         # the predictors' weight gradients need nothing from this pass but the loss gradients: first thing on the side stream
         self._wgrad(ol, None, lp.g_cls, self.tower['cls_convs'][3]['act'], N, ls, ls, cy=st.cls_pad, cd=st.cls_rows, wregion='head.cls_w',
@@ -733,6 +748,7 @@ class Plan:
 
         def gn_records(cd_, tower, j, sd):
             lay = self.tower[tower][j]
+            self._on_stream_ws(cd_, sd)
             cd_.gn_x = L.ptr(lay['pre'])                 # (set first: the query answers for the backward records' tiles)
             if L.lib.dsl_conv2d_gn_fusable(C.byref(cd_)):
                 cd_.gn_ws = L.ptr(self._gn_workspace('bwd.' + tower))      # per tower: with one stream for both (tuning side=0) the second
@@ -744,15 +760,13 @@ class Plan:
                 cd_.gn_x = None
             return cd_
         for tower, sd in towers:
-            wsf = side_ws if sd else (lambda c: c)
             g_act[tower] = self.buf(f'g_{tower}_act3', M, 256)
             if tower == 'cls_convs':
-                ol.conv(gn_records(wsf(self._dgrad('head.cls', lp.g_cls, g_act[tower], N, ls, ls, cs=st.cls_pad, cd=256, k=3, stride=1, pad=1,
-                                                         cs_real=st.cls_rows)),
-                                   tower, 3, sd), side=sd)
+                ol.conv(gn_records(self._dgrad('head.cls', lp.g_cls, g_act[tower], N, ls, ls, cs=st.cls_pad, cd=256, k=3, stride=1, pad=1,
+                                               cs_real=st.cls_rows), tower, 3, sd), side=sd)
             else:
-                ol.conv(gn_records(wsf(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=st.reg_pad, cd=256, k=3, stride=1, pad=1, cs_real=st.reg_rows)),
-                                   tower, 3, sd), side=sd)
+                ol.conv(gn_records(self._dgrad('head.regctr', lp.g_rc, g_act[tower], N, ls, ls, cs=st.reg_pad, cd=256, k=3, stride=1, pad=1,
+                                               cs_real=st.reg_rows), tower, 3, sd), side=sd)
         # layer by layer, both towers: their weight gradients go out in two groups of four (layers 3, 2 and layers 1, 0 of
         # both towers) as soon as the GroupNorm backward passes that produce their dY are queued - the side stream works from
         # the first quarter of this segment on instead of waiting for its end
@@ -776,17 +790,16 @@ class Plan:
                 if BT and SIDE:
                     ol.fork(1, other=BT)       # the weight-gradient stream also waits for the regression tower's stream
                 if self.defer:
-                    self._deferred_towers = list(tower_group)      # emitted behind the last segment, see below
+                    self._deferred_towers = list(tower_group)      # emitted behind the last segment, see _bwd_stage
                 else:
                     self._wgrad_group(ol, tower_group, side=SIDE)
                 self._flush_wgrads(ol, side=SIDE)
                 tower_group = []
             if i > 0:
                 for tower, sd in towers:
-                    wsf = side_ws if sd else (lambda c: c)
                     lay = self.tower[tower][i]
                     g_act[tower] = self.buf(f'g_{tower}_act{i - 1}', M, 256)
-                    ol.conv(gn_records(wsf(self._dgrad(lay['spec'].name, g_pre[tower], g_act[tower], N, ls, ls, cs=256, cd=256, k=3, stride=1, pad=1)),
+                    ol.conv(gn_records(self._dgrad(lay['spec'].name, g_pre[tower], g_act[tower], N, ls, ls, cs=256, cd=256, k=3, stride=1, pad=1),
                                        tower, i - 1, sd), side=sd)
             else:
                 cl, rl = self.tower['cls_convs'][0], self.tower['reg_convs'][0]
@@ -799,12 +812,16 @@ class Plan:
                 ol.conv(self._dgrad(rl['spec'].name, g_pre['reg_convs'], g_feats, N, ls, ls, cs=256, cd=256, k=3, stride=1, pad=1, addend=g_feats))
                 ol.prof(5, 1)
         self._flush_wgrads(ol, side=SIDE)          # towers + predictors: ready now, the FPN's follow below
-        # ---- FPN backward ----
+        return ol, g_feats
+
+    def _bwd_fpn(self, ol, g_feats, buckets):
+        """Segment 0, second part: the FPN and its laterals, which leave g_stage[1..3] (the gradients w.r.t. C3, C4, C5)."""
+        st, N, SIDE = self.store, self.N, self._side
         ol.tag = 'bwd.fpn'
         cv = st.convs
         fc = [cv[f'neck.fpn_convs.{i}.conv'] for i in range(5)]
         lc = [cv[f'neck.lateral_convs.{i}.conv'] for i in range(3)]
-        hw3, hw4, hw5, hw6, hw7 = ls
+        hw3, hw4, hw5, hw6, hw7 = self.level_sizes
         gseg = [g_feats.data_ptr() + self.seg_off[i] * 256 * 2 for i in range(5)]
         lat = [self.bufs[f'lat{i}'] for i in range(3)]
         p6r = self.bufs['p6r'] if self.p6_relu else self.feat_seg[3]
@@ -817,18 +834,12 @@ class Plan:
         # forward pass): the P3 / P4 output convs next to P7 -> P6 -> P5; the C3 / C4 laterals next to layer4's backward
         rla = st.backbone == 'rla'
         BB = 3 if (SIDE and not rla) else 0
-
-        def br_ws(cd_):
-            if BB:
-                cd_.workspace, cd_.workspace_bytes = L.ptr(self.conv_ws_br), self.conv_ws_br.numel()
-            return cd_
         if BB:
             ol.fork(BB)
         # P3, P4 = fpn_i(lat_i); the top-down path's nearest upsampling is a 2x2 sum in the backward direction
-        ol.conv(br_ws(self._dgrad(fc[0].name, gseg[0], g_lat[0], N, [hw3], [hw3], cs=256, cd=256, k=3, stride=1, pad=1)), side=BB)
+        self._conv_on(ol, BB, self._dgrad(fc[0].name, gseg[0], g_lat[0], N, [hw3], [hw3], cs=256, cd=256, k=3, stride=1, pad=1))
         ol.sum2x2(g_lat[0], s0, N, hw4[0], hw4[1], hw3[0], hw3[1], 256, side=BB)
-        ol.conv(br_ws(self._dgrad(fc[1].name, gseg[1], g_lat[1], N, [hw4], [hw4], cs=256, cd=256, k=3, stride=1, pad=1,
-                                  addend=s0)), side=BB)
+        self._conv_on(ol, BB, self._dgrad(fc[1].name, gseg[1], g_lat[1], N, [hw4], [hw4], cs=256, cd=256, k=3, stride=1, pad=1, addend=s0))
         ol.sum2x2(g_lat[1], s1, N, hw5[0], hw5[1], hw4[0], hw4[1], 256, side=BB)
         # P7 = fpn4(relu(P6)); relu_before_extra_convs=False: P7 = fpn4(P6), its data gradient reaches P6 unmasked
         ol.conv(self._dgrad(fc[4].name, gseg[4], g_p6, N, [hw7], [hw6], cs=256, cd=256, k=3, stride=2, pad=1,
@@ -850,7 +861,7 @@ class Plan:
         self._wgrad(ol, fc[0], gseg[0], lat[0], N, [hw3], [hw3], side=SIDE)
         # laterals -> gradients w.r.t. C3, C4, C5 (masked by the ReLU that produced them)
         self.g_stage = {}
-        self._br_pending = False        # side-stream-3 work the next segment must join before it touches g_stage[1], g_stage[2]
+        br_open = False        # side-stream-3 work the next segment joins before it touches g_stage[1], g_stage[2]
         for i, (li, hw) in ((2, (3, hw5)), (1, (2, hw4)), (0, (1, hw3))):
             cfeat = self.stage_out[li][0]
             cch = STAGE_PLANES[li] * 4
@@ -862,14 +873,11 @@ class Plan:
             # feed the recurrent path; their mask is applied once every contribution has arrived (engine_rla)
             masked = not rla or li == 3
             sd = BB if li < 3 else 0        # layer4's backward starts from the C5 lateral alone; C4, C3 are needed at its end
-            if sd and not self._br_pending:
+            if sd and not br_open:
                 ol.fork(BB)
-                self._br_pending = True
-            ol.conv(br_ws(self._dgrad(lc[i].name, g_lat[i], g0b, N, [hw], [hw], cs=256, cd=cch, k=1, stride=1, pad=0,
-                                      mask=cfeat if masked else None, mask_first=masked, ldm=ldc)) if sd else
-                    self._dgrad(lc[i].name, g_lat[i], g0b, N, [hw], [hw], cs=256, cd=cch, k=1, stride=1, pad=0,
-                                mask=cfeat if masked else None, mask_first=masked, ldm=ldc), side=sd)
-        buckets = st.grad_buckets()
+                br_open = True
+            self._conv_on(ol, sd, self._dgrad(lc[i].name, g_lat[i], g0b, N, [hw], [hw], cs=256, cd=cch, k=1, stride=1, pad=0,
+                                              mask=cfeat if masked else None, mask_first=masked, ldm=ldc))
         # no JOIN here: this segment's weight gradients keep running on the side stream under the next segment's
         # data-gradient chain.  Named event slot s marks "side-stream work of segment s queued": once it has fired, gradient
         # bucket s is complete - the data-parallel wrapper's communication stream waits for exactly that
@@ -882,133 +890,111 @@ class Plan:
         else:
             ol.record(0)
             self.bwd_segments.append((ol, dict(bucket=buckets[0], slot=0, main=False)))
-        # ================= backbone: layer4, layer3, layer2 =================
-        if rla:
-            from . import engine_rla
-            # (the recurrent path's BatchNorm post-pass runs on the weight-gradient stream behind the stage's flush)
-            self._multi_on = SIDE
-            engine_rla.build_backward(self, buckets, SIDE)
-            return
-        blocks_by_stage = {li: [b for b in self.blocks if b['stage'] == li] for li in (1, 2, 3)}
+
+    def _bwd_stage(self, li, buckets):
+        """The segment of one ResNet stage (li = 3, 2, 1: layer4, layer3, layer2), from g_stage[li] down to g_stage[li - 1]."""
+        N, SIDE, BB = self.N, self._side, self.BR
+        ol = OpList()
+        ol.tag = f'bwd.l{li + 1}'
+        if li == 1:
+            self._multi_on = False         # layer2: four tile configurations, and the caller's stream takes the tail group itself
+        g_pre = self.g_stage[li]          # gradient w.r.t. the (pre-ReLU-masked) output of the stage's last block
+        wgs = [], [], []                  # (g3, g2, g1): same-geometry weight gradients of this stage's blocks
+        # image-split data-gradient chains (as in the forward pass; tuning key img_split_bwd): images [0, ceil(N/2)) on the caller's
+        # stream, the rest on stream 3; the stage's weight gradients (whole batch) go out behind the JOIN at its end
         BSPLIT = tune('img_split_bwd')      # measured (tools/exp_env.sh): '' 372-377, 3: 378.5, 23: 382.5, 34: 381.5, 234: 379.7 img/s
-        for li in (3, 2, 1):
-            ol = OpList()
-            ol.tag = f'bwd.l{li + 1}'
-            if li == 1:
-                self._multi_on = False         # layer2: four tile configurations, and the caller's stream takes the tail group itself
-            blks = blocks_by_stage[li]
-            hw = blks[0]['out_hw']
-            planes = blks[0]['planes']
-            g_pre = self.g_stage[li]          # gradient w.r.t. the (pre-ReLU-masked) output of the stage's last block
-            g3, g2, g1 = [], [], []           # same-geometry weight gradients of this stage's blocks
-            # image-split data-gradient chains (as in the forward pass; tuning key img_split_bwd): images [0, ceil(N/2)) on the caller's
-            # stream, the rest on stream 3; the stage's weight gradients (whole batch) go out behind the JOIN at its end
-            grp_all = GROUP and (li > 1 or GROUP_LAST)
-            bsplit = bool(BB) and N >= 2 and grp_all and str(li + 1) in BSPLIT
-            groups = [(0, (N + 1) // 2, 0), ((N + 1) // 2, N, BB)] if bsplit else [(0, N, 0)]
-            if bsplit:
-                ol.join(BB)          # whatever stream 3 still runs (laterals, an earlier scatter) is visible to the caller's stream ...
-                ol.fork(BB)          # ... and stream 3 starts behind everything the caller's stream has queued
-                self._br_pending = False
-            for blk in reversed(blks):
-                p = blk['prefix']
-                c1, c2, c3 = cv[p + '.conv1'], cv[p + '.conv2'], cv[p + '.conv3']
-                gA2 = self.buf(p + '.g_a2', N, hw[0], hw[1], planes)
-                gA1 = self.buf(p + '.g_a1', N, hw[0], hw[1], planes)
-                grp = GROUP and (li > 1 or GROUP_LAST)
-                tsl = TAIL_SLOTS if li == 1 else 0      # last segment: nothing else is left to run beside these launches
-                if bsplit:
-                    g3.append(self._wgrad(ol, c3, g_pre, blk['a2'], N, [hw], [hw], side=SIDE, emit=False, slots=tsl))
-                    g2.append(self._wgrad(ol, c2, gA2, blk['a1'], N, [hw], [hw], side=SIDE, emit=False, slots=tsl))
-                    g_prev = self.buf(p + '.g_in', N, hw[0], hw[1], planes * 4) if blk['b'] > 0 else None
-                    for g0, g1_, sd in groups:
-                        wsf = br_ws if sd else (lambda d_: d_)
-                        n_ = g1_ - g0
-                        ol.conv(wsf(self._dgrad(c3.name, g_pre[g0:g1_], gA2[g0:g1_], n_, [hw], [hw], cs=c3.cout, cd=c3.cin, k=1, stride=1, pad=0,
-                                                mask=blk['a2'][g0:g1_], mask_last=True)), side=sd)
-                        ol.conv(wsf(self._dgrad(c2.name, gA2[g0:g1_], gA1[g0:g1_], n_, [hw], [hw], cs=c2.cout, cd=c2.cin, k=3, stride=1, pad=1,
-                                                mask=blk['a1'][g0:g1_], mask_last=True)), side=sd)
-                        if blk['b'] > 0:
-                            ol.conv(wsf(self._dgrad(c1.name, gA1[g0:g1_], g_prev[g0:g1_], n_, [hw], [hw], cs=c1.cout, cd=c1.cin, k=1, stride=1,
-                                                    pad=0, addend=g_pre[g0:g1_], mask=blk['xin'][g0:g1_], mask_last=True)), side=sd)
-                        elif li > 1:      # stride-2 scatters into the previous stage's gradient: downsample path, then conv1
-                            ds = cv[p + '.downsample.0']
-                            tgt, ihw = self.g_stage[li - 1], blk['in_hw']
-                            for spec, dy in ((ds, g_pre), (c1, gA1)):
-                                ol.conv(wsf(self._dgrad(spec.name, dy[g0:g1_], tgt[g0:g1_], n_, [hw], [ihw], cs=spec.cout, cd=spec.cin, k=1,
-                                                        stride=1, pad=0, os=2, addend=tgt[g0:g1_], mask=blk['xin'][g0:g1_], mask_first=True)), side=sd)
-                    if blk['b'] > 0:
-                        g1.append(self._wgrad(ol, c1, gA1, blk['xin'], N, [hw], [blk['in_hw']], side=SIDE, emit=False, slots=tsl))
-                        g_pre = g_prev
-                    else:
-                        ol.join(BB)       # both chains are done: the weight gradients below (and the groups) read whole-batch tensors
-                        d1 = self._wgrad(ol, c1, gA1, blk['xin'], N, [hw], [blk['in_hw']], side=SIDE, emit=True, slots=tsl)
-                        dwd = self._wgrad(ol, cv[p + '.downsample.0'], g_pre, blk['xin'], N, [hw], [blk['in_hw']], side=SIDE, slots=tsl)
-                        if li == 1:
-                            self._pp['wg_c1'], self._pp['wg_ds'] = d1, dwd
-                    continue
-                ds_early = BB and blk['b'] == 0 and li > 1
-                if ds_early:        # the downsample path's scatter into the previous stage's gradient, beside conv3 -> conv2 -> conv1
-                    ds = cv[p + '.downsample.0']
-                    tgt, ihw = self.g_stage[li - 1], blk['in_hw']
-                    ol.fork(BB)          # (stream 3 is in order: the lateral that initialised tgt is already queued there)
-                    ol.conv(br_ws(self._dgrad(ds.name, g_pre, tgt, N, [hw], [ihw], cs=ds.cout, cd=ds.cin, k=1, stride=1, pad=0,
-                                              os=2, addend=tgt, mask=blk['xin'], mask_first=True)), side=BB)
-                g3.append(self._wgrad(ol, c3, g_pre, blk['a2'], N, [hw], [hw], side=SIDE, emit=not grp, slots=tsl))
-                ol.conv(self._dgrad(c3.name, g_pre, gA2, N, [hw], [hw], cs=c3.cout, cd=c3.cin, k=1, stride=1, pad=0,
-                                    mask=blk['a2'], mask_last=True))
-                g2.append(self._wgrad(ol, c2, gA2, blk['a1'], N, [hw], [hw], side=SIDE, emit=not grp, slots=tsl))
-                ol.conv(self._dgrad(c2.name, gA2, gA1, N, [hw], [hw], cs=c2.cout, cd=c2.cin, k=3, stride=1, pad=1,
-                                    mask=blk['a1'], mask_last=True))
-                d1 = self._wgrad(ol, c1, gA1, blk['xin'], N, [hw], [blk['in_hw']], side=SIDE,
-                                 emit=not (grp and blk['b'] > 0), slots=tsl)
-                if li == 1 and blk['b'] == 0:
-                    self._pp['wg_c1'] = d1
-                if blk['b'] > 0:
-                    g1.append(d1)
-                if blk['b'] > 0:
-                    g_prev = self.buf(p + '.g_in', N, hw[0], hw[1], planes * 4)
-                    ol.conv(self._dgrad(c1.name, gA1, g_prev, N, [hw], [hw], cs=c1.cout, cd=c1.cin, k=1, stride=1,
-                                        pad=0, addend=g_pre, mask=blk['xin'], mask_last=True))
-                    g_pre = g_prev
-                else:
-                    ds = cv[p + '.downsample.0']
-                    dwd = self._wgrad(ol, ds, g_pre, blk['xin'], N, [hw], [blk['in_hw']], side=SIDE, slots=tsl)
-                    if li == 1:
-                        self._pp['wg_ds'] = dwd
-                    if li > 1:      # data gradient into the previous stage's output (stride-2 scatter)
-                        tgt = self.g_stage[li - 1]
-                        ihw = blk['in_hw']
-                        if BB:          # the laterals / the early downsample scatter on stream 3 wrote tgt first
-                            ol.join(BB)
-                        for spec, dy in ((c1, gA1),) if ds_early else ((ds, g_pre), (c1, gA1)):
-                            ol.conv(self._dgrad(spec.name, dy, tgt, N, [hw], [ihw], cs=spec.cout, cd=spec.cin, k=1,
-                                                stride=1, pad=0, os=2, addend=tgt, mask=blk['xin'], mask_first=True))
-            if li == PREFIX_LI:
-                ol.record(L.SLOT_TAIL, stream=0)       # from here on the next step's frozen prefix may run beside this pass
-            if GROUP and (li > 1 or GROUP_LAST):
-                # last segment: the caller's stream has nothing left to do, it takes part of the groups itself
-                on_main = '2' if li == 1 else '0'     # measured: tools/experiments_r2.txt (exp_r2w)
-                order = sorted(((3, g3), (2, g2), (1, g1)), key=lambda t: str(t[0]) in on_main)     # side-stream groups first: one FORK
-                for gi, grp_descs in order:
-                    mine = str(gi) in on_main
-                    self._wgrad_group(ol, grp_descs, side=SIDE and not mine, ws_name='wg_ws_main' if mine else 'wg_ws')
-            self._flush_wgrads(ol, side=SIDE)
-            seg = 4 - li                      # 1, 2, 3
-            ol.record(seg)
-            if li == 1:                       # last segment: everything must be complete when the list returns
-                ol.join()
-            # main=True: part of this bucket's gradients was computed on the caller's stream (the last group above)
-            self.bwd_segments.append((ol, dict(bucket=buckets[seg], slot=seg, main=(li == 1))))
-            if li == 1 and self.defer:
-                # the towers' weight gradients, last on the weight-gradient stream and NOT joined: they run under whatever the caller
-                # queues next (the next step's backbone forward); event slot 0 = "bucket 0 (head + FPN) complete"
-                dl = OpList()
-                on, self._multi_on = self._multi_on, False
-                self._wgrad_group(dl, self._deferred_towers, side=True)
-                self._multi_on = on
-                dl.record(0)
-                self.bwd_segments.append((dl, dict(bucket=buckets[0], slot=0, main=False, deferred=True)))
+        grp = GROUP and (li > 1 or GROUP_LAST)
+        bsplit = bool(BB) and N >= 2 and grp and str(li + 1) in BSPLIT
+        if bsplit:
+            ol.join(BB)          # whatever stream 3 still runs (laterals, an earlier scatter) is visible to the caller's stream ...
+            ol.fork(BB)          # ... and stream 3 starts behind everything the caller's stream has queued
+        groups = self._groups(bsplit, BB)
+        for blk in reversed(self.stage_blocks[li]):
+            g_pre = self._bwd_block(ol, li, blk, g_pre, groups, wgs, grp)
+        if li == PREFIX_LI:
+            ol.record(L.SLOT_TAIL, stream=0)       # from here on the next step's frozen prefix may run beside this pass
+        if grp:
+            # last segment: the caller's stream has nothing left to do, it takes part of the groups itself
+            on_main = '2' if li == 1 else '0'     # measured: tools/experiments_r2.txt (exp_r2w)
+            order = sorted(zip((3, 2, 1), wgs), key=lambda t: str(t[0]) in on_main)     # side-stream groups first: one FORK
+            for gi, grp_descs in order:
+                mine = str(gi) in on_main
+                self._wgrad_group(ol, grp_descs, side=SIDE and not mine, ws_name='wg_ws_main' if mine else 'wg_ws')
+        self._flush_wgrads(ol, side=SIDE)
+        seg = 4 - li                      # 1, 2, 3
+        ol.record(seg)
+        if li == 1:                       # last segment: everything must be complete when the list returns
+            ol.join()
+        # main=True: part of this bucket's gradients was computed on the caller's stream (the last group above)
+        self.bwd_segments.append((ol, dict(bucket=buckets[seg], slot=seg, main=(li == 1))))
+        if li == 1 and self.defer:
+            # the towers' weight gradients, last on the weight-gradient stream and NOT joined: they run under whatever the caller
+            # queues next (the next step's backbone forward); event slot 0 = "bucket 0 (head + FPN) complete"
+            dl = OpList()
+            on, self._multi_on = self._multi_on, False
+            self._wgrad_group(dl, self._deferred_towers, side=True)
+            self._multi_on = on
+            dl.record(0)
+            self.bwd_segments.append((dl, dict(bucket=buckets[0], slot=0, main=False, deferred=True)))
+
+    def _bwd_block(self, ol, li, blk, g_pre, groups, wgs, grp):
+        """One bottleneck's backward, chain by chain over `groups`; g_pre: the gradient w.r.t. its output.  Returns the gradient
+        w.r.t. its input (None for a stage's first block: that one goes into g_stage[li - 1], a stride-2 scatter, or - layer2 -
+        nowhere, layer1 is frozen).  Weight gradients: collected in wgs for the stage's grouped launches; those of the first
+        block's conv1 / downsample have no group and go out here, behind the data gradients that complete their dY.
+        Where they stand relative to the first block's scatters depends on the chains: ONE whole-batch chain queues them first
+        (tuning side=0 runs them right there, so the position shows in the list) and scatters behind a JOIN of stream 3, whose
+        laterals / early downsample scatter wrote the target first; TWO chains scatter inside each chain, and the weight
+        gradients, which read whole-batch tensors, follow the JOIN of both."""
+        st, N, SIDE, BB = self.store, self.N, self._side, self.BR
+        cv, p, hw, ihw, planes = st.convs, blk.prefix, blk.out_hw, blk.in_hw, blk.planes
+        c1, c2, c3 = cv[p + '.conv1'], cv[p + '.conv2'], cv[p + '.conv3']
+        first, split = blk.b == 0, len(groups) > 1
+        ds = cv[p + '.downsample.0'] if first else None
+        # tail_slots: (round 3, tools/exp_env.sh: 160 / 192 / 224 / 256 = 421.3 / 421.9 / 419.8 / 418.2 img/s)
+        tsl = tune_int('tail_slots') if li == 1 else 0      # last segment: nothing else is left to run beside these launches
+        gA2 = self.buf(p + '.g_a2', N, hw[0], hw[1], planes)
+        gA1 = self.buf(p + '.g_a1', N, hw[0], hw[1], planes)
+        g_in = None if first else self.buf(p + '.g_in', N, hw[0], hw[1], planes * 4)
+
+        def dgrad(sd, spec, dy, dst, g0, ge, **kw):
+            self._conv_on(ol, sd, self._dgrad(spec.name, dy[g0:ge], dst[g0:ge], ge - g0, [hw], [hw], cs=spec.cout, cd=spec.cin,
+                                              stride=1, mask_last=True, **kw))
+
+        def scatter(sd, spec, dy, g0, ge):      # stride-2 scatter into the previous stage's gradient
+            tgt = self.g_stage[li - 1]
+            self._conv_on(ol, sd, self._dgrad(spec.name, dy[g0:ge], tgt[g0:ge], ge - g0, [hw], [ihw], cs=spec.cout, cd=spec.cin, k=1,
+                                              stride=1, pad=0, os=2, addend=tgt[g0:ge], mask=blk.xin[g0:ge], mask_first=True))
+        scatters = [(ds, g_pre), (c1, gA1)] if first and li > 1 else []
+        if scatters and BB and not split:        # the downsample path's scatter into the previous stage's gradient, beside conv3 -> conv2 -> conv1
+            ol.fork(BB)          # (stream 3 is in order: the lateral that initialised tgt is already queued there)
+            scatter(BB, *scatters.pop(0), 0, N)
+        for g0, ge, sd in groups:
+            dgrad(sd, c3, g_pre, gA2, g0, ge, k=1, pad=0, mask=blk.a2[g0:ge])
+            dgrad(sd, c2, gA2, gA1, g0, ge, k=3, pad=1, mask=blk.a1[g0:ge])
+            if not first:
+                dgrad(sd, c1, gA1, g_in, g0, ge, k=1, pad=0, addend=g_pre[g0:ge], mask=blk.xin[g0:ge])
+            elif split:       # downsample path, then conv1
+                for spec, dy in scatters:
+                    scatter(sd, spec, dy, g0, ge)
+        if first and split:
+            ol.join(BB)       # both chains are done: the weight gradients below (and the groups) read whole-batch tensors
+        wgs[0].append(self._wgrad(ol, c3, g_pre, blk.a2, N, [hw], [hw], side=SIDE, emit=not grp, slots=tsl))
+        wgs[1].append(self._wgrad(ol, c2, gA2, blk.a1, N, [hw], [hw], side=SIDE, emit=not grp, slots=tsl))
+        d1 = self._wgrad(ol, c1, gA1, blk.xin, N, [hw], [ihw], side=SIDE, emit=first or not grp, slots=tsl)
+        if not first:
+            wgs[2].append(d1)
+            return g_in
+        dwd = self._wgrad(ol, ds, g_pre, blk.xin, N, [hw], [ihw], side=SIDE, slots=tsl)
+        if li == 1:         # they read layer1's output
+            self._tracks_l1(d1, 'x')
+            self._tracks_l1(dwd, 'x')
+        if scatters and not split:
+            if BB:          # the laterals / the early downsample scatter on stream 3 wrote tgt first
+                ol.join(BB)
+            for spec, dy in scatters:
+                scatter(0, spec, dy, 0, N)
+        return None
 
     # ---------------------------------------------------------------------------------------------
     def _split_prefix(self):
@@ -1042,21 +1028,16 @@ class Plan:
         self.fwd_rest = rest
         rest.items = [w1] + rest.items
         self.prefix = pre
-        out = self._pp['out']
-        self._l1out = [out, torch.empty_like(out)]
+        if sum(field == 'dst' for _, field, _ in self._l1_tracked) != 1:
+            raise KeyError('pipe_prefix: layer1 runs as one chain (img_split without stage 1)')
+        self._l1out = [self._l1_buf, torch.empty_like(self._l1_buf)]
         self._parity = 0
 
     def set_parity(self, p):
-        """Points the five descriptors that touch layer1's output at buffer p."""
+        """Points the descriptors that touch layer1's output (_tracks_l1) at buffer p."""
         ptr = self._l1out[p].data_ptr()
-        self._pp['c3'].dst = ptr
-        for d_, off in self._pp['c1'] + self._pp['ds']:
-            if isinstance(d_, L.BneckDesc):
-                d_.x = ptr + off
-            else:
-                d_.src = ptr + off
-        self._pp['wg_c1'].x = ptr
-        self._pp['wg_ds'].x = ptr
+        for desc, field, off in self._l1_tracked:
+            setattr(desc, field, ptr + off)
         self._parity = p
 
     def bind_image(self, img, half_last=False):

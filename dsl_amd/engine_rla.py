@@ -28,10 +28,12 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .engine import OpList, conv_out
 from .params import RLA_C, RLA_PAD, STAGE_BLOCKS, STAGE_PLANES
 from .tuning import tune, tune_int
 
 BF = torch.bfloat16
+S2_CLASSES = True         # stride-2 3x3 data gradients as four parity-class launches
 
 
 def _rla_op(ol, kind, p=(), i=(), f=(), rows=0, side=False):
@@ -49,16 +51,12 @@ def _rla_op(ol, kind, p=(), i=(), f=(), rows=0, side=False):
     return d
 
 
-def conv_out_hw(h, k, s, p):
-    return (h + 2 * p - k) // s + 1
-
-
 def build_forward(plan, emit_pool, h1, w1):
     """Stem (N, h1, w1, 64) -> max pool into the first XH (emit_pool(out, ld): the plan's stem / pool ops) -> 16 RLA blocks;
     fills plan.stage_out / stage_ld and plan.rla_blocks (what the backward needs)."""
     st, N, f = plan.store, plan.N, plan.fwd
     cv = st.convs
-    h, w = conv_out_hw(h1, 3, 2, 1), conv_out_hw(w1, 3, 2, 1)
+    h, w = conv_out(h1, 3, 2, 1), conv_out(w1, 3, 2, 1)
     cx = 64
     xh = plan.buf('rla.xh.0.0', N * h * w, cx + RLA_PAD, zero=True)
     emit_pool(xh, cx + RLA_PAD)
@@ -69,10 +67,6 @@ def build_forward(plan, emit_pool, h1, w1):
     SPLIT = tune('rla_split') if (plan.BR and N >= 2 and plan.training) else ''
     TAIL = tune('rla_tail') != '0'
     split_open = False
-
-    def br_ws(d_):
-        d_.workspace, d_.workspace_bytes = L.ptr(plan.conv_ws_br), plan.conv_ws_br.numel()
-        return d_
 
     def rows(t, g0, hw, ld):
         """Pointer to image g0's first row of a [N * hw][ld] bf16 tensor (or of a raw pointer into one)."""
@@ -87,12 +81,12 @@ def build_forward(plan, emit_pool, h1, w1):
         elif split_open and not split:
             f.join(plan.BR)
             split_open = False
-        groups = [(0, (N + 1) // 2, 0), ((N + 1) // 2, N, plan.BR)] if split else [(0, N, 0)]
+        groups = plan._groups(split, plan.BR)
         for b in range(nb):
             p = f'backbone.stages.{s_}.{b}'
             c1, c2, c3 = cv[p + '.conv1'], cv[p + '.conv2'], cv[p + '.conv3']
             stride = c2.stride
-            oh, ow = conv_out_hw(h, 3, stride, 1), conv_out_hw(w, 3, stride, 1)
+            oh, ow = conv_out(h, 3, stride, 1), conv_out(w, 3, stride, 1)
             ldx = cx + RLA_PAD
             a1 = plan.buf(p + '.a1', N * h * w, planes)
             a2 = plan.buf(p + '.a2', N * oh * ow, planes)
@@ -113,17 +107,16 @@ def build_forward(plan, emit_pool, h1, w1):
             ihw, ohw = h * w, oh * ow
             for g0, g1, sd in groups:
                 n_ = g1 - g0
-                wsf = br_ws if sd else (lambda d_: d_)
                 xh_g, a1_g, a2_g, nxt_g = rows(xh, g0, ihw, ldx), rows(a1, g0, ihw, planes), rows(a2, g0, ohw, planes), rows(nxt, g0, ohw, c4 + RLA_PAD)
-                f.conv(wsf(plan._conv(c1, xh_g, a1_g, n_, [(h, w)], [(h, w)], relu=True, cs=ldx, lds=ldx)), side=sd)
-                f.conv(wsf(plan._conv(c2, a1_g, a2_g, n_, [(h, w)], [(oh, ow)], relu=True)), side=sd)
+                plan._conv_on(f, sd, plan._conv(c1, xh_g, a1_g, n_, [(h, w)], [(h, w)], relu=True, cs=ldx, lds=ldx))
+                plan._conv_on(f, sd, plan._conv(c2, a1_g, a2_g, n_, [(h, w)], [(oh, ow)], relu=True))
                 if b == 0:
                     idt_g, idt_ld = rows(idt, g0, ohw, c4), c4
-                    f.conv(wsf(plan._conv(cv[p + '.downsample.0'], xh_g, idt_g, n_, [(h, w)], [(oh, ow)], cs=cx, lds=ldx)), side=sd)
+                    plan._conv_on(f, sd, plan._conv(cv[p + '.downsample.0'], xh_g, idt_g, n_, [(h, w)], [(oh, ow)], cs=cx, lds=ldx))
                 else:
                     idt_g, idt_ld = xh_g, ldx                  # the block input itself (x part of its rows)
-                f.conv(wsf(plan._conv(c3, a2_g, nxt_g, n_, [(oh, ow)], [(oh, ow)], relu=True, addend=idt_g, lda=idt_ld,
-                                      dst_ld=c4 + RLA_PAD)), side=sd)
+                plan._conv_on(f, sd, plan._conv(c3, a2_g, nxt_g, n_, [(oh, ow)], [(oh, ow)], relu=True, addend=idt_g, lda=idt_ld,
+                                                dst_ld=c4 + RLA_PAD))
                 if not last:
                     h_ptr, h_ld = xh_g + cx * 2, ldx           # h part of this block's input rows
                     if blk['pooled']:
@@ -137,11 +130,11 @@ def build_forward(plan, emit_pool, h1, w1):
                         _rla_op(f, L.RLA_TAIL_FWD, p=(nxt_g, h_ptr, st.w16_ptr(co), sc, bi, st.w16_ptr(rc), u_g, t_g, nxt_g + c4 * 2),
                                 i=(c4 + RLA_PAD, h_ld, c4, tw, c4 + RLA_PAD, n_, oh, ow), side=sd)
                         continue
-                    f.conv(wsf(plan._conv(co, nxt_g, u_g, n_, [(oh, ow)], [(oh, ow)], cs=c4, lds=c4 + RLA_PAD, addend=h_ptr, lda=h_ld,
-                                          dst_ld=RLA_C, affine=False)), side=sd)
+                    plan._conv_on(f, sd, plan._conv(co, nxt_g, u_g, n_, [(oh, ow)], [(oh, ow)], cs=c4, lds=c4 + RLA_PAD, addend=h_ptr, lda=h_ld,
+                                                dst_ld=RLA_C, affine=False))
                     _rla_op(f, L.RLA_BN_TANH, p=(u_g, sc, bi, t_g), i=(RLA_C, tw, RLA_C), rows=n_ * ohw, side=sd)
-                    f.conv(wsf(plan._conv(rc, t_g, nxt_g + c4 * 2, n_, [(oh, ow)], [(oh, ow)], cs=tw, dst_ld=c4 + RLA_PAD,
-                                          affine=False)), side=sd)
+                    plan._conv_on(f, sd, plan._conv(rc, t_g, nxt_g + c4 * 2, n_, [(oh, ow)], [(oh, ow)], cs=tw, dst_ld=c4 + RLA_PAD,
+                                                affine=False))
             plan.rla_blocks.append(blk)
             xh, cx, h, w = nxt, c4, oh, ow
         plan.stage_out.append((xh, (h, w)))
@@ -159,7 +152,6 @@ def build_backward(plan, buckets, SIDE):
     bn_g = lambda bn, leaf: st.t32_ptr('bn_train.' + leaf, st.grad) + st.bn_train_off[bn][0] * 4
     bn_p = lambda bn, leaf: st.t32_ptr('bn_train.' + leaf) + st.bn_train_off[bn][0] * 4
     bn_f = lambda bn, leaf: st.frozen.data_ptr() + (st.frozen_regions['bn_train.' + leaf][0] + st.bn_train_off[bn][0]) * 4
-    from .engine import OpList
     # Image-split data-gradient chains (as in the forward pass and in Plan's ResNet backward): the images of a batch are
     # independent through the backbone's backward too - per-image recurrent state, eval-mode BatchNorms - so the chain of a stage
     # runs as two chains of part-batch launches, images [0, ceil(N/2)) on the caller's stream and the rest on stream 3
@@ -172,12 +164,7 @@ def build_backward(plan, buckets, SIDE):
     # not of launch gaps, and the weight-gradient grids already hold the CUs a second chain would use.
     TAIL = tune('rla_tail') != '0'
     BSPLIT = tune('rla_split_bwd')        # default '': built, same gradients (test_rla_image_split_backward_chains_give_the_same_gradients), slower - LAB_NOTES.md
-    S2_CLASSES = True         # stride-2 3x3 data gradients as four parity-class launches
     BB = plan.BR
-
-    def br_ws(d_):
-        d_.workspace, d_.workspace_bytes = L.ptr(plan.conv_ws_br), plan.conv_ws_br.numel()
-        return d_
     gh_next = None            # gradient w.r.t. the h a block PRODUCES ([px_out][64], 32 real), written by its consumer
     for s_ in (3, 2, 1):
         ol = OpList()
@@ -187,7 +174,7 @@ def build_backward(plan, buckets, SIDE):
         gx = plan.g_stage[s_]                 # gradient w.r.t. the stage's last output (FPN lateral + next stage), unmasked for s < 3
         g3, g2, g1, g_co, g_rc, post = [], [], [], [], [], []
         bsplit = str(s_) in BSPLIT
-        groups = [(0, (N + 1) // 2, 0), ((N + 1) // 2, N, BB)] if bsplit else [(0, N, 0)]
+        groups = plan._groups(bsplit, BB)
         rec_items = []
         # the last stage's weight gradients go out behind the whole data-gradient chain, with nothing left to run beside them (0.8 ms
         # of the iteration, profiles/r03_rla_sequence.txt): they take the chip instead of the weight-gradient stream's usual budget
@@ -212,8 +199,7 @@ def build_backward(plan, buckets, SIDE):
             I = lambda t_, b_, e_: None if t_ is None else rows2d(t_)[b_ * ihw:e_ * ihw]      # rows of images [b_, e_) at the input resolution
             O = lambda t_, b_, e_: None if t_ is None else rows2d(t_)[b_ * ohw:e_ * ohw]      # ... at the output resolution
 
-            def dg(sd, d_):
-                ol.conv(br_ws(d_) if sd else d_, side=sd)
+            dg = lambda sd, d_: plan._conv_on(ol, sd, d_)
             if blk['last']:
                 g_pre = gx                                   # masked by the lateral's data gradient already
                 g_u = None

@@ -429,6 +429,82 @@ def test_pipelined_prefix_equals_inline_forward(golden):
     assert torch.equal(finals[0][0], finals[1][0]) and torch.equal(finals[0][1], finals[1][1])
 
 
+def _pointers_into(plan, bufs):
+    """{(list, op index, member, field): (index into bufs, byte offset)} over every pointer an op list of `plan` hands to a
+    launch - the op's own arguments and every field of the descriptor it points to, members of weight-gradient group arrays and
+    multi tables included - that lies inside one of the tensors `bufs`."""
+    import ctypes as C
+    from dsl_amd import _lib as L
+    from dsl_amd import ops
+    spans = [(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in bufs]
+    types = {L.OP_CONV: L.ConvDesc, L.OP_WGRAD: L.WgradDesc, L.OP_BNECK: L.BneckDesc, L.OP_GN_FWD: L.GnDesc, L.OP_GN_BWD: L.GnDesc}
+    lists = [('fwd', plan.fwd)] if plan.prefix is None else [('prefix', plan.prefix), ('fwd_rest', plan.fwd_rest)]
+    lists += [(f'bwd{k}', ol) for k, (ol, _) in enumerate(plan.bwd_segments)]
+    found = {}
+
+    def note(key, ptr):
+        for b, (lo, hi) in enumerate(spans):
+            if ptr and lo <= ptr < hi:
+                found[key] = (b, ptr - lo)
+    for name, ol in lists:
+        multis = {m.host.data_ptr(): m for m in ol.keep if isinstance(m, ops.WgradMulti)}
+        for k, op in enumerate(ol.items):
+            for j, ptr in enumerate(op.p):
+                note((name, k, -1, f'p{j}'), ptr)
+            if op.kind == L.OP_WGRAD_GROUP:
+                arr = C.cast(op.desc, C.POINTER(L.WgradDesc))
+                descs = [arr[g] for g in range(op.i[0])]
+            elif op.kind == L.OP_WGRAD_MULTI:
+                descs = list(multis[op.p[0]].descs)
+            elif op.kind in types and op.desc:
+                descs = [C.cast(op.desc, C.POINTER(types[op.kind])).contents]
+            else:
+                descs = []
+            for g, d in enumerate(descs):
+                for field, ctype in d._fields_:
+                    if ctype is C.c_void_p:
+                        note((name, k, g, field), getattr(d, field))
+    return found
+
+
+_PARITY_LEGS = [{}, dict(bneck_fwd=''), dict(img_split='', img_split_bwd=''), dict(side='0')]
+
+
+@pytest.mark.parametrize('knobs', _PARITY_LEGS, ids=[''.join(f'{k}={v},' for k, v in kn.items()) or 'default' for kn in _PARITY_LEGS])
+def test_set_parity_moves_every_pointer_into_layer1s_output(golden, monkeypatch, knobs):
+    """Pipelined prefix: layer1's output has two buffers, and Plan.set_parity(p) must point EVERY launch that reads or writes it at
+    buffer p - a reader left on the other buffer races with the previous step's weight gradients and no other test sees it.
+    After set_parity(0) and set_parity(1): every pointer the lists hold into either buffer lies in buffer p, at the offset its
+    counterpart has in the other one; there are such pointers, the same number both times.  side=0 has no prefix list: nothing
+    is re-pointed, the one buffer's readers stay where the build put them."""
+    from dsl_amd import tuning
+    tuning.tune('side')                                    # (DSL_TUNE parsed before the overrides below)
+    for k_, v_ in knobs.items():
+        monkeypatch.setitem(tuning._values, k_, v_)
+    model = build()
+    N, _, H, W = golden('net_tiny.npz')['img'].shape
+    plan = model._get_engine().plan(model.store, N, H, W, training=True)
+    if knobs.get('side') == '0':
+        assert plan.prefix is None and not hasattr(plan, '_l1out')           # no second buffer, set_parity has nothing to work on
+        l1 = plan.stage_out[0][0]
+        before = _pointers_into(plan, [l1])
+        img = T(golden('net_tiny.npz')['img']).cuda()
+        gtb, gtl = [T(golden('net_tiny.npz')[f'gt{i}']) for i in range(N)], [T(golden('net_tiny.npz')[f'gl{i}']) for i in range(N)]
+        model.forward_train(img, [dict()] * N, gtb, gtl)                     # (a step does not call it either)
+        torch.cuda.synchronize()
+        assert before and _pointers_into(plan, [l1]) == before
+        return
+    assert plan.prefix is not None
+    seen = []
+    for p in (0, 1):
+        plan.set_parity(p)
+        ptrs = _pointers_into(plan, plan._l1out)
+        print(knobs, 'parity', p, sorted(ptrs.items()))
+        assert ptrs and all(b == p for b, _ in ptrs.values()), sorted(ptrs.items())
+        seen.append({k: off for k, (_, off) in ptrs.items()})
+    assert seen[0] == seen[1] and len(seen[0]) == len(seen[1])
+
+
 def test_fused_bottleneck_stages_train_to_the_same_bits(monkeypatch):
     """Tuning key bneck_fwd: layer2 / layer3's bottlenecks as ONE launch each (dsl_bottleneck_fwd, csrc/bneck.hip) instead of three launches
     per block and image-split chain.  Same K order per MFMA chain and the same rounding points => at the benchmark's own size (2 x 3 x 800 x
