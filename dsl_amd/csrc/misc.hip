@@ -387,7 +387,23 @@ __global__ __launch_bounds__(GN_TA) void gn_bwd_apply_kernel(const GnK p) {
       const int g_lo = c0 / cpg;
       const int NG = (min(c0 + GN_CW, p.c) - 1) / cpg - g_lo + 1;
       const int NV = S * NG * 2, Q1 = GN_TA / NV;
-      {
+      if (NV > GN_TA) {
+        // more columns than threads (S > 64 with two groups in the slice, S > 128 with one; gn_check admits S <= 256, so
+        // NV <= 1024 = tot): thread t adds columns t, t + GN_TA, ... over their blocks in order and writes tot itself.  (Pointer
+        // walk, not unrolled: the kernel stays at the 72 VGPRs of its streaming rows.)
+#pragma nounroll
+        for (int v = threadIdx.x; v < NV; v += GN_TA) {
+          const int si = v / (2 * NG);
+          const GnRows rr = gn_rows(p, si, R);
+          const float* col = rr.base + (3 * p.c + 2 * g_lo + (v - si * (2 * NG)));
+          const float* end = col + (long long)rr.nb * R;
+          float a = 0.f;
+#pragma nounroll
+          for (; col < end; col += R) a += *col;
+          tot[v] = a;
+        }
+        __syncthreads();
+      } else {
         const int v = threadIdx.x % NV, j = threadIdx.x / NV;
         float a = 0.f;
         if (j < Q1) {

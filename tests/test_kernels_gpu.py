@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import op_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -592,6 +594,17 @@ def test_groupnorm_relu_fwd_bwd(K):
     assert torch.allclose(dbias.cpu(), ref_db, rtol=1e-2, atol=1e-2 * float(ref_db.abs().max()) + 1e-3), (dbias.cpu() - ref_db).abs().max()
 
 
+def _gn_checked(mem, lr, launch):
+    """one GroupNorm launch under op_ref.run_checked: every output within its bar, no byte elsewhere changed"""
+    def run():
+        launch()
+        sync()
+    res = op_ref.run_checked(mem, lr, run)
+    for name, ratio, nbad, worst in res:
+        print(f'{name}: worst |err| / bound = {ratio:.4g} ({nbad} over)')
+    assert all(ratio <= 1.0 for _, ratio, _, _ in res), res
+
+
 @pytest.mark.parametrize('N,sizes,force', [
     (2, [(12, 20), (6, 10), (3, 5), (2, 3), (1, 2)], 0),          # every (level, image) row inside one or two pixel tiles
     (3, [(40, 52), (20, 26), (10, 13), (5, 7), (3, 4)], 0),       # rows that span many tiles, ragged ends
@@ -602,7 +615,8 @@ def test_groupnorm_relu_fwd_bwd(K):
 ])
 def test_groupnorm_statistics_from_the_conv_epilogue(K, N, sizes, force):
     """conv -> GN -> ReLU (ConvModule, anchor_free_head.py:104-133) with the statistics left by the convolution's epilogue
-    (dsl_conv_desc.gn_ws) against the two-pass GroupNorm on the same convolution output."""
+    (dsl_conv_desc.gn_ws) against the two-pass GroupNorm on the same convolution output; on the first row and the 128 x 128 tile
+    also against op_ref's float64 reference (the benchmark-size row is tests/test_step_replay_gpu.py's)."""
     L, ops = K
     g = torch.Generator().manual_seed(41)
     Cc = 256
@@ -625,7 +639,13 @@ def test_groupnorm_statistics_from_the_conv_epilogue(K, N, sizes, force):
             gd.conv_stats = 1
             gd._keep[5].fill_(0xff)                   # (nothing relies on a zeroed workspace: an unwritten record would read NaN)
         L.check(L.lib.dsl_conv2d(C.byref(cd), L.stream_ptr()), 'dsl_conv2d')
-        L.check(L.lib.dsl_groupnorm_relu_fwd(C.byref(gd), L.stream_ptr()), 'gn')
+        if fused and (force == 4 or sizes[0] == (12, 20)):
+            # the fused launch's y and (mean, rstd) under op_ref's bars: float64 statistics of the convolution's own bf16 output
+            sync()
+            mem = op_ref.Memory({'t': dict(pre=pre, y=y, stats=stats, ga=ga, be=be, ws=gd._keep[5])})
+            _gn_checked(mem, op_ref.gn_fwd_ref(mem, gd), lambda: L.check(L.lib.dsl_groupnorm_relu_fwd(C.byref(gd), L.stream_ptr()), 'gn'))
+        else:
+            L.check(L.lib.dsl_groupnorm_relu_fwd(C.byref(gd), L.stream_ptr()), 'gn')
         sync()
         outs.append((pre.clone(), y.clone(), stats.clone()))
         if fused:                                    # fixed-order reductions: a second run gives the same bits
@@ -657,7 +677,8 @@ def test_groupnorm_statistics_from_the_conv_epilogue(K, N, sizes, force):
 def test_groupnorm_backward_records_from_the_data_gradient_epilogue(K, N, sizes, force):
     """dY of a tower layer's GroupNorm + ReLU comes out of the next layer's data gradient: with dsl_conv_desc.gn_x that launch also
     leaves the norm's backward block records, and dsl_groupnorm_relu_bwd (conv_stats = 1) is one pass - against the two-pass
-    backward on the same dY (autograd of ConvModule conv -> GN -> ReLU, anchor_free_head.py:104-133)."""
+    backward on the same dY (autograd of ConvModule conv -> GN -> ReLU, anchor_free_head.py:104-133); on the first row and the
+    256 x 192 tile also against op_ref's float64 reference."""
     L, ops = K
     g = torch.Generator().manual_seed(43)
     Cc = 256
@@ -691,7 +712,15 @@ def test_groupnorm_backward_records_from_the_data_gradient_epilogue(K, N, sizes,
             gd._keep[5].fill_(0xff)
         for rep in range(2):
             L.check(L.lib.dsl_conv2d(C.byref(cd), L.stream_ptr()), 'dsl_conv2d')
-            L.check(L.lib.dsl_groupnorm_relu_bwd(C.byref(gd), L.stream_ptr()), 'gn bwd')
+            if fused and rep == 0 and (force == 1 or sizes[0] == (12, 20)):
+                # the fused launch's dx, dgamma, dbeta and dbias under op_ref's bars, on the data gradient's own dY
+                sync()
+                mem = op_ref.Memory({'t': dict(x=x, dy=dy, dx=dx, ga=ga, be=be, stats=stats, dgam=dgam, dbet=dbet, dbias=dbias,
+                                               ws=gd._keep[5])})
+                _gn_checked(mem, op_ref.gn_bwd_ref(mem, gd),
+                            lambda: L.check(L.lib.dsl_groupnorm_relu_bwd(C.byref(gd), L.stream_ptr()), 'gn bwd'))
+            else:
+                L.check(L.lib.dsl_groupnorm_relu_bwd(C.byref(gd), L.stream_ptr()), 'gn bwd')
             sync()
             if rep == 0:
                 outs.append([t.clone() for t in (dy, dx, dgam, dbet, dbias)])

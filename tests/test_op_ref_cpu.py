@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gn_cases
 import op_ref as R
 
 F64 = torch.float64
@@ -240,9 +241,11 @@ def test_wgrad_strided_and_shared_group():
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # GroupNorm + ReLU, 32 groups, two segments
-def _gn_case(n=2, segs=((6, 10), (3, 5)), c=256, G=32, seed=3):
+def _gn_case(n=2, segs=((6, 10), (3, 5)), c=256, G=32, seed=3, structured=False):
     g = torch.Generator().manual_seed(seed)
     tot = sum(n * h * w for h, w in segs)
+    if structured:         # the inputs of tests/test_groupnorm_gpu.py: offset groups, dy correlated with xhat, no ReLU decision on the edge
+        return (n, list(segs), c, G, tot) + gn_cases.gn_inputs(n, segs, c, G, seed=seed)
     x = (torch.randn(tot * c, generator=g) * 2 + 0.5).bfloat16()
     gamma, beta = torch.rand(c, generator=g) + 0.5, torch.randn(c, generator=g) * 0.3
     dy = torch.randn(tot * c, generator=g).bfloat16()
@@ -276,8 +279,16 @@ def _gn_desc(n, segs, c, G, x, y, gamma, beta, stats, **kw):
     return types.SimpleNamespace(**d)
 
 
-def test_groupnorm_forward_and_backward_match_autograd():
-    n, segs, c, G, tot, x, gamma, beta, dy = _gn_case()
+# the one earlier geometry with its centred inputs, then what tests/test_groupnorm_gpu.py leans on the references for: its (C, groups)
+# pairs and its 65-row five-level geometry, on its inputs
+GN_GEOMETRIES = [dict()] + [dict(n=2, segs=((5, 7), (2, 3)), c=c, G=G, seed=11 + i, structured=True)
+                            for i, (c, G) in enumerate(gn_cases.CHANNELS)] + \
+    [dict(n=13, segs=gn_cases.TINY5, c=256, G=32, seed=19, structured=True)]
+
+
+@pytest.mark.parametrize('geo', GN_GEOMETRIES, ids=lambda g: 'N{n}-C{c}-G{G}'.format(**g) if g else 'centred')
+def test_groupnorm_forward_and_backward_match_autograd(geo):
+    n, segs, c, G, tot, x, gamma, beta, dy = _gn_case(**geo)
     y_t, st_t, dx_t, dg_t, db_t = _gn_torch(n, segs, c, G, x, gamma, beta, dy)
     y = torch.zeros(tot * c, dtype=torch.bfloat16)
     stats = st_t.float()
@@ -289,11 +300,22 @@ def test_groupnorm_forward_and_backward_match_autograd():
     assert torch.allclose(f.outs[1].ref, st_t, rtol=1e-12, atol=1e-12)
     b = R.gn_bwd_ref(mem, _gn_desc(n, segs, c, G, x, None, gamma, beta, stats, dy=dy, dx=dx, dgamma=dg, dbeta=db, dbias=dbias))
     o = {k.name.split('.')[-1]: k for k in b.outs}
-    # (the reference takes the stored fp32 statistics, autograd the exact ones: 2^-24-relative apart)
-    assert torch.allclose(o['dx'].ref, dx_t, rtol=1e-5, atol=1e-6)
-    assert torch.allclose(o['dgamma'].ref, dg_t, rtol=1e-5, atol=1e-5)
+    # (the reference takes the stored fp32 statistics, autograd the exact ones: 2^-24-relative apart.  On the offset inputs that moves
+    # xhat by 2^-24 xa with xa = (|x| + |mean|) rstd up to 40, 2.4e-6, and each term of dx, dgamma and dbias by that share of its
+    # size: the absolute bars there are 4e-5 of the output's largest element.  No ReLU decision can differ: the inputs keep
+    # every one 2^-16 relative from the edge.)
+    if geo.get('structured'):
+        ratio, sigma = gn_cases.group_statistics(x, n, segs, c, G)
+        assert float(ratio.max()) > 12 and float(ratio.min()) < 1
+        assert sigma.numel() < 16 or (float(sigma.min()) < 0.2 and float(sigma.max()) > 2)
+        assert bool((gamma == 0).any()) and bool((gamma < 0).any()) and bool((beta < -9).any()) and bool((beta > 9).any())
+        a_dx, a_dg, a_dbi = (4e-5 * float(t.abs().max()) for t in (dx_t, dg_t, dx_t.sum(0)))
+    else:
+        a_dx, a_dg, a_dbi = 1e-6, 1e-5, 1e-5
+    assert torch.allclose(o['dx'].ref, dx_t, rtol=1e-5, atol=a_dx)
+    assert torch.allclose(o['dgamma'].ref, dg_t, rtol=1e-5, atol=a_dg)
     assert torch.allclose(o['dbeta'].ref, db_t, rtol=1e-9, atol=1e-9)
-    assert torch.allclose(o['dbias'].ref, dx_t.sum(0), rtol=1e-5, atol=1e-5)
+    assert torch.allclose(o['dbias'].ref, dx_t.sum(0), rtol=1e-5, atol=a_dbi)
     for oo in b.outs:          # the autograd values pass their own bars
         ref = {'dx': dx_t, 'dgamma': dg_t, 'dbeta': db_t, 'dbias': dx_t.sum(0)}[oo.name.split('.')[-1]]
         assert R.compare(ref.view_as(oo.ref).to(oo.dtype).to(F64), oo.ref, oo.bound())[1] == 0, oo.name
