@@ -623,7 +623,8 @@ class _TrainStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, det, plan):
         ctx.det, ctx.plan, ctx.eager = det, plan, bool(getattr(det, '_eager_now', False))      # were the backward lists queued already?
-        ctx.n_losses = 4 if (plan.lossplan.desc.soft_weight != 0.0 or plan.lossplan.ld is not None) else 3      # (sisoft / loss_ld)
+        kind = plan.lossplan.kind
+        ctx.n_losses = len(kind.loss_keys) + (kind.sisoft and plan.lossplan.desc.soft_weight != 0.0)      # (+ loss_sisoft)
         # the loss terms in log order and, last, their sum - written by the loss kernel's finalize pass (dsl_fcos_desc.logvec)
         return plan.lossplan.logvec[:ctx.n_losses + 1].clone()
 
@@ -828,9 +829,9 @@ class FCOS(nn.Module):
         lp = plan.lossplan
         sw = head.effective_soft_weight(N)
         ws = self.world_size
-        # (a PAA head normalises by this rank's own stats: the reference does not reduce_mean there, paa_head.py:173-193)
+        kind = lp.kind      # (params.HEAD_KINDS: `exchange` says where the ranks' stats[0:2] are summed, None = this rank's own count)
         lp.configure(loss_weight=head.loss_weight, soft_weight=sw, grad_scale=self.loss_scale / ws,
-                     inv_world=1.0 if lp.paa is not None else 1.0 / ws)
+                     inv_world=1.0 / ws if kind.exchange else 1.0)
         pipe = self.pipeline_prefix and plan.prefix is not None
         if pipe:
             # frozen prefix of THIS step on its own stream: it waits for the previous backward's data-gradient chain only (named
@@ -876,26 +877,9 @@ class FCOS(nn.Module):
             plan.bind_image(img, half_last=half_scale_copy)
             fwd = plan.fwd
         plan.fp8_warm(fwd)
-        work = None
         # an ATSS head's valid anchors come from each image's pad_shape (atss_head.py:615-617); absent: the batch tensor's size
         pad = [tuple(m.get('pad_shape', (H, W)))[:2] for m in img_metas] if lp.atss is not None else None
-        if lp.gfl is not None:
-            # a GFL head's second normaliser, the sum of the positives' best class scores, exists only behind the predictors: the
-            # quality pass, then the 2-float all-reduce of (num_total, that sum), then the loss (gfl_head.py:348-366)
-            fwd.run()
-            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
-            plan.assign_ops.run()
-            plan.quality_ops.run()
-            if ws > 1 and not self.comm_off:
-                self._all_reduce_async(lp.stats[:2], after_current=True).wait()
-        elif lp.paa is not None:
-            # a PAA head takes the GFL branch's order - forward, targets, first assignment, then the candidates' losses and the
-            # reassignment behind the predictors (paa_head.py:141-157) - and exchanges no normaliser
-            fwd.run()
-            lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
-            plan.assign_ops.run()
-            plan.quality_ops.run()
-        elif ws > 1:
+        if kind.exchange == 'forward' and ws > 1:
             # target assignment first: the reduce_mean of (num_pos, sum centerness targets) - one 2-float all-reduce
             # (fcos_head.py:264-274) - then runs under the forward pass
             lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
@@ -906,10 +890,16 @@ class FCOS(nn.Module):
                 work.wait()
         else:
             # one process: target upload + assignment go behind the forward pass on the caller's stream, into the time it
-            # would otherwise spend waiting for the regression tower on the side stream
+            # would otherwise spend waiting for the regression tower on the side stream.  A kind with a middle pass, on any number
+            # of ranks: the same order, then that pass behind the predictors and, where the kind exchanges there, the 2-float
+            # all-reduce of (num_total, the quality pass's sum), waited for in front of the loss
             fwd.run()
             lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
             plan.assign_ops.run()
+            if kind.middle:
+                plan.quality_ops.run()
+            if kind.exchange == 'middle' and ws > 1 and not self.comm_off:
+                self._all_reduce_async(lp.stats[:2], after_current=True).wait()
         plan.loss_ops.run()
         eager_now = False
         if self.eager_backward and torch.is_grad_enabled():
@@ -921,12 +911,7 @@ class FCOS(nn.Module):
                 eager_now = True
         self._eager_now = eager_now
         out = _TrainStepFn.apply(self._anchor, self, plan)
-        third = 'loss_dfl' if lp.gfl is not None else 'loss_iou' if lp.paa is not None else 'loss_centerness'
-        losses = _LossDict(loss_cls=out[0], loss_bbox=out[1], **{third: out[2]})
-        if sw != 0.0:
-            losses['loss_sisoft'] = out[3]
-        elif lp.ld is not None:
-            losses['loss_ld'] = out[3]
+        losses = _LossDict((k, out[i]) for i, k in enumerate(kind.loss_keys + (('loss_sisoft',) if kind.sisoft and sw != 0.0 else ())))
         losses.vec = out[:len(losses)]      # the same scalars as ONE tensor: lets _parse_losses avoid per-key device ops
         losses.vec_total = out              # ... and with their sum (the loss kernel's) as the last element: no device op at all
         return losses
@@ -1106,9 +1091,8 @@ class FCOS(nn.Module):
 
     def aug_test(self, imgs, img_metas, rescale=False):
         """detectors/single_stage.py:109-135: `imgs` / `img_metas` hold one entry per view, each with ONE image."""
-        if getattr(self.bbox_head.options, 'head_kind', 'fcos') == 'paa':
-            raise NotImplementedError('PAAHead does not support test-time augmentation (aug_test): PAA only supports with_nms=True '
-                                      '(paa_head.py:536-538)')
+        if self.store.head.kind.aug_refusal:
+            raise NotImplementedError(self.store.head.kind.aug_refusal)
         from .sweep import aug_test
         self.store.wait_pending()
         return aug_test(self, imgs, img_metas, rescale)
@@ -1232,7 +1216,7 @@ class KnowledgeDistillationSingleStageDetector(GFL):
         tm = teacher_config['model'] if 'model' in teacher_config else teacher_config
         teacher = build_detector(dict(tm))
         th = getattr(getattr(teacher, 'store', None), 'head', None)
-        _expect(isinstance(teacher, FCOS) and th is not None and th.head_kind == 'gfl',
+        _expect(isinstance(teacher, FCOS) and th is not None and th.kind.dist_reg,
                 f'teacher_config: a detector with a GFL-family head (GFLHead / LDHead), got {type(teacher).__name__} with '
                 f'{type(getattr(teacher, "bbox_head", None)).__name__}')
         sh = self.store.head

@@ -162,11 +162,9 @@ class OpList:
         """d: a head's dsl_fcos_desc, for a GFL / LD head the first member of its dsl_gfl_desc / dsl_ld_desc (dsl_head_loss)."""
         self._add(L.OP_LOSS, d)
 
-    def gfl_quality(self, gfl):
-        self._add(L.OP_GFL_QUALITY, gfl)
-
-    def paa_refine(self, paa):
-        self._add(L.OP_PAA_REFINE, paa)
+    def head_middle(self, kind, d):
+        """kind: OP_GFL_QUALITY / OP_PAA_REFINE (a head kind's `middle`); d: the dsl_gfl_desc / dsl_paa_desc."""
+        self._add(kind, d)
 
     def maxpool(self, x, y, n, h, w, c):
         self._add(L.OP_MAXPOOL, i=(n, h, w, c), p=(x, y))
@@ -250,17 +248,14 @@ class Plan:
             if self._fside:             # the regression tower's side stream: joined here, not at the end of the forward list,
                 self.loss_ops.join(self._fside)       # so that target upload + assignment run while it finishes
             self.loss_ops.prof(4, 1)
-            # a GFL head: the quality pass (score, weight, stats[1]) sits between the predictors and the exchange of stats[0:2]
-            # between ranks, which the detector runs between these two lists (gfl_head.py:348-366)
+            # a kind with a middle pass.  GFL: the quality pass (score, weight, stats[1]) sits between the predictors and the exchange
+            # of stats[0:2] between ranks, which the detector runs between these two lists (gfl_head.py:348-366).  PAA: the candidates'
+            # losses and the reassignment sit in the same place, behind the predictors and the first assignment (paa_head.py:141-157);
+            # nothing crosses ranks between the two lists
             self.quality_ops = None
-            if self.lossplan.gfl is not None:
+            if self.lossplan.kind.middle:
                 self.quality_ops, self.loss_ops = self.loss_ops, OpList()
-                self.quality_ops.gfl_quality(self.lossplan.gfl)
-            elif self.lossplan.paa is not None:
-                # a PAA head: the candidates' losses and the reassignment sit where GFL's quality pass does, behind the predictors
-                # and the first assignment (paa_head.py:141-157); nothing crosses ranks between the two lists
-                self.quality_ops, self.loss_ops = self.loss_ops, OpList()
-                self.quality_ops.paa_refine(self.lossplan.paa)
+                self.quality_ops.head_middle(self.lossplan.kind.middle[0], self.lossplan.ext)
             self.loss_ops.loss(self.lossplan.desc)
             # Backward op lists.  The data-gradient chain runs on the caller's stream; every weight gradient is
             # forked onto the library's side stream (its inputs - the forward activation and a gradient buffer that is
@@ -546,7 +541,7 @@ class Plan:
         # the regression predictor four, ParamStore.ctr_on_cls - the same two launches either way)
         ncls, cls_pad, cls_ld = st.cls_rows, st.cls_pad, st.logit_ld
         nreg = st.reg_rows
-        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + (nreg if st.gfl else 5)) * 2304)
+        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + (nreg if st.head.kind.dist_reg else 5)) * 2304)
         self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + st.reg_ld) * 4.0
         f.prof(4, 0, self._head_flops, self._head_bytes)
         fp8 = getattr(st, 'fp8', None)

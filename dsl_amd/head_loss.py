@@ -10,7 +10,7 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .params import class_layout
+from .params import HeadOptions, class_layout
 
 STRIDES = (8, 16, 32, 64, 128)
 REGRESS_RANGES = ((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8))   # fcos_head.py:61-62
@@ -26,29 +26,24 @@ class FcosLossPlan:
         """head: params.HeadOptions (None = the default head).  centerness_on_reg=False: the centerness logit is column
         round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls.  The head's loss
         settings (box_loss, focal gamma / alpha, the loss weights) go into the descriptor: losses, logvec and the gradients are the
-        weighted ones.  An ATSS head (head.assigner == 'atss'): the assignment is dsl_atss_assign, fed the images' pad_shape
-        (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554).
-        A GFL head (head.head_kind == 'gfl'): the descriptor is a dsl_gfl_desc (`gfl`, whose first member is `desc`), the box
-        predictor's rows are 4 (reg_max + 1) floats / round_up(that, 64) gradient columns wide, quality() runs between the predictors
-        and the exchange of stats[0:2] and writes stats[1], loss() is dsl_gfl_loss; losses = (cls, bbox, dfl, 0).
-        An LD head (a GFL head with head.ld_weight set): the dsl_gfl_desc is the first member of a dsl_ld_desc (`ld`), bind_soft() names
-        the teacher's box predictor output, loss() is dsl_ld_loss; losses = (cls, bbox, dfl, ld), logvec has five elements.
-        A PAA head (head.head_kind == 'paa'): the descriptor is a dsl_paa_desc (`paa`, whose first member is `desc`) on an ATSS head's
-        buffers; assign() is dsl_paa_assign, refine() = dsl_paa_pos_loss + dsl_paa_reassign runs between the predictors and the loss,
-        loss() is dsl_paa_loss; losses = (cls, bbox, iou, 0); `cand_gt`, `pos_loss`, `iou_target`, `gmm_iters`, `gmm_flags` are its."""
+        weighted ones.  What the head's kind decides is in its record (params.HEAD_KINDS): the struct around `desc` and the
+        attributes that hold it (`gfl`, `ld`, `paa`; None on the other kinds), the box predictor's row widths, the kind's own buffers
+        (`score`, `weight`; `pos_loss`, `iou_target`, `cand_gt`, `gmm_iters`, `gmm_flags`; absent on the other kinds), middle(),
+        the entry of loss() and the length of logvec.  A kind with the ATSS layout: the assignment is fed the images' pad_shape
+        (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554).  An LD head:
+        bind_soft() names the teacher's box predictor output."""
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
-        self.head = head
-        self.gfl = self.ld = None
-        if head is not None and head.head_kind == 'gfl':
-            if head.ld_weight is not None:
-                self.ld = L.LdDesc()
-                self.ld.T, self.ld.w_ld = head.ld_T, head.ld_weight
-            self.gfl = self.ld.gfl if self.ld is not None else L.GflDesc()
-            self.LD_RC = 4 * (head.reg_max + 1)
-            self.LD_GRC = (self.LD_RC + 63) // 64 * 64
-        self.paa = L.PaaDesc() if head is not None and head.head_kind == 'paa' else None
+        self.head = head = head or HeadOptions()
+        self.kind = kind = head.kind
+        self.gfl = self.ld = self.paa = self.ext = None
+        inner = getattr(L, kind.loss_desc[0])()
+        for attr, member in zip(kind.loss_desc[1:], kind.loss_desc[2:] + ('fcos',)):
+            setattr(self, attr, inner)
+            self.ext, inner = inner, getattr(inner, member)
+        self.LD_RC = head.reg_layout()[1]
+        self.LD_GRC = (self.LD_RC + 63) // 64 * 64
         self.ctr_col = None
-        if head is not None and not head.centerness_on_reg:
+        if not head.centerness_on_reg:
             self.ctr_col = self.LD_CLS
             self.LD_CLS, self.LD_GCLS = self.LD_CLS + 4, (self.LD_CLS + 1 + 63) // 64 * 64
         self.num_classes = num_classes
@@ -83,7 +78,7 @@ class FcosLossPlan:
                             pad=torch.zeros(n, 2, dtype=torch.int32, pin_memory=pin), ev=None) for _ in range(4)]
         self._slot_i = 0
         self.desc = ops.fcos_desc(n=n, sizes=self.sizes, strides=strides, ranges=ranges, radius=radius,
-                                  num_classes=num_classes, into=self.gfl.fcos if self.gfl is not None else self.paa.fcos if self.paa is not None else None)
+                                  num_classes=num_classes, into=inner)
         ops.set_ptrs(self.desc, gt_boxes=self.gt_boxes, gt_labels=self.gt_labels, gt_off=self.gt_off,
                      labels=self.labels, bbox_targets=self.bbox_targets, assign_idx=self.assign_idx,
                      cls_weight=self.cls_weight, pos_weight=self.pos_weight, stats=self.stats,
@@ -91,39 +86,24 @@ class FcosLossPlan:
                      losses=self.losses, logvec=self.logvec)
         self.desc.ld_cls, self.desc.ld_rc = self.LD_CLS, self.LD_RC
         self.desc.ld_gcls, self.desc.ld_grc = self.LD_GCLS, self.LD_GRC
-        if head is not None:
-            self.desc.head_flags = head.flags()
-            # box kind, focal gamma / alpha, the three loss weights, wherever HEAD_LOSS_EXT is in the flags: a head off the default
-            # loss family, and every GFL head (dsl_gfl_loss reads w_cls / w_bbox / box_kind with no default to fall back to)
-            if not head.loss_is_default() or self.gfl is not None or self.paa is not None:
-                head.fill_loss_desc(self.desc)
+        self.desc.head_flags = head.flags()
+        # box kind, focal gamma / alpha, the three loss weights, wherever HEAD_LOSS_EXT is in the flags
+        if self.desc.head_flags & L.HEAD_LOSS_EXT:
+            head.fill_loss_desc(self.desc)
         if self.ctr_col is not None:
             self.desc.g_ctr, self.desc.ld_gctr = self.g_cls.data_ptr() + 2 * self.ctr_col, self.LD_GCLS
-        self.atss = head.atss_desc() if head is not None else None
+        self.atss = head.atss_desc()
         if self.atss is not None:
             self.pad_shapes = torch.zeros(n, 2, dtype=torch.int32, device=dev)
             self.npos = torch.zeros(n, dtype=torch.int32, device=dev)
             self.atss.max_gt, self.atss.pad_shapes, self.atss.npos = max_gt, L.ptr(self.pad_shapes), L.ptr(self.npos)
             self.desc.atss = C.addressof(self.atss)
-        if self.gfl is not None:
-            self.score = torch.zeros(M, dtype=torch.float32, device=dev)
-            self.weight = torch.zeros(M, dtype=torch.float32, device=dev)
-            g = self.gfl
-            g.reg_max, g.qfl_beta, g.w_dfl = head.reg_max, head.qfl_beta, head.dfl_weight
-            g.score, g.weight = L.ptr(self.score), L.ptr(self.weight)
-            if self.ld is None:
-                self.logvec = self.logvec[:4]      # cls, bbox, dfl, their sum (an LD head: cls, bbox, dfl, ld, their sum)
-        if self.paa is not None:
-            self.pos_loss = torch.zeros(M, dtype=torch.float32, device=dev)
-            self.iou_target = torch.zeros(M, dtype=torch.float32, device=dev)
-            self.cand_gt = torch.full((M,), -1, dtype=torch.int32, device=dev)
-            self.gmm_iters = torch.zeros(max_gt, dtype=torch.int32, device=dev)
-            self.gmm_flags = torch.zeros(max_gt, dtype=torch.int32, device=dev)
-            q = self.paa
-            q.pos_iou_thr = head.pos_iou_thr
-            q.pos_loss, q.iou_target, q.cand_gt = L.ptr(self.pos_loss), L.ptr(self.iou_target), L.ptr(self.cand_gt)
-            q.gmm_iters, q.gmm_flags = L.ptr(self.gmm_iters), L.ptr(self.gmm_flags)
-            self.logvec = self.logvec[:4]      # cls, bbox, iou, their sum
+        for attr, field, option in kind.scalars:
+            setattr(getattr(self, attr), field, getattr(head, option))
+        for name, dtype, length, fill in kind.buffers:
+            setattr(self, name, torch.full((getattr(self, length),), fill, dtype=dtype, device=dev))
+            setattr(self.ext, name, L.ptr(getattr(self, name)))
+        self.logvec = self.logvec[:len(kind.loss_keys) + kind.sisoft + 1]      # the terms in log order (cls, bbox, ...), their sum
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
         self.desc.workspace, self.desc.workspace_bytes = L.ptr(self.ws), need
@@ -203,18 +183,16 @@ class FcosLossPlan:
     def assign(self):
         L.check(L.lib.dsl_head_assign(C.byref(self.desc), L.stream_ptr()), 'dsl_head_assign')
 
-    def quality(self):
-        """GFL only: score / weight of the positives and stats[1] = sum of the weights (dsl_gfl_quality)."""
-        L.check(L.lib.dsl_gfl_quality(C.byref(self.gfl), L.stream_ptr()), 'dsl_gfl_quality')
+    def middle(self):
+        """The kind's pass between the predictors and the loss, what its op runs.  GFL / LD: score / weight of the positives and
+        stats[1] = sum of the weights; PAA: the candidates' losses, then the mixture fit and the reassignment."""
+        for name in self.kind.middle[1]:
+            L.check(getattr(L.lib, name)(C.byref(self.ext), L.stream_ptr()), name)
 
-    def refine(self):
-        """PAA only: the candidates' losses, then the mixture fit and the reassignment (what DSL_OP_PAA_REFINE runs)."""
-        L.check(L.lib.dsl_paa_pos_loss(C.byref(self.paa), L.stream_ptr()), 'dsl_paa_pos_loss')
-        L.check(L.lib.dsl_paa_reassign(C.byref(self.paa), L.stream_ptr()), 'dsl_paa_reassign')
+    quality = refine = middle
 
     def loss(self):
         """The entry point of the descriptor this plan built, not dsl_head_loss's choice by head_flags: a dsl_ld_desc whose flags lost
         DSL_HEAD_LD is then refused by dsl_ld_loss instead of running as a GFL head."""
-        name = ('dsl_ld_loss' if self.ld is not None else 'dsl_gfl_loss' if self.gfl is not None else
-                'dsl_paa_loss' if self.paa is not None else 'dsl_fcos_loss')
+        name = self.kind.loss_entry
         L.check(getattr(L.lib, name)(C.byref(self.desc), L.stream_ptr()), name)

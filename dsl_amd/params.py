@@ -12,6 +12,7 @@ into the flat buffers, so checkpoints and the EMA hook interoperate.
 Frozen tensors (stem, layer1, every BatchNorm) live in a second flat buffer (`frozen`).
 """
 import math
+from collections import namedtuple
 
 import torch
 
@@ -117,6 +118,73 @@ def class_layout(num_classes):
     return _round_up(num_classes, 64), _round_up(num_classes, 4)
 
 
+_ATSS_FIELDS = ('assigner', 'atss_topk', 'anchor_scale', 'delta_stds')
+_GFL_FIELDS = ('head_kind', 'reg_max', 'qfl_beta', 'dfl_weight')
+_F32, _I32 = torch.float32, torch.int32
+
+# What the dense heads differ in, one immutable record per kind (HeadOptions.kind); every site that serves a head reads its record:
+#   flags        kind flags of head_flags, beside the option flags.  A dsl_gfl_desc / dsl_paa_desc always carries the loss family
+#                (HEAD_LOSS_EXT: dsl_gfl_loss reads w_cls / w_bbox / box_kind with no default to fall back to)
+#   atss         the ATSS layout is forced (assigner='atss', towers without bias, ...); a dsl_atss_desc is attached, set_targets needs
+#                pad_shapes and does not read ignore boxes
+#   fields       the kind's options, in key() / repr order behind FIELDS [+ LOSS_FIELDS]
+#   loss_desc    FcosLossPlan: the outermost ctypes struct, then the plan attributes that hold it and each wrapper nested in it as
+#                first member; the dsl_fcos_desc (`desc`) is member `fcos` of the last (of the struct itself where none is named)
+#   scalars      (plan attribute, descriptor field, option) set in those structs
+#   buffers      (name, dtype, length attribute, fill): a plan attribute and the like-named pointer of the innermost wrapper
+#   det_desc     DetectPlan: the outermost ctypes struct, then the member path to its dsl_det_desc (`desc`); the struct that holds
+#                the last member holds the dsl_atss_desc pointer, set where det_mask has HEAD_ATSS
+#   det_mask     dsl_det_desc.head_flags = flags() & det_mask;  det_fields: (field of the outermost struct, option)
+#   dist_reg     the box predictor emits 4 (reg_max + 1) distribution logits, fp32 rows as wide; otherwise 4 (+ centerness) rows, 8 wide
+#   names        module names of the class / box / centerness predictors under bbox_head
+#   middle       the pass between the predictors and the loss: (op kind, direct calls, all on the innermost wrapper), or None
+#   loss_entry   what FcosLossPlan.loss() calls;  loss_keys: forward_train's dict [+ loss_sisoft where `sisoft` and the
+#                step's soft weight is not 0]; logvec holds them [+ loss_sisoft] + the sum
+#   exchange     of stats[0:2] between ranks: 'forward' = issued behind the assignment, under the forward pass; 'middle' = behind the
+#                middle pass and waited for (a GFL head's second normaliser, the sum of the positives' best class scores, exists only
+#                behind the predictors, gfl_head.py:348-366); None = none, and inv_world = 1 (a PAA head normalises by this rank's own
+#                stats: the reference does not reduce_mean there, paa_head.py:173-193)
+#   aug_refusal  aug_test raises this
+# A new head adds a record and its kernels.
+HeadKind = namedtuple('HeadKind', 'name flags atss fields loss_desc scalars buffers det_desc det_mask det_fields dist_reg names middle '
+                                  'loss_entry loss_keys sisoft exchange aug_refusal')
+_FCOS = HeadKind(
+    name='fcos', flags=0, atss=False, fields=(),
+    loss_desc=('FcosDesc',), scalars=(), buffers=(),
+    det_desc=('DetDesc',), det_mask=L.HEAD_EXP_DECODE, det_fields=(),
+    dist_reg=False, names=('conv_cls', 'conv_reg', 'conv_centerness'),
+    middle=None, loss_entry='dsl_fcos_loss', loss_keys=('loss_cls', 'loss_bbox', 'loss_centerness'), sisoft=True,
+    exchange='forward', aug_refusal=None)
+_ATSS = _FCOS._replace(
+    name='atss', flags=L.HEAD_ATSS, atss=True, fields=_ATSS_FIELDS,
+    det_desc=('DetAtssDesc', 'det'), det_mask=L.HEAD_EXP_DECODE | L.HEAD_ATSS,
+    names=('atss_cls', 'atss_reg', 'atss_centerness'))      # (atss_head.py:83-91)
+_GFL = _ATSS._replace(
+    name='gfl', flags=L.HEAD_ATSS | L.HEAD_GFL | L.HEAD_LOSS_EXT, fields=_ATSS_FIELDS + _GFL_FIELDS,
+    loss_desc=('GflDesc', 'gfl'),
+    scalars=(('gfl', 'reg_max', 'reg_max'), ('gfl', 'qfl_beta', 'qfl_beta'), ('gfl', 'w_dfl', 'dfl_weight')),
+    buffers=(('score', _F32, 'M', 0), ('weight', _F32, 'M', 0)),
+    det_desc=('DetGflDesc', 'det'), det_mask=L.HEAD_GFL, det_fields=(('reg_max', 'reg_max'),),
+    dist_reg=True, names=('gfl_cls', 'gfl_reg', None),      # (gfl_head.py:128-133: no centerness predictor)
+    middle=(L.OP_GFL_QUALITY, ('dsl_gfl_quality',)), loss_entry='dsl_gfl_loss', loss_keys=('loss_cls', 'loss_bbox', 'loss_dfl'),
+    sisoft=False, exchange='middle')
+_LD = _GFL._replace(
+    name='ld', flags=_GFL.flags | L.HEAD_LD, fields=_GFL.fields + ('ld_weight', 'ld_T'),
+    loss_desc=('LdDesc', 'ld', 'gfl'), scalars=_GFL.scalars + (('ld', 'T', 'ld_T'), ('ld', 'w_ld', 'ld_weight')),
+    loss_entry='dsl_ld_loss', loss_keys=_GFL.loss_keys + ('loss_ld',))
+_PAA = _ATSS._replace(
+    name='paa', flags=L.HEAD_ATSS | L.HEAD_PAA | L.HEAD_LOSS_EXT, fields=_ATSS_FIELDS + ('head_kind', 'pos_iou_thr', 'score_voting'),
+    loss_desc=('PaaDesc', 'paa'), scalars=(('paa', 'pos_iou_thr', 'pos_iou_thr'),),
+    buffers=(('pos_loss', _F32, 'M', 0), ('iou_target', _F32, 'M', 0), ('cand_gt', _I32, 'M', -1),
+             ('gmm_iters', _I32, 'max_gt', 0), ('gmm_flags', _I32, 'max_gt', 0)),
+    det_desc=('DetPaaDesc', 'atss', 'det'), det_mask=L.HEAD_EXP_DECODE | L.HEAD_ATSS | L.HEAD_PAA,
+    det_fields=(('score_voting', 'score_voting'),),
+    middle=(L.OP_PAA_REFINE, ('dsl_paa_pos_loss', 'dsl_paa_reassign')), loss_entry='dsl_paa_loss',
+    loss_keys=('loss_cls', 'loss_bbox', 'loss_iou'), sisoft=False, exchange=None,
+    aug_refusal='PAAHead does not support test-time augmentation (aug_test): PAA only supports with_nms=True (paa_head.py:536-538)')
+HEAD_KINDS = {k.name: k for k in (_FCOS, _ATSS, _GFL, _LD, _PAA)}
+
+
 class HeadOptions:
     """The FCOSHead options that reach the kernels and the parameter layout, fixed per model (a ParamStore holds one; every plan
     of that store is built for it).  The defaults are the fcos_semi "tricks" head; configs/fcos/fcos_r50_caffe_fpn_gn-head_*.py
@@ -154,14 +222,11 @@ class HeadOptions:
     network, parameter layout, decode and predictor names (assigner='atss' is forced; its centerness predictor is the IoU-prediction
     branch) whose targets come from MaxIoUAssigner and the Gaussian-mixture reassignment; atss_topk is PAAHead's per-level topk:
       pos_iou_thr        MaxIoUAssigner pos_iou_thr == neg_iou_thr, in (0, 1)
-      score_voting       detection: score voting behind the NMS (paa_head.py:608-673)"""
+      score_voting       detection: score voting behind the NMS (paa_head.py:608-673)
+    `kind` is the record of the resolved head kind (HEAD_KINDS above): what follows from "which head is this" is read there."""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
     BOX_KINDS = dict(giou=L.BOX_GIOU, iou=L.BOX_IOU_LOG, iou_linear=L.BOX_IOU_LINEAR, diou=L.BOX_DIOU, ciou=L.BOX_CIOU)
-    ATSS_FIELDS = ('assigner', 'atss_topk', 'anchor_scale', 'delta_stds')
-    GFL_FIELDS = ('head_kind', 'reg_max', 'qfl_beta', 'dfl_weight')
-    LD_FIELDS = ('ld_weight', 'ld_T')
-    PAA_FIELDS = ('head_kind', 'pos_iou_thr', 'score_voting')
 
     def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
                  box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0,
@@ -169,12 +234,16 @@ class HeadOptions:
                  head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0, pos_iou_thr=0.1, score_voting=True):
         if head_kind not in ('fcos', 'gfl', 'paa'):
             raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos', 'gfl' or 'paa', got {head_kind!r}")
+        if assigner not in ('fcos', 'atss'):
+            raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
+        if ld_weight is not None and head_kind != 'gfl':
+            raise NotImplementedError(f"dsl_amd hot path: ld_weight is an option of head_kind='gfl' (LDHead), got head_kind={head_kind!r}")
+        # the resolved kind: ld_weight makes a GFL head an LD head, assigner='atss' an FCOS head an ATSS head
+        self.kind = kind = HEAD_KINDS['ld' if ld_weight is not None else assigner if head_kind == 'fcos' else head_kind]
         self.head_kind = head_kind
         self.reg_max, self.qfl_beta, self.dfl_weight = reg_max, float(qfl_beta), float(dfl_weight)
         self.ld_weight, self.ld_T = None, 10.0
         if ld_weight is not None:
-            if head_kind != 'gfl':
-                raise NotImplementedError(f"dsl_amd hot path: ld_weight is an option of head_kind='gfl' (LDHead), got head_kind={head_kind!r}")
             if not (isinstance(ld_weight, (int, float)) and 0.0 <= float(ld_weight) < float('inf')):
                 raise NotImplementedError(f'dsl_amd hot path: ld_weight must be a finite number >= 0, got {ld_weight!r}')
             if not (isinstance(ld_T, (int, float)) and 1.0 <= float(ld_T) < float('inf')):
@@ -193,22 +262,15 @@ class HeadOptions:
                                     ('focal_gamma', focal_gamma, 2.0), ('focal_alpha', focal_alpha, 0.25), ('ctr_weight', ctr_weight, 1.0)):
                 if val != want:
                     raise NotImplementedError(f"dsl_amd hot path: head_kind='gfl' does not read {name} (got {val!r}; leave it at {want!r})")
-            if assigner not in ('fcos', 'atss'):
-                raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
-            assigner = 'atss'      # (the default 'fcos' stands for "not given": a GFL head's targets are ATSS's)
         self.pos_iou_thr, self.score_voting = float(pos_iou_thr), bool(score_voting)
-        if head_kind == 'paa':
-            if not (isinstance(pos_iou_thr, (int, float)) and 0.0 < self.pos_iou_thr < 1.0):
-                raise NotImplementedError(f'dsl_amd hot path: pos_iou_thr must be a number in (0, 1), got {pos_iou_thr!r}')
-            if assigner not in ('fcos', 'atss'):
-                raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
-            assigner = 'atss'      # (the anchors, valid flags, decode and parameter layout of an ATSS head)
-        if assigner not in ('fcos', 'atss'):
-            raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
-        self.assigner = assigner
+        if head_kind == 'paa' and not (isinstance(pos_iou_thr, (int, float)) and 0.0 < self.pos_iou_thr < 1.0):
+            raise NotImplementedError(f'dsl_amd hot path: pos_iou_thr must be a number in (0, 1), got {pos_iou_thr!r}')
+        # (the default 'fcos' stands for "not given": a GFL head's targets are ATSS's, a PAA head has the anchors, valid flags, decode
+        # and parameter layout of an ATSS head)
+        self.assigner = 'atss' if kind.atss else assigner
         self.atss_topk, self.anchor_scale = int(atss_topk), float(anchor_scale)
         self.delta_stds = tuple(float(v) for v in delta_stds)
-        if assigner == 'atss':
+        if kind.atss:
             if not 1 <= self.atss_topk <= L.ATSS_MAX_TOPK:
                 raise NotImplementedError(f'dsl_amd hot path: atss_topk must be in 1..{L.ATSS_MAX_TOPK}, got {atss_topk!r}')
             if not (0.0 < self.anchor_scale < float('inf')):
@@ -233,14 +295,13 @@ class HeadOptions:
         (box_eps counts for DIoU / CIoU only)."""
         return self.loss_key()[2:] == (2.0, 0.25, 1.0, 1.0, 1.0) and self.box_loss in ('giou', 'iou')
 
+    def key_fields(self):
+        """The five FIELDS for every head that existed before the loss family; the loss settings follow only where one is set, then the
+        kind's own options."""
+        return (self.FIELDS if self.loss_is_default() else self.FIELDS + self.LOSS_FIELDS) + self.kind.fields
+
     def key(self):
-        """The five FIELDS for every head that existed before the loss family; the loss settings follow only where one is set."""
-        k = tuple(getattr(self, f) for f in self.FIELDS)
-        k = k if self.loss_is_default() else k + self.loss_key()
-        k = k + tuple(getattr(self, f) for f in self.ATSS_FIELDS) if self.assigner == 'atss' else k
-        k = k + tuple(getattr(self, f) for f in self.GFL_FIELDS) if self.head_kind == 'gfl' else k
-        k = k + tuple(getattr(self, f) for f in self.PAA_FIELDS) if self.head_kind == 'paa' else k
-        return k + tuple(getattr(self, f) for f in self.LD_FIELDS) if self.ld_weight is not None else k
+        return tuple(getattr(self, f) for f in self.key_fields())
 
     def is_default(self):
         return self.key() == HeadOptions().key()
@@ -248,15 +309,18 @@ class HeadOptions:
     def flags(self):
         """dsl_fcos_desc.head_flags / dsl_det_desc.head_flags."""
         return ((0 if self.center_sampling else L.HEAD_INSIDE_BOX) | (0 if self.norm_on_bbox else L.HEAD_RAW_TARGETS | L.HEAD_EXP_DECODE)
-                | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT)
-                | (L.HEAD_ATSS if self.assigner == 'atss' else 0)
-                | (L.HEAD_GFL | L.HEAD_LOSS_EXT if self.head_kind == 'gfl' else 0)       # (a dsl_gfl_desc always carries its loss settings)
-                | (L.HEAD_PAA | L.HEAD_LOSS_EXT if self.head_kind == 'paa' else 0)       # (so does a dsl_paa_desc)
-                | (L.HEAD_LD if self.ld_weight is not None else 0))
+                | (L.HEAD_IOU_LOSS if self.box_loss == 'iou' else 0) | (0 if self.loss_is_default() else L.HEAD_LOSS_EXT) | self.kind.flags)
+
+    def reg_layout(self):
+        """(rows, fp32 row stride) of the box predictor: conv_reg (4) + conv_centerness (1, unless it sits on the classification
+        predictor), rows 8 wide; a distribution head's 4 (reg_max + 1) logits, rows exactly that wide, no centerness."""
+        if self.kind.dist_reg:
+            return 4 * (self.reg_max + 1), 4 * (self.reg_max + 1)
+        return 5 if self.centerness_on_reg else 4, 8
 
     def atss_desc(self):
         """A dsl_atss_desc with the head's settings (None for an FCOS head); the caller fills max_gt, pad_shapes and npos."""
-        if self.assigner != 'atss':
+        if not self.kind.atss:
             return None
         a = L.AtssDesc()
         a.topk, a.anchor_scale = self.atss_topk, self.anchor_scale
@@ -271,12 +335,7 @@ class HeadOptions:
         d.w_cls, d.w_bbox, d.w_ctr = self.cls_weight, self.bbox_weight, self.ctr_weight
 
     def __repr__(self):
-        fields = self.FIELDS if self.loss_is_default() else self.FIELDS + self.LOSS_FIELDS
-        fields += self.ATSS_FIELDS if self.assigner == 'atss' else ()
-        fields += self.GFL_FIELDS if self.head_kind == 'gfl' else ()
-        fields += self.LD_FIELDS if self.ld_weight is not None else ()
-        fields += self.PAA_FIELDS if self.head_kind == 'paa' else ()
-        return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in fields) + ')'
+        return 'HeadOptions(' + ', '.join(f'{f}={getattr(self, f)}' for f in self.key_fields()) + ')'
 
 
 def head_specs(conv_bias=True):
@@ -305,13 +364,10 @@ class ParamStore:
                 raise NotImplementedError(f'dsl_amd hot path: centerness_on_reg=False needs num_classes <= {MAX_CLASSES - 4} (its logit is a '
                                           f'column of the classification predictor, at most {MAX_CLASSES} columns), got {num_classes}')
             self.cls_pad = _round_up(self.cls_rows, 64)
-        # the box predictor: conv_reg (4) + conv_centerness (1, unless it sits on the classification predictor) in 64 stored rows whose
-        # fp32 output rows are 8 wide; a GFL head's 4 (reg_max + 1) distribution logits in one or two 64-row tiles (the launch shapes
-        # of a 128-row classification predictor), fp32 rows exactly that wide, no centerness
-        self.gfl = self.head.head_kind == 'gfl'
-        self.reg_rows = 4 * (self.head.reg_max + 1) if self.gfl else (4 if self.ctr_on_cls else 5)
+        # the box predictor (HeadOptions.reg_layout) in 64 stored rows; a GFL head's 4 (reg_max + 1) distribution logits in one or two
+        # 64-row tiles (the launch shapes of a 128-row classification predictor)
+        self.reg_rows, self.reg_ld = self.head.reg_layout()
         self.reg_pad = _round_up(self.reg_rows, 64)
-        self.reg_ld = self.reg_rows if self.gfl else 8
         self.defer_head = False       # deferred head update (FlatSGD._sync_defer decides; engine.Plan.defer reads it)
         self._pending_ev = None
         bspecs = backbone_specs() if backbone == 'resnet' else rla_backbone_specs()
@@ -457,19 +513,16 @@ class ParamStore:
             bn(n)
         cw, cb = self.tview('head.cls_w', tb), self.tview('head.cls_b', tb)
         rw, rb = self.tview('head.regctr_w', tb), self.tview('head.regctr_b', tb)
-        # the predictors' names: FCOSHead's conv_*, ATSSHead's atss_* (atss_head.py:83-91)
-        pc, pr, pt = [f'bbox_head.{n}' for n in self.predictor_names()]
+        pc, pr, pt = [n and f'bbox_head.{n}' for n in self.predictor_names()]
         out[pc + '.weight'] = cw[:self.num_classes].permute(0, 3, 1, 2)
         out[pc + '.bias'] = cb[:self.num_classes]
-        nbox = self.reg_rows if self.gfl else 4
+        nbox = self.reg_rows if self.head.kind.dist_reg else 4
         out[pr + '.weight'] = rw[:nbox].permute(0, 3, 1, 2)
         out[pr + '.bias'] = rb[:nbox]
-        if self.gfl:              # (gfl_head.py:128-133: no centerness predictor)
-            pass
-        elif self.ctr_on_cls:       # (row 4 of the regression predictor is then zero and stays zero)
+        if pt and self.ctr_on_cls:       # (row 4 of the regression predictor is then zero and stays zero)
             out[pt + '.weight'] = cw[self.cls_ld:self.cls_ld + 1].permute(0, 3, 1, 2)
             out[pt + '.bias'] = cb[self.cls_ld:self.cls_ld + 1]
-        else:
+        elif pt:
             out[pt + '.weight'] = rw[4:5].permute(0, 3, 1, 2)
             out[pt + '.bias'] = rb[4:5]
         sc = self.tview('head.scales', tb)
@@ -479,11 +532,7 @@ class ParamStore:
 
     def predictor_names(self):
         """Module names of the class, box and centerness predictors under bbox_head (a GFL head has no centerness predictor)."""
-        if self.gfl:
-            return 'gfl_cls', 'gfl_reg', None
-        if self.head.assigner == 'atss':
-            return 'atss_cls', 'atss_reg', 'atss_centerness'
-        return 'conv_cls', 'conv_reg', 'conv_centerness'
+        return self.head.kind.names
 
     def wait_pending(self):
         """Deferred head update (FlatSGD, Plan.defer): the last optimizer step may still be updating the head + FPN bucket on the

@@ -16,37 +16,36 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .params import HeadOptions, class_layout
 
 
 class DetectPlan:
     def __init__(self, n, sizes, strides, device, num_classes=80, nms_pre=1000, max_per_img=100, score_thr=0.05,
-                 iou_thr=0.5, ld_cls=80, ld_rc=8, head_flags=0, ctr_col=None, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, atss=None, reg_max=None, score_voting=None):
-        """atss: the dsl_atss_desc of an ATSS head (params.HeadOptions.atss_desc), with HEAD_ATSS in head_flags.
-        score_voting: of a PAA head (True / False; None = not a PAA head), with HEAD_ATSS | HEAD_PAA in head_flags and `atss` set.
-        reg_max: of a GFL head, with HEAD_GFL alone in head_flags and ld_rc >= 4 (reg_max + 1)."""
-        d = L.DetDesc()
-        self.atss = atss
-        if reg_max is not None:      # dsl_det_gfl_desc: `d` is its first member (and keeps it alive)
-            self._ext = L.DetGflDesc()
-            self._ext.reg_max = reg_max
-            d = self._ext.det
-        elif atss is not None and score_voting is not None:      # dsl_det_paa_desc around a dsl_det_atss_desc: `d` is the innermost first member
-            self._ext = L.DetPaaDesc()
-            self._ext.atss.atss, self._ext.score_voting = C.addressof(atss), int(bool(score_voting))
-            d = self._ext.atss.det
-        elif atss is not None:      # dsl_det_atss_desc: `d` is its first member (and keeps it alive)
-            self._ext = L.DetAtssDesc()
-            self._ext.atss = C.addressof(atss)
-            d = self._ext.det
+                 iou_thr=0.5, ld_cls=80, nms_method=0, soft_sigma=0.0, soft_min_score=0.0, head=None):
+        """head: params.HeadOptions (None = the default head).  Its kind's record (params.HEAD_KINDS) names the struct around the
+        dsl_det_desc `desc` (`_ext` keeps it alive), whether the head's dsl_atss_desc (`atss`) is attached, and the flags that reach
+        the kernels: DSL_HEAD_EXP_DECODE (norm_on_bbox=False), DSL_HEAD_ATSS (anchor-delta decode), DSL_HEAD_PAA, or DSL_HEAD_GFL alone
+        with rows of 4 (reg_max + 1) floats."""
+        head = head or HeadOptions()
+        kind = head.kind
+        self._ext = d = getattr(L, kind.det_desc[0])()
+        for member in kind.det_desc[1:]:
+            holder, d = d, getattr(d, member)
+        self.atss = head.atss_desc() if kind.det_mask & L.HEAD_ATSS else None
+        if self.atss is not None:
+            holder.atss = C.addressof(self.atss)
+        for field, option in kind.det_fields:
+            setattr(self._ext, field, getattr(head, option))
         d.nms_method, d.soft_sigma, d.soft_min_score = nms_method, soft_sigma, soft_min_score      # L.NMS_*; all zero: the hard NMS
         d.nlvl, d.n = len(sizes), n
         d.h, d.w = L.seg5([s[0] for s in sizes]), L.seg5([s[1] for s in sizes])
         d.stride = L.seg5(strides)
         d.num_classes, d.nms_pre, d.max_per_img = num_classes, nms_pre, max_per_img
         d.score_thr, d.iou_thr = score_thr, iou_thr
-        d.ld_cls, d.ld_rc = ld_cls, ld_rc
-        d.head_flags = head_flags      # DSL_HEAD_EXP_DECODE: norm_on_bbox=False; DSL_HEAD_ATSS: anchor-delta decode
-        self.ctr_col = ctr_col         # centerness_on_reg=False: the centerness logit is this column of the logits' rows
+        d.ld_cls, d.ld_rc = ld_cls, head.reg_layout()[1]
+        d.head_flags = head.flags() & kind.det_mask
+        # centerness_on_reg=False: the centerness logit is this column of the logits' rows (FcosLossPlan.ctr_col)
+        self.ctr_col = None if head.centerness_on_reg else class_layout(num_classes)[1]
         self.dets = torch.zeros(n, max_per_img, 5, device=device)
         self.labels = torch.zeros(n, max_per_img, dtype=torch.int64, device=device)
         self.count = torch.zeros(n, dtype=torch.int32, device=device)
@@ -151,11 +150,7 @@ def _detplan(det, plan, store, N):
     dp = getattr(plan, 'detplan', None)
     if dp is None:
         dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
-                        ld_cls=store.logit_ld, ld_rc=store.reg_ld, reg_max=store.head.reg_max if store.gfl else None,
-                        head_flags=L.HEAD_GFL if store.gfl else store.head.flags() & (L.HEAD_EXP_DECODE | L.HEAD_ATSS | L.HEAD_PAA),
-                        atss=None if store.gfl else store.head.atss_desc(),
-                        score_voting=store.head.score_voting if store.head.head_kind == 'paa' else None,
-                        ctr_col=store.cls_ld if store.ctr_on_cls else None, **_test_cfg(det))
+                        ld_cls=store.logit_ld, head=store.head, **_test_cfg(det))
         dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
         plan.detplan = dp
     return dp

@@ -140,7 +140,6 @@ def det_inputs(seed, C, n, sizes):
 
 
 def det_plan(cls, raw, ctr, scales, C, o, n, nms_pre, iou_thr=0.6):
-    from dsl_amd import _lib as L
     from dsl_amd.sweep import DetectPlan
     sizes = [tuple(c.shape[2:]) for c in cls]
     ld = (C + 3) // 4 * 4
@@ -149,8 +148,7 @@ def det_plan(cls, raw, ctr, scales, C, o, n, nms_pre, iou_thr=0.6):
     cf[:, :C] = flat
     rc = torch.zeros(flat.shape[0], 8)
     rc[:, :4], rc[:, 4] = levels_to_flat(raw), levels_to_flat(ctr)[:, 0]
-    dp = DetectPlan(n, sizes, AR.STRIDES, 'cuda', num_classes=C, nms_pre=nms_pre, ld_cls=ld, iou_thr=iou_thr, head_flags=L.HEAD_ATSS,
-                    atss=o.atss_desc())
+    dp = DetectPlan(n, sizes, AR.STRIDES, 'cuda', num_classes=C, nms_pre=nms_pre, ld_cls=ld, iou_thr=iou_thr, head=o)
     dp.bind(cf.cuda(), rc.cuda(), scales.cuda())
     return dp
 

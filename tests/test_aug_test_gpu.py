@@ -23,6 +23,7 @@ def view_inputs(seed, C, sizes, exp_decode):
 
 def bound_plan(view, C, exp_decode, score_thr=0.05, guard=False):
     from dsl_amd import _lib as L
+    from dsl_amd.params import HeadOptions
     from dsl_amd.sweep import DetectPlan
     cls, raw, ctr = view
     sizes = [tuple(c.shape[2:]) for c in cls]
@@ -34,7 +35,7 @@ def bound_plan(view, C, exp_decode, score_thr=0.05, guard=False):
     rc[:, :4] = levels_to_flat(raw)
     rc[:, 4] = levels_to_flat(ctr)[:, 0]
     dp = DetectPlan(1, sizes, A.STRIDES, 'cuda', num_classes=C, nms_pre=NMS_PRE, ld_cls=ld, score_thr=score_thr,
-                    head_flags=L.HEAD_EXP_DECODE if exp_decode else 0)
+                    head=HeadOptions(norm_on_bbox=False) if exp_decode else None)
     dp.bind(cls_f.cuda(), rc.cuda(), torch.ones(5, device='cuda'))
     if guard:          # guard words behind the view's own workspace, which collect writes as well
         need = dp.desc.workspace_bytes

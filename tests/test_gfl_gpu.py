@@ -206,15 +206,15 @@ def det_inputs(seed, C, n, sizes, reg_max):
 
 
 def det_plan(cls, raw, scales, C, reg_max, n, nms_pre, iou_thr=0.6):
-    from dsl_amd import _lib as L
+    from dsl_amd.params import HeadOptions
     from dsl_amd.sweep import DetectPlan
     sizes = [tuple(c.shape[2:]) for c in cls]
     ld = (C + 3) // 4 * 4
     fl = levels_to_flat(cls)
     cf = torch.full((fl.shape[0], ld), 30.0)
     cf[:, :C] = fl
-    dp = DetectPlan(n, sizes, AR.STRIDES, 'cuda', num_classes=C, nms_pre=nms_pre, ld_cls=ld, ld_rc=4 * (reg_max + 1), iou_thr=iou_thr,
-                    head_flags=L.HEAD_GFL, reg_max=reg_max)
+    dp = DetectPlan(n, sizes, AR.STRIDES, 'cuda', num_classes=C, nms_pre=nms_pre, ld_cls=ld, iou_thr=iou_thr,
+                    head=HeadOptions(head_kind='gfl', reg_max=reg_max))
     dp.bind(cf.cuda(), levels_to_flat(raw).contiguous().cuda(), scales.cuda())
     return dp
 

@@ -159,7 +159,7 @@ def test_iou_loss_edges_vs_fp64(golden, case):
 def test_detect_exp_decode_vs_reference(golden):
     """dsl_fcos_detect with the exp decode and the centerness logit in the classification predictor's column, on the reference's own
     head outputs, against the reference's get_bboxes (test_detect_vs_oracle's tolerances)."""
-    from dsl_amd import _lib as L
+    from dsl_amd.params import HeadOptions
     from dsl_amd.sweep import DetectPlan
     from test_num_classes_gpu import _match
     d = golden('sweep_tiny_plain.npz')
@@ -171,7 +171,7 @@ def test_detect_exp_decode_vs_reference(golden):
     rc = torch.zeros(flat.shape[0], 8)
     rc[:, :4] = levels_to_flat(reg).log()            # the fixture holds exp(scale * x)
     rc[:, 4] = 1e30
-    dp = DetectPlan(2, sizes, STRIDES, 'cuda', num_classes=80, ld_cls=84, head_flags=L.HEAD_EXP_DECODE, ctr_col=80)
+    dp = DetectPlan(2, sizes, STRIDES, 'cuda', num_classes=80, ld_cls=84, head=HeadOptions(norm_on_bbox=False, centerness_on_reg=False))
     dp.bind(flat.cuda(), rc.cuda(), torch.ones(5, device='cuda'))
     shp = tuple(int(v) for v in d['img_shape'])
     dp.set_meta([shp] * 2, [d['scale_factor']] * 2, True)

@@ -220,10 +220,11 @@ def test_whole_chain_on_the_wide_margin_case(golden):
         assert float(got[12][i]) == pytest.approx(float(d[k]), rel=1e-3), k
     assert all(torch.equal(a, b) for a, b in zip(runs[0], runs[1]))
     # the op-list form of the middle pair gives the same bits
+    from dsl_amd import _lib as L
     from dsl_amd.engine import OpList
     plan = assigned_plan(c)
     ol = OpList()
-    ol.paa_refine(plan.paa)
+    ol.head_middle(L.OP_PAA_REFINE, plan.paa)
     ol.loss(plan.desc)
     ol.run()
     torch.cuda.synchronize()
@@ -264,7 +265,6 @@ def test_refused_descriptors_name_the_field(golden):
 
 # ---- detection ------------------------------------------------------------------------------------------------------------------
 def det_plan(d, score_voting):
-    from dsl_amd import _lib as L
     from dsl_amd.params import HeadOptions
     from dsl_amd.sweep import DetectPlan
     from util import levels_to_flat
@@ -276,10 +276,9 @@ def det_plan(d, score_voting):
     cf[:, :C] = flat
     rc = torch.zeros(flat.shape[0], 8)
     rc[:, :4], rc[:, 4] = levels_to_flat(raw), levels_to_flat(iou)[:, 0]
-    o = HeadOptions(head_kind='paa')
+    o = HeadOptions(head_kind='paa', score_voting=score_voting)
     dp = DetectPlan(2, PR.SIZES, PR.STRIDES, 'cuda', num_classes=C, nms_pre=int(d['nms_pre']), ld_cls=ld, iou_thr=float(d['iou_thr']),
-                    score_thr=float(d['score_thr']), max_per_img=int(d['max_per_img']), head_flags=L.HEAD_ATSS | L.HEAD_PAA,
-                    atss=o.atss_desc(), score_voting=score_voting)
+                    score_thr=float(d['score_thr']), max_per_img=int(d['max_per_img']), head=o)
     dp.bind(cf.cuda(), rc.cuda(), T(d['scales']).cuda())
     dp.set_meta([tuple(s) for s in d['shapes']], [d['scale_factors'][i] for i in range(2)], True)
     dp.run()

@@ -6,7 +6,7 @@ refactor of dsl_amd/engine.py / engine_rla.py is checked by running this file on
 
 Pointers are printed as A<k>+<offset>(<allocation bytes>): k numbers the distinct allocations in order of first appearance in the
 leg's walk (tests/op_ref.Memory maps a pointer to its allocation), H = a non-null pointer into no tensor (host structures).
-For four legs three optimizer steps on the tests/golden/net_tiny.npz batch follow, and the sha256 of the trained weights.
+For seven legs three optimizer steps on the tests/golden/net_tiny.npz batch follow, and the sha256 of the trained weights.
 Nothing is launched beyond what building a model and a plan launches (and those steps).
 """
 import argparse
@@ -22,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'tests')]
 
 from dsl_amd import _lib as L  # noqa: E402
-from dsl_amd import detectors, ops, tuning  # noqa: E402,F401
+from dsl_amd import detectors, ops, params, tuning  # noqa: E402,F401
 from dsl_amd.optim import FlatSGD  # noqa: E402
 from dsl_amd.registry import build_detector  # noqa: E402
 import op_ref as R  # noqa: E402
@@ -92,7 +92,11 @@ def fields(names, s):
 def head_desc(op):
     """An ASSIGN / LOSS op points at a dsl_fcos_desc or at the head's wider descriptor that starts with one."""
     f = C.cast(op.desc, C.POINTER(L.FcosDesc)).contents.head_flags
-    t = L.PaaDesc if f & L.HEAD_PAA else L.LdDesc if f & L.HEAD_LD else L.GflDesc if f & L.HEAD_GFL else L.FcosDesc
+    if hasattr(params, 'HEAD_KINDS'):          # the kind whose flags are all set and the most: its record names the outer struct
+        kind = max((k for k in params.HEAD_KINDS.values() if f & k.flags == k.flags), key=lambda k: bin(k.flags).count('1'))
+        t = getattr(L, kind.loss_desc[0])
+    else:          # a tree from before the head-kind table
+        t = L.PaaDesc if f & L.HEAD_PAA else L.LdDesc if f & L.HEAD_LD else L.GflDesc if f & L.HEAD_GFL else L.FcosDesc
     return C.cast(op.desc, C.POINTER(t)).contents
 
 
@@ -177,6 +181,21 @@ def norelu_cfg():
     return cfg
 
 
+def atss_cfg():
+    from test_atss_cpu import atss_model_cfg
+    return atss_model_cfg()
+
+
+def plain_cfg():
+    from test_head_options_cpu import PLAIN_HEAD
+    return fcos_model_cfg(**PLAIN_HEAD)
+
+
+def ld_cfg():
+    from test_ld_cpu import ld_model_cfg
+    return ld_model_cfg()
+
+
 def gfl_cfg():
     from test_gfl_cpu import gfl_model_cfg
     return gfl_model_cfg()
@@ -206,8 +225,11 @@ LEGS = [
     ('resnet defer_head_update', resnet_cfg, 2, TINY, {}, dict(defer=True, steps=True)),
     ('resnet fp8 towers', fp8_cfg, 2, TINY, {}, {}),
     ('resnet relu_before_extra_convs=False', norelu_cfg, 2, TINY, {}, {}),
-    ('resnet GFL head', gfl_cfg, 2, TINY, {}, {}),
-    ('resnet PAA head', paa_cfg, 2, TINY, {}, {}),
+    ('resnet plain head', plain_cfg, 2, TINY, {}, {}),
+    ('resnet ATSS head', atss_cfg, 2, TINY, {}, dict(steps=True)),
+    ('resnet GFL head', gfl_cfg, 2, TINY, {}, dict(steps=True)),
+    ('resnet LD head', ld_cfg, 2, TINY, {}, {}),          # (signature only: its step needs the teacher's sweep, tests/test_ld_gpu.py)
+    ('resnet PAA head', paa_cfg, 2, TINY, {}, dict(steps=True)),
     ('resnet eval', resnet_cfg, 2, TINY, {}, dict(eval=True)),
     ('resnet eval single_stream', resnet_cfg, 2, TINY, {}, dict(eval=True, single_stream=True)),
     ('rla N=3', rla_cfg, 3, TINY, {}, dict(steps=True, tile=2)),
@@ -225,7 +247,7 @@ def build_model(cfg_fn, defer=False):
     cfg = cfg_fn()
     torch.manual_seed(3)
     model = build_detector(cfg)
-    if cfg['bbox_head']['type'] == 'FCOSHead':          # (the other heads keep their seeded initialisation, as their tests do)
+    if model.store.head.is_default():          # (the other heads keep their seeded initialisation, as their tests do)
         model.load_state_dict((RO if cfg['backbone']['type'] == 'RLA_ResNet' else O).synth_state_dict(0))
     model = model.cuda()
     opt = FlatSGD(model, lr=0.01, momentum=0.9, weight_decay=1e-4, paramwise_cfg=dict(bias_lr_mult=2., bias_decay_mult=0.),
