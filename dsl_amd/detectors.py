@@ -18,16 +18,13 @@ off-GPU raises.
 """
 from collections import OrderedDict
 
-import ctypes
 import os
 import weakref
 
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
-C_void = ctypes.c_void_p
-
+from .exchange import GradExchange
 from .params import HeadOptions, ParamStore, class_layout
 from .registry import BACKBONES, DETECTORS, HEADS, LOSSES, NECKS, build_backbone, build_head, build_loss, build_neck
 
@@ -622,7 +619,7 @@ class _TrainStepFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, det, plan):
-        ctx.det, ctx.plan, ctx.eager = det, plan, bool(getattr(det, '_eager_now', False))      # were the backward lists queued already?
+        ctx.det, ctx.plan, ctx.eager = det, plan, det._eager_now      # were the backward lists queued already?
         kind = plan.lossplan.kind
         ctx.n_losses = len(kind.loss_keys) + (kind.sisoft and plan.lossplan.desc.soft_weight != 0.0)      # (+ loss_sisoft)
         # the loss terms in log order and, last, their sum - written by the loss kernel's finalize pass (dsl_fcos_desc.logvec)
@@ -647,6 +644,11 @@ class _TrainStepFn(torch.autograd.Function):
         if not ctx.eager:                 # eager: the kernels were queued right behind the loss kernel
             det._run_backward(ctx.plan)
         return None, None, None
+
+
+def _forward(name):
+    """A detector attribute that IS the setting `name` of its gradient exchange."""
+    return property(lambda self: getattr(self.exchange, name), lambda self, value: setattr(self.exchange, name, value))
 
 
 @DETECTORS.register_module()
@@ -682,8 +684,9 @@ class FCOS(nn.Module):
         self._params = None
         self._engine = None
         self._anchor = None
-        self.dist_group = None        # set by the DDP wrapper
-        self.world_size = 1
+        # data parallel: buckets, streams, pending work and every option of the gradient exchange live here; the
+        # names callers know (world_size, comm_proxy, clip_partials, ... below the constructor) forward to it
+        self.exchange = GradExchange(self.store)
         self.CLASSES = None
         # Product defaults = what bench.py measures (round 4; both were opt-in and only bench.py set them):
         # lazy_log True: train_step's log_vars stay 0-dim device tensors; the host reads them when it logs (TextLoggerHook: every
@@ -704,39 +707,28 @@ class FCOS(nn.Module):
         # loss tensor instead of FCOS.loss_scale must set this False (tuning key check_backward_grad=1 checks the incoming gradient on every step; by default the first three are checked).
         # A direct forward_train() call (no train_step around it) stays lazy unless eager_backward == 'always'.
         self.eager_backward = True
-        self._in_train_step, self._deferred_plan = False, None
+        self._in_train_step, self._deferred_plan, self._eager_now = False, None, False
         # The frozen prefix of the forward pass - image layout, stem, pool, layer1 - runs on its own stream; when the batch's image
         # tensor carries its producer's event (dsl_amd.data.mark_ready: resident inputs, a loader that renders on its own stream)
         # it starts under the tail of the PREVIOUS step's backward pass and optimizer step, otherwise it is ordered behind
         # everything queued on the caller's stream (always correct, no overlap)
         self.pipeline_prefix = True
-        self._prefix_stream = None
+        self._prefix_stream, self._prefix_plan = None, None          # (_prefix_plan: the plan whose prefix ran last)
         self.loss_scale = 1.0         # constant factor on every gradient (gradient accumulation: 1/k); the reported losses stay unscaled
-        self._pending = []
-        self._comm_stream = None
-        self.rccl = None              # parallel.RcclComm: the exchanges go through the C-ABI's communicator instead of torch.distributed
-        self.comm_trace = None        # set to [] (bench.py --gpus N): per step, per gradient bucket, timed events of its all-reduce
-        # data-parallel options (set by HipDistributedDataParallel)
-        self.grad_bf16 = False        # gradient buckets cross xGMI as bf16 copies (half the bytes); master gradient, norm, update stay fp32
-        self.comm_off = False         # DSL_COMM=none / bench.py's attribution probe: every collective skipped (timing only - WRONG gradients)
-        # Communication proxy (one-GPU measurement of what the collectives cost the DEVICE; bench.py extra.comm_proxy):
-        # dict(carrier='lib' | 'torch', wgs=32, passes=2).  The step then runs its data-parallel schedule - bucket events, communication
-        # stream, per-bucket optimizer steps behind each bucket's "all-reduce" - with dsl_comm_proxy (value-preserving passes over the
-        # bucket on `wgs` workgroups) in place of RCCL; carrier 'lib' = the library's placed communication stream (what comm='rccl'
-        # uses), 'torch' = a stream from torch's pool, as ProcessGroupNCCL runs its kernels on one of its own
-        self.comm_proxy = None
-        self._proxy_stream = None
-        # Gradient accumulation (FlatSGD.accumulate / set_closing, GradientCumulativeOptimizerHook).  accum_closing False: the next
-        # backward pass is a window's non-closing micro-step - it queues NO gradient collective (each rank banks its local gradient,
-        # the window's sum is exchanged once).  _fold_acc: the optimizer's bank while a window is open - the closing pass's
-        # exchange(info) folds it into the bucket (DSL_ACC_FOLD) in front of the collective and lists the bucket in _folded
-        self.accum_closing = True
-        self._fold_acc = None
-        self._folded = set()
-        self._bwd_exchanged = self._bwd_unexchanged = False
-        self.clip_partials = None     # [buckets * SUMSQ_PARTS] floats: FlatSGD with grad_clip asks for the norm in pieces, per bucket
-        self._partials_valid = False
-        self._g16 = None
+
+    # ---- the gradient exchange's settings under the detector's names (GradExchange.__init__ says what each is) -------------------
+    dist_group = _forward('group')          # (set by the DDP wrapper, with world_size)
+    world_size = _forward('world_size')
+    rccl = _forward('rccl')
+    grad_bf16 = _forward('grad_bf16')
+    comm_off = _forward('comm_off')
+    comm_proxy = _forward('comm_proxy')
+    comm_trace = _forward('comm_trace')
+    late_exchange = _forward('late_wanted')
+    clip_partials = _forward('clip_partials')
+
+    def wait_grads(self):
+        self.exchange.wait()
 
     # ---- nn.Module surface redirected to the flat store ------------------------------------------
     def init_weights(self):
@@ -809,7 +801,7 @@ class FCOS(nn.Module):
         img[-1] (semi_epoch_based_runner.py:186-204), whose metas / boxes are the lists' last entries; the stem kernel samples it
         from img[-1] (dsl_stem_pool_half), it is never written to memory."""
         eng = self._get_engine()
-        if self._pending or getattr(self, '_late_todo', None):
+        if self.exchange.pending or self.exchange.todo:
             # a second training pass before step() (gradient accumulation, an aborted step): the previous backward pass's collectives
             # are queued now (late exchange) and waited for - none is dropped (the ranks would disagree on the collective sequence)
             # and none still writes store.grad under this pass.  Here and not in _run_backward: this pass's loss kernel already
@@ -851,7 +843,7 @@ class FCOS(nn.Module):
                 except AttributeError:
                     pass
             staged = plan._img_ref is None                     # bind_image copied the batch into plan.img on the CALLER's stream
-            if getattr(self, '_prefix_plan', None) is not plan:
+            if self._prefix_plan is not plan:
                 # first use of this plan (or the first step at all): SLOT_TAIL was never recorded, so nothing orders the prefix
                 # stream behind the caller's stream, which wrote the frozen packs (store.refresh) and possibly the image
                 self._prefix_stream.wait_stream(torch.cuda.current_stream())
@@ -884,7 +876,7 @@ class FCOS(nn.Module):
             # (fcos_head.py:264-274) - then runs under the forward pass
             lp.set_targets(gt_bboxes, gt_labels, gt_bboxes_ignore, pad)
             plan.assign_ops.run()
-            work = None if self.comm_off else self._all_reduce_async(lp.stats[:2], after_current=True)
+            work = None if self.comm_off else self.exchange.all_reduce_async(lp.stats[:2], after_current=True)
             fwd.run()
             if work is not None:
                 work.wait()
@@ -899,7 +891,7 @@ class FCOS(nn.Module):
             if kind.middle:
                 plan.quality_ops.run()
             if kind.exchange == 'middle' and ws > 1 and not self.comm_off:
-                self._all_reduce_async(lp.stats[:2], after_current=True).wait()
+                self.exchange.all_reduce_async(lp.stats[:2], after_current=True).wait()
         plan.loss_ops.run()
         eager_now = False
         if self.eager_backward and torch.is_grad_enabled():
@@ -916,157 +908,20 @@ class FCOS(nn.Module):
         losses.vec_total = out              # ... and with their sum (the loss kernel's) as the last element: no device op at all
         return losses
 
-    def _all_reduce_async(self, t, after_current=False):
-        """Sum `t` over the ranks beside the caller's stream; returns an object whose wait() orders the current stream behind it.
-        after_current: the collective must see everything queued on the current stream so far (torch's process group
-        orders its own stream that way by itself)."""
-        if self.rccl is None or not t.is_cuda:
-            return dist.all_reduce(t, group=self.dist_group, async_op=True)
-        from .parallel import StreamWork
-        if self._comm_stream is None:
-            self._comm_stream = role_stream('comm', self.store.device)
-        cs = self._comm_stream
-        if after_current:
-            cs.wait_stream(torch.cuda.current_stream())
-        t.record_stream(cs)
-        self.rccl.all_reduce(t, cs)
-        return StreamWork(cs)
-
     def _run_backward(self, plan):
         """Hand-written backward.  Data parallel: gradient bucket s (head+FPN, layer4, layer3, layer2) is all-reduced as
         soon as the side stream has finished its weight gradients - the communication stream waits for the named event
         the segment recorded (dsl_stream_wait_slot), not for the caller's stream, which is already running the next
         segment's data-gradient chain - so the bulk RCCL traffic overlaps the remaining backward (what torch DDP's bucket
-        hooks do at mmdet/apis/train.py:92-96); only the last, smallest bucket (layer2, 5 MB) is exposed."""
-        self._pending = []
-        self._last_bwd_infos = [info for _, info in plan.bwd_segments]      # bucket ranges / event slots, for the optimizer
-        proxy = self.comm_proxy if (self.comm_proxy and self.world_size == 1 and self.store.grad.is_cuda) else None
-        ddp = (self.world_size > 1 and not self.comm_off) or proxy is not None
-        # a non-closing micro-step of an accumulation window exchanges nothing: _pending / _late_todo stay empty, no norm partials
-        closing = bool(getattr(self, 'accum_closing', True))
-        self._bwd_unexchanged = bool(ddp and not closing)
-        ddp = ddp and closing
-        self._bwd_exchanged = bool(ddp)
-        self._folded = set()
-        on_gpu = self.store.grad.is_cuda
-        if ddp and on_gpu and self._comm_stream is None:
-            self._comm_stream = role_stream('comm', self.store.device)
-        if proxy is not None and proxy.get('carrier', 'lib') == 'torch' and self._proxy_stream is None:
-            self._proxy_stream = torch.cuda.Stream()
-        self._partials_valid = False
-        # Late exchange (round 6; set by an optimizer that updates bucket by bucket without a global norm, FlatSGD._sync_defer): the
-        # collectives are queued BEHIND the whole backward pass, in the order the next forward pass needs the parameters (layer2's
-        # bucket first, head + FPN last), and nothing waits for them at the end of the step - the per-bucket updates record named
-        # events SLOT_UPD + k, the next step's forward list waits for them stage by stage (engine.Plan._fwd_resnet).  Queued
-        # bucket by bucket behind each segment ("eager") the traffic shared the tail of the backward pass with the weight
-        # gradients, the next step's frozen prefix and the step boundary: the one-GPU proxy priced that at 10 % of the step
-        # whatever queue carried it, the late exchange on the weight-gradient queue at 5.7 % (profiles/r06_comm_queue_sweep.txt).
-        late = bool(ddp and on_gpu and getattr(self, 'late_exchange', False) and self.clip_partials is None
-                    and self.store.backbone != 'rla' and not getattr(plan, 'defer', False))
-        nbc = [0]
-
-        def exchange(info):
-            lo, hi = info['bucket']
-            acc = self._fold_acc
-            if not on_gpu:            # host tensors (the gloo unit test of the bucket order): nothing to order against
-                if acc is not None:
-                    raise NotImplementedError('dsl_amd: gradient accumulation runs on the GPU only (dsl_grad_accumulate)')
-                self._pending.append(dist.all_reduce(self.store.grad[lo:hi], group=self.dist_group, async_op=True))
-                return
-            from . import _lib as L
-            from .parallel import StreamWork
-            cs = self._proxy_stream if (proxy is not None and proxy.get('carrier', 'lib') == 'torch') else self._comm_stream
-            csp = C_void(cs.cuda_stream)
-            L.check(min(L.lib.dsl_stream_wait_slot(info['slot'], csp), 0), 'dsl_stream_wait_slot')
-            if info['main']:
-                cs.wait_stream(torch.cuda.current_stream())
-            g = self.store.grad[lo:hi]
-            if acc is not None:
-                # the closing micro-step of an accumulation window: the bucket becomes the window's sum (bank + this pass) on the
-                # communication stream, behind the bucket's weight gradients and in front of everything that reads it from here on
-                L.check(L.lib.dsl_grad_accumulate(C_void(acc.data_ptr() + lo * 4), L.ptr(g), hi - lo, L.ACC_FOLD, csp), 'dsl_grad_accumulate')
-                self._folded.add((int(lo), int(hi)))
-            if proxy is not None:
-                # the bucket's stand-in collective (no peer: the values stay): same stream, same event, same optimizer hand-over
-                L.check(L.lib.dsl_comm_proxy(L.ptr(g), (hi - lo) // 4 * 4, int(proxy.get('wgs', 32)), int(proxy.get('passes', 2)), csp),
-                        'dsl_comm_proxy')
-                self._pending.append(StreamWork(cs))
-                nbc[0] += 1
-                return
-            with torch.cuda.stream(cs):
-                if self.comm_trace:
-                    es = torch.cuda.Event(enable_timing=True)
-                    es.record()            # the bucket's named event has fired and the previous bucket's traffic is queued
-                    self.comm_trace[-1]['buckets'].append(dict(mb=(hi - lo) * (2 if self.grad_bf16 else 4) / 1e6, start=es, done=None))
-                work = None
-                if self.grad_bf16:
-                    # the bucket crosses xGMI as a bf16 copy (RCCL's own ring then adds in bf16 per hop; the fp32 master gradient
-                    # gets the result back): cast -> all-reduce -> cast back, all on the communication stream
-                    if self._g16 is None or self._g16.device != g.device:
-                        self._g16 = torch.empty(self.store.grad.numel(), dtype=torch.bfloat16, device=g.device)
-                    g16 = self._g16[lo:hi]
-                    L.check(L.lib.dsl_cast_bf16(L.ptr(g), L.ptr(g16), hi - lo, csp), 'dsl_cast_bf16')
-                    if self.rccl is not None:
-                        L.check(L.lib.dsl_allreduce_bucket_bf16(self.rccl.comm, L.ptr(g16), hi - lo, csp), 'dsl_allreduce_bucket_bf16')
-                    elif dist.get_backend(self.dist_group) == 'gloo':
-                        # (the CPU-side test carrier has no bf16 sum: the bf16-rounded values are added in fp32 and rounded back)
-                        t32 = g16.float()
-                        dist.all_reduce(t32, group=self.dist_group, async_op=True).wait()
-                        g16.copy_(t32)
-                    else:
-                        dist.all_reduce(g16, group=self.dist_group, async_op=True).wait()      # (orders cs behind the collective)
-                    L.check(L.lib.dsl_cast_f32(L.ptr(g16), L.ptr(g), hi - lo, csp), 'dsl_cast_f32')
-                elif self.rccl is not None:
-                    self.rccl.all_reduce(g, cs)
-                else:
-                    work = dist.all_reduce(g, group=self.dist_group, async_op=True)
-                if self.clip_partials is not None:
-                    # the clipping norm of the REDUCED bucket, as soon as it has arrived: only the fold + the update stay behind the
-                    # last bucket (FlatSGD.step)
-                    if work is not None:
-                        work.wait()
-                        work = None
-                    L.check(L.lib.dsl_sumsq_partial(L.ptr(g), hi - lo, C_void(self.clip_partials.data_ptr() + nbc[0] * L.SUMSQ_PARTS * 4), csp),
-                            'dsl_sumsq_partial')
-                self._pending.append(work if work is not None else StreamWork(cs))
-            nbc[0] += 1
-
-        todo = []
+        hooks do at mmdet/apis/train.py:92-96); only the last, smallest bucket (layer2, 5 MB) is exposed.  Or, the default
+        without clipping, behind the whole pass: GradExchange says which, and does it."""
+        ex = self.exchange
+        ex.begin(plan)
         for ol, info in plan.bwd_segments:
             ol.run()
-            if not ddp or info['bucket'] is None:       # (bucket None: the deferred head update - its bucket completes with a later list)
-                continue
-            if late:
-                todo.append(info)
-            else:
-                exchange(info)
-        # late: nothing is queued here - the optimizer asks for each bucket's exchange right in front of that bucket's update
-        # (exchange_late), so that on ONE hardware queue the order is exchange, update, exchange, update ... in the order the next
-        # forward pass needs the parameters; queued all at once the first update sat behind every exchange (measured: 13 - 18 %)
-        self._late_todo = todo[::-1] if late else []
-        self._exchange_fn = exchange if late else None
-        nb = nbc[0]
-        self._partials_valid = bool(ddp and on_gpu and self.clip_partials is not None and 0 < nb * 256 <= self.clip_partials.numel())
-        self._n_partials = nb * 256
+            ex.segment_done(info)
+        ex.finish()
         self._rebind_grads()
-
-    def exchange_late(self):
-        """Late exchange: queues the next bucket's collective (order: layer2, layer3, layer4, head + FPN) and returns (info, work), or
-        None when every bucket of the last backward pass has been handed out."""
-        todo = getattr(self, '_late_todo', None)
-        if not todo:
-            return None
-        info = todo.pop(0)
-        n = len(self._pending)
-        self._exchange_fn(info)
-        return info, self._pending[n]
-
-    def wait_grads(self):
-        while self.exchange_late() is not None:      # (a late exchange nobody asked for bucket by bucket: an optimizer with a global norm)
-            pass
-        for w in self._pending:
-            w.wait()
-        self._pending = []
 
     def forward(self, img, img_metas, return_loss=True, **kwargs):
         """detectors/base.py:155-173."""
@@ -1129,10 +984,7 @@ class FCOS(nn.Module):
 
     def _finish_log_vars(self, loss, vec, keys):
         if self.world_size > 1 and not self.comm_off:      # ONE all-reduce for all log vars instead of one per key
-            if self.rccl is not None and vec.is_cuda:
-                self.rccl.all_reduce(vec)
-            else:
-                dist.all_reduce(vec, group=self.dist_group)
+            self.exchange.all_reduce_log(vec)
             vec = vec / self.world_size
         if self.lazy_log:
             log_vars = OrderedDict((k, vec[i]) for i, k in enumerate(keys))

@@ -8,6 +8,7 @@ import os
 import torch
 
 from . import _lib as L
+from .exchange import BANKED, EAGER, LATE
 from .registry import OPTIMIZERS
 
 
@@ -23,6 +24,7 @@ class FlatSGD:
         assert not kw.get('nesterov', False) and kw.get('dampening', 0) == 0
         self.model = model
         self.store = model.store
+        self.exchange = model.exchange          # the detector's gradient exchange (data parallel, accumulation windows)
         pw = paramwise_cfg or {}
         self.bias_lr_mult = float(pw.get('bias_lr_mult', 1.0))
         self.bias_decay_mult = float(pw.get('bias_decay_mult', 1.0))
@@ -37,6 +39,9 @@ class FlatSGD:
         self.momentum_buf = None
         self.gnorm_sq = None
         self.steps = 0
+        self._loaded_regions = None          # load_state_dict: name -> (offset, size) of the restored momentum, until step() adopts it
+        self._side1 = self._opt_stream = None          # the walk's streams, made at first need
+        self._sumsq_ws = None
         self._acc = None          # gradient accumulation (accumulate()): the open window's running sum, laid out like store.grad
         self.acc_count = 0        # micro-steps banked in the open window
         self.late_exchange = bool(late_exchange)      # data parallel without clipping: collectives behind the backward pass (see _sync_defer)
@@ -51,7 +56,7 @@ class FlatSGD:
                 and self.store.backbone != 'rla')
         # Late exchange (data parallel): with an element-wise per-bucket update nothing at the end of a step has to
         # wait for the collectives - the detector queues them behind the backward pass and the next forward pass waits stage by stage
-        self.model.late_exchange = bool(self.max_norm is None and _PACK_SIDE and self.late_exchange and self.store.backbone != 'rla')
+        self.exchange.late_wanted = bool(self.max_norm is None and _PACK_SIDE and self.late_exchange and self.store.backbone != 'rla')
         if bool(getattr(self.store, 'defer_head', False)) != want:
             self.store.wait_pending() if self.store.train.is_cuda else None
             self.store.defer_head = want        # plans are keyed by it (Engine.plan): lists built the other way are not reused
@@ -70,7 +75,7 @@ class FlatSGD:
         # without a region table whose size is off by more than that is refused instead of being attached to the wrong parameters.
         src = self.momentum_buf.reshape(-1)
         buf = torch.zeros_like(st.train)
-        regs = getattr(self, '_loaded_regions', None)
+        regs = self._loaded_regions
         cur = {k: (int(v[0]), int(v[1])) for k, v in st.train_regions.items()}
         if regs:
             regs = {k: (int(v[0]), int(v[1])) for k, v in regs.items()}
@@ -103,19 +108,19 @@ class FlatSGD:
             self.steps = 0
             fresh = True
         elif (self.momentum_buf.device != st.device or self.momentum_buf.shape != st.train.shape
-              or getattr(self, '_loaded_regions', None) is not None):
+              or self._loaded_regions is not None):
             self._adopt_loaded_state()
             fresh = True          # (copied into place on the caller's stream just now: the same ordering as for the zero fill)
         if self.gnorm_sq is None or self.gnorm_sq.device != st.device:
             self.gnorm_sq = torch.zeros(1, device=st.device)
-        if getattr(self.model, '_bwd_unexchanged', False):
+        if self.exchange.mode == BANKED:
             raise RuntimeError('FlatSGD.step(): the last backward pass was declared non-closing (set_closing(False)) and queued no '
                                'gradient exchange: call set_closing(True) in front of the train_step whose step() closes the window')
         self._walk(True, fresh)
         self.steps += 1
         if self.acc_count:
             self.acc_count = 0
-            self.model._fold_acc = None
+            self.exchange.close_window()
         self.set_closing(True)
 
     def set_closing(self, closing):
@@ -123,17 +128,17 @@ class FlatSGD:
         step() (True, the default) or by accumulate() (False: that pass queues no gradient collective - the window's sum is exchanged
         once, by the closing pass).  Call it in front of train_step (the eager backward pass is queued in there);
         GradientCumulativeOptimizerHook does so in before_train_iter.  step() sets it back to True."""
-        self.model.accum_closing = bool(closing)
+        self.exchange.closing = bool(closing)
 
     def accumulate(self):
         """Banks the gradient of the backward pass that has just run instead of applying it: step() with the update kernel swapped
         for dsl_grad_accumulate - the same buckets on the same streams behind the same events (_walk), so the next backward pass
         cannot overwrite a bucket this call still reads.  The next step() folds the bank into store.grad (DSL_ACC_FOLD) in front
         of whatever reads each bucket first.  The bank is one fp32 tensor like store.grad, made at the first call."""
-        st, m = self.store, self.model
+        st, ex = self.store, self.exchange
         if not st.grad.is_cuda:
             raise RuntimeError('FlatSGD.accumulate() runs on the GPU only (dsl_grad_accumulate; no host fallback)')
-        if getattr(m, '_bwd_exchanged', False) or getattr(m, '_pending', None) or getattr(m, '_late_todo', None):
+        if ex.mode in (LATE, EAGER) or ex.pending or ex.todo:
             raise RuntimeError('FlatSGD.accumulate(): the last backward pass queued its gradient exchange - a window is exchanged once, '
                                'by its closing pass: call set_closing(False) in front of the train_step of a micro-step that accumulates')
         fresh = False
@@ -144,7 +149,7 @@ class FlatSGD:
             fresh = True
         self._walk(False, fresh)
         self.acc_count += 1
-        m._fold_acc = self._acc          # (the detector folds it into each bucket in front of that bucket's exchange)
+        ex.open_window(self._acc)          # (the exchange folds it into each bucket in front of that bucket's exchange)
 
     def _acc_launch(self, lo, hi, mode, tp):
         L.check(L.lib.dsl_grad_accumulate(C.c_void_p(self._acc.data_ptr() + lo * 4), C.c_void_p(self.store.grad.data_ptr() + lo * 4),
@@ -155,19 +160,15 @@ class FlatSGD:
         which events.  accumulate() swaps dsl_sgd_step for dsl_grad_accumulate and leaves the data-gradient packs alone (the
         weights did not move: SLOT_PACKS still stands for packs of the current weights); every wait and record is the same.
         step() with banked micro-steps (acc_count > 0) folds the bank into each bucket first, unless that bucket's exchange did
-        (the detector lists those in model._folded)."""
-        st = self.store
+        (the exchange lists those in `folded`)."""
+        st, ex = self.store, self.exchange
         window = update and self.acc_count > 0
-
-        def folded():          # (read when asked: the late exchanges run, and fold, inside this walk)
-            return getattr(self.model, '_folded', None) or ()
         acc_mode = L.ACC_ADD if self.acc_count else L.ACC_SET
         sp = L.stream_ptr()
         lr = float(self.param_groups[0]['lr'])
         blr = float(self.param_groups[1]['lr']) / lr if lr != 0 else self.bias_lr_mult
         self._sync_defer()          # (OptimizerHook may set max_norm after construction)
-        infos = getattr(self.model, '_last_bwd_infos', None)
-        infos = [i for i in infos if i['bucket'] is not None] if infos else infos      # completion order; a deferred bucket comes last
+        infos = ex.buckets          # completion order; a deferred bucket comes last
         if self.max_norm is None and infos and st.grad.is_cuda and all(i['bucket'][0] % 4 == 0 for i in infos):
             # No gradient clipping (the supervised config): the update is element-wise, so each gradient bucket - head + FPN,
             # layer4, layer3, layer2, in the order the backward pass completes them - is updated on the optimizer's own stream
@@ -181,19 +182,19 @@ class FlatSGD:
                 # towers' group.  A stream of the optimizer's own would do logically, but streams share four hardware queues: it
                 # landed on the weight-gradient stream's queue, and the three early updates - hence the whole next forward pass -
                 # then sat behind the deferred 0.5 ms group (measured: 401 instead of 430 img/s, profiles/r04_defer_first.txt).
-                if getattr(self, '_side1', None) is None:
+                if self._side1 is None:
                     h = C.c_void_p()
                     L.check(L.lib.dsl_side_stream(1, C.byref(h)), 'dsl_side_stream')
                     self._side1 = torch.cuda.ExternalStream(h.value)
                 os_ = None
             else:
-                if getattr(self, '_opt_stream', None) is None:
+                if self._opt_stream is None:
                     from .detectors import role_stream          # one optimizer stream per device and process (hardware queues)
                     self._opt_stream = role_stream('optimizer', st.device)
                 os_ = self._opt_stream
-            pend = list(getattr(self.model, '_pending', []) or [])
-            # late exchange: the detector queued no collective - each is asked for here, in front of its bucket's update
-            late = bool(getattr(self.model, '_late_todo', None)) and not deferred and not pend
+            pend = list(ex.pending)
+            # late exchange: the backward pass queued no collective - each is asked for here, in front of its bucket's update
+            late = bool(ex.todo) and not deferred and not pend
             seq = list(enumerate(infos[::-1] if late else infos))
             if fresh:
                 for s_ in ([self._side1] if deferred else [os_]):
@@ -203,13 +204,13 @@ class FlatSGD:
                 tgt = (self._side1 if info.get('deferred') else cur) if deferred else os_
                 tp = C.c_void_p(tgt.cuda_stream)
                 if late:
-                    got = self.model.exchange_late()
+                    got = ex.next_late()
                     assert got is not None and got[0] is info, 'late exchange: bucket order'
                     pend.append(got[1])
                 if pend:
                     with torch.cuda.stream(tgt):
                         pend[k].wait()
-                        tr = getattr(self.model, 'comm_trace', None)
+                        tr = ex.comm_trace
                         if tr and k < len(tr[-1]['buckets']):
                             ed = torch.cuda.Event(enable_timing=True)
                             ed.record()
@@ -218,7 +219,7 @@ class FlatSGD:
                     never = L.lib.dsl_stream_wait_slot(int(info['slot']), tp)
                     # (data parallel with the exchanges already waited for on the caller's stream - FCOS.wait_grads: the update must
                     #  follow them, not only its weight gradients)
-                    if (info['main'] or never != 0 or getattr(self.model, 'world_size', 1) > 1) and tgt is not cur:
+                    if (info['main'] or never != 0 or ex.world_size > 1) and tgt is not cur:
                         tgt.wait_stream(cur)
                 o4, o2, o1 = lo * 4, lo * 2, lo
                 if 'sgd' in skip_items():          # step-level ablation (tools/step_ablation.sh): timing only
@@ -226,7 +227,8 @@ class FlatSGD:
                 if not update:
                     self._acc_launch(lo, hi, acc_mode, tp)
                     continue
-                if window and (int(lo), int(hi)) not in folded():          # (no exchange in front of this bucket's update: the fold goes here)
+                # (ex.folded is read bucket by bucket: the late exchanges run, and fold, inside this walk)
+                if window and (int(lo), int(hi)) not in ex.folded:          # (no exchange in front of this bucket's update: the fold goes here)
                     self._acc_launch(lo, hi, L.ACC_FOLD, tp)
                 L.check(L.lib.dsl_sgd_step(C.c_void_p(st.train.data_ptr() + o4), C.c_void_p(st.grad.data_ptr() + o4),
                                            C.c_void_p(self.momentum_buf.data_ptr() + o4), C.c_void_p(st.train16.data_ptr() + o2),
@@ -234,8 +236,7 @@ class FlatSGD:
                                            self.bias_decay_mult, None, 0.0, int(self.steps == 0), tp), 'dsl_sgd_step')
                 if late:          # "gradient bucket <slot> is updated": what the next forward pass waits for in front of that stage
                     L.check(L.lib.dsl_stream_record_slot(L.SLOT_UPD + int(info['slot']), tp), 'dsl_stream_record_slot')
-            if hasattr(self.model, '_pending'):
-                self.model._pending = []
+            ex.clear_pending()
             if deferred:
                 s1p = C.c_void_p(self._side1.cuda_stream)
                 L.check(L.lib.dsl_stream_record_slot(L.SLOT_HEADW, s1p), 'dsl_stream_record_slot')
@@ -257,9 +258,8 @@ class FlatSGD:
                 if update:
                     st.repack_dgrad(sp, side=_PACK_SIDE)
             return
-        if hasattr(self.model, 'wait_grads'):
-            self.model.wait_grads()
-        for i in infos or []:
+        ex.wait()
+        for i in infos:
             if i.get('deferred'):        # a list built for the deferred head update left its last weight gradients unjoined
                 L.lib.dsl_stream_wait_slot(int(i['slot']), sp)
         if not update:
@@ -267,22 +267,18 @@ class FlatSGD:
             return
         if window:
             # the buckets whose exchange folded them (data parallel) are done; the rest - one GPU: everything - in front of the norm
-            done = folded()
-            rest = [(0, st.n_train)] if not done else [i['bucket'] for i in infos or [] if (int(i['bucket'][0]), int(i['bucket'][1])) not in done]
+            done = ex.folded
+            rest = [(0, st.n_train)] if not done else [i['bucket'] for i in infos if (int(i['bucket'][0]), int(i['bucket'][1])) not in done]
             for lo, hi in rest:
                 self._acc_launch(lo, hi, L.ACC_FOLD, sp)
         gptr = None
         if self.max_norm is not None:
-            m = self.model
-            if getattr(m, 'world_size', 1) > 1 and st.grad.is_cuda and getattr(m, 'clip_partials', None) is None and hasattr(m, 'clip_partials'):
-                # data parallel + clipping: from the next backward pass on, the norm arrives in pieces - one partial sum per bucket,
-                # computed on the communication stream behind that bucket's all-reduce - and only their fold precedes the update
-                m.clip_partials = torch.zeros(8 * L.SUMSQ_PARTS, device=st.device)
-            if getattr(m, '_partials_valid', False):
-                L.check(L.lib.dsl_sumsq_fold(L.ptr(m.clip_partials), int(m._n_partials), L.ptr(self.gnorm_sq), sp), 'dsl_sumsq_fold')
-                m._partials_valid = False
+            ex.want_norm_partials()          # (data parallel: from the next backward pass on the norm arrives in pieces, per bucket)
+            parts = ex.take_norm_partials()
+            if parts is not None:
+                L.check(L.lib.dsl_sumsq_fold(L.ptr(parts[0]), parts[1], L.ptr(self.gnorm_sq), sp), 'dsl_sumsq_fold')
             else:
-                if getattr(self, '_sumsq_ws', None) is None or self._sumsq_ws.device != st.device:
+                if self._sumsq_ws is None or self._sumsq_ws.device != st.device:
                     self._sumsq_ws = torch.zeros(1024, device=st.device)
                 L.check(L.lib.dsl_sumsq_det(L.ptr(st.grad), st.n_train, L.ptr(self.gnorm_sq), L.ptr(self._sumsq_ws), sp), 'dsl_sumsq_det')
             gptr = self.gnorm_sq
@@ -313,7 +309,7 @@ class FlatSGD:
         self.gnorm_sq = None
         self._sumsq_ws = None
         self.acc_count = 0          # (the accumulation window is not part of the state: a resume starts a fresh one)
-        self.model._fold_acc = None
+        self.exchange.close_window()
 
 
 def build_optimizer(model, cfg, grad_clip=None):

@@ -84,18 +84,19 @@ class HipDistributedDataParallel(nn.Module):
         assert dist.is_initialized(), 'init_process_group first (tools/train.py:116-123)'
         self.module = module
         self.group = process_group
-        module.dist_group = process_group
-        module.world_size = dist.get_world_size(process_group)
+        ex = module.exchange          # (the detector's GradExchange: every data-parallel setting lives there)
+        ex.group = process_group
+        ex.world_size = dist.get_world_size(process_group)
         comm = comm if comm is not None else os.environ.get('DSL_COMM', 'torch')
         assert comm in ('torch', 'rccl', 'none'), comm
-        module.comm_off = comm == 'none'
+        ex.comm_off = comm == 'none'
         grad_dtype = grad_dtype if grad_dtype is not None else os.environ.get('DSL_GRAD_DTYPE', 'fp32')
         assert grad_dtype in ('fp32', 'bf16'), grad_dtype
-        module.grad_bf16 = grad_dtype == 'bf16'
+        ex.grad_bf16 = grad_dtype == 'bf16'
         if wgrad_slots is not None:
             from .tuning import set_tune
             set_tune('lib.wgrad_slots', int(wgrad_slots))      # (an explicit library setter: read when a launch is planned)
-        module.rccl = RcclComm(process_group) if (comm == 'rccl' and module.store.train.is_cuda) else None
+        ex.rccl = RcclComm(process_group) if (comm == 'rccl' and module.store.train.is_cuda) else None
         # initial parameter broadcast from rank 0 (what DDP's constructor does)
         st = module.store
         for buf in (st.train, st.frozen):

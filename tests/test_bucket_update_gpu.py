@@ -236,7 +236,7 @@ def test_bucket_update_vs_host_reference(leg):
             out = model.train_step(batch, opt)
             out['loss'].backward()
             if leg == 'proxy_late':
-                assert model.late_exchange and len(model._late_todo) == 4, (model.late_exchange, len(model._late_todo))
+                assert model.late_exchange and len(model.exchange.todo) == 4, (model.late_exchange, len(model.exchange.todo))
             if not capture:
                 opt.step()
                 continue
@@ -327,7 +327,7 @@ def _schedules(rank, comm, grad_dtype):
             _set_lr(opt, s)
             out = ddp.train_step(batch, opt)
             out['loss'].backward()
-            todo, pend = len(getattr(model, '_late_todo', []) or []), len(model._pending)
+            todo, pend = len(model.exchange.todo), len(model.exchange.pending)
             if late and not (model.late_exchange and todo == 4 and pend == 0):
                 errs.append(f'{name} step {s}: not the late path (late_exchange {model.late_exchange}, {todo} buckets left, {pend} queued)')
             if not late and (model.late_exchange or todo or pend != 4):

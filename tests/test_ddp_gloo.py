@@ -55,8 +55,8 @@ def _worker(rank, world, port, q, deferred=False):
             Plan.bwd_segments = ([(_NoOps(), dict(bucket=None, slot=None, main=False))] + Plan.bwd_segments[1:]
                                  + [(_NoOps(), dict(bucket=_b[0], slot=0, main=False, deferred=True))])
         det._run_backward(Plan)
-        assert len(det._pending) == 4
-        done = [i['bucket'] for i in det._last_bwd_infos if i['bucket'] is not None]
+        assert len(det.exchange.pending) == 4
+        done = [i['bucket'] for i in det.exchange.buckets]
         assert done == ([_b[1], _b[2], _b[3], _b[0]] if deferred else list(_b))
         assert sorted(done) == sorted(_b) and sum(hi - lo for lo, hi in done) == det.store.n_train      # the buckets tile the buffer
         det.wait_grads()

@@ -250,7 +250,7 @@ def _worker_opts(rank, world, port, q):
         for it in range(2):
             out = ddp.train_step(make_batch(rank), opt)
             out['loss'].backward()
-            used_partials = bool(model._partials_valid)
+            used_partials = bool(model.exchange.partials_valid)
             opt.step()
             torch.cuda.synchronize()
             ref = torch.zeros(1, device='cuda')

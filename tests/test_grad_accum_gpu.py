@@ -187,10 +187,10 @@ def _accumulated_window(model, opt, batches, leg):
         out['loss'].backward()
         if leg == 'proxy':
             if not closing:
-                assert model._pending == [] and model._late_todo == [] and model._partials_valid is False
+                assert model.exchange.pending == [] and model.exchange.todo == [] and model.exchange.partials_valid is False
             else:
-                n_buckets = len([i for i in model._last_bwd_infos if i['bucket'] is not None])
-                assert len(model._pending) + len(model._late_todo) == n_buckets == 4
+                n_buckets = len(model.exchange.buckets)
+                assert len(model.exchange.pending) + len(model.exchange.todo) == n_buckets == 4
         assert opt.acc_count == j
         if closing:
             opt.step()
@@ -198,7 +198,7 @@ def _accumulated_window(model, opt, batches, leg):
             opt.accumulate()
     assert opt.acc_count == 0
     if leg == 'proxy':          # every bucket was folded on the communication stream, in front of its stand-in collective
-        assert len(model._folded) == n_buckets and model._pending == [] and model._late_todo == []
+        assert len(model.exchange.folded) == n_buckets and model.exchange.pending == [] and model.exchange.todo == []
 
 
 @pytest.mark.parametrize('leg', LEGS)
@@ -249,7 +249,7 @@ def test_window_equals_its_manual_sum(leg):
     a_opt.accumulate()
     assert a_opt.acc_count == 1
     a_opt.load_state_dict(sd)
-    assert a_opt.acc_count == 0 and a_model._fold_acc is None
+    assert a_opt.acc_count == 0 and a_model.exchange.fold_acc is None
     torch.cuda.synchronize()
 
 
@@ -327,7 +327,7 @@ def _rank_main(rank, port, clip):
     for b in batches:
         out = r_model.train_step(b, r_opt)
         out['loss'].backward()
-        assert r_model.late_exchange and len(r_model._late_todo) == 4 and not r_model._pending
+        assert r_model.late_exchange and len(r_model.exchange.todo) == 4 and not r_model.exchange.pending
         torch.cuda.synchronize()
         acc = r_model.store.grad.clone() if acc is None else acc.add_(r_model.store.grad)
     r_model.wait_grads()
@@ -351,18 +351,18 @@ def _rank_main(rank, port, clip):
         out = model.train_step(b, opt)
         out['loss'].backward()
         if not closing:
-            if model._pending or model._late_todo or model._partials_valid:
+            if model.exchange.pending or model.exchange.todo or model.exchange.partials_valid:
                 errs.append('a non-closing micro-step queued a gradient collective')
             opt.accumulate()
             continue
-        if clip and not (model._partials_valid and len(model._pending) == 4):
-            errs.append(f'clipping: not the norm in pieces ({model._partials_valid}, {len(model._pending)} queued)')
-        if not clip and not (model.late_exchange and len(model._late_todo) == 4):
-            errs.append(f'no clipping: not the late exchange ({model.late_exchange}, {len(model._late_todo)} left)')
+        if clip and not (model.exchange.partials_valid and len(model.exchange.pending) == 4):
+            errs.append(f'clipping: not the norm in pieces ({model.exchange.partials_valid}, {len(model.exchange.pending)} queued)')
+        if not clip and not (model.late_exchange and len(model.exchange.todo) == 4):
+            errs.append(f'no clipping: not the late exchange ({model.late_exchange}, {len(model.exchange.todo)} left)')
         opt.step()
     torch.cuda.synchronize()
-    if len(model._folded) != 4:
-        errs.append(f'{len(model._folded)} of 4 buckets folded in front of their exchange')
+    if len(model.exchange.folded) != 4:
+        errs.append(f'{len(model.exchange.folded)} of 4 buckets folded in front of their exchange')
     if not _same(model.store.grad, total):
         errs.append(f'store.grad != acc_rank0 + acc_rank1 on {int((_bits(model.store.grad) != _bits(total)).sum())} elements')
     got = _state(model, opt)
@@ -370,7 +370,7 @@ def _rank_main(rank, port, clip):
         a, b_ = gather(_bits(t).to(torch.int32))
         if not torch.equal(a, b_):
             errs.append(f'{what} differs between the ranks on {int((a != b_).sum())} words')
-    infos = [i for i in model._last_bwd_infos if i['bucket'] is not None]
+    infos = model.exchange.buckets
 
     # host reference: one process, one update with the summed accumulators
     h_model = build()
@@ -385,7 +385,7 @@ def _rank_main(rank, port, clip):
             lo, hi = info['bucket']
             L.check(L.lib.dsl_sumsq_partial(L.ptr(h_model.store.grad[lo:hi]), hi - lo,
                                             C.c_void_p(h_model.clip_partials.data_ptr() + n_ * L.SUMSQ_PARTS * 4), L.stream_ptr()), 'dsl_sumsq_partial')
-        h_model._partials_valid, h_model._n_partials = True, len(infos) * L.SUMSQ_PARTS
+        h_model.exchange.partials_valid, h_model.exchange.n_partials = True, len(infos) * L.SUMSQ_PARTS
     torch.cuda.synchronize()
     h_opt.step()
     want = _state(h_model, h_opt)
