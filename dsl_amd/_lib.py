@@ -46,6 +46,16 @@ SLOT_UPD = 8         # named events 8 .. 11: gradient bucket 0 .. 3 of the last 
 SLOT_HEADW = 12      # named event: the head + FPN bucket of the last optimizer step is updated (deferred head update)
 (RLA_AVGPOOL, RLA_AVGPOOL_BWD, RLA_BN_TANH, RLA_BN_TANH_BWD, RLA_BN_FOLD, RLA_BN_POST, RLA_REC_SUM, RLA_TAIL_FWD, RLA_TAIL_BWD) = range(2, 11)
 MAX_GROUP = 8
+OPT_SGD, OPT_ADAM, OPT_ADAMW = 0, 1, 2      # DSL_OPT_*: dsl_optim_desc.kind
+OPT_MAX_GROUPS = 16
+
+
+class OptimDesc(C.Structure):      # dsl_optim_desc: passed by pointer, copied into the launch's kernel arguments
+    _fields_ = [('kind', C.c_int32), ('n_groups', C.c_int32),
+                ('lr', C.c_float * OPT_MAX_GROUPS), ('wd', C.c_float * OPT_MAX_GROUPS),
+                ('momentum', C.c_float), ('nesterov', C.c_int32), ('first_step', C.c_int32),
+                ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('step_scale', C.c_float), ('rsqrt_bc2', C.c_float),
+                ('max_norm', C.c_float)]
 
 
 class ConvDesc(C.Structure):
@@ -328,6 +338,7 @@ _SIGS = {
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],
     'dsl_grad_accumulate': [_vp, _vp, _l, _i, _vp],
+    'dsl_optim_step': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp, _vp],
     'dsl_ema_lerp': [_vp, _vp, _l, _f, _vp], 'dsl_ema_lerp_bf16': [_vp, _vp, _vp, _l, _f, _vp], 'dsl_cast_bf16': [_vp, _vp, _l, _vp],
     'dsl_pack_dgrad': [_vp, _vp, _vp, _i, _i, _i, _i, _vp], 'dsl_pack_dgrad_batched': [_vp, _i, _i, _vp],
     'dsl_detect_workspace_bytes': [_vp], 'dsl_fcos_detect': [_vp, _vp],

@@ -68,6 +68,63 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
   }
 }
 
+// The optimizer family (dsl_optim_step): sgd_kernel's pass - clip, update, bf16 re-pack, float4, grid stride - with a per-group
+// (lr, wd) table instead of the one-bit bias flag, Nesterov momentum, and a second moment for the Adam kinds.  One instance per
+// kind: the SGD instance has no v traffic.  The table is indexed by a per-lane value, so it is staged from the kernel arguments
+// into LDS once per block (a runtime-indexed argument array would live in scratch): per group the step length (lr; the Adam
+// kinds: lr * step_scale), the weight decay and AdamW's decay factor 1 - lr wd.  Group bytes are masked to the table's size.
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_kernel(const dsl_optim_desc d, float* __restrict__ p, const float* __restrict__ g,
+                                                    float* __restrict__ m, float* __restrict__ v, uint16_t* __restrict__ p16,
+                                                    const uint8_t* __restrict__ group, long long n, const float* gnorm_sq) {
+  __shared__ float tab[3][DSL_OPT_MAX_GROUPS];
+  if (threadIdx.x < DSL_OPT_MAX_GROUPS) {
+    const int k = threadIdx.x;
+    float lr = 0.f, wd = 0.f;
+    // (compile-time indices: the arguments stay in SGPRs)
+#pragma unroll
+    for (int j = 0; j < DSL_OPT_MAX_GROUPS; ++j)
+      if (j == k && j < d.n_groups) lr = d.lr[j], wd = d.wd[j];
+    tab[0][k] = KIND == DSL_OPT_SGD ? lr : lr * d.step_scale;
+    tab[1][k] = wd;
+    tab[2][k] = 1.f - lr * wd;
+  }
+  __syncthreads();
+  float clip = 1.f;
+  if (gnorm_sq) clip = fminf(d.max_norm / (sqrtf(*gnorm_sq) + 1e-6f), 1.f);
+  const float mom = d.momentum, b1 = d.beta1, b2 = d.beta2, omb1 = 1.f - d.beta1, omb2 = 1.f - d.beta2;
+  const long long n4 = n / 4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    f32x4 pv = *reinterpret_cast<const f32x4*>(p + 4 * i);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(g + 4 * i);
+    f32x4 mv = *reinterpret_cast<const f32x4*>(m + 4 * i);
+    f32x4 vv = {0.f, 0.f, 0.f, 0.f};
+    if (KIND != DSL_OPT_SGD) vv = *reinterpret_cast<const f32x4*>(v + 4 * i);
+    const uint32_t gr = *reinterpret_cast<const uint32_t*>(group + 4 * i);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int k = (gr >> (8 * e)) & (DSL_OPT_MAX_GROUPS - 1);
+      const float l = tab[0][k], w = tab[1][k];
+      if (KIND == DSL_OPT_SGD) {
+        const float dd = gv[e] * clip + w * pv[e];
+        mv[e] = d.first_step ? dd : mom * mv[e] + dd;
+        pv[e] -= l * (d.nesterov ? dd + mom * mv[e] : mv[e]);
+      } else {
+        float dd = gv[e] * clip;
+        if (KIND == DSL_OPT_ADAM) dd += w * pv[e];
+        else pv[e] *= tab[2][k];
+        mv[e] = b1 * mv[e] + omb1 * dd;
+        vv[e] = b2 * vv[e] + omb2 * dd * dd;
+        pv[e] -= l * (mv[e] / (sqrtf(vv[e]) * d.rsqrt_bc2 + d.eps));
+      }
+    }
+    *reinterpret_cast<f32x4*>(p + 4 * i) = pv;
+    *reinterpret_cast<f32x4*>(m + 4 * i) = mv;
+    if (KIND != DSL_OPT_SGD) *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
+    if (p16) *reinterpret_cast<u32x2*>(p16 + 4 * i) = u32x2{pack2bf(pv[0], pv[1]), pack2bf(pv[2], pv[3])};
+  }
+}
+
 __global__ void ema_kernel(float* __restrict__ t, const float* __restrict__ s, long long n, float keep, uint16_t* __restrict__ t16) {
   const long long n4 = n / 4;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
@@ -200,6 +257,34 @@ extern "C" int dsl_sgd_step(float* p, const float* g, float* m, void* p16, const
                      (uint16_t*)p16, group, (long long)n, lr, momentum, wd, bias_lr_mult, bias_decay_mult, gnorm_sq,
                      max_norm, first_step);
   DSL_LAUNCH_CHECK("sgd_kernel");
+  return 0;
+}
+
+extern "C" int dsl_optim_step(const dsl_optim_desc* d, float* p, const float* g, float* m, float* v, void* p16, const uint8_t* group,
+                              long n, const float* gnorm_sq, void* stream) {
+  DSL_CHECK(d, "dsl_optim_step: d is null");
+  DSL_CHECK(p, "dsl_optim_step: p is null");
+  DSL_CHECK(g, "dsl_optim_step: g is null");
+  DSL_CHECK(m, "dsl_optim_step: m is null");
+  DSL_CHECK(group, "dsl_optim_step: group is null");
+  DSL_CHECK(d->kind >= DSL_OPT_SGD && d->kind <= DSL_OPT_ADAMW, "dsl_optim_step: kind=%d is none of DSL_OPT_SGD / _ADAM / _ADAMW", d->kind);
+  DSL_CHECK(d->n_groups >= 1 && d->n_groups <= DSL_OPT_MAX_GROUPS, "dsl_optim_step: n_groups=%d must be 1 .. %d", d->n_groups,
+            DSL_OPT_MAX_GROUPS);
+  DSL_CHECK(d->kind == DSL_OPT_SGD || v, "dsl_optim_step: v is null (the Adam kinds need the second moment)");
+  DSL_CHECK(n > 0 && n % 4 == 0, "dsl_optim_step: n=%ld must be positive and a multiple of 4", n);
+  DSL_CHECK(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0 && (uintptr_t)p16 % 8 == 0 && (uintptr_t)group % 4 == 0,
+            "dsl_optim_step: p, g, m, v must be 16-byte aligned, p16 8-byte, group 4-byte (p=%p g=%p m=%p v=%p p16=%p group=%p)", (void*)p,
+            (const void*)g, (void*)m, (void*)v, p16, (const void*)group);
+  DSL_CHECK(d->kind != DSL_OPT_SGD || !d->nesterov || d->momentum != 0.f, "dsl_optim_step: nesterov needs momentum != 0");
+  const dim3 grid(nblocks(n / 4, 4096)), block(256);
+  const hipStream_t st = (hipStream_t)stream;
+  if (d->kind == DSL_OPT_SGD)
+    hipLaunchKernelGGL(optim_kernel<DSL_OPT_SGD>, grid, block, 0, st, *d, p, g, m, (float*)nullptr, (uint16_t*)p16, group, (long long)n, gnorm_sq);
+  else if (d->kind == DSL_OPT_ADAM)
+    hipLaunchKernelGGL(optim_kernel<DSL_OPT_ADAM>, grid, block, 0, st, *d, p, g, m, v, (uint16_t*)p16, group, (long long)n, gnorm_sq);
+  else
+    hipLaunchKernelGGL(optim_kernel<DSL_OPT_ADAMW>, grid, block, 0, st, *d, p, g, m, v, (uint16_t*)p16, group, (long long)n, gnorm_sq);
+  DSL_LAUNCH_CHECK("optim_kernel");
   return 0;
 }
 

@@ -1,8 +1,14 @@
 """Fused SGD over the flat parameter buffer (dsl_sgd_step): momentum, weight decay, the reference's
 paramwise rules (bias_lr_mult / bias_decay_mult), gradient-norm clipping and the bf16 re-pack in one
 pass.  Replaces torch.optim.SGD + mmcv OptimizerHook's clip_grad_norm_
-(mmdet/apis/train.py:111,157-166; configs/fcos_semi/*.py `optimizer`, `optimizer_config`)."""
+(mmdet/apis/train.py:111,157-166; configs/fcos_semi/*.py `optimizer`, `optimizer_config`).
+
+The optimizer family (dsl_optim_step): Nesterov SGD, Adam and AdamW, and mmcv's full paramwise_cfg as a table of up to 16
+(lr_mult, decay_mult) groups (param_group_mults / build_groups below).  Plain momentum SGD with at most the two bias keys keeps
+launching dsl_sgd_step with store.group, unchanged."""
+import bisect
 import ctypes as C
+import math
 import os
 
 import torch
@@ -14,28 +20,122 @@ from .registry import OPTIMIZERS
 
 from .tuning import skip_items
 
+PARAMWISE_KEYS = ('custom_keys', 'bias_lr_mult', 'bias_decay_mult', 'norm_decay_mult', 'dwconv_decay_mult', 'dcn_offset_lr_mult')
+LEGACY_KEYS = ('bias_lr_mult', 'bias_decay_mult')          # what dsl_sgd_step's one-bit flag expresses
+
+
+def is_norm_param(name):
+    """mmcv decides by module type (_BatchNorm, _InstanceNorm, GroupNorm, LayerNorm); here by the state-dict name: the towers'
+    GroupNorms (`.gn.`), BatchNorms (`.bnN`, `downsample.1`) and RLA_ResNet's per-block `stage_bns`."""
+    return ('.gn.' in name) or ('.bn' in name) or ('downsample.1' in name) or ('.stage_bns.' in name)
+
+
+def param_group_mults(name, paramwise_cfg=None):
+    """(lr_mult, decay_mult) of the parameter with state-dict name `name`: mmcv 1.3.x DefaultOptimizerConstructor.add_params,
+    restated FROM MEMORY (mmcv is not a dependency):
+      1. custom_keys first: the keys sorted alphabetically, then by length descending (stable); the first key that is a substring
+         of the name wins, its lr_mult / decay_mult (default 1) apply and NO other rule does.
+      2. otherwise lr_mult = bias_lr_mult for a leaf `bias` outside norm layers (and outside DCN modules: none are built);
+      3. otherwise decay_mult = norm_decay_mult for any parameter of a norm layer; else dwconv_decay_mult for a depth-wise
+         convolution (none are built); else bias_decay_mult for a leaf `bias`; else 1.
+    dwconv_decay_mult and dcn_offset_lr_mult are accepted and have no parameter to apply to."""
+    pw = paramwise_cfg or {}
+    unknown = [k for k in pw if k not in PARAMWISE_KEYS]
+    if unknown:
+        raise NotImplementedError(f'dsl_amd: paramwise_cfg keys {unknown} are not built ({", ".join(PARAMWISE_KEYS)})')
+    custom = pw.get('custom_keys') or {}
+    for key in sorted(sorted(custom), key=len, reverse=True):
+        if key in name:
+            return float(custom[key].get('lr_mult', 1.0)), float(custom[key].get('decay_mult', 1.0))
+    leaf = name.rsplit('.', 1)[-1]
+    norm = is_norm_param(name)
+    lm = dm = 1.0
+    if leaf == 'bias' and not norm:
+        lm = float(pw.get('bias_lr_mult', 1.0))
+    if norm:
+        dm = float(pw.get('norm_decay_mult', 1.0))
+    elif leaf == 'bias':
+        dm = float(pw.get('bias_decay_mult', 1.0))
+    return lm, dm
+
+
+def build_groups(model, paramwise_cfg=None):
+    """The group table and the per-element group ids of a detector's flat parameter buffer: one group per distinct
+    (lr_mult, decay_mult) pair over model.named_parameters() (trainable ones), group 0 always (1, 1).  Every parameter is a view
+    into store.train and has to lie inside one region of store.train_regions; what no parameter covers (tile padding, the
+    predictors' padding rows) is group 0.  Returns ([(lr_mult, decay_mult)], uint8 CPU tensor [n_train], {name: group})."""
+    st = model.store
+    regs = sorted((int(o), int(n), k) for k, (o, n, _) in st.train_regions.items())
+    starts = [r[0] for r in regs]
+    table, by_name, todo = [(1.0, 1.0)], {}, []
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        lo = int(p.storage_offset())
+        hi = lo + sum((int(d) - 1) * int(s) for d, s in zip(p.shape, p.stride()))
+        r = regs[max(bisect.bisect_right(starts, lo) - 1, 0)]
+        if not (r[0] <= lo and hi < r[0] + r[1]):
+            raise RuntimeError(f'parameter {name} [{lo}, {hi}] is not inside one region of the flat parameter buffer (nearest: {r[2]})')
+        pair = param_group_mults(name, paramwise_cfg)
+        if pair not in table:
+            table.append(pair)
+        by_name[name] = table.index(pair)
+        todo.append((p, by_name[name]))
+    if len(table) > L.OPT_MAX_GROUPS:
+        raise NotImplementedError(f'dsl_amd: paramwise_cfg yields {len(table)} distinct (lr_mult, decay_mult) pairs; '
+                                  f'dsl_optim_step has {L.OPT_MAX_GROUPS} groups')
+    ids = torch.zeros(st.n_train, dtype=torch.uint8)
+    for p, k in todo:
+        if k:
+            ids.as_strided(tuple(p.shape), tuple(p.stride()), int(p.storage_offset())).fill_(k)
+    return table, ids, by_name
+
+
 _PACK_SIDE = True                          # data-gradient weight packs off the caller's stream (measured: tools/experiments_r2.txt (exp_r2l))
 
 
 @OPTIMIZERS.register_module(name='SGD')
 class FlatSGD:
     def __init__(self, model, lr=0.01, momentum=0.9, weight_decay=0.0, paramwise_cfg=None, grad_clip=None,
-                 defer_head_update=False, late_exchange=True, **kw):
-        assert not kw.get('nesterov', False) and kw.get('dampening', 0) == 0
+                 defer_head_update=False, late_exchange=True, nesterov=False, dampening=0, **kw):
+        if dampening != 0:
+            raise NotImplementedError(f'dsl_amd: SGD dampening={dampening!r} is not built (0 only)')
+        self.nesterov = bool(nesterov)
+        if self.nesterov and float(momentum) == 0:
+            raise ValueError('Nesterov momentum requires a momentum and zero dampening')          # (torch.optim.SGD's wording)
+        self.momentum = float(momentum)
+        self._setup(model, lr, weight_decay, paramwise_cfg, grad_clip, defer_head_update, late_exchange,
+                    legacy=not self.nesterov and all(k in LEGACY_KEYS for k in (paramwise_cfg or {})))
+
+    kind = 'SGD'          # saved with the state (family path); a state of another kind is refused
+    STATE = ('momentum_buf',)          # the flat state buffers, laid out like store.train (state_dict key: _STATE_KEYS)
+    _STATE_KEYS = dict(momentum_buf='momentum', exp_avg_sq='exp_avg_sq')
+
+    def _setup(self, model, lr, weight_decay, paramwise_cfg, grad_clip, defer_head_update, late_exchange, legacy):
         self.model = model
         self.store = model.store
         self.exchange = model.exchange          # the detector's gradient exchange (data parallel, accumulation windows)
-        pw = paramwise_cfg or {}
+        pw = dict(paramwise_cfg or {})
+        self.paramwise_cfg = pw
         self.bias_lr_mult = float(pw.get('bias_lr_mult', 1.0))
         self.bias_decay_mult = float(pw.get('bias_decay_mult', 1.0))
-        self.momentum, self.weight_decay = float(momentum), float(weight_decay)
+        self.weight_decay = float(weight_decay)
         self.max_norm = None
         if grad_clip:
             assert grad_clip.get('norm_type', 2) == 2
             self.max_norm = float(grad_clip['max_norm'])
-        # two groups so that LR schedulers written against torch optimizers keep working
-        self.param_groups = [dict(lr=lr, initial_lr=lr, name='weights'),
-                             dict(lr=lr * self.bias_lr_mult, initial_lr=lr * self.bias_lr_mult, name='conv_bias')]
+        self.legacy = bool(legacy)          # plain momentum SGD, bias keys only: dsl_sgd_step on store.group, as ever
+        if self.legacy:
+            # two groups so that LR schedulers written against torch optimizers keep working
+            self.param_groups = [dict(lr=lr, initial_lr=lr, name='weights'),
+                                 dict(lr=lr * self.bias_lr_mult, initial_lr=lr * self.bias_lr_mult, name='conv_bias')]
+            self.group_table = self.group_ids = self.group_of = None
+        else:
+            # one group per distinct (lr_mult, decay_mult) pair (build_groups); the ids belong to this optimizer, store.group stays
+            self.group_table, self.group_ids, self.group_of = build_groups(model, pw)
+            self.param_groups = [dict(lr=lr * lm, initial_lr=lr * lm, lr_mult=lm, decay_mult=dm, name=f'lr_mult={lm:g},decay_mult={dm:g}')
+                                 for lm, dm in self.group_table]
+        self._group_dev = None
         self.momentum_buf = None
         self.gnorm_sq = None
         self.steps = 0
@@ -68,12 +168,17 @@ class FlatSGD:
     def _adopt_loaded_state(self):
         """A momentum tensor restored by load_state_dict (CPU tensor, possibly laid out by another build) -> a buffer laid out like this
         model's parameter buffer.  Called by step(); separate so that it can be checked without a device."""
-        st = self.store
         # state restored from a checkpoint (CPU tensor, possibly laid out by another build): move it into a buffer laid out like
         # the parameter buffer, REGION BY REGION (name -> offset, size, saved with the state), and keep the step count (resume
         # must not re-zero momentum).  A prefix copy is only right when the two layouts differ by trailing padding; a state
         # without a region table whose size is off by more than that is refused instead of being attached to the wrong parameters.
-        src = self.momentum_buf.reshape(-1)
+        for attr in self.STATE:          # (the Adam kinds: the second moment the same way)
+            setattr(self, attr, self._remap(getattr(self, attr)))
+        self._loaded_regions = None
+
+    def _remap(self, loaded):
+        st = self.store
+        src = loaded.reshape(-1)
         buf = torch.zeros_like(st.train)
         regs = self._loaded_regions
         cur = {k: (int(v[0]), int(v[1])) for k, v in st.train_regions.items()}
@@ -92,8 +197,7 @@ class FlatSGD:
                                    'state carries no region table to remap it by (saved by an older build with another layout?)')
             n = min(buf.numel(), src.numel())
             buf.view(-1)[:n].copy_(src[:n].to(device=st.device, dtype=buf.dtype))
-        self.momentum_buf = buf
-        self._loaded_regions = None
+        return buf
 
     def step(self):
         st = self.store
@@ -104,13 +208,17 @@ class FlatSGD:
             # bucket's update had written its momentum - that bucket then started its second step from zero momentum; which buckets,
             # if any, depended on how far the GPU lagged behind the host: found as a flaky bit-exactness test once the optimizer's
             # stream was shared between model instances)
-            self.momentum_buf = torch.zeros_like(st.train)
+            for attr in self.STATE:
+                setattr(self, attr, torch.zeros_like(st.train))
             self.steps = 0
             fresh = True
         elif (self.momentum_buf.device != st.device or self.momentum_buf.shape != st.train.shape
               or self._loaded_regions is not None):
             self._adopt_loaded_state()
             fresh = True          # (copied into place on the caller's stream just now: the same ordering as for the zero fill)
+        if not self.legacy and (self._group_dev is None or self._group_dev.device != st.device):
+            self._group_dev = self.group_ids.to(st.device)
+            fresh = True          # (uploaded on the caller's stream: the same ordering again)
         if self.gnorm_sq is None or self.gnorm_sq.device != st.device:
             self.gnorm_sq = torch.zeros(1, device=st.device)
         if self.exchange.mode == BANKED:
@@ -155,6 +263,35 @@ class FlatSGD:
         L.check(L.lib.dsl_grad_accumulate(C.c_void_p(self._acc.data_ptr() + lo * 4), C.c_void_p(self.store.grad.data_ptr() + lo * 4),
                                           hi - lo, mode, tp), 'dsl_grad_accumulate')
 
+    def _desc(self):
+        """dsl_optim_desc of the step about to run: the groups' current rates (the LR hooks write param_groups[k]['lr']), weight
+        decay per group, and this kind's scalars."""
+        d = L.OptimDesc()
+        d.kind, d.n_groups = L.OPT_SGD, len(self.param_groups)
+        for k, g in enumerate(self.param_groups):
+            d.lr[k] = float(g['lr'])
+            d.wd[k] = self.weight_decay * float(g['decay_mult'])
+        d.momentum, d.nesterov, d.first_step = self.momentum, int(self.nesterov), int(self.steps == 0)
+        d.max_norm = self.max_norm or 0.0
+        return d
+
+    def _update(self, lo, hi, gptr, stream_ptr):
+        """The update of elements [lo, hi) of the flat buffers on the stream `stream_ptr`; gptr: the squared gradient norm on the
+        device (clipping), or None.  _walk's one way to the kernels, per bucket and flat."""
+        st = self.store
+        at = lambda t, size: C.c_void_p(t.data_ptr() + lo * size)          # noqa: E731
+        if self.legacy:
+            lr = float(self.param_groups[0]['lr'])
+            blr = float(self.param_groups[1]['lr']) / lr if lr != 0 else self.bias_lr_mult
+            L.check(L.lib.dsl_sgd_step(at(st.train, 4), at(st.grad, 4), at(self.momentum_buf, 4), at(st.train16, 2), at(st.group, 1),
+                                       hi - lo, lr, self.momentum, self.weight_decay, blr, self.bias_decay_mult, L.ptr(gptr),
+                                       self.max_norm or 0.0, int(self.steps == 0), stream_ptr), 'dsl_sgd_step')
+            return
+        v = getattr(self, 'exp_avg_sq', None)
+        L.check(L.lib.dsl_optim_step(C.byref(self._desc()), at(st.train, 4), at(st.grad, 4), at(self.momentum_buf, 4),
+                                     at(v, 4) if v is not None else None, at(st.train16, 2), at(self._group_dev, 1), hi - lo,
+                                     L.ptr(gptr), stream_ptr), 'dsl_optim_step')
+
     def _walk(self, update, fresh):
         """The schedule shared by step() (update=True) and accumulate() (False): which stream touches which gradient bucket behind
         which events.  accumulate() swaps dsl_sgd_step for dsl_grad_accumulate and leaves the data-gradient packs alone (the
@@ -165,8 +302,6 @@ class FlatSGD:
         window = update and self.acc_count > 0
         acc_mode = L.ACC_ADD if self.acc_count else L.ACC_SET
         sp = L.stream_ptr()
-        lr = float(self.param_groups[0]['lr'])
-        blr = float(self.param_groups[1]['lr']) / lr if lr != 0 else self.bias_lr_mult
         self._sync_defer()          # (OptimizerHook may set max_norm after construction)
         infos = ex.buckets          # completion order; a deferred bucket comes last
         if self.max_norm is None and infos and st.grad.is_cuda and all(i['bucket'][0] % 4 == 0 for i in infos):
@@ -221,7 +356,6 @@ class FlatSGD:
                     #  follow them, not only its weight gradients)
                     if (info['main'] or never != 0 or ex.world_size > 1) and tgt is not cur:
                         tgt.wait_stream(cur)
-                o4, o2, o1 = lo * 4, lo * 2, lo
                 if 'sgd' in skip_items():          # step-level ablation (tools/step_ablation.sh): timing only
                     continue
                 if not update:
@@ -230,10 +364,7 @@ class FlatSGD:
                 # (ex.folded is read bucket by bucket: the late exchanges run, and fold, inside this walk)
                 if window and (int(lo), int(hi)) not in ex.folded:          # (no exchange in front of this bucket's update: the fold goes here)
                     self._acc_launch(lo, hi, L.ACC_FOLD, tp)
-                L.check(L.lib.dsl_sgd_step(C.c_void_p(st.train.data_ptr() + o4), C.c_void_p(st.grad.data_ptr() + o4),
-                                           C.c_void_p(self.momentum_buf.data_ptr() + o4), C.c_void_p(st.train16.data_ptr() + o2),
-                                           C.c_void_p(st.group.data_ptr() + o1), hi - lo, lr, self.momentum, self.weight_decay, blr,
-                                           self.bias_decay_mult, None, 0.0, int(self.steps == 0), tp), 'dsl_sgd_step')
+                self._update(lo, hi, None, tp)
                 if late:          # "gradient bucket <slot> is updated": what the next forward pass waits for in front of that stage
                     L.check(L.lib.dsl_stream_record_slot(L.SLOT_UPD + int(info['slot']), tp), 'dsl_stream_record_slot')
             ex.clear_pending()
@@ -282,25 +413,39 @@ class FlatSGD:
                     self._sumsq_ws = torch.zeros(1024, device=st.device)
                 L.check(L.lib.dsl_sumsq_det(L.ptr(st.grad), st.n_train, L.ptr(self.gnorm_sq), L.ptr(self._sumsq_ws), sp), 'dsl_sumsq_det')
             gptr = self.gnorm_sq
-        L.check(L.lib.dsl_sgd_step(L.ptr(st.train), L.ptr(st.grad), L.ptr(self.momentum_buf), L.ptr(st.train16),
-                                   L.ptr(st.group), st.n_train, lr, self.momentum, self.weight_decay, blr,
-                                   self.bias_decay_mult, L.ptr(gptr), self.max_norm or 0.0, int(self.steps == 0), sp),
-                'dsl_sgd_step')
+        self._update(0, st.n_train, gptr, sp)
         st.repack_dgrad(sp, side=_PACK_SIDE)
 
     def state_dict(self):
         # regions: where every named parameter lives in the flat momentum buffer - what load_state_dict / step remap by.
         # (late exchange / deferred head update: the last step's updates may still be writing the momentum on another stream)
         self.store.wait_pending()
-        return dict(momentum=self.momentum_buf, steps=self.steps, param_groups=self.param_groups,
-                    regions={k: (int(v[0]), int(v[1])) for k, v in self.store.train_regions.items()})
+        sd = dict(momentum=self.momentum_buf, steps=self.steps, param_groups=self.param_groups,
+                  regions={k: (int(v[0]), int(v[1])) for k, v in self.store.train_regions.items()})
+        if not self.legacy:          # (the legacy path's state keeps its four keys: checkpoints of every earlier build)
+            sd.update(kind=self.kind, groups=[tuple(g) for g in self.group_table])
+            for attr in self.STATE[1:]:
+                sd[self._STATE_KEYS[attr]] = getattr(self, attr)
+        return sd
 
     def load_state_dict(self, sd):
         """Restores momentum, the step count (first-step rule of torch.optim.SGD: buf = grad) and the groups' learning
-        rates.  The momentum tensor may live on the CPU (runner.resume loads with map_location='cpu'); step() moves it."""
+        rates.  The momentum tensor may live on the CPU (runner.resume loads with map_location='cpu'); step() moves it.
+        A state of another kind (no `kind`: plain SGD) or with another group table is refused: its moments mean something else."""
+        theirs = sd.get('kind', 'SGD')
+        if theirs != self.kind:
+            raise RuntimeError(f'optimizer state: saved by kind {theirs!r}, this optimizer is of kind {self.kind!r}')
+        groups = [tuple(float(x) for x in g) for g in sd['groups']] if sd.get('groups') else None
+        if groups != (None if self.legacy else [tuple(g) for g in self.group_table]):
+            raise RuntimeError(f'optimizer state: its parameter groups (lr_mult, decay_mult) {groups or "of plain SGD (bias flag)"} are not '
+                               f'this optimizer\'s {self.group_table or "of plain SGD (bias flag)"}: nesterov / paramwise_cfg differ')
         self.store.wait_pending()          # (the buffer replaced here may still be written by the last step's updates)
-        m = sd['momentum']
-        self.momentum_buf = m.detach().clone() if isinstance(m, torch.Tensor) else None
+        for attr in self.STATE:
+            m = sd.get(self._STATE_KEYS[attr])
+            setattr(self, attr, m.detach().clone() if isinstance(m, torch.Tensor) else None)
+        if any(getattr(self, attr) is None for attr in self.STATE):          # (saved before the first step)
+            for attr in self.STATE:
+                setattr(self, attr, None)
         self.steps = int(sd['steps']) if self.momentum_buf is not None else 0
         self.param_groups = [dict(g) for g in sd['param_groups']]
         self._loaded_regions = dict(sd['regions']) if sd.get('regions') else None
@@ -310,6 +455,48 @@ class FlatSGD:
         self._sumsq_ws = None
         self.acc_count = 0          # (the accumulation window is not part of the state: a resume starts a fresh one)
         self.exchange.close_window()
+
+
+@OPTIMIZERS.register_module(name='Adam')
+class FlatAdam(FlatSGD):
+    """torch.optim.Adam (and AdamW: FlatAdamW) over the flat parameter buffer, dsl_optim_step's Adam kinds.  The first moment is
+    `momentum_buf` (exp_avg), so every reader of FlatSGD's state keeps working; the second, `exp_avg_sq`, lies beside it, laid out
+    like store.train and zero-filled with it on the caller's stream.  The bias corrections of step t = steps + 1 are computed
+    here in double (there is no device step counter).  The schedule - buckets, streams, late exchange, deferred head update,
+    accumulation, clipping - is FlatSGD._walk's, unchanged."""
+    kind = 'Adam'
+    STATE = ('momentum_buf', 'exp_avg_sq')
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, paramwise_cfg=None, grad_clip=None,
+                 defer_head_update=False, late_exchange=True, amsgrad=False, **kw):
+        if amsgrad:
+            raise NotImplementedError('dsl_amd: amsgrad=True is not built (Adam / AdamW without the running maximum)')
+        self.beta1, self.beta2, self.eps = float(betas[0]), float(betas[1]), float(eps)
+        if not (0.0 <= self.beta1 < 1.0 and 0.0 <= self.beta2 < 1.0 and self.eps >= 0.0):
+            raise ValueError(f'invalid betas {betas!r} / eps {eps!r}')
+        self.momentum, self.nesterov = 0.0, False
+        self.exp_avg_sq = None
+        self._setup(model, lr, weight_decay, paramwise_cfg, grad_clip, defer_head_update, late_exchange, legacy=False)
+
+    exp_avg = property(lambda self: self.momentum_buf)
+
+    def _desc(self):
+        d = super()._desc()
+        d.kind = L.OPT_ADAMW if self.kind == 'AdamW' else L.OPT_ADAM
+        t = self.steps + 1
+        d.beta1, d.beta2, d.eps = self.beta1, self.beta2, self.eps
+        d.step_scale = 1.0 / (1.0 - self.beta1 ** t)
+        d.rsqrt_bc2 = 1.0 / math.sqrt(1.0 - self.beta2 ** t)
+        return d
+
+
+@OPTIMIZERS.register_module(name='AdamW')
+class FlatAdamW(FlatAdam):
+    """torch.optim.AdamW: the decay leaves the gradient and multiplies the weight (p *= 1 - lr wd) in front of Adam's update."""
+    kind = 'AdamW'
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, **kw)
 
 
 def build_optimizer(model, cfg, grad_clip=None):

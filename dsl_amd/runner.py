@@ -12,6 +12,7 @@ refresh runs the teacher and its post-processing on the GPU and keeps the labels
 bank (the reference's per-image JSON layout is kept as an optional export)."""
 import gc
 import json
+import math
 import os
 import time
 
@@ -108,14 +109,12 @@ class SemiEpochBasedRunner:
                                 log_config=None, momentum_config=None, timer_config=None, custom_hooks_config=None):
         if lr_config is not None:
             if isinstance(lr_config, dict):
-                c = dict(lr_config)
-                policy = c.pop('policy')
-                assert policy == 'step', f'lr policy {policy!r}: only the step policy of configs/fcos_semi is built'
-                hook = StepLrUpdaterHook(**c)
+                hook = build_lr_hook(lr_config)
             else:
                 hook = lr_config
             self.register_hook(hook, priority='VERY_HIGH')
-        assert momentum_config is None, 'momentum schedules are not used by configs/fcos_semi'
+        if momentum_config is not None:
+            raise NotImplementedError('dsl_amd: momentum_config (momentum schedules) is not built; configs/fcos_semi use none')
         if optimizer_config is not None:
             hook = optimizer_config
             if isinstance(optimizer_config, dict):
@@ -395,30 +394,142 @@ class GradientCumulativeOptimizerHook(OptimizerHook):
         self._restore(runner)
 
 
-@HOOKS.register_module()
-class StepLrUpdaterHook(Hook):
-    """policy='step', by_epoch, gamma 0.1; warm-up over warmup_iters: 'linear' from warmup_ratio, or 'constant' at warmup_ratio
-    (mmcv LrUpdaterHook.get_warmup_lr; configs/fcos/fcos_r50_caffe_fpn_gn-head_1x_coco.py uses 'constant')."""
+class LrUpdaterHook(Hook):
+    """mmcv LrUpdaterHook: the warm-up every policy shares.  The regular rate of a group is get_lr(runner, base) with base the
+    group's initial_lr; policies whose rate is base times a number state that number (factor()).  During the first warmup_iters
+    iterations (warmup_by_epoch: warmup_iters counts epochs, times len(runner.data_loader)) the regular rate is multiplied by
+      'constant'  warmup_ratio
+      'linear'    1 - (1 - iter / warmup_iters)(1 - warmup_ratio)
+      'exp'       warmup_ratio^(1 - iter / warmup_iters)
+    and iteration warmup_iters is the first at the regular rate.  by_epoch: the policy's progress counts epochs (of max_epochs),
+    else iterations (of max_iters).  Rates are recomputed from runner.epoch / runner.iter in front of every iteration."""
+    WARMUPS = (None, 'constant', 'linear', 'exp')
 
-    def __init__(self, step, gamma=0.1, warmup=None, warmup_iters=0, warmup_ratio=0.1, by_epoch=True, **kw):
-        self.step = [step] if isinstance(step, int) else list(step)
-        self.gamma, self.warmup, self.warmup_iters, self.warmup_ratio = gamma, warmup, warmup_iters, warmup_ratio
-        if warmup not in (None, 'linear', 'constant'):
-            raise NotImplementedError(f"dsl_amd: lr warm-up {warmup!r} is not built (None, 'linear', 'constant')")
+    def __init__(self, by_epoch=True, warmup=None, warmup_iters=0, warmup_ratio=0.1, warmup_by_epoch=False, **kw):
+        if warmup not in self.WARMUPS:
+            raise NotImplementedError(f"dsl_amd: lr warm-up {warmup!r} is not built (None, 'constant', 'linear', 'exp')")
+        if warmup is not None and not (warmup_iters > 0 and 0 < warmup_ratio <= 1.0):
+            raise ValueError(f'lr warm-up needs warmup_iters > 0 and 0 < warmup_ratio <= 1 (got {warmup_iters!r}, {warmup_ratio!r})')
+        self.by_epoch, self.warmup, self.warmup_ratio, self.warmup_by_epoch = bool(by_epoch), warmup, warmup_ratio, bool(warmup_by_epoch)
+        self.warmup_iters = None if self.warmup_by_epoch else warmup_iters
+        self.warmup_epochs = warmup_iters if self.warmup_by_epoch else None
 
-    def _factor(self, runner):
-        f = self.gamma ** sum(1 for s in self.step if runner.epoch >= s)
-        if self.warmup == 'linear' and runner.iter < self.warmup_iters:
+    def at(self, runner):
+        return runner.epoch if self.by_epoch else runner.iter
+
+    def progress(self, runner):
+        return self.at(runner) / (runner.max_epochs if self.by_epoch else runner.max_iters)
+
+    def factor(self, runner):
+        return None
+
+    def get_lr(self, runner, base_lr):
+        return base_lr * self.factor(runner)
+
+    def warmup_factor(self, runner):
+        if self.warmup is None:
+            return None
+        if self.warmup_by_epoch:
+            self.warmup_iters = self.warmup_epochs * len(runner.data_loader)
+        if runner.iter >= self.warmup_iters:
+            return None
+        if self.warmup == 'constant':
+            return self.warmup_ratio
+        if self.warmup == 'linear':
             k = (1 - runner.iter / self.warmup_iters) * (1 - self.warmup_ratio)
-            f = f * (1 - k)
-        elif self.warmup == 'constant' and runner.iter < self.warmup_iters:
-            f = f * self.warmup_ratio
-        return f
+            return 1 - k
+        return self.warmup_ratio ** (1 - runner.iter / self.warmup_iters)
 
     def before_train_iter(self, runner):
-        f = self._factor(runner)
+        f, w = self.factor(runner), self.warmup_factor(runner)
         for g in runner.optimizer.param_groups:
-            g['lr'] = g['initial_lr'] * f
+            if f is not None:
+                g['lr'] = g['initial_lr'] * (f if w is None else f * w)
+            else:
+                lr = self.get_lr(runner, g['initial_lr'])
+                g['lr'] = lr if w is None else lr * w
+
+
+@HOOKS.register_module()
+class StepLrUpdaterHook(LrUpdaterHook):
+    """policy='step': gamma (0.1) to the number of milestones in `step` reached - epochs, or iterations with by_epoch=False.
+    Warm-up: LrUpdaterHook (configs/fcos/fcos_r50_caffe_fpn_gn-head_1x_coco.py uses 'constant')."""
+
+    def __init__(self, step, gamma=0.1, min_lr=None, **kw):
+        super().__init__(**kw)
+        if min_lr is not None:
+            raise NotImplementedError("dsl_amd: the step policy's min_lr is not built")
+        self.step = [step] if isinstance(step, int) else list(step)
+        self.gamma = gamma
+
+    def factor(self, runner):
+        at = self.at(runner)
+        return self.gamma ** sum(1 for s in self.step if at >= s)
+
+    def _factor(self, runner):          # (the regular factor times the warm-up's: what before_train_iter multiplies initial_lr by)
+        f, w = self.factor(runner), self.warmup_factor(runner)
+        return f if w is None else f * w
+
+
+@HOOKS.register_module()
+class CosineAnnealingLrUpdaterHook(LrUpdaterHook):
+    """policy='CosineAnnealing': target + 0.5 (base - target)(1 + cos(pi progress / max)), target = min_lr, or base min_lr_ratio."""
+
+    def __init__(self, min_lr=None, min_lr_ratio=None, **kw):
+        super().__init__(**kw)
+        if (min_lr is None) == (min_lr_ratio is None):
+            raise ValueError('CosineAnnealing: give exactly one of min_lr and min_lr_ratio')
+        self.min_lr, self.min_lr_ratio = min_lr, min_lr_ratio
+
+    def get_lr(self, runner, base_lr):
+        target = base_lr * self.min_lr_ratio if self.min_lr_ratio is not None else self.min_lr
+        return target + 0.5 * (base_lr - target) * (1 + math.cos(math.pi * self.progress(runner)))
+
+
+@HOOKS.register_module()
+class PolyLrUpdaterHook(LrUpdaterHook):
+    """policy='poly': (base - min_lr)(1 - progress / max)^power + min_lr."""
+
+    def __init__(self, power=1.0, min_lr=0.0, **kw):
+        super().__init__(**kw)
+        self.power, self.min_lr = power, min_lr
+
+    def get_lr(self, runner, base_lr):
+        return (base_lr - self.min_lr) * (1 - self.progress(runner)) ** self.power + self.min_lr
+
+
+@HOOKS.register_module()
+class ExpLrUpdaterHook(LrUpdaterHook):
+    """policy='exp': base gamma^progress."""
+
+    def __init__(self, gamma, **kw):
+        super().__init__(**kw)
+        self.gamma = gamma
+
+    def factor(self, runner):
+        return self.gamma ** self.at(runner)
+
+
+@HOOKS.register_module()
+class FixedLrUpdaterHook(LrUpdaterHook):
+    """policy='fixed': the base rate (and the warm-up)."""
+
+    def factor(self, runner):
+        return 1.0
+
+
+# mmcv BaseRunner.register_lr_hook: policy -> <Policy>LrUpdaterHook (a lower-case policy is title()d, 'CosineAnnealing' taken as it is)
+LR_POLICIES = dict(step=StepLrUpdaterHook, CosineAnnealing=CosineAnnealingLrUpdaterHook, poly=PolyLrUpdaterHook, exp=ExpLrUpdaterHook,
+                   fixed=FixedLrUpdaterHook)
+
+
+def build_lr_hook(lr_config):
+    c = dict(lr_config)
+    policy = c.pop('policy')
+    cls = LR_POLICIES.get(policy)
+    if cls is None:
+        raise NotImplementedError(f'dsl_amd: lr policy {policy!r} is not built ({", ".join(LR_POLICIES)})')
+    return cls(**c)
 
 
 @HOOKS.register_module()

@@ -796,6 +796,32 @@ int dsl_sumsq_det(const float* x, long n, float* out /* [1] */, float* workspace
 int dsl_sgd_step(float* p, const float* g, float* m, void* p16, const uint8_t* group, long n,
                  float lr, float momentum, float wd, float bias_lr_mult, float bias_decay_mult,
                  const float* gnorm_sq, float max_norm, int first_step, void* stream);
+/* The optimizer family: what mmdet/apis/train.py:111 `build_optimizer(model, cfg.optimizer)` builds beyond plain momentum SGD -
+ * torch.optim.SGD(nesterov=True), Adam, AdamW - with mmcv DefaultOptimizerConstructor's paramwise_cfg as a table of up to
+ * DSL_OPT_MAX_GROUPS (lr, wd) pairs; group[i] is element i's row.  One pass like dsl_sgd_step: clip, update, bf16(p) to p16.
+ * With d0 = g * clip, clip = min(max_norm / (sqrt(*gnorm_sq) + 1e-6), 1) when gnorm_sq != NULL (else 1), k = group[i]:
+ *   SGD    d = d0 + wd[k] p;  m = d (first_step) or momentum m + d;  p -= lr[k] (nesterov ? d + momentum m : m)
+ *   ADAM   d = d0 + wd[k] p;  m = beta1 m + (1 - beta1) d;  v = beta2 v + (1 - beta2) d d;
+ *          p -= lr[k] step_scale * m / (sqrt(v) rsqrt_bc2 + eps)
+ *   ADAMW  p *= 1 - lr[k] wd[k], then ADAM's update with d = d0
+ * (torch's single-tensor formulas).  The bias corrections come from the host, computed in double for step t = 1, 2, ..:
+ * step_scale = 1 / (1 - beta1^t), rsqrt_bc2 = 1 / sqrt(1 - beta2^t); there is no device step counter.  The descriptor is copied
+ * into the launch's kernel arguments: nothing is allocated and no device table has to stay alive.  Refused before anything is
+ * launched: a null d / p / g / m / group, v == NULL for an Adam kind, n <= 0 or n % 4 != 0, p / g / m / v not 16-byte aligned
+ * (p16: 8, group: 4), kind or n_groups out of range, nesterov with momentum == 0.  v may be NULL for SGD, p16 may be NULL. */
+#define DSL_OPT_SGD   0
+#define DSL_OPT_ADAM  1
+#define DSL_OPT_ADAMW 2
+#define DSL_OPT_MAX_GROUPS 16
+typedef struct dsl_optim_desc {
+  int32_t kind, n_groups;
+  float lr[DSL_OPT_MAX_GROUPS], wd[DSL_OPT_MAX_GROUPS];      /* absolute, per group */
+  float momentum; int32_t nesterov, first_step;              /* SGD */
+  float beta1, beta2, eps, step_scale, rsqrt_bc2;            /* Adam kinds */
+  float max_norm;
+} dsl_optim_desc;
+int dsl_optim_step(const dsl_optim_desc* d, float* p, const float* g, float* m, float* v /* NULL for SGD */, void* p16 /* may be NULL */,
+                   const uint8_t* group, long n, const float* gnorm_sq /* NULL: no clip */, void* stream);
 /* Gradient accumulation over flat fp32 buffers (mmcv GradientCumulativeOptimizerHook): the gradient of one micro-step joins the
  * window's running sum.  Plain fp32 adds in micro-step order - one rounding per element and call, no atomics, denormals kept - i.e.
  * the bits of torch's `p.grad += g`.  n > 0, n % 4 == 0, both pointers 16-byte aligned (checked before anything is launched). */
