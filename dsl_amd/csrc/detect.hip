@@ -28,6 +28,10 @@
 // PAAHead (DSL_HEAD_PAA beside DSL_HEAD_ATSS, the descriptor then being a dsl_det_paa_desc; PAAHead._get_bboxes and score_voting,
 // mmdet/models/dense_heads/paa_head.py:519-673): ATSS's decode; the key and the pair score are sqrt(sigmoid(cls) * sigmoid(iou)),
 // which score_thr tests and which is the final score (no centerness factor); with score_voting det_vote_kernel runs behind the NMS.
+//
+// FoveaHead (DSL_HEAD_FOVEA, the descriptor then being a dsl_det_fovea_desc; FoveaHead._get_bboxes, mmdet/models/dense_heads/
+// fovea_head.py:298-348): det_decode takes the distances as base_len * exp(x) from the point s (x + 0.5) and clamps to img_shape - 1;
+// no Scale and no centerness factor (GFL's unit logit kNoCtr).  dsl_fcos_detect_collect refuses the flag.
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -49,6 +53,8 @@ struct DetK {
   float anchor_scale, stds[4];
   int gfl_R;                         // DSL_HEAD_GFL: reg_max + 1 bins per side (0 = not a GFL head)
   int paa;                           // DSL_HEAD_PAA: the pair score is sqrt(sigmoid(cls) * sigmoid(iou)), threshold and final score alike
+  int fovea;                         // DSL_HEAD_FOVEA: base_len * exp(x) from the point s (x + 0.5), clamp to img_shape - 1; no Scale
+  float base_len[DSL_MAX_SEG];
   const float* scales; const float* img_shapes; const float* scale_factors;
   float* dets; long long* det_labels; int* det_count;
   // workspace
@@ -73,7 +79,7 @@ struct AugK {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-// the "centerness logit" of a head without centerness (DSL_HEAD_GFL): expf(-100) is 0, sigmoidf_ gives exactly 1
+// the "centerness logit" of a head without centerness (DSL_HEAD_GFL, DSL_HEAD_FOVEA): expf(-100) is 0, sigmoidf_ gives exactly 1
 __device__ __attribute__((used)) float kNoCtr = 100.f;      // (never written)
 
 // key[m] = max_c sigmoid(cls) * sigmoid(ctr)     (fcos_head.py:472-473).  Full groups of 4 classes, then the partial
@@ -279,9 +285,20 @@ __device__ __forceinline__ void det_decode(const DetK& p, int img, int lvl, int 
   const float* rc = p.rc + (long long)m * p.ld_rc;
   const int s = p.stride[lvl];
   const int y = loc / p.w[lvl], x = loc - y * p.w[lvl];
+  const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
+  if (p.fovea) {
+    // the point (s (x + 0.5), s (y + 0.5)), distances base_len * exp(raw) - no Scale: p.scales is not read - and the clamp to
+    // img_shape - 1 (fovea_head.py:130-132,317,326-333)
+    const float fx = (float)s * ((float)x + 0.5f), fy = (float)s * ((float)y + 0.5f);
+    const float bl = p.base_len[lvl];
+    b[0] = fminf(fmaxf(fx - bl * expf(rc[0]), 0.f), W - 1.f);
+    b[1] = fminf(fmaxf(fy - bl * expf(rc[1]), 0.f), H - 1.f);
+    b[2] = fminf(fmaxf(fx + bl * expf(rc[2]), 0.f), W - 1.f);
+    b[3] = fminf(fmaxf(fy + bl * expf(rc[3]), 0.f), H - 1.f);
+    return;
+  }
   const float px = (float)x * (float)s + (float)(s / 2), py = (float)y * (float)s + (float)(s / 2);
   const float sc = p.scales[lvl];
-  const float H = p.img_shapes[2 * img], W = p.img_shapes[2 * img + 1];
   if (p.gfl_R) {
     // per side the softmax expectation over its R bins of scale x (Integral, gfl_head.py:15-48), times the stride; distance2bbox from
     // the anchor centre (x s, y s), clipped to img_shape (gfl_head.py:416-426)
@@ -992,6 +1009,17 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
     DSL_CHECK(!k.exp_decode && !k.atss && !d->ctr, "%s: DSL_HEAD_GFL goes with no other decode flag and has no centerness", who);
     DSL_CHECK(d->ld_rc >= 4 * (g->reg_max + 1), "%s: ld_rc must hold 4 (reg_max + 1) columns", who);
     k.gfl_R = g->reg_max + 1;
+  }
+  if (d->head_flags & DSL_HEAD_FOVEA) {
+    const dsl_det_fovea_desc* f = reinterpret_cast<const dsl_det_fovea_desc*>(d);      // the flag says: d is a dsl_det_fovea_desc's first member
+    DSL_CHECK(d->head_flags == DSL_HEAD_FOVEA && !d->ctr, "%s: DSL_HEAD_FOVEA goes with no other flag and has no centerness", who);
+    for (int l = 0; l < d->nlvl; ++l) {
+      DSL_CHECK(f->base_len[l] > 0.f && f->base_len[l] < 1e30f, "%s: DSL_HEAD_FOVEA needs a dsl_det_fovea_desc with base_len > 0", who);
+      k.base_len[l] = f->base_len[l];
+    }
+    k.fovea = 1;
+  }
+  if (d->head_flags & (DSL_HEAD_GFL | DSL_HEAD_FOVEA)) {      // no centerness factor: the unit "logit"
     void* one = nullptr;
     DSL_CHECK(hipGetSymbolAddress(&one, HIP_SYMBOL(kNoCtr)) == hipSuccess && one, "%s: no address for the unit centerness", who);
     k.ctr = (const float*)one; k.ld_ctr = 0;
@@ -1022,10 +1050,11 @@ extern "C" size_t dsl_detect_workspace_bytes(const dsl_det_desc* d) {
 
 extern "C" int dsl_fcos_detect(const dsl_det_desc* d, void* stream) {
   DSL_CHECK(d && d->nlvl >= 1 && d->nlvl <= DSL_MAX_SEG && d->n >= 1, "dsl_fcos_detect: bad descriptor");
-  DSL_CHECK(d->cls_logits && d->regctr && d->scales && d->img_shapes && d->dets && d->det_labels && d->det_count &&
+  const bool fovea = (d->head_flags & DSL_HEAD_FOVEA) != 0;      // no Scale, four box columns
+  DSL_CHECK(d->cls_logits && d->regctr && (d->scales || fovea) && d->img_shapes && d->dets && d->det_labels && d->det_count &&
                 d->workspace,
             "dsl_fcos_detect: null pointer");
-  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr ? 4 : 5),
+  DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_rc >= (d->ctr || fovea ? 4 : 5),
             "dsl_fcos_detect: unsupported layout");
   DSL_CHECK(d->max_per_img > 0 && d->max_per_img <= NMS_THREADS && d->nms_pre > 0, "dsl_fcos_detect: max_per_img must be in 1..%d", NMS_THREADS);
   if (soft_check(d, "dsl_fcos_detect")) return -1;
@@ -1060,6 +1089,8 @@ extern "C" int dsl_fcos_detect_collect(const dsl_det_desc* d, const dsl_det_desc
                                        size_t pool_bytes, void* stream) {
   if (aug_check(d, nviews, "dsl_fcos_detect_collect")) return -1;
   DSL_CHECK(!(d->head_flags & DSL_HEAD_PAA), "dsl_fcos_detect_collect: DSL_HEAD_PAA has no test-time augmentation (paa_head.py:536-538)");
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_FOVEA),
+            "dsl_fcos_detect_collect: DSL_HEAD_FOVEA has no test-time augmentation (FoveaHead.get_bboxes has no with_nms argument)");
   DSL_CHECK(pool_desc, "dsl_fcos_detect_collect: null pool descriptor");
   if (soft_check(pool_desc, "dsl_fcos_detect_collect")) return -1;          // its nms_method sizes the pool's scratch (aug_layout)
   // the pool is laid out by ITS nlvl / nms_pre / num_classes: a view that differs would write into other views' rows

@@ -1,4 +1,4 @@
-// What the head-loss translation units (fcos_loss.hip, gfl_loss.hip) share: the level geometry of a dsl_fcos_desc with its one host
+// What the head-loss translation units (fcos_loss.hip, gfl_loss.hip, fovea_loss.hip) share: the level geometry of a dsl_fcos_desc with its one host
 // fill, the location decoder, the kernel arguments every head's kernels read, and the fixed-order sum of per-block records.
 // Include after common.hpp.
 #pragma once

@@ -266,6 +266,17 @@ class KnowledgeDistillationKLDivLoss(_LossCfg):
         self.T = float(T)
 
 
+@LOSSES.register_module()
+class SmoothL1Loss(_LossCfg):
+    """mmdet/models/losses/smooth_l1_loss.py:11-29,49-101: 0.5 d^2 / beta where |d| < beta, else |d| - 0.5 beta.  FoveaHead's loss_bbox
+    (dsl_fovea_desc.smooth_l1_beta); the other heads refuse it."""
+
+    def __init__(self, beta=1.0, **kw):
+        super().__init__(**kw)
+        _expect(isinstance(beta, (int, float)) and 0.0 < float(beta) < float('inf'), f'SmoothL1Loss beta > 0 (got {beta!r})')
+        self.beta = float(beta)
+
+
 def _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, no_dcn, anchor_head=True):
     """The network every head here is built on: four 256-channel GN-32 tower convolutions, no DCN.  anchor_head: the refusals name
     AnchorHead's arguments (conv_cfg, norm_cfg), else FCOSHead's."""
@@ -544,6 +555,43 @@ class LDHead(GFLHead):
 # pool stream it happened to get (profiles/r04_td_first.txt).
 _ROLE_STREAMS = {}
 _ROLE_IDS = dict(prefix=4, comm=5, sweep=6, optimizer=1)      # the library's stream ids (csrc/api.hip side_init)
+
+
+@HEADS.register_module()
+class FoveaHead(nn.Module):
+    """mmdet/models/dense_heads/fovea_head.py:50-348 on AnchorFreeHead (anchor_free_head.py:40-133): FCOSHead's towers and predictor
+    geometry without centerness and without Scale; painted-rectangle targets (dsl_fovea_assign), focal + SmoothL1 loss on log
+    distances in units of base_edge_list (dsl_fovea_loss), base_len * exp decode clamped to img_shape - 1 (DSL_HEAD_FOVEA).  The
+    signature is the reference's; what the kernels do not build is refused, naming the option."""
+
+    def __init__(self, num_classes, in_channels, base_edge_list=(16, 32, 64, 128, 256),
+                 scale_ranges=((8, 32), (16, 64), (32, 128), (64, 256), (128, 512)), sigma=0.4, with_deform=False, deform_groups=4,
+                 init_cfg=None, feat_channels=256, stacked_convs=4, strides=(4, 8, 16, 32, 64), dcn_on_last_conv=False, conv_bias='auto',
+                 loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                 loss_bbox=dict(type='IoULoss', loss_weight=1.0), conv_cfg=None, norm_cfg=None, train_cfg=None, test_cfg=None, **kw):
+        super().__init__()
+        class_layout(num_classes)
+        _expect_no_dsl_keys('FoveaHead', kw)
+        _expect(not with_deform, 'with_deform=False (FeatureAlign is a deformable convolution)')
+        _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, conv_cfg is None and not dcn_on_last_conv)
+        _expect(list(strides) == [8, 16, 32, 64, 128], 'strides 8..128')
+        _expect(conv_bias is True or conv_bias is False or conv_bias == 'auto', "conv_bias True, False or 'auto'")
+        self.conv_bias = conv_bias is True          # (mmcv ConvModule: 'auto' = no bias in front of the GroupNorm)
+        self.num_classes, self.strides = num_classes, (8, 16, 32, 64, 128)
+        self.base_edge_list, self.scale_ranges, self.sigma = tuple(base_edge_list), tuple(tuple(r) for r in scale_ranges), sigma
+        self.with_deform, self.deform_groups = False, deform_groups
+        self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
+        self.loss_cls, self.loss_bbox = build_loss(loss_cls), build_loss(loss_bbox)
+        _expect(isinstance(self.loss_cls, FocalLoss), 'loss_cls: FocalLoss(use_sigmoid=True, gamma, alpha, loss_weight)')
+        _expect(isinstance(self.loss_bbox, SmoothL1Loss), 'loss_bbox: SmoothL1Loss(beta, loss_weight)')
+        self.options = HeadOptions(head_kind='fovea', sigma=sigma, base_edge_list=self.base_edge_list, scale_ranges=self.scale_ranges,
+                                   smooth_l1_beta=self.loss_bbox.beta, conv_bias=self.conv_bias, focal_gamma=self.loss_cls.gamma,
+                                   focal_alpha=self.loss_cls.alpha, cls_weight=self.loss_cls.loss_weight,
+                                   bbox_weight=self.loss_bbox.loss_weight)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    def effective_soft_weight(self, batch_size):
+        return 0.0
 
 
 def role_stream(role, device=None):
@@ -1041,6 +1089,16 @@ class PAA(FCOS):
 
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
         _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'PAAHead', "PAA with bbox_head type='PAAHead'")
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
+
+
+@DETECTORS.register_module()
+class FOVEA(FCOS):
+    """mmdet/models/detectors/fovea.py:5-18: SingleStageDetector with a FoveaHead, on the FCOS detector's machinery (the same network
+    without the centerness predictor and the Scale layers; assignment, losses, normalisers and box decode are the head's)."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
+        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'FoveaHead', "FOVEA with bbox_head type='FoveaHead'")
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
 
 

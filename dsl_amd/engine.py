@@ -241,9 +241,10 @@ class Plan:
             self._split_prefix()
         if training:
             self.lossplan = FcosLossPlan(N, self.level_sizes, dev, num_classes=store.num_classes, max_gt=max_gt, head=store.head)
-            self.lossplan.bind_outputs(self.bufs['cls_logits'], self.bufs['regctr'], store.t32_ptr('head.scales'))
-            # scale gradients go straight into the flat gradient buffer
-            self.lossplan.desc.g_scales = store.t32_ptr('head.scales', store.grad)
+            self.lossplan.bind_outputs(self.bufs['cls_logits'], self.bufs['regctr'], store.scales_ptr())
+            # scale gradients go straight into the flat gradient buffer (a head without Scale: the plan's own buffer stays, unwritten)
+            if store.head.has_scale():
+                self.lossplan.desc.g_scales = store.scales_ptr(store.grad)
             self.assign_ops.assign(self.lossplan.desc)
             if self._fside:             # the regression tower's side stream: joined here, not at the end of the forward list,
                 self.loss_ops.join(self._fside)       # so that target upload + assignment run while it finishes
@@ -541,7 +542,7 @@ class Plan:
         # the regression predictor four, ParamStore.ctr_on_cls - the same two launches either way)
         ncls, cls_pad, cls_ld = st.cls_rows, st.cls_pad, st.logit_ld
         nreg = st.reg_rows
-        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + (nreg if st.head.kind.dist_reg else 5)) * 2304)
+        self._head_flops = 2.0 * self.M * (8 * 256 * 2304 + (ncls + (nreg if st.head.kind.dist_reg or not st.head.kind.names[2] else 5)) * 2304)
         self._head_bytes = self.M * 256 * 2.0 * (8 * 2 + 8 * 3 + 2) + self.M * (ncls + st.reg_ld) * 4.0
         f.prof(4, 0, self._head_flops, self._head_bytes)
         fp8 = getattr(st, 'fp8', None)

@@ -27,7 +27,7 @@ class FcosLossPlan:
         round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls.  The head's loss
         settings (box_loss, focal gamma / alpha, the loss weights) go into the descriptor: losses, logvec and the gradients are the
         weighted ones.  What the head's kind decides is in its record (params.HEAD_KINDS): the struct around `desc` and the
-        attributes that hold it (`gfl`, `ld`, `paa`; None on the other kinds), the box predictor's row widths, the kind's own buffers
+        attributes that hold it (`gfl`, `ld`, `paa`, `fovea`; None on the other kinds), the box predictor's row widths, the kind's own buffers
         (`score`, `weight`; `pos_loss`, `iou_target`, `cand_gt`, `gmm_iters`, `gmm_flags`; absent on the other kinds), middle(),
         the entry of loss() and the length of logvec.  A kind with the ATSS layout: the assignment is fed the images' pad_shape
         (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554).  An LD head:
@@ -35,7 +35,7 @@ class FcosLossPlan:
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head = head or HeadOptions()
         self.kind = kind = head.kind
-        self.gfl = self.ld = self.paa = self.ext = None
+        self.gfl = self.ld = self.paa = self.fovea = self.ext = None
         inner = getattr(L, kind.loss_desc[0])()
         for attr, member in zip(kind.loss_desc[1:], kind.loss_desc[2:] + ('fcos',)):
             setattr(self, attr, inner)
@@ -116,6 +116,8 @@ class FcosLossPlan:
         if self.atss is not None:
             if pad_shapes is None or len(pad_shapes) != self.n:
                 raise ValueError('an ATSS head needs the pad_shape of every image (set_targets(pad_shapes=...))')
+            gt_bboxes_ignore = None
+        if self.desc.head_flags & L.HEAD_FOVEA:      # FoveaHead.loss takes gt_bboxes_ignore and does not read it (fovea_head.py:134-182)
             gt_bboxes_ignore = None
         slot = self._slots[self._slot_i]
         self._slot_i = (self._slot_i + 1) % len(self._slots)

@@ -107,6 +107,7 @@ def neck_specs():
     return specs
 
 
+MAX_LEVELS = 5       # DSL_MAX_SEG: the FPN levels of a head
 MAX_CLASSES = 128    # the classification predictor is stored round_up(C, 64) rows wide: one or two 64-row weight tiles
 
 
@@ -145,7 +146,8 @@ _F32, _I32 = torch.float32, torch.int32
 #                behind the predictors, gfl_head.py:348-366); None = none, and inv_world = 1 (a PAA head normalises by this rank's own
 #                stats: the reference does not reduce_mean there, paa_head.py:173-193)
 #   aug_refusal  aug_test raises this
-# A new head adds a record and its kernels.
+# A new head adds a record and its kernels.  (The records' fields are pinned by tests/test_fovea_cpu.py; what no field says - a head
+# without Scale layers - HeadOptions.has_scale() reads from `flags`.)
 HeadKind = namedtuple('HeadKind', 'name flags atss fields loss_desc scalars buffers det_desc det_mask det_fields dist_reg names middle '
                                   'loss_entry loss_keys sisoft exchange aug_refusal')
 _FCOS = HeadKind(
@@ -182,7 +184,20 @@ _PAA = _ATSS._replace(
     middle=(L.OP_PAA_REFINE, ('dsl_paa_pos_loss', 'dsl_paa_reassign')), loss_entry='dsl_paa_loss',
     loss_keys=('loss_cls', 'loss_bbox', 'loss_iou'), sisoft=False, exchange=None,
     aug_refusal='PAAHead does not support test-time augmentation (aug_test): PAA only supports with_nms=True (paa_head.py:536-538)')
-HEAD_KINDS = {k.name: k for k in (_FCOS, _ATSS, _GFL, _LD, _PAA)}
+# FoveaHead (fovea_head.py): an anchor-free head like FCOS's - same towers, strides and predictor geometry - without centerness and
+# without Scale; painted-rectangle targets, focal + SmoothL1 loss, base_len * exp decode.  No reduce_mean: this rank's own normalisers
+_FOVEA_FIELDS = ('head_kind', 'sigma', 'base_edge_list', 'scale_ranges', 'smooth_l1_beta')
+_FOVEA = _FCOS._replace(
+    name='fovea', flags=L.HEAD_FOVEA | L.HEAD_LOSS_EXT, fields=_FOVEA_FIELDS,
+    loss_desc=('FoveaDesc', 'fovea'),
+    scalars=(('fovea', 'sigma', 'sigma'), ('fovea', 'base_len', 'base_edge_list'), ('fovea', 'lo', 'range_lo'), ('fovea', 'hi', 'range_hi'),
+             ('fovea', 'smooth_l1_beta', 'smooth_l1_beta')),
+    det_desc=('DetFoveaDesc', 'det'), det_mask=L.HEAD_FOVEA, det_fields=(('base_len', 'base_edge_list'),),
+    names=('conv_cls', 'conv_reg', None),      # (fovea_head.py:77-86: no centerness predictor)
+    loss_entry='dsl_fovea_loss', loss_keys=('loss_cls', 'loss_bbox'), sisoft=False, exchange=None,
+    aug_refusal='FoveaHead does not support test-time augmentation (aug_test): FoveaHead.get_bboxes has no with_nms argument, so '
+                'aug_test_bboxes asserts (dense_test_mixins.py:62-70)')
+HEAD_KINDS = {k.name: k for k in (_FCOS, _ATSS, _GFL, _LD, _PAA, _FOVEA)}
 
 
 class HeadOptions:
@@ -223,6 +238,13 @@ class HeadOptions:
     branch) whose targets come from MaxIoUAssigner and the Gaussian-mixture reassignment; atss_topk is PAAHead's per-level topk:
       pos_iou_thr        MaxIoUAssigner pos_iou_thr == neg_iou_thr, in (0, 1)
       score_voting       detection: score voting behind the NMS (paa_head.py:608-673)
+    FoveaBox (head_kind 'fovea' = FoveaHead, mmdet/models/dense_heads/fovea_head.py, dsl_fovea_desc): an anchor-free head with FCOS's
+    towers and predictor geometry, no centerness predictor and no Scale; conv_bias, focal_gamma / focal_alpha, cls_weight and bbox_weight
+    count, every other FCOS / ATSS / GFL / PAA option is refused off its default:
+      sigma              the fovea's share of a box, in (0, 1]
+      base_edge_list     per level: the unit of the log distances, > 0
+      scale_ranges       per level: (lo, hi) bounds of sqrt(box area), lo <= hi
+      smooth_l1_beta     SmoothL1Loss(beta) > 0 (losses/smooth_l1_loss.py:11-29)
     `kind` is the record of the resolved head kind (HEAD_KINDS above): what follows from "which head is this" is read there."""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
@@ -231,9 +253,11 @@ class HeadOptions:
     def __init__(self, center_sampling=True, norm_on_bbox=True, centerness_on_reg=True, iou_loss=False, conv_bias=True,
                  box_loss=None, box_eps=1e-6, focal_gamma=2.0, focal_alpha=0.25, cls_weight=1.0, bbox_weight=1.0, ctr_weight=1.0,
                  assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2),
-                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0, pos_iou_thr=0.1, score_voting=True):
-        if head_kind not in ('fcos', 'gfl', 'paa'):
-            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos', 'gfl' or 'paa', got {head_kind!r}")
+                 head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0, pos_iou_thr=0.1, score_voting=True,
+                 sigma=0.4, base_edge_list=(16, 32, 64, 128, 256), scale_ranges=((8, 32), (16, 64), (32, 128), (64, 256), (128, 512)),
+                 smooth_l1_beta=0.11):
+        if head_kind not in ('fcos', 'gfl', 'paa', 'fovea'):
+            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos', 'gfl', 'paa' or 'fovea', got {head_kind!r}")
         if assigner not in ('fcos', 'atss'):
             raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
         if ld_weight is not None and head_kind != 'gfl':
@@ -262,6 +286,28 @@ class HeadOptions:
                                     ('focal_gamma', focal_gamma, 2.0), ('focal_alpha', focal_alpha, 0.25), ('ctr_weight', ctr_weight, 1.0)):
                 if val != want:
                     raise NotImplementedError(f"dsl_amd hot path: head_kind='gfl' does not read {name} (got {val!r}; leave it at {want!r})")
+        if head_kind == 'fovea':
+            # what a Fovea head does not read is refused off its default instead of being dropped
+            for name, val, want in (('center_sampling', center_sampling, True), ('norm_on_bbox', norm_on_bbox, True),
+                                    ('centerness_on_reg', centerness_on_reg, True), ('iou_loss', iou_loss, False), ('box_loss', box_loss, None),
+                                    ('ctr_weight', ctr_weight, 1.0), ('assigner', assigner, 'fcos'), ('atss_topk', atss_topk, 9),
+                                    ('anchor_scale', anchor_scale, 8.0), ('delta_stds', tuple(delta_stds), (0.1, 0.1, 0.2, 0.2)),
+                                    ('reg_max', reg_max, 16), ('qfl_beta', qfl_beta, 2.0), ('dfl_weight', dfl_weight, 0.25), ('ld_T', ld_T, 10.0),
+                                    ('pos_iou_thr', pos_iou_thr, 0.1), ('score_voting', score_voting, True)):
+                if val != want:
+                    raise NotImplementedError(f"dsl_amd hot path: head_kind='fovea' does not read {name} (got {val!r}; leave it at {want!r})")
+            if not (isinstance(sigma, (int, float)) and 0.0 < float(sigma) <= 1.0):
+                raise NotImplementedError(f'dsl_amd hot path: sigma must be a number in (0, 1], got {sigma!r}')
+            if not (isinstance(smooth_l1_beta, (int, float)) and 0.0 < float(smooth_l1_beta) < float('inf')):
+                raise NotImplementedError(f'dsl_amd hot path: smooth_l1_beta must be a finite number > 0, got {smooth_l1_beta!r}')
+            if len(base_edge_list) != MAX_LEVELS or not all(0.0 < float(v) < float('inf') for v in base_edge_list):
+                raise NotImplementedError(f'dsl_amd hot path: base_edge_list must be {MAX_LEVELS} finite numbers > 0, got {base_edge_list!r}')
+            if len(scale_ranges) != MAX_LEVELS or not all(len(r) == 2 and float(r[0]) <= float(r[1]) for r in scale_ranges):
+                raise NotImplementedError(f'dsl_amd hot path: scale_ranges must be {MAX_LEVELS} pairs (lo, hi) with lo <= hi, got {scale_ranges!r}')
+        self.sigma, self.smooth_l1_beta = float(sigma), float(smooth_l1_beta)
+        self.base_edge_list = tuple(float(v) for v in base_edge_list)
+        self.scale_ranges = tuple((float(lo), float(hi)) for lo, hi in scale_ranges)
+        self.range_lo, self.range_hi = tuple(r[0] for r in self.scale_ranges), tuple(r[1] for r in self.scale_ranges)
         self.pos_iou_thr, self.score_voting = float(pos_iou_thr), bool(score_voting)
         if head_kind == 'paa' and not (isinstance(pos_iou_thr, (int, float)) and 0.0 < self.pos_iou_thr < 1.0):
             raise NotImplementedError(f'dsl_amd hot path: pos_iou_thr must be a number in (0, 1), got {pos_iou_thr!r}')
@@ -316,7 +362,12 @@ class HeadOptions:
         predictor), rows 8 wide; a distribution head's 4 (reg_max + 1) logits, rows exactly that wide, no centerness."""
         if self.kind.dist_reg:
             return 4 * (self.reg_max + 1), 4 * (self.reg_max + 1)
-        return 5 if self.centerness_on_reg else 4, 8
+        return 5 if self.centerness_on_reg and self.kind.names[2] else 4, 8
+
+    def has_scale(self):
+        """The head has a Scale per level (parameters bbox_head.scales.i.scale, read by the loss and detection kernels); a Fovea head
+        uses conv_reg's outputs raw (fovea_head.py:117-128)."""
+        return not self.kind.flags & L.HEAD_FOVEA
 
     def atss_desc(self):
         """A dsl_atss_desc with the head's settings (None for an FCOS head); the caller fills max_gt, pad_shapes and npos."""
@@ -429,7 +480,8 @@ class ParamStore:
         toff = add(self.train_regions, toff, 'head.cls_b', (self.cls_pad,))
         toff = add(self.train_regions, toff, 'head.regctr_w', (self.reg_pad, 3, 3, 256))
         toff = add(self.train_regions, toff, 'head.regctr_b', (self.reg_pad,))
-        toff = add(self.train_regions, toff, 'head.scales', (8,))
+        if self.head.has_scale():
+            toff = add(self.train_regions, toff, 'head.scales', (8,))
         self.n_train, self.n_frozen = toff, foff
         self.device = torch.device(device)
         self.train = torch.zeros(toff, dtype=torch.float32, device=device)
@@ -525,9 +577,10 @@ class ParamStore:
         elif pt:
             out[pt + '.weight'] = rw[4:5].permute(0, 3, 1, 2)
             out[pt + '.bias'] = rb[4:5]
-        sc = self.tview('head.scales', tb)
-        for i in range(5):
-            out[f'bbox_head.scales.{i}.scale'] = sc[i]
+        if self.head.has_scale():
+            sc = self.tview('head.scales', tb)
+            for i in range(5):
+                out[f'bbox_head.scales.{i}.scale'] = sc[i]
         return out
 
     def predictor_names(self):
@@ -757,6 +810,10 @@ class ParamStore:
 
     def t32_ptr(self, region, buf=None):
         return (self.train if buf is None else buf).data_ptr() + self.toff(region) * 4
+
+    def scales_ptr(self, buf=None):
+        """Address of the five Scale values in the flat buffer (`buf`: the gradient buffer), None for a head without Scale."""
+        return self.t32_ptr('head.scales', buf) if self.head.has_scale() else None
 
     def wT_ptr(self, name):
         lay, _ = self.wT_layout()

@@ -151,7 +151,7 @@ def _detplan(det, plan, store, N):
     if dp is None:
         dp = DetectPlan(N, plan.level_sizes, det.bbox_head.strides, store.device, num_classes=store.num_classes,
                         ld_cls=store.logit_ld, head=store.head, **_test_cfg(det))
-        dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.t32_ptr('head.scales'))
+        dp.bind(plan.bufs['cls_logits'], plan.bufs['regctr'], store.scales_ptr())
         plan.detplan = dp
     return dp
 

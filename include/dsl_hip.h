@@ -774,11 +774,70 @@ int dsl_paa_pos_loss(const dsl_paa_desc* q, void* stream);
 int dsl_paa_reassign(const dsl_paa_desc* q, void* stream);
 int dsl_paa_loss(const dsl_paa_desc* q, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * FoveaBox: FoveaHead's painted-rectangle targets, focal + SmoothL1 loss and base_len * exp decode
+ * (mmdet/models/dense_heads/fovea_head.py:130-132 points, :134-182 loss, :206-265 targets, :298-348 detection;
+ * mmdet/models/losses/smooth_l1_loss.py:11-29; losses/focal_loss.py:11-56), fp32, contraction off.
+ *
+ * A dsl_fovea_desc wraps a dsl_fcos_desc with DSL_HEAD_FOVEA | DSL_HEAD_LOSS_EXT in head_flags and no other head or option flag.
+ * The point of location (x, y) of a level with stride s is (s (x + 0.5), s (y + 0.5)).  fcos.regctr holds conv_reg's four raw
+ * outputs (ld_rc >= 4): there is no Scale, no centerness (scales, g_scales, ctr, g_ctr are not read or written), no ignore boxes
+ * (ig_boxes must be NULL), no stream weight (loss_weight == 1) and no sisoft term (soft_weight == 0).  fcos.range_lo / range_hi /
+ * radius are not read: the levels' ranges are lo / hi below.
+ *
+ * dsl_fovea_assign, one thread per location, the image's boxes staged through LDS in chunks (no cap but the capacity of gt_boxes):
+ * area = sqrtf((x2 - x1) * (y2 - y1)); a box hits level l iff lo[l] <= area <= hi[l].  With b = box / s (four divisions; when every
+ * stride is a power of two, four products with the exact 1 / s, which are the same bits for every coordinate that is not subnormal),
+ * half_w = 0.5 (b.x2 - b.x1):  left = clamp(ceil((b.x1 + (1 - sigma) half_w) - 0.5), 0, w_l - 1),
+ * right = clamp(floor((b.x1 + (1 + sigma) half_w) - 0.5), 0, w_l - 1), top / down likewise; 1 - sigma and 1 + sigma are formed in
+ * fp64 from the descriptor's float and rounded once (the reference multiplies by the Python float).  The box covers the location
+ * iff left <= x <= right and top <= y <= down - both ranges tested after the clamp, so a fovea wholly beyond an edge still covers
+ * the border cell and one between two cell centres covers nothing.  Every sum and product above is a separate fp32 operation in
+ * the order written (the file is compiled without contraction), which is the reference's torch arithmetic.  Among the covering
+ * hits the one of smallest area wins (the reference paints in order of decreasing area).  EQUAL areas: the higher box index wins -
+ * what a stable sort gives; the reference's torch.sort is not stable there, so this order is unpinned.
+ * Outputs: labels (the box's label, else num_classes), assign_idx (box index within the image, -1 = none), bbox_targets =
+ * log(clamp(((px - x1) / base_len, (py - y1) / base_len, (x2 - px) / base_len, (y2 - py) / base_len), 1/16, 16)) from the undivided
+ * box, and exactly 0 where nothing was painted (the reference leaves uninitialised memory there and never reads it); cls_weight =
+ * pos_weight = 1.  stats[0] = num_pos + n (loss_cls's avg_factor, fovea_head.py:165-166), stats[1] = max(num_pos, 1), stats[2..7] =
+ * 0: per-workgroup counts added in workgroup order - no atomics on floats, a second run is bit-identical.
+ *
+ * dsl_fovea_loss (forward and backward in one launch + the fixed-order sum of its block records), num = max(norm[0] * inv_world,
+ * 1), avg = max(norm[1] * inv_world, 1) - the host passes its own stats and inv_world = 1, the reference does not reduce_mean:
+ *   losses[0] = w_cls / num * sum_m cls_weight[m] sum_c focal(m, c), gamma >= 0 and 0 <= alpha <= 1 as the loss family's; for gamma
+ *               != 2 the modulating factor is formed as exp(-gamma * softplus), not by powf (gamma = 1.5 in configs/foveabox)
+ *   losses[1] = w_bbox / avg * sum_pos sum_k sl1(regctr[m][k] - bbox_targets[m][k]),
+ *               sl1(d) = 0.5 d^2 / beta where |d| < beta, else |d| - 0.5 beta;  exactly 0 without a positive
+ *   losses[2] = losses[3] = 0; logvec = [cls, bbox, their sum].
+ * g_cls as dsl_fcos_loss (columns from C on stay zero).  g_rc[m][0..3] = w_bbox / avg * grad_scale * (d / beta or sign(d)), bf16, for
+ * a positive; columns 0..7 of every row are rewritten by every launch (zero for a non-positive and in columns 4..7).  A wavefront
+ * walks 64 locations.  Workspace: dsl_fcos_workspace_bytes(&f->fcos).
+ * Refused, with dsl_last_error naming the field: head_flags other than DSL_HEAD_FOVEA | DSL_HEAD_LOSS_EXT, fcos.ig_boxes,
+ * fcos.soft_weight != 0, fcos.loss_weight != 1, fcos.ctr / g_ctr, sigma outside (0, 1], base_len <= 0, lo > hi, smooth_l1_beta <= 0,
+ * a workspace below dsl_fcos_workspace_bytes.
+ *
+ * Detection (DSL_HEAD_FOVEA in dsl_det_desc.head_flags, the descriptor being a dsl_det_fovea_desc): the pair score is the class
+ * sigmoid alone, x1 = clamp(px - base_len exp(p0), 0, img_w - 1) and so on (fovea_head.py:326-333: the clamp is to img_shape - 1);
+ * scales and ctr are not read.  dsl_fcos_detect_collect refuses the flag: FoveaHead.get_bboxes has no with_nms argument.
+ * ---------------------------------------------------------------------------------------- */
+#define DSL_HEAD_FOVEA 512      /* FoveaHead: dsl_fcos_desc inside a dsl_fovea_desc; dsl_det_desc inside a dsl_det_fovea_desc */
+typedef struct dsl_fovea_desc {
+  dsl_fcos_desc fcos;
+  float sigma;                         /* the fovea's share of the box, in (0, 1] (0.4) */
+  float base_len[DSL_MAX_SEG];         /* base_edge_list: the unit of a level's log distances, > 0 (16, 32, 64, 128, 256) */
+  float lo[DSL_MAX_SEG], hi[DSL_MAX_SEG];   /* scale_ranges: sqrt(area) bounds of a level, lo <= hi */
+  float smooth_l1_beta;                /* SmoothL1Loss beta > 0 (0.11 in the reference's configs) */
+} dsl_fovea_desc;
+int dsl_fovea_assign(const dsl_fovea_desc* f, void* stream);
+int dsl_fovea_loss(const dsl_fovea_desc* f, void* stream);
+
 /* One dispatch for every head, on head_flags.  The contract the flags state: with DSL_HEAD_GFL `d` is the first member of a
  * dsl_gfl_desc, with DSL_HEAD_LD of a dsl_ld_desc (whose first member is that dsl_gfl_desc), so the three share one address.
- * With DSL_HEAD_PAA `d` is the first member of a dsl_paa_desc.
- * dsl_head_assign: DSL_HEAD_PAA -> dsl_paa_assign, else DSL_HEAD_ATSS -> dsl_atss_assign(d, d->atss), else dsl_fcos_assign.
- * dsl_head_loss: DSL_HEAD_PAA -> dsl_paa_loss, else DSL_HEAD_LD -> dsl_ld_loss (which refuses the flag without DSL_HEAD_GFL), else
+ * With DSL_HEAD_PAA `d` is the first member of a dsl_paa_desc, with DSL_HEAD_FOVEA of a dsl_fovea_desc.
+ * dsl_head_assign: DSL_HEAD_FOVEA -> dsl_fovea_assign, else DSL_HEAD_PAA -> dsl_paa_assign, else DSL_HEAD_ATSS ->
+ * dsl_atss_assign(d, d->atss), else dsl_fcos_assign.
+ * dsl_head_loss: DSL_HEAD_FOVEA -> dsl_fovea_loss, else DSL_HEAD_PAA -> dsl_paa_loss, else DSL_HEAD_LD -> dsl_ld_loss (which refuses
+ * the flag without DSL_HEAD_GFL), else
  * DSL_HEAD_GFL -> dsl_gfl_loss, else dsl_fcos_loss.  DSL_OP_ASSIGN / DSL_OP_LOSS of an op list are these two calls on the op's desc. */
 int dsl_head_assign(const dsl_fcos_desc* d, void* stream);
 int dsl_head_loss(const dsl_fcos_desc* d, void* stream);
@@ -909,6 +968,16 @@ typedef struct dsl_det_paa_desc {
   dsl_det_atss_desc atss;
   int32_t score_voting;                      /* 0 = the NMS output as it is */
 } dsl_det_paa_desc;
+/* A Fovea head's detection descriptor (DSL_HEAD_FOVEA in det.head_flags, no other flag; FoveaHead._get_bboxes,
+ * mmdet/models/dense_heads/fovea_head.py:298-348): regctr holds conv_reg's four raw outputs, the box is (px - base_len exp(p0),
+ * py - base_len exp(p1), px + base_len exp(p2), py + base_len exp(p3)) from the point (s (x + 0.5), s (y + 0.5)), clamped to
+ * [0, img_w - 1] x [0, img_h - 1]; the candidate score is the class sigmoid alone (scales and ctr are not read).  Test-time
+ * augmentation is refused for this head, as in the reference (FoveaHead.get_bboxes has no with_nms argument,
+ * dense_test_mixins.py:62-70): dsl_fcos_detect_collect refuses the flag. */
+typedef struct dsl_det_fovea_desc {
+  dsl_det_desc det;
+  float base_len[DSL_MAX_SEG];               /* base_edge_list, > 0 */
+} dsl_det_fovea_desc;
 /* dsl_det_desc.nms_method.  Soft-NMS is mmcv's batched_nms with nms=dict(type='soft_nms', method=...) (stated by
  * mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127), per image and class over the candidates the hard NMS would get: pick the highest current score
  * (equal scores: the candidate that comes first in (level, slot, class) order - with views, (view, level, slot, class)), emit it
