@@ -142,6 +142,7 @@ GFL_MAX_REG = 16
 HEAD_LD = 128           # LDHead: the dsl_gfl_desc is a dsl_ld_desc's first member (dsl_ld_loss)
 HEAD_PAA = 256          # PAAHead: the dsl_fcos_desc is a dsl_paa_desc's first member, the dsl_det_desc a dsl_det_paa_desc's
 HEAD_FOVEA = 512        # FoveaHead: the dsl_fcos_desc is a dsl_fovea_desc's first member, the dsl_det_desc a dsl_det_fovea_desc's
+HEAD_AUTOASSIGN = 1024  # AutoAssignHead: the dsl_fcos_desc is a dsl_aa_desc's first member
 BOX_GIOU, BOX_IOU_LOG, BOX_IOU_LINEAR, BOX_DIOU, BOX_CIOU = range(5)      # DSL_BOX_*: dsl_fcos_desc.box_kind
 NMS_HARD, NMS_LINEAR, NMS_GAUSSIAN, NMS_NAIVE = range(4)      # DSL_NMS_*: dsl_det_desc.nms_method
 EVAL_COCO, EVAL_VOC, EVAL_MAX_THRS, EVAL_MAX_RANGES = 0, 1, 16, 4      # DSL_EVAL_*: dsl_eval_match
@@ -179,6 +180,11 @@ class PaaDesc(C.Structure):      # dsl_paa_desc: a PAA head's loss descriptor (H
 
 class FoveaDesc(C.Structure):      # dsl_fovea_desc: a Fovea head's loss descriptor (HEAD_FOVEA | HEAD_LOSS_EXT in fcos.head_flags)
     _fields_ = [('fcos', FcosDesc), ('sigma', C.c_float), ('base_len', F5), ('lo', F5), ('hi', F5), ('smooth_l1_beta', C.c_float)]
+
+
+class AaDesc(C.Structure):      # dsl_aa_desc: an AutoAssign head's loss descriptor (HEAD_AUTOASSIGN | HEAD_LOSS_EXT in fcos.head_flags)
+    _fields_ = [('fcos', FcosDesc), ('w_pos', C.c_float), ('w_neg', C.c_float), ('w_center', C.c_float), ('max_gt', C.c_int32),
+                ('mean', C.c_void_p), ('sigma', C.c_void_p), ('g_mean', C.c_void_p), ('g_sigma', C.c_void_p), ('iou', C.c_void_p)]
 
 
 class DetFoveaDesc(C.Structure):      # dsl_det_fovea_desc: the detection descriptor of a Fovea head (HEAD_FOVEA in det.head_flags)
@@ -343,7 +349,7 @@ _SIGS = {
     'dsl_sum2x2': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp], 'dsl_colsum': [_vp, _vp, _l, _i, _i, _vp],
     'dsl_fcos_points': [_vp, _vp, _vp], 'dsl_fcos_workspace_bytes': [_vp], 'dsl_fcos_assign': [_vp, _vp], 'dsl_atss_assign': [_vp, _vp, _vp], 'dsl_fcos_loss': [_vp, _vp],
     'dsl_gfl_quality': [_vp, _vp], 'dsl_gfl_loss': [_vp, _vp], 'dsl_ld_loss': [_vp, _vp], 'dsl_head_assign': [_vp, _vp], 'dsl_head_loss': [_vp, _vp],
-    'dsl_fovea_assign': [_vp, _vp], 'dsl_fovea_loss': [_vp, _vp],
+    'dsl_fovea_assign': [_vp, _vp], 'dsl_fovea_loss': [_vp, _vp], 'dsl_aa_assign': [_vp, _vp], 'dsl_aa_loss': [_vp, _vp],
     'dsl_paa_assign': [_vp, _vp],'dsl_paa_pos_loss': [_vp, _vp], 'dsl_paa_reassign': [_vp, _vp], 'dsl_paa_loss': [_vp, _vp],
     'dsl_sumsq': [_vp, _l, _vp, _vp], 'dsl_sumsq_det': [_vp, _l, _vp, _vp, _vp],
     'dsl_sgd_step': [_vp, _vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _f, _i, _vp],

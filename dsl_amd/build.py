@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libdsl_hip.so')
-SOURCES = ['api.hip', 'conv.hip', 'wgrad.hip', 'misc.hip', 'fcos_loss.hip', 'gfl_loss.hip', 'fovea_loss.hip', 'optim.hip', 'detect.hip', 'rla.hip', 'datapath.hip', 'comm.hip', 'stem.hip', 'bneck.hip', 'evalmap.hip']
+SOURCES = ['api.hip', 'conv.hip', 'wgrad.hip', 'misc.hip', 'fcos_loss.hip', 'gfl_loss.hip', 'fovea_loss.hip', 'autoassign_loss.hip', 'optim.hip', 'detect.hip', 'rla.hip', 'datapath.hip', 'comm.hip', 'stem.hip', 'bneck.hip', 'evalmap.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-result', '-Wno-unused-value']
 # conv.hip only: its kernels carry a scalar hot header in front of their by-value parameter struct, which this makes the
 # compiler preload into user SGPRs (.amdhsa_user_sgpr_kernarg_preload_length; DESIGN.md section 3.1, "front end")

@@ -32,6 +32,10 @@
 // FoveaHead (DSL_HEAD_FOVEA, the descriptor then being a dsl_det_fovea_desc; FoveaHead._get_bboxes, mmdet/models/dense_heads/
 // fovea_head.py:298-348): det_decode takes the distances as base_len * exp(x) from the point s (x + 0.5) and clamps to img_shape - 1;
 // no Scale and no centerness factor (GFL's unit logit kNoCtr).  dsl_fcos_detect_collect refuses the flag.
+//
+// AutoAssignHead (DSL_HEAD_AUTOASSIGN on a plain dsl_det_desc; autoassign_head.py:173-187,204-212 with FCOSHead.get_bboxes): FCOS's
+// decode relu(scale x) s and score sigmoid(cls) * sigmoid(objectness) from the point (x s, y s) - no half-stride offset - in the
+// single-view path and in a view's collect alike (both decode through det_decode).
 #include "common.hpp"
 #pragma clang fp contract(off)
 
@@ -53,6 +57,7 @@ struct DetK {
   float anchor_scale, stds[4];
   int gfl_R;                         // DSL_HEAD_GFL: reg_max + 1 bins per side (0 = not a GFL head)
   int paa;                           // DSL_HEAD_PAA: the pair score is sqrt(sigmoid(cls) * sigmoid(iou)), threshold and final score alike
+  int point_origin;                  // DSL_HEAD_AUTOASSIGN: the point is (x s, y s), FCOS's decode otherwise
   int fovea;                         // DSL_HEAD_FOVEA: base_len * exp(x) from the point s (x + 0.5), clamp to img_shape - 1; no Scale
   float base_len[DSL_MAX_SEG];
   const float* scales; const float* img_shapes; const float* scale_factors;
@@ -297,7 +302,8 @@ __device__ __forceinline__ void det_decode(const DetK& p, int img, int lvl, int 
     b[3] = fminf(fmaxf(fy + bl * expf(rc[3]), 0.f), H - 1.f);
     return;
   }
-  const float px = (float)x * (float)s + (float)(s / 2), py = (float)y * (float)s + (float)(s / 2);
+  const float half = p.point_origin ? 0.f : (float)(s / 2);      // (autoassign_head.py:173-187: no half-stride offset)
+  const float px = (float)x * (float)s + half, py = (float)y * (float)s + half;
   const float sc = p.scales[lvl];
   if (p.gfl_R) {
     // per side the softmax expectation over its R bins of scale x (Integral, gfl_head.py:15-48), times the stride; distance2bbox from
@@ -1018,6 +1024,11 @@ int view_detk(const dsl_det_desc* d, DetK& k, int& m_out, const char* who) {
       k.base_len[l] = f->base_len[l];
     }
     k.fovea = 1;
+  }
+  if (d->head_flags & DSL_HEAD_AUTOASSIGN) {
+    DSL_CHECK(d->head_flags == DSL_HEAD_AUTOASSIGN && !d->ctr,
+              "%s: DSL_HEAD_AUTOASSIGN goes with no other flag and the objectness on the regression tower (ctr must be null)", who);
+    k.point_origin = 1;
   }
   if (d->head_flags & (DSL_HEAD_GFL | DSL_HEAD_FOVEA)) {      // no centerness factor: the unit "logit"
     void* one = nullptr;

@@ -1100,6 +1100,7 @@ extern "C" size_t dsl_fcos_workspace_bytes(const dsl_fcos_desc* d) {
   // (DSL_HEAD_FOVEA: one count per assignment workgroup and the loss records - within `need`)
   const size_t assign_rec = (size_t)((g.M + 255) / 256) * 2, loss_rec = 2048 * 16;
   const size_t need = (assign_rec > loss_rec ? assign_rec : loss_rec) * sizeof(float);
+  if (d->head_flags & DSL_HEAD_AUTOASSIGN) return need + dsl_aa_workspace_extra(d);      // the boxes' and the images' records (max_gt, n)
   if (d->head_flags & DSL_HEAD_PAA) {      // the boxes' records and maxima (d->atss->max_gt of them)
     const size_t paa = d->atss ? paa_bytes(d->atss->max_gt > 0 ? d->atss->max_gt : 0) : 0;
     return need > paa ? need : paa;
@@ -1125,6 +1126,7 @@ extern "C" int dsl_fcos_assign(const dsl_fcos_desc* d, void* stream) {
             "dsl_fcos_assign: null pointer");
   DSL_CHECK(!(d->head_flags & DSL_HEAD_ATSS), "dsl_fcos_assign: a DSL_HEAD_ATSS descriptor is assigned by dsl_atss_assign");
   DSL_CHECK(!(d->head_flags & DSL_HEAD_FOVEA), "dsl_fcos_assign: a DSL_HEAD_FOVEA descriptor is assigned by dsl_fovea_assign");
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_AUTOASSIGN), "dsl_fcos_assign: a DSL_HEAD_AUTOASSIGN descriptor is assigned by dsl_aa_assign");
   hipStream_t st = (hipStream_t)stream;
   const int nb = (k.M + 255) / 256;
   DSL_CHECK(d->workspace && d->workspace_bytes >= dsl_fcos_workspace_bytes(d), "dsl_fcos_assign: workspace too small");
@@ -1166,6 +1168,7 @@ extern "C" int dsl_fcos_loss(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(!(d->head_flags & DSL_HEAD_GFL), "dsl_fcos_loss: a DSL_HEAD_GFL descriptor's loss is dsl_gfl_loss");
   DSL_CHECK(!(d->head_flags & DSL_HEAD_PAA), "dsl_fcos_loss: a DSL_HEAD_PAA descriptor's loss is dsl_paa_loss");
   DSL_CHECK(!(d->head_flags & DSL_HEAD_FOVEA), "dsl_fcos_loss: a DSL_HEAD_FOVEA descriptor's loss is dsl_fovea_loss");
+  DSL_CHECK(!(d->head_flags & DSL_HEAD_AUTOASSIGN), "dsl_fcos_loss: a DSL_HEAD_AUTOASSIGN descriptor's loss is dsl_aa_loss");
   if (head_loss_ptrs(d, "dsl_fcos_loss")) return -1;
   DSL_CHECK(d->pos_weight, "dsl_fcos_loss: null pointer");
   DSL_CHECK(d->num_classes >= 1 && d->ld_cls % 4 == 0 && d->ld_cls >= d->num_classes && d->ld_gcls % 4 == 0 &&
@@ -1227,6 +1230,7 @@ extern "C" int dsl_paa_loss(const dsl_paa_desc* q, void* stream) {
 /* one dispatch for every head: the entry point a descriptor's head_flags name (include/dsl_hip.h) */
 extern "C" int dsl_head_assign(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(d, "dsl_head_assign: null descriptor");
+  if (d->head_flags & DSL_HEAD_AUTOASSIGN) return dsl_aa_assign((const dsl_aa_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_FOVEA) return dsl_fovea_assign((const dsl_fovea_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_PAA) return dsl_paa_assign((const dsl_paa_desc*)d, stream);
   return (d->head_flags & DSL_HEAD_ATSS) ? dsl_atss_assign(d, d->atss, stream) : dsl_fcos_assign(d, stream);
@@ -1234,6 +1238,7 @@ extern "C" int dsl_head_assign(const dsl_fcos_desc* d, void* stream) {
 
 extern "C" int dsl_head_loss(const dsl_fcos_desc* d, void* stream) {
   DSL_CHECK(d, "dsl_head_loss: null descriptor");
+  if (d->head_flags & DSL_HEAD_AUTOASSIGN) return dsl_aa_loss((const dsl_aa_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_FOVEA) return dsl_fovea_loss((const dsl_fovea_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_PAA) return dsl_paa_loss((const dsl_paa_desc*)d, stream);
   if (d->head_flags & DSL_HEAD_LD) return dsl_ld_loss((const dsl_ld_desc*)d, stream);

@@ -1,4 +1,4 @@
-// What the head-loss translation units (fcos_loss.hip, gfl_loss.hip, fovea_loss.hip) share: the level geometry of a dsl_fcos_desc with its one host
+// What the head-loss translation units (fcos_loss.hip, gfl_loss.hip, fovea_loss.hip, autoassign_loss.hip) share: the level geometry of a dsl_fcos_desc with its one host
 // fill, the location decoder, the kernel arguments every head's kernels read, and the fixed-order sum of per-block records.
 // Include after common.hpp.
 #pragma once
@@ -86,6 +86,9 @@ inline int head_loss_settings(const dsl_fcos_desc* d, float w3, HeadK& k, const 
   k.box_kind = d->box_kind; k.box_eps = d->box_eps; k.w_cls = d->w_cls; k.w_bbox = d->w_bbox;
   return 0;
 }
+
+// autoassign_loss.hip: what a DSL_HEAD_AUTOASSIGN descriptor (the first member of a dsl_aa_desc) adds to dsl_fcos_workspace_bytes
+size_t dsl_aa_workspace_extra(const dsl_fcos_desc* d);
 
 // grid of a loss pass: one thread per 4 classes of a location, capped at the 2048 records of 16 floats the workspace holds
 inline int head_loss_blocks(const HeadK& k) {

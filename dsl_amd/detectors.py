@@ -594,6 +594,49 @@ class FoveaHead(nn.Module):
         return 0.0
 
 
+@HEADS.register_module()
+class AutoAssignHead(nn.Module):
+    """mmdet/models/dense_heads/autoassign_head.py:123-509 on FCOSHead: FCOS's towers (conv_bias=True forced, :151), predictors, Scale
+    layers, strides and get_bboxes; points without the half-stride offset, bbox = relu(scale x) s in training and in test, and no
+    hard assigner - the positive / negative / centre-prior losses over every location inside a box (dsl_aa_assign, dsl_aa_loss,
+    DSL_HEAD_AUTOASSIGN).  The signature is the reference's; what the kernels do not build is refused, naming the option."""
+
+    def __init__(self, num_classes, in_channels, force_topk=False, topk=9, pos_loss_weight=0.25, neg_loss_weight=0.75,
+                 center_loss_weight=0.75, regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, 1e8)),
+                 center_sampling=False, center_sample_radius=1.5, norm_on_bbox=False, centerness_on_reg=False,
+                 feat_channels=256, stacked_convs=4, strides=(4, 8, 16, 32, 64), dcn_on_last_conv=False, conv_cfg=None,
+                 loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                 loss_bbox=dict(type='IoULoss', loss_weight=1.0),
+                 loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True), train_cfg=None, test_cfg=None, init_cfg=None, **kw):
+        super().__init__()
+        class_layout(num_classes)
+        _expect('conv_bias' not in kw, 'AutoAssignHead: no conv_bias argument (the head passes conv_bias=True itself, autoassign_head.py:151)')
+        _expect_no_dsl_keys('AutoAssignHead', kw)
+        _expect(not force_topk, 'force_topk=False (the top-k centre prior of boxes that hold no point is not built; topk is then unread)')
+        _expect_towers(in_channels, feat_channels, stacked_convs, norm_cfg, conv_cfg is None and not dcn_on_last_conv, anchor_head=False)
+        _expect(list(strides) == [8, 16, 32, 64, 128], 'strides 8..128')
+        # FCOSHead arguments that AutoAssignHead's own forward_single, get_targets and loss never read (:189-212, :314-509): the
+        # class defaults only - a config that sets them expects a behaviour the head does not have
+        _expect(not center_sampling and not norm_on_bbox and not centerness_on_reg,
+                'center_sampling / norm_on_bbox / centerness_on_reg at their defaults (AutoAssignHead does not read them)')
+        self.num_classes, self.strides = num_classes, (8, 16, 32, 64, 128)
+        self.force_topk, self.topk = False, topk
+        self.loss_weight, self.soft_weight, self.soft_warm_up = 1.0, 0.0, 0
+        # loss_cls and loss_centerness are built by FCOSHead.__init__ and never called (:402-417: the head forms its own terms)
+        self.loss_cls, self.loss_centerness = build_loss(loss_cls), build_loss(loss_centerness)
+        self.loss_bbox, self.bbox_weight = _build_loss_bbox(loss_bbox, 'loss_bbox: GIoULoss(loss_weight)')
+        _expect(isinstance(self.loss_bbox, GIoULoss), 'loss_bbox: GIoULoss(loss_weight)')
+        self.options = HeadOptions(head_kind='autoassign', bbox_weight=self.bbox_weight, pos_loss_weight=pos_loss_weight,
+                                   neg_loss_weight=neg_loss_weight, center_loss_weight=center_loss_weight)
+        self.pos_loss_weight, self.neg_loss_weight, self.center_loss_weight = (
+            self.options.pos_loss_weight, self.options.neg_loss_weight, self.options.center_loss_weight)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+
+    def effective_soft_weight(self, batch_size):
+        return 0.0
+
+
 def role_stream(role, device=None):
     """The library's own stream for `role` on `device`: created and PICKED by the C library together with its side streams (csrc/api.hip
     side_init: a spin-kernel probe finds streams on hardware queues of their own) - not drawn from torch's pool, whose streams share
@@ -1099,6 +1142,16 @@ class FOVEA(FCOS):
 
     def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
         _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'FoveaHead', "FOVEA with bbox_head type='FoveaHead'")
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
+
+
+@DETECTORS.register_module()
+class AutoAssign(FCOS):
+    """mmdet/models/detectors/autoassign.py:5-18: SingleStageDetector with an AutoAssignHead, on the FCOS detector's machinery (the
+    same network; the losses, their normalisers and the point of a location are the head's)."""
+
+    def __init__(self, backbone, neck=None, bbox_head=None, train_cfg=None, test_cfg=None, pretrained=None, init_cfg=None, fp8=None):
+        _expect(isinstance(bbox_head, dict) and bbox_head.get('type') == 'AutoAssignHead', "AutoAssign with bbox_head type='AutoAssignHead'")
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained, init_cfg, fp8)
 
 

@@ -245,6 +245,15 @@ class Plan:
             # scale gradients go straight into the flat gradient buffer (a head without Scale: the plan's own buffer stays, unwritten)
             if store.head.has_scale():
                 self.lossplan.desc.g_scales = store.scales_ptr(store.grad)
+            if store.head.has_prior():      # the centre prior and its gradient live in the flat buffers too
+                self.lossplan.bind_prior(*store.prior_ptrs(), *store.prior_ptrs(store.grad))
+                # The first assignment that reads trained parameters.  With several ranks it runs in front of the forward list
+                # (detectors.forward_train, exchange='forward'), whose own waits for the last optimizer step sit in front of the FPN:
+                # the prior lies in bucket 0 (head + FPN), which the late exchange updates last, on the optimizer's stream - and under
+                # the deferred head update on the weight-gradient stream.  The same two waits, then (no-ops until recorded)
+                self.assign_ops.wait(L.SLOT_UPD + 0, stream=0)
+                if self.defer:
+                    self.assign_ops.wait(L.SLOT_HEADW, stream=0)
             self.assign_ops.assign(self.lossplan.desc)
             if self._fside:             # the regression tower's side stream: joined here, not at the end of the forward list,
                 self.loss_ops.join(self._fside)       # so that target upload + assignment run while it finishes

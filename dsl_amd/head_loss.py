@@ -27,7 +27,7 @@ class FcosLossPlan:
         round_up(C, 4) of the logits' rows, which are four floats longer, and its gradient that column of g_cls.  The head's loss
         settings (box_loss, focal gamma / alpha, the loss weights) go into the descriptor: losses, logvec and the gradients are the
         weighted ones.  What the head's kind decides is in its record (params.HEAD_KINDS): the struct around `desc` and the
-        attributes that hold it (`gfl`, `ld`, `paa`, `fovea`; None on the other kinds), the box predictor's row widths, the kind's own buffers
+        attributes that hold it (`gfl`, `ld`, `paa`, `fovea`, `aa`; None on the other kinds), the box predictor's row widths, the kind's own buffers
         (`score`, `weight`; `pos_loss`, `iou_target`, `cand_gt`, `gmm_iters`, `gmm_flags`; absent on the other kinds), middle(),
         the entry of loss() and the length of logvec.  A kind with the ATSS layout: the assignment is fed the images' pad_shape
         (set_targets); `npos` holds the positives per image, stats[0] their sum_i max(npos_i, 1) (atss_head.py:554).  An LD head:
@@ -35,7 +35,7 @@ class FcosLossPlan:
         self.LD_GCLS, self.LD_CLS = class_layout(num_classes)
         self.head = head = head or HeadOptions()
         self.kind = kind = head.kind
-        self.gfl = self.ld = self.paa = self.fovea = self.ext = None
+        self.gfl = self.ld = self.paa = self.fovea = self.aa = self.ext = None
         inner = getattr(L, kind.loss_desc[0])()
         for attr, member in zip(kind.loss_desc[1:], kind.loss_desc[2:] + ('fcos',)):
             setattr(self, attr, inner)
@@ -103,6 +103,13 @@ class FcosLossPlan:
         for name, dtype, length, fill in kind.buffers:
             setattr(self, name, torch.full((getattr(self, length),), fill, dtype=dtype, device=dev))
             setattr(self.ext, name, L.ptr(getattr(self, name)))
+        if self.aa is not None:
+            # the per-box launches and records are sized by the capacity of gt_boxes; the centre prior (mean, then sigma, each [C][2])
+            # and its gradient are the plan's own until bind_prior names the parameter store's
+            self.aa.max_gt = max_gt
+            self.prior = torch.cat([torch.zeros(num_classes, 2), torch.ones(num_classes, 2)]).to(dev)
+            self.g_prior = torch.zeros(2 * num_classes, 2, dtype=torch.float32, device=dev)
+            self.bind_prior(*(t.data_ptr() + o for t in (self.prior, self.g_prior) for o in (0, 8 * num_classes)))
         self.logvec = self.logvec[:len(kind.loss_keys) + kind.sisoft + 1]      # the terms in log order (cls, bbox, ...), their sum
         need = L.lib.dsl_fcos_workspace_bytes(C.byref(self.desc))
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -117,8 +124,14 @@ class FcosLossPlan:
             if pad_shapes is None or len(pad_shapes) != self.n:
                 raise ValueError('an ATSS head needs the pad_shape of every image (set_targets(pad_shapes=...))')
             gt_bboxes_ignore = None
-        if self.desc.head_flags & L.HEAD_FOVEA:      # FoveaHead.loss takes gt_bboxes_ignore and does not read it (fovea_head.py:134-182)
+        if self.desc.head_flags & (L.HEAD_FOVEA | L.HEAD_AUTOASSIGN):      # their loss takes gt_bboxes_ignore and does not read it (fovea_head.py:134-182, autoassign_head.py:314-321)
             gt_bboxes_ignore = None
+        if self.aa is not None:
+            # the centre prior has one row per class: labels handed over on the host are checked here (no device read; what the
+            # kernels do with an out-of-range label that arrives on the device is stated at dsl_aa_desc in include/dsl_hip.h)
+            for l in gt_labels:
+                if not l.is_cuda and l.numel() and not (0 <= int(l.min()) and int(l.max()) < self.num_classes):
+                    raise ValueError(f'an AutoAssign head needs gt_labels in 0..{self.num_classes - 1}, got {int(l.min())}..{int(l.max())}')
         slot = self._slots[self._slot_i]
         self._slot_i = (self._slot_i + 1) % len(self._slots)
         if slot['ev'] is not None:
@@ -176,6 +189,10 @@ class FcosLossPlan:
         ops.set_ptrs(self.desc, cls_logits=cls_logits, regctr=regctr, scales=scales)
         if self.ctr_col is not None:
             self.desc.ctr, self.desc.ld_ctr = self.desc.cls_logits + 4 * self.ctr_col, self.LD_CLS
+
+    def bind_prior(self, mean, sigma, g_mean, g_sigma):
+        """AutoAssign only: the addresses of center_prior.mean / .sigma ([C][2] fp32 each) and of their gradients."""
+        self.aa.mean, self.aa.sigma, self.aa.g_mean, self.aa.g_sigma = mean, sigma, g_mean, g_sigma
 
     def bind_soft(self, regctr, ld, scales):
         """LD only: the teacher's box predictor output (fp32 [M][ld], the layout of bind_outputs' regctr) and its five Scale values."""

@@ -197,7 +197,18 @@ _FOVEA = _FCOS._replace(
     loss_entry='dsl_fovea_loss', loss_keys=('loss_cls', 'loss_bbox'), sisoft=False, exchange=None,
     aug_refusal='FoveaHead does not support test-time augmentation (aug_test): FoveaHead.get_bboxes has no with_nms argument, so '
                 'aug_test_bboxes asserts (dense_test_mixins.py:62-70)')
-HEAD_KINDS = {k.name: k for k in (_FCOS, _ATSS, _GFL, _LD, _PAA, _FOVEA)}
+# AutoAssignHead (autoassign_head.py): FCOS's network - towers with bias, predictors, centerness (here: objectness) on the regression
+# tower, Scale - with no hard assigner: the positive, negative and centre-prior losses of dsl_aa_loss.  Its two normalisers (boxes in
+# the batch, sum of the centre prior) come out of the assignment stage, so they cross the ranks under the forward pass
+_AA_FIELDS = ('head_kind', 'pos_loss_weight', 'neg_loss_weight', 'center_loss_weight')
+_AA = _FCOS._replace(
+    name='autoassign', flags=L.HEAD_AUTOASSIGN | L.HEAD_LOSS_EXT, fields=_AA_FIELDS,
+    loss_desc=('AaDesc', 'aa'),
+    scalars=(('aa', 'w_pos', 'pos_loss_weight'), ('aa', 'w_neg', 'neg_loss_weight'), ('aa', 'w_center', 'center_loss_weight')),
+    buffers=(('iou', _F32, 'M', 0),),
+    det_mask=L.HEAD_AUTOASSIGN,
+    loss_entry='dsl_aa_loss', loss_keys=('loss_pos', 'loss_neg', 'loss_center'), sisoft=False, exchange='forward', aug_refusal=None)
+HEAD_KINDS = {k.name: k for k in (_FCOS, _ATSS, _GFL, _LD, _PAA, _FOVEA, _AA)}
 
 
 class HeadOptions:
@@ -245,6 +256,11 @@ class HeadOptions:
       base_edge_list     per level: the unit of the log distances, > 0
       scale_ranges       per level: (lo, hi) bounds of sqrt(box area), lo <= hi
       smooth_l1_beta     SmoothL1Loss(beta) > 0 (losses/smooth_l1_loss.py:11-29)
+    AutoAssign (head_kind 'autoassign' = AutoAssignHead, mmdet/models/dense_heads/autoassign_head.py, dsl_aa_desc): FCOS's network with
+    conv_bias=True forced (:151), points without the half-stride offset and a trained per-class centre prior (the parameter region
+    head.center_prior: mean, then sigma, each [C][2]); bbox_weight counts (GIoULoss(loss_weight)), box_loss must be GIoU, every other
+    FCOS / ATSS / GFL / PAA / Fovea option is refused off its default:
+      pos_loss_weight, neg_loss_weight, center_loss_weight      finite and >= 0 (0.25, 0.75, 0.75)
     `kind` is the record of the resolved head kind (HEAD_KINDS above): what follows from "which head is this" is read there."""
     FIELDS = ('center_sampling', 'norm_on_bbox', 'centerness_on_reg', 'iou_loss', 'conv_bias')
     LOSS_FIELDS = ('box_loss', 'box_eps', 'focal_gamma', 'focal_alpha', 'cls_weight', 'bbox_weight', 'ctr_weight')
@@ -255,9 +271,9 @@ class HeadOptions:
                  assigner='fcos', atss_topk=9, anchor_scale=8.0, delta_stds=(0.1, 0.1, 0.2, 0.2),
                  head_kind='fcos', reg_max=16, qfl_beta=2.0, dfl_weight=0.25, ld_weight=None, ld_T=10.0, pos_iou_thr=0.1, score_voting=True,
                  sigma=0.4, base_edge_list=(16, 32, 64, 128, 256), scale_ranges=((8, 32), (16, 64), (32, 128), (64, 256), (128, 512)),
-                 smooth_l1_beta=0.11):
-        if head_kind not in ('fcos', 'gfl', 'paa', 'fovea'):
-            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos', 'gfl', 'paa' or 'fovea', got {head_kind!r}")
+                 smooth_l1_beta=0.11, pos_loss_weight=0.25, neg_loss_weight=0.75, center_loss_weight=0.75):
+        if head_kind not in ('fcos', 'gfl', 'paa', 'fovea', 'autoassign'):
+            raise NotImplementedError(f"dsl_amd hot path: head_kind must be 'fcos', 'gfl', 'paa', 'fovea' or 'autoassign', got {head_kind!r}")
         if assigner not in ('fcos', 'atss'):
             raise NotImplementedError(f"dsl_amd hot path: assigner must be 'fcos' or 'atss', got {assigner!r}")
         if ld_weight is not None and head_kind != 'gfl':
@@ -304,6 +320,28 @@ class HeadOptions:
                 raise NotImplementedError(f'dsl_amd hot path: base_edge_list must be {MAX_LEVELS} finite numbers > 0, got {base_edge_list!r}')
             if len(scale_ranges) != MAX_LEVELS or not all(len(r) == 2 and float(r[0]) <= float(r[1]) for r in scale_ranges):
                 raise NotImplementedError(f'dsl_amd hot path: scale_ranges must be {MAX_LEVELS} pairs (lo, hi) with lo <= hi, got {scale_ranges!r}')
+        if head_kind == 'autoassign':
+            # what an AutoAssign head does not read, or fixes itself, is refused off its default instead of being dropped
+            for name, val, want in (('center_sampling', center_sampling, True), ('norm_on_bbox', norm_on_bbox, True),
+                                    ('centerness_on_reg', centerness_on_reg, True), ('iou_loss', iou_loss, False), ('conv_bias', conv_bias, True),
+                                    ('box_eps', box_eps, 1e-6), ('focal_gamma', focal_gamma, 2.0), ('focal_alpha', focal_alpha, 0.25),
+                                    ('cls_weight', cls_weight, 1.0), ('ctr_weight', ctr_weight, 1.0), ('assigner', assigner, 'fcos'),
+                                    ('atss_topk', atss_topk, 9), ('anchor_scale', anchor_scale, 8.0),
+                                    ('delta_stds', tuple(delta_stds), (0.1, 0.1, 0.2, 0.2)), ('reg_max', reg_max, 16), ('qfl_beta', qfl_beta, 2.0),
+                                    ('dfl_weight', dfl_weight, 0.25), ('ld_T', ld_T, 10.0), ('pos_iou_thr', pos_iou_thr, 0.1),
+                                    ('score_voting', score_voting, True), ('sigma', sigma, 0.4),
+                                    ('base_edge_list', tuple(base_edge_list), (16, 32, 64, 128, 256)),
+                                    ('scale_ranges', tuple(tuple(r) for r in scale_ranges), ((8, 32), (16, 64), (32, 128), (64, 256), (128, 512))),
+                                    ('smooth_l1_beta', smooth_l1_beta, 0.11)):
+                if val != want:
+                    raise NotImplementedError(f"dsl_amd hot path: head_kind='autoassign' does not read {name} (got {val!r}; leave it at {want!r})")
+            if box_loss not in (None, 'giou'):
+                raise NotImplementedError(f"dsl_amd hot path: head_kind='autoassign' is built for box_loss='giou' (GIoULoss), got {box_loss!r}")
+            for name, val in (('bbox_weight', bbox_weight), ('pos_loss_weight', pos_loss_weight), ('neg_loss_weight', neg_loss_weight),
+                              ('center_loss_weight', center_loss_weight)):
+                if not (isinstance(val, (int, float)) and 0.0 <= float(val) < float('inf')):
+                    raise NotImplementedError(f'dsl_amd hot path: {name} must be a finite number >= 0, got {val!r}')
+        self.pos_loss_weight, self.neg_loss_weight, self.center_loss_weight = float(pos_loss_weight), float(neg_loss_weight), float(center_loss_weight)
         self.sigma, self.smooth_l1_beta = float(sigma), float(smooth_l1_beta)
         self.base_edge_list = tuple(float(v) for v in base_edge_list)
         self.scale_ranges = tuple((float(lo), float(hi)) for lo, hi in scale_ranges)
@@ -368,6 +406,10 @@ class HeadOptions:
         """The head has a Scale per level (parameters bbox_head.scales.i.scale, read by the loss and detection kernels); a Fovea head
         uses conv_reg's outputs raw (fovea_head.py:117-128)."""
         return not self.kind.flags & L.HEAD_FOVEA
+
+    def has_prior(self):
+        """The head has AutoAssign's centre prior (parameters bbox_head.center_prior.mean / .sigma, region head.center_prior)."""
+        return bool(self.kind.flags & L.HEAD_AUTOASSIGN)
 
     def atss_desc(self):
         """A dsl_atss_desc with the head's settings (None for an FCOS head); the caller fills max_gt, pad_shapes and npos."""
@@ -482,6 +524,8 @@ class ParamStore:
         toff = add(self.train_regions, toff, 'head.regctr_b', (self.reg_pad,))
         if self.head.has_scale():
             toff = add(self.train_regions, toff, 'head.scales', (8,))
+        if self.head.has_prior():      # center_prior.mean [C][2], then center_prior.sigma [C][2]: weights (decayed, lr_mult 1), no bias, no norm
+            toff = add(self.train_regions, toff, 'head.center_prior', (2, num_classes, 2))
         self.n_train, self.n_frozen = toff, foff
         self.device = torch.device(device)
         self.train = torch.zeros(toff, dtype=torch.float32, device=device)
@@ -581,6 +625,9 @@ class ParamStore:
             sc = self.tview('head.scales', tb)
             for i in range(5):
                 out[f'bbox_head.scales.{i}.scale'] = sc[i]
+        if self.head.has_prior():      # (autoassign_head.py:39-40)
+            cp = self.tview('head.center_prior', tb)
+            out['bbox_head.center_prior.mean'], out['bbox_head.center_prior.sigma'] = cp[0], cp[1]
         return out
 
     def predictor_names(self):
@@ -815,6 +862,11 @@ class ParamStore:
         """Address of the five Scale values in the flat buffer (`buf`: the gradient buffer), None for a head without Scale."""
         return self.t32_ptr('head.scales', buf) if self.head.has_scale() else None
 
+    def prior_ptrs(self, buf=None):
+        """Addresses of center_prior.mean and .sigma in the flat buffer (`buf`: the gradient buffer)."""
+        base = self.t32_ptr('head.center_prior', buf)
+        return base, base + 8 * self.num_classes
+
     def wT_ptr(self, name):
         lay, _ = self.wT_layout()
         return self.wT16.data_ptr() + lay[name][0] * 2
@@ -838,7 +890,7 @@ class ParamStore:
                 t = torch.tensor(1.0)
             elif leaf == 'running_mean':
                 t = torch.zeros(shape)
-            elif leaf == 'running_var':
+            elif leaf == 'running_var' or k == 'bbox_head.center_prior.sigma':      # (autoassign_head.py:39-40: mean 0, sigma 1)
                 t = torch.ones(shape)
             elif len(shape) == 4:
                 fan_in = shape[1] * shape[2] * shape[3]
@@ -858,6 +910,11 @@ class ParamStore:
                 t = torch.zeros(shape)
                 if k == f'bbox_head.{self.predictor_names()[0]}.bias':      # (atss_head.py:30-42, gfl_head.py:135-142: the same prior on atss_cls / gfl_cls)
                     t = torch.full(shape, -math.log((1 - 0.01) / 0.01))
+                if self.head.has_prior():      # autoassign_head.py:161-171: class bias from probability 0.02, box bias 4.0
+                    if k == f'bbox_head.{self.predictor_names()[0]}.bias':
+                        t = torch.full(shape, -math.log((1 - 0.02) / 0.02))
+                    elif k == f'bbox_head.{self.predictor_names()[1]}.bias':
+                        t = torch.full(shape, 4.0)
             sd[k] = t
         self.load_named(sd)
         return self

@@ -831,12 +831,82 @@ typedef struct dsl_fovea_desc {
 int dsl_fovea_assign(const dsl_fovea_desc* f, void* stream);
 int dsl_fovea_loss(const dsl_fovea_desc* f, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * AutoAssign: AutoAssignHead's differentiable label assignment - no hard assigner - and its three losses
+ * (mmdet/models/dense_heads/autoassign_head.py:81-119 centre prior, :173-187 points, :204-212 forward, :238-256 positive loss,
+ * :282-310 negative loss, :384-437 IoU / normalisers / centre loss / the batch without boxes, :492-509 inside mask;
+ * bbox_overlaps and GIoULoss as the other heads'), fp32, contraction off.
+ *
+ * A dsl_aa_desc wraps a dsl_fcos_desc with DSL_HEAD_AUTOASSIGN | DSL_HEAD_LOSS_EXT in head_flags and no other head or option flag.
+ * The point of location (x, y) of a level with stride s is (x s, y s): no half-stride offset.  fcos.regctr holds conv_reg's four raw
+ * outputs and the objectness logit (conv_centerness on the regression tower) in column 4 (ld_rc >= 8); the box prediction is
+ * relu(scales[l] x) s, decoded as (px - d0, py - d1, px + d2, py + d3).  No ignore boxes (ig_boxes must be NULL), no stream weight
+ * (loss_weight == 1), no sisoft term (soft_weight == 0), fcos.ctr / g_ctr NULL; fcos.range_lo / range_hi / radius, the focal
+ * settings, w_cls and w_ctr are not read, box_kind must be DSL_BOX_GIOU.  labels, bbox_targets, assign_idx, cls_weight and
+ * pos_weight are neither read nor written: there is no per-location target.
+ * A pair (point i, box g of its image) is INSIDE iff min(px - x1, py - y1, x2 - px, y2 - py) > 0 in fp32.  For inside pairs
+ *   c(i, g) = prod_{d = x, y} exp(-(((p_d - centre_d(g)) / s - mean[label_g][d])^2) / (2 sigma[label_g][d]^2)),  else 0,
+ * mean / sigma fp32 [C][2] (the trained parameters center_prior.mean / .sigma).  A box whose label is outside [0, C) has no row in
+ * the prior; the host refuses such labels where it sees them (FcosLossPlan.set_targets, labels on the host).  Arriving on the
+ * device, the box is never dereferenced by its label and: counts in stats[0] and in its image's n_boxes of the centre loss (both are
+ * gt_off differences); adds nothing to stats[1], to sum c of its image, to the positive loss (its term is 0, not 100), to any
+ * gradient or negative weight; and still takes part in iou(i), which is over all boxes of the image.
+ *
+ * dsl_aa_assign - what depends on the boxes and the prior alone, so that the ranks' sums can be exchanged while the forward
+ * pass runs: stats[0] = the boxes of the batch (gt_off[n]), stats[1] = sum over all pairs of c, stats[2..7] = 0.  One wavefront per
+ * box walks the box's footprint on every level; lane partial sums in footprint order, an xor butterfly, then the boxes' records
+ * in box order.
+ *
+ * dsl_aa_loss (forward and backward), with N_pos = max(norm[0] * inv_world, 1), N_neg = max(norm[1] * inv_world, 1) - norm holds
+ * the sum over ranks of stats[0:2] (reduce_mean, :407-408, :414-416):
+ *   iou(i)   = max over ALL boxes of image(i) of the plain IoU (union clamped at 1e-6) of the decoded box - not only the boxes that
+ *              hold i; written to `iou`; no gradient
+ *   reg(i,g) = w_bbox * (1 - giou(decoded box, box g)),  p_pos = sigmoid(cls[i][label_g]) sigmoid(obj[i]) exp(-reg),
+ *   w = exp(3 p_pos) c,  R_g = sum_i p_pos w / max(sum_i w, 1e-12)
+ *   losses[0] = w_pos / N_pos * sum_g -max(log R_g, -100)      (a box that holds no point: R = 0, its term is 100)
+ *   t(i) = 1 / max(1 - iou(i), 1e-12), per box over its inside points t_norm = (t - min + 1e-12) / (max - min + 1e-12);
+ *   p_neg_weight[i][label_g] = 1 - t_norm, 1 elsewhere; where several boxes of one class hold a point, the HIGHEST box index wins
+ *   (the reference's index assignment on the CPU; pinned by the fixtures)
+ *   q = sigmoid(cls) sigmoid(obj) p_neg_weight,  losses[1] = w_neg / N_neg * sum_{i, c} q^2 * -max(log(1 - q), -100)
+ *   losses[2] = w_center / n * sum_images [ n_boxes / max(sum c, 1e-12) if the image has an inside pair, else 0 ]  (this rank's)
+ *   a batch without boxes: losses[0] = losses[2] = 0 and no gradient for the prior; losses[1] with weights 1.  losses[3] = 0;
+ *   logvec = [pos, neg, center, their sum].
+ * Gradients, all times grad_scale: g_cls [M][ld_gcls] bf16 (columns below C written), g_rc [M][ld_grc] bf16 - columns 0..3 through
+ * the stride, the ReLU and the Scale, column 4 the objectness, 5..7 zero - g_scales [nlvl], g_mean / g_sigma fp32 [C][2]
+ * (overwritten).  The gradient flows through exp(3 p_pos) and through c (into R and into the centre loss); the BCE derivatives
+ * are torch's, (x - target) / max((1 - x) x, 1e-12).  N_pos and N_neg carry none.
+ * Launches: a per-point pass (boxes staged through LDS in chunks of 64) for iou; a per-box pass (one wavefront per box over its
+ * footprint) for sum c, sum w, sum p w, min / max t; a per-image pass; a per-point pass, one wavefront per location - a lane per box
+ * for the positive terms, the boxes that hold the point then taken in ascending index by the lane that owns their class, a lane per
+ * class for the negative loss; a per-box pass for one d mean / d sigma record per box; one workgroup that adds the block records,
+ * the boxes' terms and, per class, the boxes' records in box order.  No float atomics; a second run is bit-identical.
+ * Workspace: dsl_fcos_workspace_bytes(&f->fcos) (it reads max_gt).
+ * Refused, with dsl_last_error naming the field: head_flags other than DSL_HEAD_AUTOASSIGN | DSL_HEAD_LOSS_EXT, fcos.ig_boxes,
+ * fcos.soft_weight != 0, fcos.loss_weight != 1, fcos.ctr / g_ctr, num_classes outside 1..128, max_gt outside 1..2^20, a negative
+ * or non-finite weight, box_kind other than DSL_BOX_GIOU, ld_rc < 8, null mean / sigma / g_mean / g_sigma / iou, a workspace
+ * below dsl_fcos_workspace_bytes.  dsl_fcos_assign / dsl_fcos_loss refuse the flag.
+ * ---------------------------------------------------------------------------------------- */
+#define DSL_HEAD_AUTOASSIGN 1024   /* AutoAssignHead: dsl_fcos_desc inside a dsl_aa_desc */
+typedef struct dsl_aa_desc {
+  dsl_fcos_desc fcos;
+  float w_pos, w_neg, w_center;        /* pos_loss_weight, neg_loss_weight, center_loss_weight (0.25, 0.75, 0.75) */
+  int32_t max_gt;                      /* capacity of fcos.gt_boxes / gt_labels in boxes: sizes the per-box launches and records */
+  const float* mean;                   /* [C][2] center_prior.mean */
+  const float* sigma;                  /* [C][2] center_prior.sigma (!= 0) */
+  float* g_mean;                       /* [C][2], overwritten by dsl_aa_loss */
+  float* g_sigma;                      /* [C][2], overwritten by dsl_aa_loss */
+  float* iou;                          /* [M], written by dsl_aa_loss */
+} dsl_aa_desc;
+int dsl_aa_assign(const dsl_aa_desc* f, void* stream);
+int dsl_aa_loss(const dsl_aa_desc* f, void* stream);
+
 /* One dispatch for every head, on head_flags.  The contract the flags state: with DSL_HEAD_GFL `d` is the first member of a
  * dsl_gfl_desc, with DSL_HEAD_LD of a dsl_ld_desc (whose first member is that dsl_gfl_desc), so the three share one address.
- * With DSL_HEAD_PAA `d` is the first member of a dsl_paa_desc, with DSL_HEAD_FOVEA of a dsl_fovea_desc.
- * dsl_head_assign: DSL_HEAD_FOVEA -> dsl_fovea_assign, else DSL_HEAD_PAA -> dsl_paa_assign, else DSL_HEAD_ATSS ->
+ * With DSL_HEAD_PAA `d` is the first member of a dsl_paa_desc, with DSL_HEAD_FOVEA of a dsl_fovea_desc, with DSL_HEAD_AUTOASSIGN of a
+ * dsl_aa_desc.
+ * dsl_head_assign: DSL_HEAD_AUTOASSIGN -> dsl_aa_assign, else DSL_HEAD_FOVEA -> dsl_fovea_assign, else DSL_HEAD_PAA -> dsl_paa_assign, else DSL_HEAD_ATSS ->
  * dsl_atss_assign(d, d->atss), else dsl_fcos_assign.
- * dsl_head_loss: DSL_HEAD_FOVEA -> dsl_fovea_loss, else DSL_HEAD_PAA -> dsl_paa_loss, else DSL_HEAD_LD -> dsl_ld_loss (which refuses
+ * dsl_head_loss: DSL_HEAD_AUTOASSIGN -> dsl_aa_loss, else DSL_HEAD_FOVEA -> dsl_fovea_loss, else DSL_HEAD_PAA -> dsl_paa_loss, else DSL_HEAD_LD -> dsl_ld_loss (which refuses
  * the flag without DSL_HEAD_GFL), else
  * DSL_HEAD_GFL -> dsl_gfl_loss, else dsl_fcos_loss.  DSL_OP_ASSIGN / DSL_OP_LOSS of an op list are these two calls on the op's desc. */
 int dsl_head_assign(const dsl_fcos_desc* d, void* stream);
@@ -978,6 +1048,10 @@ typedef struct dsl_det_fovea_desc {
   dsl_det_desc det;
   float base_len[DSL_MAX_SEG];               /* base_edge_list, > 0 */
 } dsl_det_fovea_desc;
+/* An AutoAssign head's detection (DSL_HEAD_AUTOASSIGN in a plain dsl_det_desc's head_flags, no other flag, ctr NULL;
+ * autoassign_head.py:173-187,204-212 with FCOSHead._get_bboxes, fcos_head.py:419-516): FCOS's decode relu(scales[l] x) s and candidate
+ * score sigmoid(cls) * sigmoid(regctr[m][4]) from the point (x s, y s) - no half-stride offset - clipped to img_shape.
+ * get_bboxes has with_nms, so dsl_fcos_detect_collect / _finish serve the head as they serve FCOS's. */
 /* dsl_det_desc.nms_method.  Soft-NMS is mmcv's batched_nms with nms=dict(type='soft_nms', method=...) (stated by
  * mmdet/ops/nms/src/soft_nms_cpu.pyx:22-127), per image and class over the candidates the hard NMS would get: pick the highest current score
  * (equal scores: the candidate that comes first in (level, slot, class) order - with views, (view, level, slot, class)), emit it

@@ -6,7 +6,7 @@ refactor of dsl_amd/engine.py / engine_rla.py is checked by running this file on
 
 Pointers are printed as A<k>+<offset>(<allocation bytes>): k numbers the distinct allocations in order of first appearance in the
 leg's walk (tests/op_ref.Memory maps a pointer to its allocation), H = a non-null pointer into no tensor (host structures).
-For seven legs three optimizer steps on the tests/golden/net_tiny.npz batch follow, and the sha256 of the trained weights.
+For eight legs three optimizer steps on the tests/golden/net_tiny.npz batch follow, and the sha256 of the trained weights.
 Nothing is launched beyond what building a model and a plan launches (and those steps).
 """
 import argparse
@@ -206,6 +206,11 @@ def paa_cfg():
     return paa_model_cfg()
 
 
+def autoassign_cfg():
+    from test_autoassign_cpu import aa_model_cfg
+    return aa_model_cfg()
+
+
 TINY = (64, 96)         # tests/golden/net_tiny.npz
 ODD = (160, 224)        # test_train_step_vs_oracle_other_batch_sizes_and_shapes: levels 20x28, 10x14, 5x7, 3x4, 2x2
 # (name, config, N, (H, W), tuning knobs, options: defer / eval / single_stream / steps = also train three steps)
@@ -238,6 +243,7 @@ LEGS = [
     ('rla rla_split=', rla_cfg, 3, TINY, dict(rla_split=''), {}),
     ('rla rla_split_bwd=123', rla_cfg, 3, TINY, dict(rla_split_bwd='123'), {}),
     ('rla rla_tail=0', rla_cfg, 3, TINY, dict(rla_tail='0'), {}),
+    ('resnet AutoAssign head', autoassign_cfg, 2, TINY, {}, dict(steps=True)),          # (last: the legs above keep their text)
 ]
 
 
