@@ -30,6 +30,10 @@ HEADS = [
     ('gfl reg_max=16', lambda: HeadOptions(head_kind='gfl', reg_max=16)),
     ('ld', lambda: HeadOptions(head_kind='gfl', reg_max=16, ld_weight=0.5, ld_T=4.0)),
     ('paa', lambda: HeadOptions(head_kind='paa', atss_topk=3, anchor_scale=4.0, bbox_weight=1.3, pos_iou_thr=0.2, score_voting=False)),
+    ('fovea', lambda: HeadOptions(head_kind='fovea', sigma=0.5, base_edge_list=(8, 16, 32, 64, 128), smooth_l1_beta=0.2, conv_bias=False,
+                                  focal_gamma=1.5)),
+    ('autoassign', lambda: HeadOptions(head_kind='autoassign', bbox_weight=2.0, pos_loss_weight=0.5, neg_loss_weight=0.6,
+                                       center_loss_weight=0.7)),
 ]
 
 
